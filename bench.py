@@ -59,6 +59,31 @@ def spawn_ranks(n, argv):
     return farm.spawn_local_ranks(n, os.path.abspath(__file__), argv)
 
 
+MODEL_FIELDS = ("cx", "cy", "dx", "dy", "rot", "div", "cnt", "total_dx", "total_dy", "total_rot", "total_div")
+RUN_FIELDS = ("rc", "iterations", "events", "x_divider", "y_divider", "rot_divider", "div_divider")
+DUMP_BUDGET_BYTES = 32 << 20    # --dump-outputs: the per-event flow sample of the whole job stays under this
+
+
+def dump_outputs(out_dir, prefix, models, runs, flows=None, sample_per_lane=0):
+    """--dump-outputs: what the timed path returned in its last step, as float64 .npy files (one row per slice context,
+    or per slice for config 5): model.npy (MODEL_FIELDS), run_info.npy (those of RUN_FIELDS the path returns: config 5's
+    records carry the first three) and, when the path returns the per-event flow, u.npy / v.npy at the event indices
+    uv_index.npy -- a fixed seeded sample of `sample_per_lane` events per context (all of them when the slice is no larger)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"model": np.array([[float(m[k]) for k in MODEL_FIELDS] for m in models], dtype=np.float64),
+              "run_info": np.array([[float(r[k]) for k in RUN_FIELDS if k in r] for r in runs], dtype=np.float64)}
+    if flows:
+        k = min([sample_per_lane] + [len(u) for u, _ in flows])
+        idx = [np.sort(np.random.default_rng(lane).choice(len(u), k, replace=False)) if k < len(u) else np.arange(k)
+               for lane, (u, _) in enumerate(flows)]
+        arrays["uv_index"] = np.array(idx, dtype=np.float64)
+        arrays["u"] = np.array([u[i] for (u, _), i in zip(flows, idx)], dtype=np.float64)
+        arrays["v"] = np.array([v[i] for (_, v), i in zip(flows, idx)], dtype=np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -92,6 +117,9 @@ def main():
     ap.add_argument("--farm-costs", default=None, metavar="JSON",
                     help="--config 5: a previous run's JSON line (its config.per_slice.iterations): slices are handed out longest first")
     ap.add_argument("--farm-record", default=None, metavar="PATH", help="--config 5: also write the JSON line to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy "
+                         "(float64; several ranks: rank<r>_<name>.npy) so that two builds can be compared output for output")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="allow more ranks than visible devices (rank r on device r %% devices): tests only")
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
@@ -112,6 +140,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: this process only spawns the N ranks and relays the outcome
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -258,6 +288,10 @@ def main():
             if args.farm_record:
                 with open(args.farm_record, "w") as f:
                     f.write(line + "\n")
+            if args.dump_outputs:   # the batch's per-slice records, gathered from every rank: one row per slice, in slice order
+                recs = [merged[i] for i in range(args.farm_slices)]
+                dump_outputs(args.dump_outputs, "", [r["model"] for r in recs],
+                             [{k: r[k] for k in ("rc", "iterations", "events")} for r in recs])
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -297,6 +331,8 @@ def main():
         rc, m, info = a.run(o)
         return n, m, info
 
+    last = [None] * B   # (events, model, info) of each lane's latest step: --dump-outputs
+
     def run_steps(first, count):
         """`count` steps; a step = B independent cold slices, one per lane, in flight together
         (ctypes releases the GIL inside the C-ABI calls).  Returns (events, iterations)."""
@@ -304,9 +340,10 @@ def main():
 
         def lane_loop(lane):
             for k in range(count):
-                n, _, info = step(first + k + lane, lane=lane)   # consecutive steps of a lane: different slices
+                n, m, info = step(first + k + lane, lane=lane)   # consecutive steps of a lane: different slices
                 tot[lane][0] += n
                 tot[lane][1] += info.iterations
+                last[lane] = (n, m, info)
         if B == 1:
             lane_loop(0)
         else:
@@ -335,6 +372,12 @@ def main():
     elapsed = time.perf_counter() - t0
     ru1 = resource.getrusage(resource.RUSAGE_SELF)
     host_cores_busy = ((ru1.ru_utime - ru0.ru_utime) + (ru1.ru_stime - ru0.ru_stime)) / max(elapsed, 1e-9)
+    if args.dump_outputs:
+        # the last timed step of every lane: its model, its run info and its per-event (u, v), which the final warp of that
+        # run left on the device (want_uv) and compute_uv reads back -- nothing is recomputed
+        runs = [dict({k: getattr(info_, k) for k in RUN_FIELDS if k != "events"}, events=n_) for n_, _, info_ in last]
+        dump_outputs(args.dump_outputs, "rank%d_" % rank if world > 1 else "", [m_.as_dict() for _, m_, _ in last], runs,
+                     flows=[a_.compute_uv() for a_ in accs], sample_per_lane=DUMP_BUDGET_BYTES // (3 * 8 * B * world))
     # The CPU baseline (one host core, ~10 s to the loop's own termination) starts NOW, in a side process, and runs under the
     # GPU legs that follow (regimes, roofline, other geometries: several seconds of kernels) instead of after them: the
     # headline above was timed without it, and whoever samples the GPU's activity during this run sees it busy.

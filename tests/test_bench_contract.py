@@ -124,29 +124,87 @@ def test_bench_config5_gpus_flag_spawns_its_own_ranks():
 
 
 @pytest.mark.gpu
-def test_bench_eight_ranks_on_one_gpu():
-    """First contact with the target world size (no 8-GPU node was ever available to this build): `bench.py --gpus 8` as the
-    driver calls it, all eight ranks on GPU 0 (--oversubscribe), one slice context per rank, two steps of config 2 -- one JSON
-    line, n_gpus 8, the whole-job aggregate, the host-core budget in it."""
-    d = _line([sys.executable, "bench.py", "--gpus", "8", "--oversubscribe", "--concurrent", "1", "--steps", "2", "--warmup", "1",
+def test_bench_four_ranks_on_one_gpu():
+    """`bench.py --gpus N` as the driver calls it with more ranks than the two tests above: four ranks, all on GPU 0
+    (--oversubscribe), one slice context per rank, two steps of config 2 -- one JSON line, n_gpus 4, the whole-job
+    aggregate, the host-core budget in it.  (Four ranks and this process make five processes on the device, within the six
+    a shared GPU node allows; world size 8 itself is covered without a device by test_farm_gloo.py.)"""
+    d = _line([sys.executable, "bench.py", "--gpus", "4", "--oversubscribe", "--concurrent", "1", "--steps", "2", "--warmup", "1",
                "--slices", "2"])
-    _check(d, 8, 2, 1)
-    assert "8 GPU(s)" in d["config"]["parallelism"] and d["cpu_baseline"] is None
-    assert d["config"]["host_budget"]["ranks"] == 8
+    _check(d, 4, 2, 1)
+    assert "4 GPU(s)" in d["config"]["parallelism"] and d["cpu_baseline"] is None
+    assert d["config"]["host_budget"]["ranks"] == 4
     assert abs(d["config"]["events_per_slice"] - 1e6) < 5e4 and d["config"]["iterations_per_slice"] > 400
 
 
 @pytest.mark.gpu
-def test_bench_config5_eight_ranks_on_one_gpu():
-    """BASELINE config 5's job shape at its world size: 8 ranks (all on GPU 0) x 1 slice context claim 16 full-size 1280x720
-    slices from ONE queue, the slices exchanged through the shared directory; one JSON line with the per-rank records."""
-    d = _line([sys.executable, "bench.py", "--gpus", "8", "--oversubscribe", "--config", "5", "--farm-slices", "16", "--concurrent", "1"])
-    assert d["n_gpus"] == 8 and d["unit"] == "Mevents/s" and d["value"] > 0 and d["value_definition"] == "host_to_host"
+def test_bench_config5_four_ranks_on_one_gpu():
+    """BASELINE config 5's job shape with several ranks: 4 ranks (all on GPU 0) x 1 slice context claim 16 full-size
+    1280x720 slices from ONE queue, the slices exchanged through the shared directory; one JSON line with the per-rank
+    records."""
+    d = _line([sys.executable, "bench.py", "--gpus", "4", "--oversubscribe", "--config", "5", "--farm-slices", "16", "--concurrent", "1"])
+    assert d["n_gpus"] == 4 and d["unit"] == "Mevents/s" and d["value"] > 0 and d["value_definition"] == "host_to_host"
     c = d["config"]
     assert c["slices"] == 16 and c["slices_failed"] == 0 and "1280x720" in c["workload"]
-    assert len(c["ranks"]["busy_s"]) == 8 and sum(c["ranks"]["slices"]) == 16 and min(c["ranks"]["slices"]) >= 1
-    assert sorted(set(c["per_slice"]["rank"])) == list(range(8)) and len(c["per_slice"]["iterations"]) == 16
-    assert c["host_budget"]["ranks"] == 8
+    assert len(c["ranks"]["busy_s"]) == 4 and sum(c["ranks"]["slices"]) == 16 and min(c["ranks"]["slices"]) >= 1
+    assert sorted(set(c["per_slice"]["rank"])) == list(range(4)) and len(c["per_slice"]["iterations"]) == 16
+    assert c["host_budget"]["ranks"] == 4
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs: the last timed step's model, run info and sampled per-event flow of every slice context, float64,
+    under 64 MB, and the same bits from a second run with the same arguments."""
+    import numpy as np
+    cmd = [sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--concurrent", "2", "--no-cpu-baseline", "--no-front-end",
+           "--dump-outputs"]
+    runs = []
+    for k in range(2):
+        out = tmp_path / ("run%d" % k)
+        d = _line(cmd + [str(out)])
+        assert d["steps"] == 2
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["model.npy", "run_info.npy", "u.npy", "uv_index.npy", "v.npy"], files
+        assert sum(p.stat().st_size for p in out.iterdir()) < 64 << 20
+        runs.append({f[:-4]: np.load(str(out / f)) for f in files})
+    a, b = runs
+    for name, arr in a.items():
+        assert arr.dtype == np.float64 and np.all(np.isfinite(arr)), name
+        assert arr.tobytes() == b[name].tobytes(), name
+    assert a["model"].shape[0] == a["run_info"].shape[0] == a["u"].shape[0] == 2
+    assert np.all(a["run_info"][:, 0] == 0) and np.all(a["run_info"][:, 1] > 400)       # rc, iterations of each lane's slice
+    assert a["u"].shape == a["v"].shape == a["uv_index"].shape and a["u"].shape[1] > 1000
+    assert np.any(a["u"] != 0) and np.any(a["v"] != 0)
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """(CPU) The --dump-outputs writer: float64 arrays, one row per slice context, a seeded sample of the per-event flow
+    that is the same for the same inputs."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    models = [{k: float(i + j) for j, k in enumerate(bench.MODEL_FIELDS)} for i in range(2)]
+    runs = [{k: float(i) for k in bench.RUN_FIELDS} for i in range(2)]
+    rng = np.random.default_rng(0)
+    flows = [(rng.standard_normal(5000), rng.standard_normal(5000)) for _ in range(2)]
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), "", models, runs, flows=flows, sample_per_lane=300)
+    for name in ("model", "run_info", "uv_index", "u", "v"):
+        x, y = np.load(str(tmp_path / "0" / (name + ".npy"))), np.load(str(tmp_path / "1" / (name + ".npy")))
+        assert x.dtype == np.float64 and x.tobytes() == y.tobytes(), name
+    idx = np.load(str(tmp_path / "0" / "uv_index.npy")).astype(np.int64)
+    assert idx.shape == (2, 300) and np.all(np.diff(idx, axis=1) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "0" / "u.npy"))[1], flows[1][0][idx[1]])
+    assert np.load(str(tmp_path / "0" / "model.npy")).shape == (2, len(bench.MODEL_FIELDS))
+    bench.dump_outputs(str(tmp_path / "all"), "", models, runs, flows=flows, sample_per_lane=1 << 20)   # sample > slice: every event
+    assert np.array_equal(np.load(str(tmp_path / "all" / "v.npy")), np.array([v for _, v in flows]))
+
+
+def test_bench_steps_must_be_positive():
+    """(CPU) --steps is the number of timed steps: zero is refused, not a division by zero after the fact."""
+    r = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                       timeout=120)
+    assert r.returncode != 0 and b"--steps must be" in r.stderr and b"{" not in r.stdout
 
 
 def test_bench_refuses_more_ranks_than_host_cores():

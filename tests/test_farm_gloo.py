@@ -40,11 +40,11 @@ def _worker(rank, world, port, n_slices, q):
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
     mine = farm.shard(n_slices, rank, world)
     res = farm.run_shard(mine, _process)
-    dist.barrier()
+    dist.monitored_barrier()   # (gloo's own barrier: dist.barrier() would probe for -- and open -- a GPU)
     merged = farm.gather(res, dist)
     if rank == 0:
         q.put(merged)
-    dist.barrier()
+    dist.monitored_barrier()   # (gloo's own barrier: dist.barrier() would probe for -- and open -- a GPU)
     dist.destroy_process_group()
 
 
@@ -97,7 +97,7 @@ def _queue_worker(rank, world, port, n_slices, use_costs, q):
     dist.init_process_group("gloo", init_method="tcp://127.0.0.1:%d" % port, rank=rank, world_size=world)
     costs = [24000 if i % 2 == 0 else 2000 for i in range(n_slices)] if use_costs else None
     work = farm.SliceQueue(n_slices, costs=costs, dist=dist, name="test")
-    dist.barrier()
+    dist.monitored_barrier()   # (gloo's own barrier: dist.barrier() would probe for -- and open -- a GPU)
     res = farm.run_queue(work, _process_uneven, lanes=1)
     for r in res.values():
         r["rank"] = rank
@@ -105,7 +105,7 @@ def _queue_worker(rank, world, port, n_slices, use_costs, q):
     merged = farm.gather(res, dist)
     if rank == 0:
         q.put(merged)
-    dist.barrier()
+    dist.monitored_barrier()   # (gloo's own barrier: dist.barrier() would probe for -- and open -- a GPU)
     dist.destroy_process_group()
 
 
@@ -246,7 +246,7 @@ def test_eight_ranks_one_queue_shared_slices(tmp_path):
             assert merged[str(i)][k] == single[k], (i, k)
     ranks = [merged[str(i)]["rank"] for i in range(n)]
     assert sorted(set(ranks)) == list(range(8)), ranks           # every rank claimed something
-    first = sorted(range(n), key=lambda i: merged[str(i)]["t0"])[:8]
+    first = sorted(range(n), key=lambda i: merged[str(i)]["started"])[:8]   # (one clock for all ranks: t0 is per rank)
     assert all(i % 5 == 0 for i in first), first                 # longest first: the eight heavy slices are the first claims
     bal = farm.balance({i: merged[str(i)] for i in range(n)}, 8)
     print("8 ranks: slices per rank %s, busy %s s, imbalance %.2f, wall %.1f s" %

@@ -3,6 +3,8 @@ oracle (oracle/bf_oracle.c), the oracle-backed C-ABI shim and the WHOLE host fro
 slice ring, DVS_flow with the overlap de-duplication, -o writer, frame writer -- built into one instrumented binary and
 run on BASELINE config 1, plus the ring / reader unit programs.  Any report aborts the program (-fno-sanitize-recover)."""
 import os
+import platform
+import shutil
 import subprocess
 import sys
 
@@ -79,6 +81,10 @@ def test_stream_engine_and_slice_farm_under_thread_sanitizer(tmp_path):
     txt = str(tmp_path / "ev.txt")
     synth.write_txt(txt, sl)
     env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
-    r = subprocess.run([exe, txt], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1800)
+    # GCC's ThreadSanitizer runtime cannot place its shadow memory under the high mmap ASLR entropy of recent kernels
+    # ("FATAL: ThreadSanitizer: unexpected memory mapping"): the program runs with address randomisation off for itself
+    # (setarch -R: a personality flag of this one process)
+    pre = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []
+    r = subprocess.run(pre + [exe, txt], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1800)
     assert r.returncode == 0 and b"ThreadSanitizer" not in r.stderr, r.stderr.decode()[-4000:]
     assert r.stdout.decode().count("\nOK ") + r.stdout.decode().startswith("OK ") == 8
