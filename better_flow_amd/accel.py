@@ -113,6 +113,29 @@ class LocalTileOpts(C.Structure):
     ]
 
 
+class GlobalWindow(C.Structure):
+    _fields_ = [
+        ("scale", C.c_int32), ("metric_wsize", C.c_int32),
+        ("x_min", C.c_int32), ("y_min", C.c_int32), ("x_max", C.c_int32), ("y_max", C.c_int32),
+        ("scale_img_x", C.c_int32), ("scale_img_y", C.c_int32),
+        ("scale_bordered_img_x", C.c_int32), ("scale_bordered_img_y", C.c_int32),
+    ]
+
+
+class GlobalSearchOpts(C.Structure):
+    _fields_ = [
+        ("x_low", C.c_double), ("x_hi", C.c_double), ("x_step", C.c_double),
+        ("y_low", C.c_double), ("y_hi", C.c_double), ("y_step", C.c_double), ("nz", C.c_double),
+    ]
+
+
+class GlobalResult(C.Structure):
+    _fields_ = [
+        ("best_nx", C.c_double), ("best_ny", C.c_double), ("best_sum", C.c_int64),
+        ("n_x", C.c_int64), ("n_y", C.c_int64),
+    ]
+
+
 # every symbol include/bf_accel.h declares
 EXPORTS = [
     "bf_device_count", "bf_create", "bf_destroy", "bf_last_error", "bf_version",
@@ -125,6 +148,7 @@ EXPORTS = [
     "bf_local_set_window", "bf_local_iteration_step", "bf_local_run", "bf_local_run_tiles",
     "bf_upload_ring_async", "bf_upload_ring16_async", "bf_upload_ring16t32_async", "bf_upload_events16_async", "bf_compute_uv_ring", "bf_wait_uploads", "bf_projection_img",
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
+    "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
 ]
 
 _lib = None
@@ -222,6 +246,13 @@ def load(path=None):
         L.bf_local_iteration_step.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(C.c_double), C.c_void_p]
         L.bf_local_run.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.POINTER(LocalState)]
         L.bf_local_run_tiles.argtypes = [C.c_void_p, C.POINTER(LocalTileOpts), C.c_void_p, C.c_void_p]
+        L.bf_global_search_opts_default.argtypes = [C.POINTER(GlobalSearchOpts)]
+        L.bf_global_search_opts_default.restype = None
+        L.bf_global_set_window.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(GlobalWindow)]
+        L.bf_global_project_all.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int64)]
+        L.bf_global_search.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(GlobalResult), C.c_void_p, C.c_int64]
+        L.bf_global_get_events.argtypes = [C.c_void_p] + [C.c_void_p] * 7
         L.bf_projection_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_color_time_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_upload_ring_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
@@ -278,6 +309,16 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _sweep(lo, hi, step):
+    """The reference's `for (v = lo; v < hi; v += step)` (optimizer_global.cpp:134-135)."""
+    out = []
+    v = lo
+    while step > 0 and v < hi and len(out) <= (1 << 26):
+        out.append(v)
+        v += step
+    return out
+
+
 class Accel:
     """One bf_ctx: the AccelLib-equivalent plus the fused OptimizerRolling::run."""
 
@@ -291,6 +332,7 @@ class Accel:
         self.h = h
         self.n = 0
         self.window = None
+        self._gwin = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -397,6 +439,56 @@ class Accel:
         img = np.empty((self._lwin.scale_img_x, self._lwin.scale_img_y), dtype=np.uint8) if want_img else None
         self._chk(self.L.bf_local_iteration_step(self.h, nx, ny, C.byref(sc), _ptr(img) if want_img else None))
         return (sc.value, img) if want_img else sc.value
+
+    # ---- OptimizerGlobal (optimizer_global.h:11-57): the exhaustive (nx, ny) search ----
+    def global_set_window(self, scale=None, metric_wsize=0):
+        """The constructors (optimizer_global.h:27-41) + update_fields; resets every event's best state.
+        No argument: OptimizerGlobal(events) -- scale 5, window 21; scale only: window 5 * scale."""
+        if scale is None:
+            scale, metric_wsize = 5, 21
+        w = GlobalWindow()
+        self._chk(self.L.bf_global_set_window(self.h, scale, metric_wsize, C.byref(w)))
+        self._gwin = w
+        return w
+
+    def global_project_all(self, nx, ny, nz=127.0, want_img=True, want_scores=True):
+        """One project_all.  Returns (S, blurred bordered image or None, current_scores or None)."""
+        w = self._gwin   # None before global_set_window: the library reports BF_ERR_ARG
+        img = np.empty((w.scale_bordered_img_x, w.scale_bordered_img_y), dtype=np.uint8) if want_img and w else None
+        sc = np.empty((w.scale_img_x, w.scale_img_y), dtype=np.float32) if want_scores and w else None
+        S = C.c_int64()
+        self._chk(self.L.bf_global_project_all(self.h, nx, ny, nz, _ptr(img), _ptr(sc), C.byref(S)))
+        return S.value, img, sc
+
+    @staticmethod
+    def global_search_opts(**kw):
+        """bf_global_search_opts with the reference's defaults, overridden by keyword."""
+        o = GlobalSearchOpts()
+        load().bf_global_search_opts_default(C.byref(o))
+        for k, v in kw.items():
+            setattr(o, k, v)
+        return o
+
+    def global_search(self, opts=None, want_surface=True, surface_cap=None):
+        """compute_flow_bruteforce over opts (None: the defaults).  Returns (GlobalResult, surface [n_x, n_y] int64 or None)."""
+        r = GlobalResult()
+        o = opts if opts is not None else self.global_search_opts()
+        surf = None
+        if want_surface:
+            nx = len(_sweep(o.x_low, o.x_hi, o.x_step))
+            ny = len(_sweep(o.y_low, o.y_hi, o.y_step))
+            surf = np.zeros(nx * ny if surface_cap is None else surface_cap, dtype=np.int64)
+        self._chk(self.L.bf_global_search(self.h, C.byref(o), C.byref(r), _ptr(surf), 0 if surf is None else len(surf)))
+        if surf is not None:
+            surf = surf[:r.n_x * r.n_y].reshape(r.n_x, r.n_y)
+        return r, surf
+
+    def global_get_events(self):
+        """Per-event state in upload order: dict of max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v."""
+        keys = ("max_score", "best_nx", "best_ny", "best_pr_x", "best_pr_y", "best_u", "best_v")
+        out = {k: np.zeros(self.n, dtype=np.float64) for k in keys}
+        self._chk(self.L.bf_global_get_events(self.h, *[_ptr(out[k]) for k in keys]))
+        return out
 
     def projection_img(self, scale, res_x, res_y, show_final=False):
         """EventFile::projection_img (event_file.h:460-515): the (motion-compensated) 8-bit event image."""

@@ -182,6 +182,7 @@ void bf_destroy(bf_ctx* c) {
         }
         (void)hipFree(c->d_tl);
     }
+    global_free(c);
     for (auto& r : c->prof_pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) if (c->poll_ev[i]) (void)hipEventDestroy(c->poll_ev[i]);

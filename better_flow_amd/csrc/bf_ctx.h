@@ -33,6 +33,8 @@ using namespace bf;
 // so a context takes it only while it is the one context on its device.
 extern std::atomic<int> g_live_ctx[64];
 
+struct GlobalSearch;   // bf_global_search.cpp: the exhaustive search's window, scratch and per-event state
+
 namespace {
 
 struct ProfRec {
@@ -197,6 +199,9 @@ struct bf_ctx {
     bf_local_window lwin;
     bool have_lwin = false;
     int lcur = 0;
+    // exhaustive search (bf_global.hip / bf_global_search.cpp)
+    GlobalSearch* glob = nullptr;
+    bool glob_valid = false;         // bf_global_set_window ran on the slice uploaded now (every upload clears it)
     SliceStats stats;                // folded k_prepare statistics of the uploaded slice
     bool stats_valid = false;
 
@@ -234,6 +239,9 @@ struct bf_ctx {
     char err[512];
     std::mutex err_mu;   // fail() may be called from the uploading thread and the solving thread at once (see bf_accel.h: threading)
 };
+
+// frees what bf_global_search.cpp allocated for ctx (bf_destroy)
+void global_free(bf_ctx* c);
 
 namespace {
 
@@ -601,6 +609,7 @@ int after_upload(bf_ctx* c, long long n) {
     c->p_clean = true;   // k_prepare wrote p = 0
     c->stats_valid = false;
     c->have_lwin = false;
+    c->glob_valid = false;
     c->n = n;
     c->uploaded = true;
     c->have_window = false;

@@ -1,0 +1,248 @@
+// bf_global.hip -- OptimizerGlobal (optimizer_global.cpp:4-150): a batched sweep of (nx, ny) candidates, each
+// scored the way project_all does it, for gfx950.  B candidates per batch, three launches:
+//
+//   G1  k_global_project : Event::project (event.h:65-70,164-168) of every event under candidate b, the acceptance
+//       test of :17-21, and the point form of the saturating scale x scale splat (:23-32): one 32-bit atomic at the
+//       splat's centre in point plane b.
+//   G2  k_global_tile    : per 32 x 64 tile of the bordered image of candidate b, in LDS: box sum of the points
+//       (== the splat), saturation at 255 (each `if (< 255) ++` is order independent: min(255, total)), this build's
+//       8-bit Gaussian (ksize = scale, BORDER_REFLECT_101; defined in include/bf_accel.h), and the non-zero sum and
+//       count of the metric_wsize^2 window of get_event_score (:82-101) as separable integer sums.  Writes one u32 per
+//       pixel: sum in bits 0-19, count in bits 20-31 (metric_wsize <= 63).
+//   G3  k_global_fold    : per event, the B candidates IN ORDER: its window word, score = sum / count (double, then
+//       float like current_scores), apply_score's strict `>` (event.h:113-121) into the running best, and
+//       floor(score * 2^32) = (sum << 32) / count summed per candidate with integer atomics -- S(k), order free.
+//
+// Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
+// order in which work-groups run.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+
+#include "bf_device.h"
+#include "bf_device_fns.h"
+#include "bf_kernels.h"
+
+namespace bf {
+
+namespace {
+constexpr int kGT = 256;        // threads per work-group
+constexpr int kGTR = 32;        // G2 tile rows
+constexpr int kGTC = 64;        // G2 tile columns
+constexpr uint32_t kCntShift = 20;
+constexpr uint32_t kSumMask = (1u << kCntShift) - 1u;
+
+__device__ __forceinline__ int reflect101g(int i, int n) {   // cv::BORDER_REFLECT_101
+    if (n == 1) return 0;
+    while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
+    return i;
+}
+
+// optimizer_global.cpp:17-21 for one event under one candidate; false when rejected
+__device__ __forceinline__ bool global_pixel(const GlobalGeom& g, const GlobalCand& c, uint32_t v, int32_t t, double& pr_x,
+                                             double& pr_y, int& X, int& Y) {
+    const float ft = (float)t;
+    pr_x = pr_from_p(v & 0xffffu, c.kx * ft);
+    pr_y = pr_from_p(v >> 16, c.ky * ft);
+    X = trunc_x86(pr_x * (double)g.scale - (double)g.xs);
+    Y = trunc_x86(pr_y * (double)g.scale - (double)g.ys);
+    return !((X >= g.sx - g.scale) || (X < 0) || (Y >= g.sy - g.scale) || (Y < 0));
+}
+}  // namespace
+
+__global__ __launch_bounds__(kGT) void k_global_project(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
+                                                        long long n, GlobalGeom g, const GlobalCand* __restrict__ cands,
+                                                        uint32_t* __restrict__ pts) {
+    const long long i = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (i >= n) return;
+    const int b = blockIdx.y;
+    double pr_x, pr_y;
+    int X, Y;
+    if (!global_pixel(g, cands[b], xy[i], t[i], pr_x, pr_y, X, Y)) return;
+    const int off = g.scale / 2 + g.mw / 2;   // :23-24: the splat's centre in the bordered image
+    atomicAdd(&pts[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)], 1u);
+}
+
+// LDS layout (rows x columns, H = scale / 2, W = metric_wsize / 2):
+//   P  points          [r0 - W - 2H, r0 + TR + W + 2H) x [c0 - W - 2H, ...)  u32   (later reused for the row sums)
+//   N  counts          [r0 - W - H,  r0 + TR + W + H)  x ...                  u16   (value at the REFLECTED pixel)
+//   V  blurred, packed [r0 - W,      r0 + TR + W)      x ...                  u32   v | (v != 0) << 20
+//   Hs row sums        [r0 - W,      r0 + TR + W)      x [c0, c0 + TC)        u32   (in P's space)
+template <int H>
+__global__ __launch_bounds__(kGT) void k_global_tile(const uint32_t* __restrict__ pts, GlobalGeom g,
+                                                     uint32_t* __restrict__ win, uint8_t* __restrict__ img_out) {
+    extern __shared__ uint32_t s_g[];
+    const int W = g.mw / 2;
+    const int Rb = g.Rb, Cb = g.Cb, tid = threadIdx.x, b = blockIdx.z;
+    const int r0 = blockIdx.y * kGTR, c0 = blockIdx.x * kGTC;
+    const int VR = kGTR + 2 * W, VC = kGTC + 2 * W;
+    const int NR = VR + 2 * H, NC = VC + 2 * H;
+    const int PR = NR + 2 * H, PC = NC + 2 * H;
+    uint32_t* sP = s_g;
+    uint32_t* sV = s_g + PR * PC;
+    uint16_t* sN = reinterpret_cast<uint16_t*>(sV + VR * VC);
+    const uint32_t* plane = pts + (size_t)b * g.plane;
+    const int pr0 = r0 - W - 2 * H, pc0 = c0 - W - 2 * H;
+    for (int idx = tid; idx < PR * PC; idx += kGT) {
+        const int lr = idx / PC, lc = idx - lr * PC;
+        const int gr = pr0 + lr, gc = pc0 + lc;
+        sP[idx] = (gr >= 0 && gr < Rb && gc >= 0 && gc < Cb) ? plane[(size_t)gr * Cb + gc] : 0u;
+    }
+    __syncthreads();
+    // counts: min(255, box sum of the points) at the reflected pixel (so that the blur below is a plain convolution);
+    // a reflected box that leaves the tile's point window reads the plane itself
+    const int nr0 = r0 - W - H, nc0 = c0 - W - H;
+    for (int idx = tid; idx < NR * NC; idx += kGT) {
+        const int lr = idx / NC, lc = idx - lr * NC;
+        const int gr = reflect101g(nr0 + lr, Rb), gc = reflect101g(nc0 + lc, Cb);
+        uint32_t acc = 0;
+        const int ar = gr - H - pr0, ac = gc - H - pc0;
+        if (ar >= 0 && ar + 2 * H < PR && ac >= 0 && ac + 2 * H < PC) {
+#pragma unroll
+            for (int da = 0; da <= 2 * H; ++da)
+#pragma unroll
+                for (int db = 0; db <= 2 * H; ++db) acc += sP[(ar + da) * PC + ac + db];
+        } else {
+            for (int da = -H; da <= H; ++da)
+                for (int db = -H; db <= H; ++db) {
+                    const int rr = gr + da, cc = gc + db;
+                    if (rr >= 0 && rr < Rb && cc >= 0 && cc < Cb) acc += plane[(size_t)rr * Cb + cc];
+                }
+        }
+        sN[idx] = (uint16_t)(acc < 255u ? acc : 255u);   // optimizer_global.cpp:27-31
+    }
+    __syncthreads();
+    // this build's 8-bit Gaussian (scale 1: none, :34-36); outside the image 0 (no event window reaches there)
+    constexpr int kTap[4][7] = {{1, 0, 0, 0, 0, 0, 0}, {1, 2, 1, 0, 0, 0, 0}, {1, 4, 6, 4, 1, 0, 0}, {2, 7, 14, 18, 14, 7, 2}};
+    constexpr int kNorm[4] = {1, 4, 16, 64};
+    constexpr int n2 = kNorm[H] * kNorm[H];
+    for (int idx = tid; idx < VR * VC; idx += kGT) {
+        const int lr = idx / VC, lc = idx - lr * VC;
+        const int gr = r0 - W + lr, gc = c0 - W + lc;
+        uint32_t pv = 0;
+        if (gr >= 0 && gr < Rb && gc >= 0 && gc < Cb) {
+            int acc = 0;
+#pragma unroll
+            for (int a = 0; a <= 2 * H; ++a) {
+                int row = 0;
+#pragma unroll
+                for (int bb = 0; bb <= 2 * H; ++bb) row += kTap[H][bb] * (int)sN[(lr + a) * NC + lc + bb];
+                acc += kTap[H][a] * row;
+            }
+            const uint32_t v = (uint32_t)((acc + n2 / 2) / n2);
+            pv = v | ((v != 0u ? 1u : 0u) << kCntShift);
+            if (img_out && lr >= W && lr < W + kGTR && lc >= W && lc < W + kGTC) img_out[(size_t)gr * Cb + gc] = (uint8_t)v;
+        }
+        sV[idx] = pv;
+    }
+    __syncthreads();
+    // window sums, separable: along the columns into P's space, then along the rows
+    uint32_t* sH = sP;
+    for (int idx = tid; idx < VR * kGTC; idx += kGT) {
+        const int lr = idx / kGTC, lc = idx - lr * kGTC;
+        uint32_t acc = 0;
+        for (int d = 0; d <= 2 * W; ++d) acc += sV[lr * VC + lc + d];
+        sH[idx] = acc;
+    }
+    __syncthreads();
+    uint32_t* out = win + (size_t)b * g.plane;
+    for (int idx = tid; idx < kGTR * kGTC; idx += kGT) {
+        const int lr = idx / kGTC, lc = idx - lr * kGTC;
+        const int gr = r0 + lr, gc = c0 + lc;
+        if (gr >= Rb || gc >= Cb) continue;
+        uint32_t acc = 0;
+        for (int d = 0; d <= 2 * W; ++d) acc += sH[(lr + d) * kGTC + lc];
+        out[(size_t)gr * Cb + gc] = acc;
+    }
+}
+
+__global__ __launch_bounds__(kGT) void k_global_fold(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
+                                                     const uint32_t* __restrict__ perm, long long n, GlobalGeom g,
+                                                     const GlobalCand* __restrict__ cands, int nb,
+                                                     const uint32_t* __restrict__ win, GlobalEventState st,
+                                                     unsigned long long* __restrict__ S, float* __restrict__ scores_out) {
+    const long long i = (long long)blockIdx.x * kGT + threadIdx.x;
+    const bool live = i < n;
+    const long long e = live ? (perm ? (long long)perm[i] : i) : 0;   // the event's upload index
+    uint32_t v = 0;
+    int32_t ti = 0;
+    double mx = 0, bnx = 0, bny = 0, bnz = 0, bpx = 0, bpy = 0;
+    if (live) {
+        v = xy[i]; ti = t[i];
+        mx = st.max_score[e]; bnx = st.best_nx[e]; bny = st.best_ny[e]; bnz = st.best_nz[e];
+        bpx = st.best_pr_x[e]; bpy = st.best_pr_y[e];
+    }
+    bool changed = false;
+    const int off = g.scale / 2 + g.mw / 2;
+    for (int b = 0; b < nb; ++b) {
+        const GlobalCand c = cands[b];
+        unsigned long long contrib = 0;
+        double pr_x, pr_y;
+        int X, Y;
+        if (live && global_pixel(g, c, v, ti, pr_x, pr_y, X, Y)) {
+            const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
+            const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
+            const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
+            const float f = (float)score;                                        // current_scores (CV_32FC1)
+            if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
+            if (scores_out) scores_out[(size_t)X * (size_t)g.sy + (size_t)Y] = f;   // the same value from every event there
+            if ((double)f > mx) {   // apply_score, event.h:113-121
+                mx = f; bnx = c.nx; bny = c.ny; bnz = c.nz; bpx = pr_x; bpy = pr_y;
+                changed = true;
+            }
+        }
+        const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
+        if ((threadIdx.x & 63) == 63 && tot) atomicAdd(&S[b], tot);
+    }
+    if (changed) {
+        st.max_score[e] = mx; st.best_nx[e] = bnx; st.best_ny[e] = bny; st.best_nz[e] = bnz;
+        st.best_pr_x[e] = bpx; st.best_pr_y[e] = bpy;
+    }
+}
+
+// Event(x, y, t) of the reference (event.h:31-35): max_score 0, best_pr = fr; best (nx, ny) = 0 (best_u / best_v 0)
+__global__ __launch_bounds__(kGT) void k_global_reset(const uint32_t* __restrict__ xy, const uint32_t* __restrict__ perm,
+                                                      long long n, GlobalEventState st) {
+    const long long i = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (i >= n) return;
+    const long long e = perm ? (long long)perm[i] : i;
+    const uint32_t v = xy[i];
+    st.max_score[e] = 0.0; st.best_nx[e] = 0.0; st.best_ny[e] = 0.0; st.best_nz[e] = 127.0;
+    st.best_pr_x[e] = (double)(v & 0xffffu); st.best_pr_y[e] = (double)(v >> 16);
+}
+
+size_t global_tile_lds(int scale, int mw) {
+    const int H = scale / 2, W = mw / 2;
+    const int VR = kGTR + 2 * W, VC = kGTC + 2 * W;
+    const int NR = VR + 2 * H, NC = VC + 2 * H;
+    const int PR = NR + 2 * H, PC = NC + 2 * H;
+    size_t p = (size_t)PR * PC;
+    const size_t hs = (size_t)VR * kGTC;
+    if (hs > p) p = hs;
+    return (p + (size_t)VR * VC) * 4 + (size_t)NR * NC * 2;
+}
+
+void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, const GlobalEventState& st, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_global_reset, dim3((unsigned)((n + kGT - 1) / kGT)), dim3(kGT), 0, s, xy, perm, n, st);
+}
+
+int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
+                        const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
+                        const GlobalEventState& st, unsigned long long* S, float* scores_out, hipStream_t s) {
+    if (nb <= 0 || n <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
+    if (g.scale / 2 > 3) return -1;
+    const unsigned eg = (unsigned)((n + kGT - 1) / kGT);
+    hipLaunchKernelGGL(k_global_project, dim3(eg, (unsigned)nb), dim3(kGT), 0, s, xy, t, n, g, cands, pts);
+    void (*k)(const uint32_t*, GlobalGeom, uint32_t*, uint8_t*) =
+        g.scale / 2 == 0 ? k_global_tile<0> : (g.scale / 2 == 1 ? k_global_tile<1> : (g.scale / 2 == 2 ? k_global_tile<2> : k_global_tile<3>));
+    const size_t lds = global_tile_lds(g.scale, g.mw);
+    if (lds > 160 * 1024) return -3;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -2;
+    const dim3 grid((unsigned)((g.Cb + kGTC - 1) / kGTC), (unsigned)((g.Rb + kGTR - 1) / kGTR), (unsigned)nb);
+    hipLaunchKernelGGL(k, grid, dim3(kGT), lds, s, pts, g, win, img_out);
+    hipLaunchKernelGGL(k_global_fold, dim3(eg), dim3(kGT), 0, s, xy, t, perm, n, g, cands, nb, win, st, S, scores_out);
+    return 0;
+}
+
+}  // namespace bf

@@ -259,6 +259,28 @@ int launch_local_tile_optimizer(const uint32_t* xy, const int32_t* t, const uint
                                 const TileGrid& g, int scale, int wsz, int guard_res_x, int guard_res_y, long long max_evaluations,
                                 hipStream_t s);
 
+// bf_global.hip -- the candidate sweep of OptimizerGlobal (optimizer_global.cpp:4-150)
+struct GlobalGeom {
+    int32_t scale, mw;        // scale, metric_wsize
+    int32_t xs, ys;           // x_min * scale, y_min * scale (an int product, as at :17-18)
+    int32_t sx, sy;           // scale_img_x / _y
+    int32_t Rb, Cb;           // scale_bordered_img_x / _y
+    long long plane;          // Rb * Cb: the stride of one candidate's planes
+};
+struct GlobalCand {
+    double nx, ny, nz;
+    float kx, ky;             // float(n) / nz of Event::apply_project (event.h:164-165)
+};
+struct GlobalEventState {     // per event, upload order
+    double *max_score, *best_nx, *best_ny, *best_nz, *best_pr_x, *best_pr_y;
+};
+size_t global_tile_lds(int scale, int mw);
+void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, const GlobalEventState& st, hipStream_t s);
+// one batch of nb candidates; `pts` must be all zero (nb planes); < 0: scale above 7 / kernel attributes / LDS
+int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
+                        const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
+                        const GlobalEventState& st, unsigned long long* S, float* scores_out, hipStream_t s);
+
 void launch_proj_count(const uint32_t* xy, const float2* p, const uint8_t* noise, long long n, int scale, int res_x,
                        int res_y, int show_final, uint32_t* plane, hipStream_t s);
 void launch_proj_scale(uint8_t* img, long long n, const unsigned long long* score, hipStream_t s);

@@ -108,6 +108,19 @@ public:
         this->size = events->size();
         this->ctx = bf::DeviceContext::get((long long)(size > 1024 ? size : 1024), nRows > 64 ? nRows : 64,
                                            nCols > 64 ? nCols : 64);
+        this->upload(events);
+    }
+
+    // The same staging on a context the caller created and owns (bf_create), which no other object uses: for state that
+    // must outlive other optimisers on the thread (OptimizerGlobal's per-event state and window).
+    template <class T> inline void init_gpu_on(bf_ctx *own, T *events) {
+        this->size = events->size();
+        this->ctx = own;
+        this->upload(events);
+    }
+
+private:
+    template <class T> inline void upload(T *events) {
         std::vector<int32_t> fx(size), fy(size), ft(size);
         std::vector<uint8_t> noise(size);
         bool any_noise = false;
@@ -127,6 +140,8 @@ public:
                                (int64_t)size), "init_gpu");
         this->staged = true;
     }
+
+public:
 
     // OptimizerRolling::set_cloud's device half: bounding box, window, Event::reset on the device.
     inline bf_window set_window(int scale) {
@@ -246,6 +261,26 @@ public:
         int rc = bf_local_run(ctx, RES_X, RES_Y, 0, st);
         check(rc, "local_run");
         return rc;
+    }
+
+    // OptimizerGlobal on the device (optimizer_global.h:27-41; optimizer_global.cpp:4-150)
+    void global_set_window(int scale, int metric_wsize, bf_global_window *w) {
+        check(bf_global_set_window(ctx, scale, metric_wsize, w), "global_set_window");
+    }
+    long long global_project_all(double nx, double ny, double nz, uint8_t *img_out, float *scores_out) {
+        int64_t sum = 0;
+        check(bf_global_project_all(ctx, nx, ny, nz, img_out, scores_out, &sum), "global_project_all");
+        return (long long)sum;
+    }
+    void global_search(const bf_global_search_opts &o, bf_global_result *r, std::vector<int64_t> *surface) {
+        int64_t *sp = nullptr;
+        int64_t cap = 0;
+        if (surface && !surface->empty()) { sp = surface->data(); cap = (int64_t)surface->size(); }
+        check(bf_global_search(ctx, &o, r, sp, cap), "global_search");
+    }
+    void global_get_events(double *max_score, double *best_nx, double *best_ny, double *best_pr_x, double *best_pr_y,
+                           double *best_u, double *best_v) {
+        check(bf_global_get_events(ctx, max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v), "global_get_events");
     }
 
     // The fused OptimizerRolling::run (optimizer_rolling.h:48-125) on the device.

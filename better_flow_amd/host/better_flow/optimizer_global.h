@@ -1,0 +1,148 @@
+// optimizer_global.h -- the exhaustive (nx, ny) search (mirror of the reference's better_flow/optimizer_global.h:11-57 and
+// optimizer_global.cpp).  Same constructors and public methods (project_all, compute_flow_bruteforce); every candidate's
+// projection, saturating 8-bit image, Gaussian blur and per-event window score run on the GPU behind bf_global_* (batches
+// of candidates per launch).  manual() (:153-185) is an OpenCV trackbar GUI and is not part of this path.
+//
+// Two definitions of this build (include/bf_accel.h, DESIGN.md "OptimizerGlobal"): each event's result is the candidate
+// that gave its largest score (best_nx, best_ny; best_u / best_v = Event::compute_uv of it), and the slice's answer is the
+// first candidate in sweep order with the largest S = sum of floor(score * 2^32).  The blur is this build's stated 8-bit
+// Gaussian, not pinned to any OpenCV.
+//
+// Each object stages its slice on a device context of its OWN (not the thread's shared one that OptimizerLocal and
+// OptimizerRolling use): the window and the per-event best state live there and accumulate over project_all /
+// compute_flow_bruteforce calls, so no other optimiser on the thread may replace them.  Objects are not copyable.
+#ifndef BF_HOST_OPTIMIZER_GLOBAL_H
+#define BF_HOST_OPTIMIZER_GLOBAL_H
+
+#include <better_flow/accel_lib.h>
+#include <better_flow/common.h>
+#include <better_flow/datastructures.h>
+#include <better_flow/event.h>
+
+#include <vector>
+
+class OptimizerGlobal {
+protected:
+    struct OwnedContext {   // bf_create'd for this object alone; released with it
+        bf_ctx *ctx = nullptr;
+        ~OwnedContext() { if (ctx) bf_destroy(ctx); }
+    };
+    LinearEventCloud *events;
+    OwnedContext own;       // (declared before accel: accel refers to it, and is gone first)
+    AccelLib accel;
+    bf::Image2D<uint8_t> project_img;
+    std::vector<float> current_scores;   // scale_img_x x scale_img_y, row-major
+
+    int scale;
+    int metric_wsize;
+    int scale_img_x, scale_img_y;
+    int scale_bordered_img_x, scale_bordered_img_y;
+
+    bf_global_search_opts range;
+    bf_global_result result;
+    std::vector<int64_t> surface;
+    long long last_sum;
+
+    void stage() {   // the slice goes to the device once; the window resets every event's best state
+        if (accel.is_staged()) return;
+        if (!own.ctx) {
+            const long long n = (long long)this->events->size();
+            int rc = bf_create(bf::DeviceContext::device(), n > 1024 ? n : 1024, 64, 64, nullptr, &own.ctx);
+            if (rc != BF_OK) {
+                own.ctx = nullptr;
+                throw bf::AccelError(rc, "OptimizerGlobal: bf_create failed (" + std::to_string(rc) + "): the search needs a "
+                                         "HIP device (there is no CPU fallback)");
+            }
+        }
+        accel.init_gpu_on(own.ctx, this->events);
+        bf_global_window w;
+        accel.global_set_window(this->scale, this->metric_wsize, &w);
+        this->scale_img_x = w.scale_img_x; this->scale_img_y = w.scale_img_y;
+        this->scale_bordered_img_x = w.scale_bordered_img_x; this->scale_bordered_img_y = w.scale_bordered_img_y;
+    }
+
+    void update_fields() {   // optimizer_global.cpp:187-205 (the device recomputes the same numbers in stage())
+        assert(this->scale % 2 != 0);
+        assert(this->metric_wsize % 2 != 0);
+        bf_global_search_opts_default(&this->range);
+        memset(&this->result, 0, sizeof(this->result));
+        this->last_sum = 0;
+        const bool empty = this->events->size() == 0;
+        this->scale_img_x = empty ? 0 : (this->events->x_max - this->events->x_min + 1) * this->scale;
+        this->scale_img_y = empty ? 0 : (this->events->y_max - this->events->y_min + 1) * this->scale;
+        this->scale_bordered_img_x = this->scale_img_x + this->metric_wsize;
+        this->scale_bordered_img_y = this->scale_img_y + this->metric_wsize;
+    }
+
+public:
+    OptimizerGlobal(const OptimizerGlobal &) = delete;
+    OptimizerGlobal &operator=(const OptimizerGlobal &) = delete;
+
+    // optimizer_global.h:27-41
+    OptimizerGlobal(LinearEventCloud *events_) : events(events_), scale(5), metric_wsize(21) { this->update_fields(); }
+    OptimizerGlobal(LinearEventCloud *events_, int sc_) : events(events_), scale(sc_), metric_wsize(5 * sc_) {
+        this->update_fields();
+    }
+    OptimizerGlobal(LinearEventCloud *events_, int sc_, int wsz_) : events(events_), scale(sc_), metric_wsize(wsz_) {
+        this->update_fields();
+    }
+
+    // optimizer_global.cpp:4-79: one candidate; project_img and current_scores are refreshed, every accepted event's
+    // best state folds in.  Returns S of the candidate.
+    long long project_all(double nx_, double ny_, double nz_ = NZ) {
+        this->stage();
+        this->project_img = bf::Image2D<uint8_t>(scale_bordered_img_x, scale_bordered_img_y);
+        this->current_scores.assign((size_t)scale_img_x * (size_t)scale_img_y, 0.0f);
+        this->last_sum = accel.global_project_all(nx_, ny_, nz_, this->project_img.ptr(0),
+                                                  this->current_scores.empty() ? nullptr : this->current_scores.data());
+        return this->last_sum;
+    }
+
+    // optimizer_global.cpp:104-150 over the search range (the reference's defaults unless set_search_range was called),
+    // continuing from the current per-event state.
+    void compute_flow_bruteforce() {
+        this->stage();
+        long long nx = 0, ny = 0;   // the candidate counts of the reference's loops (:134-135), for the surface buffer
+        if (this->range.x_step > 0 && this->range.y_step > 0) {
+            for (double v = this->range.x_low; v < this->range.x_hi && nx <= (1ll << 26); v += this->range.x_step) ++nx;
+            for (double v = this->range.y_low; v < this->range.y_hi && ny <= (1ll << 26); v += this->range.y_step) ++ny;
+        }
+        this->surface.assign(nx * ny > 0 && nx * ny <= (1ll << 26) ? (size_t)(nx * ny) : 0, 0);
+        accel.global_search(this->range, &this->result, &this->surface);
+    }
+
+    // The search range (optimizer_global.cpp:106-108 hard-codes x in [-0.09, 0.09), y in [-0.04, 0.04), step 0.001:
+    // about +-71 x +-31 px/s).
+    void set_search_range(double x_low, double x_hi, double x_step, double y_low, double y_hi, double y_step,
+                          double nz = NZ) {
+        this->range.x_low = x_low; this->range.x_hi = x_hi; this->range.x_step = x_step;
+        this->range.y_low = y_low; this->range.y_hi = y_hi; this->range.y_step = y_step;
+        this->range.nz = nz;
+    }
+
+    double get_best_nx() const { return result.best_nx; }
+    double get_best_ny() const { return result.best_ny; }
+    long long get_best_sum() const { return (long long)result.best_sum; }
+    long long get_n_x() const { return (long long)result.n_x; }
+    long long get_n_y() const { return (long long)result.n_y; }
+    long long get_last_sum() const { return last_sum; }
+    const std::vector<int64_t> &get_surface() const { return surface; }   // S per candidate, [n_x][n_y]
+    const bf::Image2D<uint8_t> &get_project_img() const { return project_img; }
+    const std::vector<float> &get_current_scores() const { return current_scores; }
+
+    // The per-event state into the cloud's Event fields: max_score, best_pr_x / _y, best_u / _v (compute_uv of the
+    // event's winning candidate).
+    void read_back() {
+        this->stage();
+        const size_t n = this->events->size();
+        std::vector<double> ms(n), px(n), py(n), u(n), v(n);
+        if (n) accel.global_get_events(ms.data(), nullptr, nullptr, px.data(), py.data(), u.data(), v.data());
+        size_t i = 0;
+        for (auto &e : *this->events) {
+            e.max_score = ms[i]; e.best_pr_x = px[i]; e.best_pr_y = py[i]; e.best_u = u[i]; e.best_v = v[i];
+            ++i;
+        }
+    }
+};
+
+#endif  // BF_HOST_OPTIMIZER_GLOBAL_H

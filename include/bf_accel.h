@@ -507,6 +507,65 @@ typedef struct bf_local_tile_opts {
 } bf_local_tile_opts;
 int bf_local_run_tiles(bf_ctx *ctx, const bf_local_tile_opts *opts, bf_local_state *states_out, int32_t *rc_out);
 
+/* ---- exhaustive search: OptimizerGlobal (optimizer_global.h:11-57, optimizer_global.cpp) ----------
+ * A sweep over a grid of (nx, ny) candidates that scores every event's neighbourhood under each one: for every
+ * candidate, Event::project of every event, the saturating scale x scale splat into the bordered 8-bit image, this build's
+ * stated 8-bit Gaussian (above: binomial taps, BORDER_REFLECT_101, exact integer sum, one rounding; NOT pinned to any
+ * OpenCV -- the reference calls cv::GaussianBlur), and per accepted event the mean of the NON-ZERO blurred pixels in the
+ * metric_wsize^2 window centred on it (get_event_score, :82-101).  apply_score (event.h:113-121) then folds that score
+ * into the event's running best, strict `>`, in candidate order.  Two definitions of this build ("OptimizerGlobal"):
+ *   - the per-event result is the winning candidate (best_nx, best_ny); best_u / best_v are Event::compute_uv of it
+ *     (event.h:135-142) -- the reference copies a u / v that apply_project never updates;
+ *   - the objective of candidate k is S(k) = sum over the events accepted under k of floor(score * 2^32), an exact int64
+ *     (computed as (sum << 32) / count); the slice's best candidate is the first in sweep order (nx outer, ny inner) with
+ *     the largest S (candidate 0 when every S is 0).
+ * Every result is bit-reproducible: integers and single IEEE operations only.  scale in {1, 3, 5, 7}; metric_wsize odd,
+ * 1..63.  Scratch is sized from the window (two 32-bit planes of the bordered image per candidate of a batch), not from
+ * bf_create's max_rows / max_cols.  The uploaded events are not moved (their projected positions are untouched). */
+typedef struct bf_global_window {       /* optimizer_global.cpp:187-205 */
+    int32_t scale, metric_wsize;
+    int32_t x_min, y_min, x_max, y_max; /* bounding box of fr_x / fr_y (empty cloud: 0, 0, -1, -1) */
+    int32_t scale_img_x, scale_img_y, scale_bordered_img_x, scale_bordered_img_y;
+} bf_global_window;
+
+typedef struct bf_global_search_opts {  /* optimizer_global.cpp:106-108 */
+    double x_low, x_hi, x_step, y_low, y_hi, y_step, nz;
+} bf_global_search_opts;
+
+typedef struct bf_global_result {
+    double best_nx, best_ny;   /* first candidate in sweep order with the largest S */
+    int64_t best_sum;          /* S(best) */
+    int64_t n_x, n_y;          /* candidates swept (180 x 80 for the defaults) */
+} bf_global_result;
+
+/* The reference's defaults: x in [-0.09, 0.09), y in [-0.04, 0.04), step 0.001, nz = NZ = 127. */
+void bf_global_search_opts_default(bf_global_search_opts *o);
+
+/* The constructors (optimizer_global.h:27-41) + update_fields over the uploaded cloud.  metric_wsize <= 0: 5 * scale.
+ * Resets every event's best state (max_score = 0, best (nx, ny) = 0, best_pr = fr).  BF_ERR_ARG for a scale outside
+ * {1, 3, 5, 7} or an even / out-of-range metric_wsize; BF_ERR_STATE before bf_upload_events. */
+int bf_global_set_window(bf_ctx *ctx, int32_t scale, int32_t metric_wsize, bf_global_window *out);
+
+/* One project_all (optimizer_global.cpp:4-79), folding into the per-event state like the reference.  Any output may be
+ * NULL: img_out (scale_bordered_img_x * scale_bordered_img_y bytes) the blurred bordered image; scores_out (float,
+ * scale_img_x * scale_img_y) current_scores; sum_out S.  BF_ERR_ARG without a window; BF_ERR_STATE when any upload (of
+ * any size, synchronous or committed asynchronous) happened since bf_global_set_window -- the same for bf_global_search and
+ * bf_global_get_events. */
+int bf_global_project_all(bf_ctx *ctx, double nx, double ny, double nz, uint8_t *img_out, float *scores_out, int64_t *sum_out);
+
+/* compute_flow_bruteforce (optimizer_global.cpp:104-150) over the grid of opts (NULL: the defaults), continuing from the
+ * current per-event state.  The host builds the candidate values by the reference's repeated double addition (for (v = lo;
+ * v < hi; v += step)).  surface_out (may be NULL) receives S of every candidate, row-major [n_x][n_y]; surface_cap is its
+ * length.  BF_ERR_ARG for a step <= 0, lo >= hi, nz <= 0, a surface buffer shorter than n_x * n_y, more than 2^26
+ * candidates, or no window. */
+int bf_global_search(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_result *out, int64_t *surface_out,
+                     int64_t surface_cap);
+
+/* Per-event state in upload order (n doubles each); any pointer may be NULL.  best_u / best_v: Event::compute_uv of the
+ * event's winning candidate (0 for an event never accepted). */
+int bf_global_get_events(bf_ctx *ctx, double *max_score, double *best_nx, double *best_ny, double *best_pr_x,
+                         double *best_pr_y, double *best_u, double *best_v);
+
 /* NUMA placement of a feeder thread (no reference counterpart: the reference is single-threaded, SURVEY 8(b) "Threading"; the
  * 8-GPU farm of SURVEY 8(e) wants one feeder thread per GPU with NUMA-local pinned buffers).
  *   bf_device_numa_node          host NUMA node of HIP device `device` (sysfs numa_node of its PCI function); -1: unknown.
