@@ -149,6 +149,7 @@ EXPORTS = [
     "bf_upload_ring_async", "bf_upload_ring16_async", "bf_upload_ring16t32_async", "bf_upload_events16_async", "bf_compute_uv_ring", "bf_wait_uploads", "bf_projection_img",
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
+    "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
 ]
 
 _lib = None
@@ -293,6 +294,17 @@ def load(path=None):
         L.bf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         L.bf_upload_events_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
         L.bf_commit_upload.argtypes = [C.c_void_p]
+        # the device-side -o table (include/bf_accel.h: bf_emit_*)
+        L.bf_emit_create.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.POINTER(C.c_void_p)]
+        L.bf_emit_destroy.argtypes = [C.c_void_p]
+        L.bf_emit_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.bf_emit_output.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint64)), C.POINTER(C.POINTER(C.c_uint16)),
+                                     C.POINTER(C.POINTER(C.c_uint16)), C.POINTER(C.POINTER(C.c_double)),
+                                     C.POINTER(C.POINTER(C.c_double)), C.POINTER(C.c_int64)]
+        L.bf_emit_slice.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, C.c_uint64, C.c_int32,
+                                    C.c_int32, C.POINTER(C.c_int64)]
+        L.bf_emit_wait.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
+        L.bf_emit_release.argtypes = [C.c_void_p, C.c_uint64]
         _libs[path] = L
         if path == LIB_PATH:
             _lib = L

@@ -242,6 +242,8 @@ struct bf_ctx {
 
 // frees what bf_global_search.cpp allocated for ctx (bf_destroy)
 void global_free(bf_ctx* c);
+// the live slice's per-event flow in upload order on the device, or null (bf_operators.cpp)
+extern "C" int ctx_device_uv(bf_ctx* c, const double2** uv);
 
 namespace {
 

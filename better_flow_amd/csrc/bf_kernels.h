@@ -298,4 +298,29 @@ void launch_color_time(const uint32_t* xy, const int32_t* t, const float2* p, co
 void launch_copy(const void* src, void* dst, long long bytes, int blocks, bool nontemporal, hipStream_t s);
 void launch_eval_sincos(const double* x, long long n, int table, double* sn, double* cs, hipStream_t s);
 
+// bf_emit.hip -- the -o table accumulated on the device (bf_emit_slice).  One slice: M = lead + n elements, element 0 the
+// lead (if any), element lead + i upload index i; every array below holds M entries.
+struct EmitSlice {
+    // the committed slice (live event set, slot order) and its flow (upload order; null: zero flow)
+    const uint32_t* xy; const int32_t* tloc; const uint32_t* perm; const double2* uv;
+    long long n; int lead;
+    unsigned long long first, cap, start_time, prev_end, last;   // ring positions / logical ns
+    unsigned long long lead_t; uint32_t lead_row, lead_col;
+    int rows, cols;
+    // persistent state: covered plane (cap bytes), per-pixel tail (rows * cols)
+    uint8_t* plane; unsigned long long *tail_t, *tail_g;
+    // scratch; sort key = pixel << jbits | element (jbits: enough bits for the elements, kbits: for the whole key)
+    unsigned long long* t; uint32_t* rc; uint8_t* flag; unsigned long long* keys; uint32_t* pos;
+    int jbits, kbits;
+    uint32_t* err;
+    // rows out: a ring of out_rows rows in pinned, device-mapped host memory (row r at r % out_rows); the slice's rows start at
+    // *off_in, and *off_out = *off_in + rows afterwards; rec[0..2] = first row, rows, error bits (pinned)
+    unsigned long long* out_t; uint16_t *out_row, *out_col; double *out_u, *out_v;
+    unsigned long long out_rows;
+    const unsigned long long* off_in; unsigned long long* off_out;
+    unsigned long long* rec;
+};
+size_t emit_temp_bytes(long long m);
+hipError_t launch_emit(const EmitSlice& a, unsigned long long* keys_sorted, void* temp, size_t temp_bytes, hipStream_t s);
+
 }  // namespace bf

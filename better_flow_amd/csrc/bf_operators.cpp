@@ -445,6 +445,25 @@ static int materialize_outputs(bf_ctx* c) {
     return BF_OK;
 }
 
+// The per-event flow of the live slice in upload order on the device, as bf_compute_uv_ring would read it back; null when
+// no warp has run (Event::reset: zero flow) or the window is degenerate.  For bf_emit_slice (bf_emit.cpp).
+int ctx_device_uv(bf_ctx* c, const double2** uv) {
+    *uv = nullptr;
+    int rc = flush_pending(c);
+    if (rc != BF_OK) return rc;
+    if (c->n == 0 || !c->n_valid || !c->have_window || c->degenerate) return BF_OK;
+    rc = materialize_outputs(c);
+    if (rc != BF_OK) return rc;
+    if (!c->uv_valid) {
+        ProfScope ps(c, 3);
+        launch_compute_uv(c->d_nxny, c->d_uv, c->n, c->stream);
+        c->uv_valid = true;
+    }
+    HIP_TRY(c, hipGetLastError());
+    *uv = c->d_uv;
+    return BF_OK;
+}
+
 static int copy_pairs(bf_ctx* c, const double2* d_src, double* a, double* b) {
     std::vector<double2> tmp((size_t)c->n);
     HIP_TRY(c, hipMemcpyAsync(tmp.data(), d_src, (size_t)c->n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));

@@ -10,6 +10,11 @@
 //           extraction (~0.4 us per value) was the slowest stage of the CLI.
 //   binary  structure-of-arrays, little endian: char magic[8] = "BFEVSOA1", u64 n, then u64 t_ns[n]
 //           (absolute), u16 x[n] (column), u16 y[n] (row), u8 p[n].  No parsing, 13 B per event.
+//
+// And one output format beside the -o text (bf_motion_compensator --outfile-bin, write_flow_binary below; Python:
+// better_flow_amd/flowio.py): the per-event flow table, little endian: char magic[8] = "BFFLSOA1", u64 n, then u64 t_ns[n]
+// (logical: the input's timestamps), u16 row[n], u16 col[n], f64 u[n], f64 v[n] (best_u, best_v).  28 B per row; a row
+// formats to the text line "t row col 1 v u" of -o.
 #ifndef BF_HOST_EVENT_READER_H
 #define BF_HOST_EVENT_READER_H
 
@@ -237,6 +242,19 @@ public:
         return std::fclose(f) == 0 && w;
     }
 };
+
+// Writes the binary flow table (BFFLSOA1, above) from the columns of a FlowTable.
+inline bool write_flow_binary(const std::string &path, const std::vector<uint64_t> &t_ns, const std::vector<uint16_t> &row,
+                              const std::vector<uint16_t> &col, const std::vector<double> &u, const std::vector<double> &v) {
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    const uint64_t n = t_ns.size();
+    bool w = row.size() == n && col.size() == n && u.size() == n && v.size() == n;
+    w = w && std::fwrite("BFFLSOA1", 1, 8, f) == 8 && std::fwrite(&n, 8, 1, f) == 1;
+    w = w && (n == 0 || (std::fwrite(t_ns.data(), 8, n, f) == n && std::fwrite(row.data(), 2, n, f) == n &&
+                         std::fwrite(col.data(), 2, n, f) == n && std::fwrite(u.data(), 8, n, f) == n && std::fwrite(v.data(), 8, n, f) == n));
+    return std::fclose(f) == 0 && w;
+}
 
 // The binary event file read column block by column block, without a copy of the whole file in memory: pread()
 // straight into the caller's arrays (for StreamEngine: into the pinned ring itself), on several threads.

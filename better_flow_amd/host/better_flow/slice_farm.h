@@ -38,6 +38,7 @@ namespace bf {
 class SliceFarm {
 public:
     enum class Warm { Cold, FromPrevious, FromModel };
+    struct Result;
 
     struct Task {
         // -- the events: a slice of a structure-of-arrays ring with 16-bit addresses (pinned memory makes the copy a
@@ -60,6 +61,11 @@ public:
         double *uv_ring = nullptr;
         int64_t uv_cap = 0, uv_first = 0;
         uint64_t user = 0;                               // passed through to the result
+        // -- called on the worker right after the solve, with the slice still on its context, for every task (failed ones
+        // too); may fail the result by setting rc < 0 and error.  want_uv: bf_run writes the per-event flow on the device even
+        // without uv_ring (the hook reads it there).
+        std::function<void(bf_ctx *, Result &)> on_solved;
+        bool want_uv = false;
     };
 
     struct Result {
@@ -251,7 +257,7 @@ private:
             if (rc < 0) return fail(rc, "set_model");
             bf_run_opts o;
             bf_run_opts_default(&o);
-            o.max_iter = t.max_iter; o.res_x = t.res_x; o.res_y = t.res_y; o.want_uv = t.uv_ring ? 1 : 0;
+            o.max_iter = t.max_iter; o.res_x = t.res_x; o.res_y = t.res_y; o.want_uv = (t.uv_ring || t.want_uv) ? 1 : 0;
             rc = bf_run(wk.ctx, &o, &r.model, &r.info);
             if (rc < 0) return fail(rc, "run");
             r.rc = rc;
@@ -319,6 +325,7 @@ private:
             Staged s = staged.front();
             staged.pop_front();
             Result r = solve(wk, s);
+            if (s.task.on_solved) s.task.on_solved(wk.ctx, r);
             const bool restage = chained_ && r.window_guard;
             publish(std::move(r));
             if (restage) {

@@ -18,7 +18,11 @@
 //     slice k is being solved and slice k + 1 uploaded (an STM chain stays sequential on one worker); with
 //     --stm-disable style independent slices, several workers / GPUs take them in parallel.  Results are applied in
 //     slice order either way;
-//   * per-event flow comes back only if asked for (set_want_flow / set_accumulate), straight into a pinned (u, v) ring.
+//   * per-event flow comes back only if asked for (set_want_flow / set_accumulate), straight into a pinned (u, v) ring;
+//   * set_accumulate_device: the same table as get_accumulated(), built on the device slice by slice (bf_emit_slice) --
+//     no per-slice flow block, no history, no walk at the end; memory grows with the output rows only.  The solving worker
+//     only enqueues the emit kernels; they store the rows in a pinned output ring, and deliver() -- in slice order, after
+//     the solve -- waits for them and moves the rows into blocks of the table.
 //
 // Semantics: those of DVS_flow, element for element --
 //   * ring of at most MAX_SZ events spanning at most SPAN ns (push_back :31-44, fix_span :46-59);
@@ -42,7 +46,21 @@
 #include <better_flow/object_model.h>
 #include <better_flow/slice_farm.h>
 
+#include <algorithm>
 #include <memory>
+
+// (weak: the host classes also link against C-ABI implementations that lack the device-side table -- the CPU stand-in the
+// tests build -- and set_accumulate_device then fails at warm-up)
+extern "C" {
+int bf_emit_create(bf_ctx *ctx, int64_t ring_cap, int32_t rows, int32_t cols, int64_t out_rows, bf_emit **out) __attribute__((weak));
+int bf_emit_destroy(bf_emit *emit) __attribute__((weak));
+int bf_emit_output(bf_emit *emit, uint64_t **t, uint16_t **row, uint16_t **col, double **u, double **v, int64_t *out_rows)
+    __attribute__((weak));
+int bf_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
+                  int32_t lead_row, int32_t lead_col, int64_t *ticket_out) __attribute__((weak));
+int bf_emit_wait(bf_ctx *ctx, bf_emit *emit, int64_t ticket, uint64_t *first_row, int64_t *rows) __attribute__((weak));
+int bf_emit_release(bf_emit *emit, uint64_t upto_row) __attribute__((weak));
+}
 
 namespace bf {
 
@@ -103,6 +121,7 @@ public:
             if (col_) (void)bf_host_free(c, col_);
             if (noise) (void)bf_host_free(c, noise);
             if (uv) (void)bf_host_free(c, uv);
+            if (emit_state && bf_emit_destroy) (void)bf_emit_destroy(emit_state);
         }
         farm.reset();
     }
@@ -115,6 +134,12 @@ public:
     void set_stm_disable(bool v = true) { stm_disable = v; }
     void set_want_flow(bool v = true) { want_flow = v; }     // fetch per-event (u, v) after every slice
     void set_accumulate(bool v = true) { accumulate = v; }   // keep every slice's events + flow for get_accumulated()
+    // build get_accumulated()'s table on the device as the slices are solved (get_accumulated_device).  Needs non-decreasing
+    // timestamps (set_assume_sorted, the default), a span below 2^31 ns (the device keeps slice-local times as int32), every
+    // worker on one device (the covered state lives there; the workers enqueue their slices in slice order) and every event
+    // on the RES_X x RES_Y sensor (an address outside it fails the run; get_accumulated takes any 16-bit address).
+    // Independent of set_accumulate: both may be on.
+    void set_accumulate_device(bool v = true) { accumulate_device = v; }
     void set_pipelined(bool v = true) { pipelined = v; }     // add_event(s) return at the trigger; drain() waits
     void set_assume_sorted(bool v = true) { assume_sorted = v; }
     void set_time_base(ull t) { time_base = t; }             // ring timestamps are absolute; logical time = timestamp - base
@@ -276,6 +301,19 @@ public:
         t.t0 = p.start_time + time_base;
         t.scale = scale; t.res_x = RES_X; t.res_y = RES_Y; t.max_iter = max_iter;
         t.warm = stm_disable ? SliceFarm::Warm::Cold : SliceFarm::Warm::FromPrevious;
+        if (accumulate_device) {
+            // (the lead: the ring's oldest element, left out of a full ring's slice, that no slice has held -- as Kept::lead)
+            const bool lead = p.full && oldest + 1 > last_trigger_plus1;
+            const size_t ls = (size_t)(oldest % cap);
+            const ull lt = lead ? logical(oldest) : 0;
+            const int lr = lead ? row_[ls] : 0, lc = lead ? col_[ls] : 0;
+            const uint64_t idx = p.index, first = p.first, n = p.n;
+            const ull st = p.start_time;
+            t.want_uv = true;
+            t.on_solved = [this, idx, first, n, st, lead, lt, lr, lc](bf_ctx *ctx, SliceFarm::Result &r) {
+                emit_slice(idx, ctx, r, first, n, st, lead, lt, lr, lc);
+            };
+        }
         if ((accumulate || (want_flow && farm->workers() > 1)) && p.n > 0) {
             // A private block per slice, copied into the ring by deliver() -- which runs in SLICE order.  Needed for
             // get_accumulated(), and whenever several workers solve overlapping slices at once: written straight into
@@ -338,6 +376,39 @@ public:
     // rare occasions another event; marked events are left out.  An event whose slice-local time is exactly -1 counts
     // as marked from the start (the reference uses t == -1 as the mark).
     FlowTable get_accumulated();
+    // The same table, element for element, from the device (set_accumulate_device); drains first.
+    FlowTable get_accumulated_device() {
+        drain();
+        std::lock_guard<std::mutex> g(emit_mu);
+        FlowTable out;
+        out.timestamp.resize(dev_rows); out.row.resize(dev_rows); out.col.resize(dev_rows); out.u.resize(dev_rows); out.v.resize(dev_rows);
+        size_t at = 0;
+        for (const RowBlock &b : dev_blocks) {
+            std::memcpy(out.timestamp.data() + at, b.t.get(), b.n * 8);
+            std::memcpy(out.row.data() + at, b.row.get(), b.n * 2);
+            std::memcpy(out.col.data() + at, b.col.get(), b.n * 2);
+            std::memcpy(out.u.data() + at, b.u.get(), b.n * 8);
+            std::memcpy(out.v.data() + at, b.v.get(), b.n * 8);
+            at += b.n;
+        }
+        return out;
+    }
+    // The same table written straight from its blocks as the binary flow file (BFFLSOA1, event_reader.h); drains first.
+    bool write_accumulated_device_binary(const std::string &path) {
+        drain();
+        std::lock_guard<std::mutex> g(emit_mu);
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) return false;
+        const uint64_t n = dev_rows;
+        bool w = std::fwrite("BFFLSOA1", 1, 8, f) == 8 && std::fwrite(&n, 8, 1, f) == 1;
+        for (const RowBlock &b : dev_blocks) w = w && std::fwrite(b.t.get(), 8, b.n, f) == b.n;
+        for (const RowBlock &b : dev_blocks) w = w && std::fwrite(b.row.get(), 2, b.n, f) == b.n;
+        for (const RowBlock &b : dev_blocks) w = w && std::fwrite(b.col.get(), 2, b.n, f) == b.n;
+        for (const RowBlock &b : dev_blocks) w = w && std::fwrite(b.u.get(), 8, b.n, f) == b.n;
+        for (const RowBlock &b : dev_blocks) w = w && std::fwrite(b.v.get(), 8, b.n, f) == b.n;
+        return std::fclose(f) == 0 && w;
+    }
+    size_t rows_accumulated_device() { std::lock_guard<std::mutex> g(emit_mu); return dev_rows; }
 
 protected:
     struct Pending {
@@ -397,6 +468,86 @@ protected:
     std::vector<uint64_t> hist_ts;           // logical timestamps of every event seen
     std::vector<uint16_t> hist_row, hist_col;
     std::vector<Kept> kept;
+    // accumulate_device
+    struct RowBlock {             // one slice's rows (uninitialised storage: every element is written)
+        size_t n = 0;
+        std::unique_ptr<uint64_t[]> t;
+        std::unique_ptr<uint16_t[]> row, col;
+        std::unique_ptr<double[]> u, v;
+    };
+    bool accumulate_device = false;
+    bf_emit *emit_state = nullptr;
+    std::mutex emit_mu;                      // enqueueing in slice order; the blocks
+    std::condition_variable emit_cv;
+    uint64_t emit_turn = 0;                  // index of the next slice to enqueue
+    std::deque<int64_t> emit_tickets;        // per slice enqueued, in slice order: its ticket (-1: nothing emitted)
+    uint64_t emit_released = 0;              // rows of the output ring read so far
+    std::vector<RowBlock> dev_blocks;
+    size_t dev_rows = 0;
+
+    // the emit step of slice `idx`, on the worker that solved it (SliceFarm::Task::on_solved): enqueue only
+    void emit_slice(uint64_t idx, bf_ctx *ctx, SliceFarm::Result &r, uint64_t first, uint64_t n, ull start, bool lead, ull lead_t,
+                    int lead_row, int lead_col) {
+        std::unique_lock<std::mutex> g(emit_mu);
+        emit_cv.wait(g, [&] { return emit_turn == idx; });
+        int64_t ticket = -1;
+        if (r.rc >= 0 && n + (lead ? 1 : 0) > 0) {
+            for (;;) {
+                const int rc = bf_emit_slice(ctx, emit_state, (int64_t)n, first, start, lead ? 1 : 0, lead_t, lead_row, lead_col, &ticket);
+                if (rc == BF_ERR_CAPACITY && emit_tickets.size() > 0) {   // the output ring holds rows not read yet: wait for deliver()
+                    const uint64_t seen = emit_released;
+                    const size_t waiting = emit_tickets.size();
+                    emit_cv.wait(g, [&] { return emit_released != seen || emit_tickets.size() != waiting; });
+                    continue;
+                }
+                if (rc < 0) { r.rc = rc; r.error = std::string("SliceFarm: emit failed (") + std::to_string(rc) + "): " + bf_last_error(ctx); ticket = -1; }
+                break;
+            }
+        }
+        emit_tickets.push_back(ticket);
+        ++emit_turn;
+        g.unlock();
+        emit_cv.notify_all();
+    }
+
+    // deliver(), in slice order: the slice's rows out of the output ring into a block of the table
+    void collect_rows(bf_ctx *ctx, uint64_t index) {
+        int64_t ticket;
+        {
+            std::lock_guard<std::mutex> g(emit_mu);
+            ticket = emit_tickets.front();
+        }
+        RowBlock b;
+        uint64_t first_row = 0;
+        int64_t rows = 0;
+        int rc = BF_OK;
+        if (ticket >= 0 && (rc = bf_emit_wait(ctx, emit_state, ticket, &first_row, &rows)) == BF_OK && rows > 0) {
+            uint64_t *rt; uint16_t *rr, *rcol; double *ru, *rv; int64_t R;
+            (void)bf_emit_output(emit_state, &rt, &rr, &rcol, &ru, &rv, &R);
+            b.n = (size_t)rows;
+            b.t.reset(new uint64_t[b.n]); b.row.reset(new uint16_t[b.n]); b.col.reset(new uint16_t[b.n]);
+            b.u.reset(new double[b.n]); b.v.reset(new double[b.n]);
+            const size_t s0 = (size_t)(first_row % (uint64_t)R), n0 = b.n < (size_t)R - s0 ? b.n : (size_t)R - s0;
+            auto two = [&](void *dst, const void *src, size_t el) {
+                std::memcpy(dst, (const char *)src + s0 * el, n0 * el);
+                std::memcpy((char *)dst + n0 * el, src, (b.n - n0) * el);
+            };
+            two(b.t.get(), rt, 8); two(b.row.get(), rr, 2); two(b.col.get(), rcol, 2); two(b.u.get(), ru, 8); two(b.v.get(), rv, 8);
+            (void)bf_emit_release(emit_state, first_row + (uint64_t)rows);
+        }
+        {
+            std::lock_guard<std::mutex> g(emit_mu);
+            emit_tickets.pop_front();
+            if (rc < 0) {
+                if (!failed) { fail_code = rc; fail_text = "StreamEngine: slice " + std::to_string(index) + ": emit: " + bf_last_error(ctx); failed = true; }
+            } else if (b.n) {
+                dev_rows += b.n;
+                emit_released += b.n;
+                dev_blocks.push_back(std::move(b));
+            }
+        }
+        emit_cv.notify_all();
+    }
 
     static uint16_t narrow(uint32_t v) {
         if (v > 65535u) throw AccelError(BF_ERR_ARG, "StreamEngine: event address " + std::to_string(v) + " does not fit 16 bits");
@@ -457,6 +608,13 @@ protected:
                                  [this](const SliceFarm::Result &r) { deliver(r); }, chained));
         size_t extra = lookahead ? lookahead : (2 * max_sz > 65536 ? 2 * max_sz : 65536);   // the producer may run two slices ahead
         cap = max_sz + extra;
+        if (accumulate_device) {
+            if (!assume_sorted) throw AccelError(BF_ERR_ARG, "StreamEngine: the device-accumulated table needs non-decreasing timestamps (set_assume_sorted)");
+            if (span >= (sll)INT_MAX)
+                throw AccelError(BF_ERR_ARG, "StreamEngine: the device-accumulated table needs a span below 2^31 ns (slice-local times are int32 on the device)");
+            for (int d : devices)
+                if (d != devices[0]) throw AccelError(BF_ERR_ARG, "StreamEngine: the device-accumulated table needs every context on one device");
+        }
         for (size_t w = 0; w < farm->workers(); ++w) (void)bf_set_option(farm->context(w), "stream_prealloc", 1);   // staging slots, copy stream: now, not at the first slice
         bf_ctx *c = farm->context(0);
         void *p = nullptr;   // (pinned host memory is not tied to the ctx object)
@@ -471,6 +629,12 @@ protected:
         noise = (uint8_t *)alloc(cap);
         std::memset(noise, 0, cap);
         if (want_flow_any()) { uv = (double *)alloc(cap * 16); std::memset(uv, 0, cap * 16); }
+        if (accumulate_device) {
+            if (!bf_emit_create) throw AccelError(BF_ERR_STATE, "StreamEngine: this C-ABI library has no device-side flow table (bf_emit_create)");
+            // (the output ring: a slice emits at most max_sz + 1 rows, and rows wait there only until their slice is delivered)
+            const int rc = bf_emit_create(c, (int64_t)cap, RES_X, RES_Y, (int64_t)cap, &emit_state);
+            if (rc < 0) throw AccelError(rc, std::string("StreamEngine: bf_emit_create failed: ") + bf_last_error(c));
+        }
     }
 
     void archive(uint64_t g, uint64_t end) {   // (two contiguous pieces of the ring, appended in bulk)
@@ -527,6 +691,7 @@ protected:
             }
             if (p.zero_excluded && uv) { const size_t s = (size_t)((p.first - 1) % cap); uv[2 * s] = uv[2 * s + 1] = 0.0; }
         }
+        if (accumulate_device) collect_rows(farm->context((size_t)r.worker), p.index);
         SliceRecord rec;
         rec.index = p.index; rec.first_event = p.first; rec.events = p.n; rec.ring_size = p.ring_size; rec.new_events = p.new_events;
         rec.start_time = p.start_time; rec.trigger_time = p.trigger_time; rec.time_diff = p.time_diff;

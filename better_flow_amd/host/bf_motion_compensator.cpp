@@ -38,6 +38,8 @@ struct Options {
     int video_fps = 60;
     int scale = 3, max_iter = -1;
     std::string input, output, to_bin, slice_log;
+    std::string output_bin;                // --outfile-bin: the -o table as a binary file, accumulated on the device
+    bool have_output_bin = false;
     std::vector<std::string> more_inputs;  // further recordings: each is a stream of its own
     bool have_input = false, have_output = false;
     // the event ring (EVENT_WIDTH / TIME_WIDTH of the reference, bf_motion_compensator.cpp:6-7)
@@ -106,6 +108,10 @@ const std::vector<Flag> &flag_table() {
         {"-o", Arg::Next, [](Options &o, const char *v) { o.output = v; o.have_output = true; }, "<file>",
          "write every event with its flow: \"t x y 1 v u\""},
         {"--outfile", Arg::Inline, [](Options &o, const char *v) { o.output = v; o.have_output = true; }, "<file>", "same as -o"},
+        {"--outfile-bin", Arg::Inline, [](Options &o, const char *v) { o.output_bin = v; o.have_output_bin = true; }, "<file>",
+         "write the -o table as a binary file (BFFLSOA1: u64 t, u16 row, u16 col, f64 u, f64 v columns), built on the device "
+         "as the slices are solved; with -o, the text comes from the same table (stream engine; every event on the "
+         "--res-x x --res-y sensor, --span below 2.147 s)"},
         {"--res-x", Arg::Inline, [](Options &, const char *v) { bf::sensor().res_x = atoi(v); }, "<rows>", "sensor rows"},
         {"--res-y", Arg::Inline, [](Options &, const char *v) { bf::sensor().res_y = atoi(v); }, "<columns>", "sensor columns"},
         {"--scale", Arg::Inline, [](Options &o, const char *v) { o.scale = atoi(v); }, "<odd>", "image scale of the minimizer"},
@@ -194,6 +200,11 @@ int parse(int argc, char **argv, Options &o) {
     const bool needs_ring = o.frames || o.video || o.interactive;
     if (o.engine.empty()) o.engine = needs_ring ? "ring" : "stream";
     if (o.engine == "stream" && needs_ring) { std::fprintf(stderr, "--img / --video / -i work on the reference ring: drop --engine=stream\n"); return 1; }
+    if (o.have_output_bin && o.output_bin.empty()) { std::fprintf(stderr, "--outfile-bin needs a file name: --outfile-bin=<file>\n"); return 1; }
+    if (o.engine == "ring" && o.have_output_bin) {
+        std::fprintf(stderr, "--outfile-bin belongs to the stream engine (the reference ring writes only the -o text)\n");
+        return 1;
+    }
     if (o.engine == "ring" && (o.ring_flags || !o.devices.empty() || o.contexts != 1)) {
         std::fprintf(stderr, "--max-events / --span / --devices / --contexts belong to the stream engine (the reference ring is compiled for %zu events, %g s, one device)\n",
                      kMaxEvents, kMaxSpanSec);
@@ -309,7 +320,8 @@ int run_stream(const Options &o) {
     engine.set_max_iter(o.max_iter);
     engine.set_stm_disable(o.stm_disable);
     engine.set_want_flow(false);                       // per-event flow only travels back for -o
-    if (o.have_output) engine.set_accumulate();
+    if (o.have_output_bin) engine.set_accumulate_device();   // (-o then writes the same table)
+    else if (o.have_output) engine.set_accumulate();
     engine.set_pipelined(!o.sync && !o.bufferize);
     if (!o.devices.empty() || o.contexts > 1)
         engine.set_devices(o.devices.empty() ? std::vector<int>{bf::DeviceContext::device()} : o.devices, o.contexts);
@@ -388,7 +400,32 @@ int run_stream(const Options &o) {
     const double s_steady = engine.get_slices_done() > 1 ? seconds_since(t_first_slice) : 0.0;
 
     const auto t_out = std::chrono::steady_clock::now();
-    if (o.have_output) {
+    double s_output_bin = 0.0;
+    if (o.have_output_bin) {
+        const auto t_bin = std::chrono::steady_clock::now();
+        if (!o.have_output) {   // the binary file alone: straight from the table's blocks
+            if (!engine.write_accumulated_device_binary(o.output_bin)) {
+                std::fprintf(stderr, "cannot write '%s'\n", o.output_bin.c_str());
+                return 1;
+            }
+            s_output_bin = seconds_since(t_bin);
+            if (!o.quiet) std::cout << "Written " << engine.rows_accumulated_device() << " events to " << o.output_bin << std::endl;
+        } else {
+            bf::FlowTable all = engine.get_accumulated_device();
+            if (!bf::write_flow_binary(o.output_bin, all.timestamp, all.row, all.col, all.u, all.v)) {
+                std::fprintf(stderr, "cannot write '%s'\n", o.output_bin.c_str());
+                return 1;
+            }
+            s_output_bin = seconds_since(t_bin);
+            if (!o.quiet) std::cout << "Written " << all.size() << " events to " << o.output_bin << std::endl;
+            std::cout << "Writing events and flow to file... (" << o.output << ")" << std::endl;
+            if (!bf::write_flow_text(o.output, all.timestamp, all.row, all.col, all.u, all.v, o.parse_threads)) {
+                std::fprintf(stderr, "cannot write '%s'\n", o.output.c_str());
+                return 1;
+            }
+            std::cout << "Written " << all.size() << " events, finished" << std::endl;
+        }
+    } else if (o.have_output) {
         if (!o.quiet) std::cout << "Aggregating events into one cloud...\n";
         bf::FlowTable all = engine.get_accumulated();
         if (!o.quiet) std::cout << "Final buffer contains " << all.size() << " events." << std::endl;
@@ -406,10 +443,10 @@ int run_stream(const Options &o) {
     if (o.timing)
         std::fprintf(stderr, "{\"engine\": \"stream\", \"events\": %llu, \"slices\": %llu, \"iterations\": %llu, \"init_s\": %.6f, "
                              "\"stream_s\": %.6f, \"read_s\": %.6f, \"blocked_s\": %.6f, \"output_s\": %.6f, \"total_s\": %.6f, \"mevents_per_s\": %.3f, "
-                             "\"steady_s\": %.6f, \"steady_mevents_per_s\": %.3f}\n",
+                             "\"steady_s\": %.6f, \"steady_mevents_per_s\": %.3f, \"output_bin_s\": %.6f}\n",
                      n_events, (unsigned long long)engine.get_slices_done(), (unsigned long long)engine.get_iterations_total(), s_init,
                      s_stream, s_read, engine.seconds_blocked(), s_output, seconds_since(t_start), s_stream > 0 ? n_events / s_stream * 1e-6 : 0.0,
-                     s_steady, s_steady > 0 ? (n_events - events_first_slice) / s_steady * 1e-6 : 0.0);
+                     s_steady, s_steady > 0 ? (n_events - events_first_slice) / s_steady * 1e-6 : 0.0, s_output_bin);
     if (slice_log) std::fclose(slice_log);
     return 0;
 }
@@ -434,6 +471,7 @@ int run_streams(const Options &o) {
             oi.devices = std::vector<int>{devs[i % devs.size()]};
             oi.contexts = 1;
             if (o.have_output) oi.output = o.output + "." + std::to_string(i);
+            if (o.have_output_bin) oi.output_bin = o.output_bin + "." + std::to_string(i);
             if (!o.slice_log.empty()) oi.slice_log = o.slice_log + "." + std::to_string(i);
             try {
                 rc[i] = run_stream(oi);

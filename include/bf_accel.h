@@ -566,6 +566,44 @@ int bf_global_search(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_r
 int bf_global_get_events(bf_ctx *ctx, double *max_score, double *best_nx, double *best_ny, double *best_pr_x,
                          double *best_pr_y, double *best_u, double *best_v);
 
+/* ---- per-event flow table on the device: DVS_flow::get_accumulated (dvs_flow.h:351-389) -----------------------------
+ * The -o table (every event once, with the flow of the first slice that solved it) built slice by slice on the device,
+ * with the marking rule of bf::StreamEngine::get_accumulated (stream_flow.h), for slices cut from one event ring whose
+ * timestamps do not decrease.  A bf_emit holds what carries from slice to slice: a covered byte per ring position
+ * (ring_cap of them: event g lives at g % ring_cap), per pixel of a rows x cols sensor the newest timestamp at which an
+ * emitted event can still mark later arrivals, and the running row count.  Every event of an emitted slice must lie on that
+ * sensor.  The rows go to an output ring of out_rows rows in pinned host memory that the state owns (bf_emit_output: five
+ * column arrays, row r at index r % out_rows), written by the device directly.  The state lives on the device of the context
+ * it was created with; any context on that device may emit into it.
+ *   bf_emit_create   state for a ring of ring_cap positions (>= the largest slice + 1) and a rows x cols sensor.
+ *   bf_emit_reset    forget every slice and every row (a new stream).  Waits for the slices in flight.
+ *   bf_emit_slice    ENQUEUES the rows of one solved slice on ctx's stream, solving nothing, and returns at once with a ticket
+ *                    (0, 1, 2, ...).  n events = the context's committed slice (n == 0: an empty slice, the context is not
+ *                    read), the oldest at ring position `first`; start_time its origin in the timestamps' units (an event
+ *                    with timestamp start_time - 1 carries the reference's t == -1 mark and is left out); lead != 0: event
+ *                    first - 1, which the full ring left out of the slice and no slice has held, is emitted first with zero
+ *                    flow (its logical timestamp and address in lead_t / lead_row / lead_col).  Slices run on the device in
+ *                    the order of these calls, whatever contexts they come from (the caller makes the calls in slice order,
+ *                    one at a time); a context may start its next upload at once.  The flow is what bf_compute_uv_ring reads
+ *                    back (zero when no warp ran).  BF_ERR_CAPACITY when the slice's n + (lead != 0) rows might not fit the
+ *                    output ring beside the rows not yet released, or 1024 slices wait -- checked first: nothing runs and the
+ *                    state is unchanged.  BF_ERR_ARG for a slice starting before the previous one or more elements than
+ *                    ring_cap; BF_ERR_STATE when n is not the context's slice.  *ticket_out = -1 for a slice without elements.
+ *   bf_emit_wait     waits for slice `ticket` (tickets in order) and gives its rows: [*first_row, *first_row + *rows) of the
+ *                    output ring, oldest -> newest.  BF_ERR_ARG if an address lay outside the sensor (then the state is
+ *                    undefined until bf_emit_reset).
+ *   bf_emit_release  the rows below upto_row have been read: their ring space may be reused.
+ * The kernels are in bf_emit.hip; DESIGN.md, "Device-side -o table", states the rule and why the device form is exact. */
+typedef struct bf_emit bf_emit;
+int bf_emit_create(bf_ctx *ctx, int64_t ring_cap, int32_t rows, int32_t cols, int64_t out_rows, bf_emit **out);
+int bf_emit_destroy(bf_emit *emit);
+int bf_emit_reset(bf_ctx *ctx, bf_emit *emit);
+int bf_emit_output(bf_emit *emit, uint64_t **t, uint16_t **row, uint16_t **col, double **u, double **v, int64_t *out_rows);
+int bf_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
+                  int32_t lead_row, int32_t lead_col, int64_t *ticket_out);
+int bf_emit_wait(bf_ctx *ctx, bf_emit *emit, int64_t ticket, uint64_t *first_row, int64_t *rows);
+int bf_emit_release(bf_emit *emit, uint64_t upto_row);
+
 /* NUMA placement of a feeder thread (no reference counterpart: the reference is single-threaded, SURVEY 8(b) "Threading"; the
  * 8-GPU farm of SURVEY 8(e) wants one feeder thread per GPU with NUMA-local pinned buffers).
  *   bf_device_numa_node          host NUMA node of HIP device `device` (sysfs numa_node of its PCI function); -1: unknown.
