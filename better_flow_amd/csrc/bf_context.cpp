@@ -53,12 +53,8 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
     int rc = [&]() -> int {
         HIP_TRY(c, hipSetDevice(device));
         (void)hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, device);
-        if (hip_stream) {
-            c->stream = (hipStream_t)hip_stream;
-        } else {
-            HIP_TRY(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-            c->own_stream = true;
-        }
+        if (hip_stream) c->stream.borrow((hipStream_t)hip_stream);
+        else HIP_TRY(c, c->stream.create(hipStreamNonBlocking));
         const long long gran = (long long)kThreads * kEvPerThread;
         c->cap_events = ((long long)max_events + gran - 1) / gran * gran;
         c->cap_px = (size_t)max_rows * (size_t)max_cols;
@@ -67,36 +63,32 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
         // a window with the same pixel count but another aspect ratio can need more tiles
         c->cap_blocks = gx * gy * 2 + 64;
         const size_t ne = (size_t)c->cap_events;
-        HIP_TRY(c, hipMalloc(&c->set[0].xy, ne * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->set[0].t, ne * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->set[0].p, ne * sizeof(float2)));
-        HIP_TRY(c, hipMalloc(&c->d_noise, ne));
-        HIP_TRY(c, hipMalloc(&c->d_in_x, ne * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_in_y, ne * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_in_t, ne * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_nxny, ne * sizeof(double2)));
-        HIP_TRY(c, hipMalloc(&c->d_uv, ne * sizeof(double2)));
-        for (int i = 0; i < 2; ++i)
-            HIP_TRY(c, hipMalloc(&c->d_plane[i], c->cap_px * sizeof(unsigned long long)));
-        HIP_TRY(c, hipMalloc(&c->d_time, c->cap_px * sizeof(float)));
-        HIP_TRY(c, hipMalloc(&c->d_gx, c->cap_px * sizeof(float)));
-        HIP_TRY(c, hipMalloc(&c->d_gy, c->cap_px * sizeof(float)));
-        HIP_TRY(c, hipMalloc(&c->d_img, c->cap_px * sizeof(float)));
-        HIP_TRY(c, hipMalloc(&c->d_count, c->cap_px * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_acc, (3 * kAccGroups + 1) * sizeof(MomentAcc)));
+        HIP_TRY(c, c->set[0].xy.grow(ne));
+        HIP_TRY(c, c->set[0].t.grow(ne));
+        HIP_TRY(c, c->set[0].p.grow(ne));
+        HIP_TRY(c, c->d_noise.grow(ne));
+        HIP_TRY(c, c->d_in_x.grow(ne));
+        HIP_TRY(c, c->d_in_y.grow(ne));
+        HIP_TRY(c, c->d_in_t.grow(ne));
+        HIP_TRY(c, c->d_nxny.grow(ne));
+        HIP_TRY(c, c->d_uv.grow(ne));
+        for (int i = 0; i < 2; ++i) HIP_TRY(c, c->d_plane[i].grow(c->cap_px));
+        for (DevArray<float>* a : {&c->d_time, &c->d_gx, &c->d_gy, &c->d_img}) HIP_TRY(c, a->grow(c->cap_px));
+        HIP_TRY(c, c->d_count.grow(c->cap_px));
+        HIP_TRY(c, c->d_acc.grow(3 * kAccGroups + 1));
         HIP_TRY(c, hipMemsetAsync(c->d_acc, 0, (3 * kAccGroups + 1) * sizeof(MomentAcc), c->stream));
-        HIP_TRY(c, hipMalloc(&c->d_ovf, 3 * kOvfSlotWords * sizeof(uint32_t)));   // (three slots of 17 lines: bf_device_fns.h)
+        HIP_TRY(c, c->d_ovf.grow(3 * kOvfSlotWords));   // (three slots of 17 lines: bf_device_fns.h)
         HIP_TRY(c, hipMemsetAsync(c->d_ovf, 0, 3 * kOvfSlotWords * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMalloc(&c->d_state, 2 * sizeof(DevState)));
-        HIP_TRY(c, hipMalloc(&c->d_ticket, 16 * 64 * sizeof(unsigned int)));   // 1 + 32 counters, 64 B apart
+        HIP_TRY(c, c->d_state.grow(2));
+        HIP_TRY(c, c->d_ticket.grow(16 * 64));   // 1 + 32 counters, 64 B apart
         HIP_TRY(c, hipMemsetAsync(c->d_ticket, 0, 16 * 64 * sizeof(unsigned int), c->stream));
 
-        HIP_TRY(c, hipHostMalloc(&c->h_state, 2 * sizeof(DevState) + 64, hipHostMallocDefault));
         // (behind the two snapshots: the sequence word a warm start's k_finish_update stores AFTER its snapshot -- bf_run.cpp)
-        c->h_seq = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->h_state) + 2 * sizeof(DevState));
+        HIP_TRY(c, c->h_state.grow(3));
+        c->h_seq = reinterpret_cast<unsigned long long*>(c->h_state.get() + 2);
         *c->h_seq = 0ull;
-        for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventCreateWithFlags(&c->poll_ev[i], hipEventDisableTiming));
-        HIP_TRY(c, hipHostMalloc(&c->h_stats, kPrepBlocks * sizeof(SliceStats), hipHostMallocDefault));
+        for (int i = 0; i < 2; ++i) HIP_TRY(c, c->poll_ev[i].create(hipEventDisableTiming));
+        HIP_TRY(c, c->h_stats.grow(kPrepBlocks));
         c->d_stats = c->h_stats;   // k_prepare writes its per-work-group records straight into pinned host memory: no copy command
         HIP_TRY(c, hipMemsetAsync(c->d_state, 0, 2 * sizeof(DevState), c->stream));
         // Test hooks and the phase-stamp dump exist only in the debug / timeline builds (`make debug`: debug/libbf_accel.so,
@@ -118,7 +110,7 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
 #ifdef BF_TIMELINE
         c->tl_path = getenv("BF_TIMELINE");
         if (c->tl_path && *c->tl_path) {
-            HIP_TRY(c, hipMalloc(&c->d_tl, 3 * 64 * 2 * 16 * sizeof(unsigned long long)));
+            HIP_TRY(c, c->d_tl.grow(3 * 64 * 2 * 16));
             HIP_TRY(c, hipMemsetAsync(c->d_tl, 0, 3 * 64 * 2 * 16 * sizeof(unsigned long long), c->stream));
         }
 #endif
@@ -167,11 +159,15 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
     return BF_OK;
 }
 
+// Teardown in one order: uncount, device, wait for BOTH streams (early staging writes the slots' arrays and pinned records on the
+// copy stream), drop uploads that were only recorded, dump the debug timeline; the handles then free everything.
 void bf_destroy(bf_ctx* c) {
     if (!c) return;
     if (c->counted) g_live_ctx[c->device & 63].fetch_sub(1);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    for (auto& f : c->deferred) f = nullptr;
     if (c->d_tl) {   // debug timeline dump: launch group slot ticks(100 MHz)
         std::vector<unsigned long long> tl(3 * 64 * 2 * 16);   // [kernel][launch][group][slot]
         (void)hipMemcpy(tl.data(), c->d_tl, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
@@ -180,42 +176,7 @@ void bf_destroy(bf_ctx* c) {
                 if (tl[i]) fprintf(f, "%zu %zu %zu %zu %llu\n", i / 2048, (i / 32) % 64, (i / 16) % 2, i % 16, tl[i]);
             fclose(f);
         }
-        (void)hipFree(c->d_tl);
     }
-    global_free(c);
-    for (auto& r : c->prof_pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; ++i) if (c->poll_ev[i]) (void)hipEventDestroy(c->poll_ev[i]);
-    for (int i = 0; i < 2; ++i) if (c->copy_done[i]) (void)hipEventDestroy(c->copy_done[i]);
-    for (int i = 0; i < 2; ++i) if (c->staged[i]) (void)hipEventDestroy(c->staged[i]);
-    for (int i = 0; i < 2; ++i) {
-        if (c->prepared[i]) (void)hipEventDestroy(c->prepared[i]);
-        if (c->inc_free[i]) (void)hipEventDestroy(c->inc_free[i]);
-        if (c->inc[i].xy) (void)hipFree(c->inc[i].xy);
-        if (c->inc[i].t) (void)hipFree(c->inc[i].t);
-        if (c->inc[i].p) (void)hipFree(c->inc[i].p);
-        if (c->h_stats_slot[i]) (void)hipHostFree(c->h_stats_slot[i]);
-    }
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    for (int i = 0; i < 3; ++i) if (c->d_in2[i]) (void)hipFree(c->d_in2[i]);
-    for (int i = 0; i < 2; ++i) if (c->d_in_ts[i]) (void)hipFree(c->d_in_ts[i]);
-    for (int i = 0; i < 2; ++i) if (c->d_in16[i]) (void)hipFree(c->d_in16[i]);
-    for (int i = 0; i < 2; ++i) if (c->d_in_noise[i]) (void)hipFree(c->d_in_noise[i]);
-    void* bufs[] = {c->d_xrec, c->d_xred, c->d_verdict, c->d_xscratch[0], c->d_xscratch[1], c->d_xscratch[2], c->d_xscratch[3], c->set[0].p2, c->set[1].p2, c->d_ftab, c->set[0].xy, c->set[0].t, c->set[0].p, c->set[0].perm, c->set[1].xy, c->set[1].t,
-                    c->set[1].p, c->set[1].perm, c->d_binid, c->d_hist_cnt, c->d_bin_start,
-                    c->d_cursor, c->d_slabs, c->d_cidx, c->d_chdr, c->d_mplane[0], c->d_mplane[1], c->d_mlist, c->d_mcount, c->d_ovf_bits[0], c->d_ovf_bits[1], c->d_armed, c->d_acc, c->d_ovf, c->d_out_tmp, c->d_lplane[0], c->d_lplane[1], c->d_lscore, c->d_limg, c->d_col_planes, c->d_col_img, c->d_tile_hist, c->d_tile_start, c->d_tile_cursor, c->d_tile_states, c->d_many_args, c->d_ltile,
-                    c->d_noise, c->d_in_x, c->d_in_y, c->d_in_t, c->d_nxny,
-                    c->d_uv, c->d_plane[0], c->d_plane[1], c->d_cplane[0], c->d_cplane[1], c->d_time,
-                    c->d_gx, c->d_gy, c->d_img, c->d_count, c->d_ticket, c->d_state,
-                    c->d_trace};   // (d_stats is h_stats: freed below)
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    if (c->h_many_args) (void)hipHostFree(c->h_many_args);
-    if (c->h_state) (void)hipHostFree(c->h_state);
-    if (c->h_stats) (void)hipHostFree(c->h_stats);
-    if (c->h_lscore) (void)hipHostFree(c->h_lscore);
-    if (c->h_broken) (void)hipHostFree(c->h_broken);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
 }
 
@@ -278,9 +239,9 @@ int bf_set_option(bf_ctx* c, const char* key, int64_t value) {
         const int rc = streaming_setup(c);
         if (rc != BF_OK) return rc;
         for (int slot = 0; slot < 2; ++slot) {
-            if (!c->d_in_ts[slot]) HIP_TRY(c, hipMalloc(&c->d_in_ts[slot], (size_t)c->cap_events * sizeof(unsigned long long)));
-            if (!c->d_in16[slot]) HIP_TRY(c, hipMalloc(&c->d_in16[slot], (size_t)c->cap_events * 2 * sizeof(uint16_t)));
-            if (!c->d_in_noise[slot]) HIP_TRY(c, hipMalloc(&c->d_in_noise[slot], (size_t)c->cap_events));   // (else: first use, possibly in the middle of a solve)
+            HIP_TRY(c, c->d_in_ts[slot].grow((size_t)c->cap_events));
+            HIP_TRY(c, c->d_in16[slot].grow((size_t)c->cap_events * 2));
+            HIP_TRY(c, c->d_in_noise[slot].grow((size_t)c->cap_events));   // (else: first use, possibly in the middle of a solve)
         }
         return BF_OK;
     }
@@ -291,6 +252,7 @@ int bf_set_option(bf_ctx* c, const char* key, int64_t value) {
     }
     if (!strcmp(key, "defer_uploads")) {
         if (!value) {   // (what was recorded goes out before the mode ends)
+            HIP_TRY(c, hipSetDevice(c->device));
             const int rc = issue_deferred_uploads(c);
             if (rc != BF_OK) return rc;
         }
@@ -471,56 +433,44 @@ int bf_eval_sincos(bf_ctx* c, const double* x, int64_t n, int32_t table, double*
     if (!c || !x || !sin_out || !cos_out || n < 0) return BF_ERR_ARG;
     if (n == 0) return BF_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    double* d = nullptr;
-    HIP_TRY(c, hipMalloc(&d, (size_t)n * 3 * sizeof(double)));
-    int rc = [&]() -> int {
-        HIP_TRY(c, hipMemcpyAsync(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        launch_eval_sincos(d, n, table ? 1 : 0, d + n, d + 2 * n, c->stream);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(sin_out, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cos_out, d + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return BF_OK;
-    }();
-    (void)hipFree(d);
-    return rc;
+    DevArray<double> d;
+    HIP_TRY(c, d.grow((size_t)n * 3));
+    HIP_TRY(c, hipMemcpyAsync(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    launch_eval_sincos(d, n, table ? 1 : 0, d + n, d + 2 * n, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(sin_out, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cos_out, d + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BF_OK;
 }
 
 int bf_copy_bandwidth(bf_ctx* c, int64_t bytes, int32_t reps, double* gbps_out) {
     if (!c || !gbps_out || bytes < 4096 || reps < 1) return BF_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
     bytes &= ~(int64_t)15;
-    void *a = nullptr, *b = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevArray<uint8_t> a, b;
+    Event e0, e1;
     double best = 0.0;
-    const int rc = [&]() -> int {   // (whatever fails, the buffers and events below are released)
-        HIP_TRY(c, hipMalloc(&a, (size_t)bytes));
-        HIP_TRY(c, hipMalloc(&b, (size_t)bytes));
-        HIP_TRY(c, hipMemsetAsync(a, 1, (size_t)bytes, c->stream));
-        HIP_TRY(c, hipEventCreate(&e0));
-        HIP_TRY(c, hipEventCreate(&e1));
-        // the ceiling is the best of a few launch shapes (work-groups per CU, plain / non-temporal accesses), each warmed up
-        for (int nt = 0; nt < 2; ++nt)
-            for (int blocks : {1024, 2048, 4096, 8192}) {
-                launch_copy(a, b, bytes, blocks, nt != 0, c->stream);   // warm-up
-                for (int r = 0; r < reps; ++r) {
-                    HIP_TRY(c, hipEventRecord(e0, c->stream));
-                    launch_copy(a, b, bytes, blocks, nt != 0, c->stream);
-                    HIP_TRY(c, hipEventRecord(e1, c->stream));
-                    HIP_TRY(c, hipEventSynchronize(e1));
-                    float ms = 0.f;
-                    HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
-                    const double g = 2.0 * (double)bytes / ((double)ms * 1e-3) / 1e9;
-                    if (g > best) best = g;
-                }
+    HIP_TRY(c, a.grow((size_t)bytes));
+    HIP_TRY(c, b.grow((size_t)bytes));
+    HIP_TRY(c, hipMemsetAsync(a, 1, (size_t)bytes, c->stream));
+    HIP_TRY(c, e0.create());
+    HIP_TRY(c, e1.create());
+    // the ceiling is the best of a few launch shapes (work-groups per CU, plain / non-temporal accesses), each warmed up
+    for (int nt = 0; nt < 2; ++nt)
+        for (int blocks : {1024, 2048, 4096, 8192}) {
+            launch_copy(a, b, bytes, blocks, nt != 0, c->stream);   // warm-up
+            for (int r = 0; r < reps; ++r) {
+                HIP_TRY(c, hipEventRecord(e0, c->stream));
+                launch_copy(a, b, bytes, blocks, nt != 0, c->stream);
+                HIP_TRY(c, hipEventRecord(e1, c->stream));
+                HIP_TRY(c, hipEventSynchronize(e1));
+                float ms = 0.f;
+                HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
+                const double g = 2.0 * (double)bytes / ((double)ms * 1e-3) / 1e9;
+                if (g > best) best = g;
             }
-        return BF_OK;
-    }();
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
-    if (rc != BF_OK) return rc;
+        }
     *gbps_out = best;
     return BF_OK;
 }

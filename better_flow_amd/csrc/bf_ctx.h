@@ -1,6 +1,8 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_run.cpp,
-// bf_extras.cpp): the context structure behind `bf_ctx`, and the small helpers they share (error text, profiling brackets,
-// kernel-argument builders, buffer management).  Nothing here is part of the ABI (include/bf_accel.h).
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
+// context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  Nothing here is part
+// of the ABI (include/bf_accel.h).
 #pragma once
 #pragma clang diagnostic ignored "-Wunused-function"   // (every file uses its own subset of the helpers below)
 #include <functional>
@@ -16,6 +18,7 @@
 #include <chrono>
 #include <cstring>
 #include <ctime>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <utility>
@@ -25,8 +28,14 @@
 
 #include "bf_device.h"
 #include "bf_kernels.h"
+#include "bf_mem.h"
 
 using namespace bf;
+using bf_mem::DevArray;
+using bf_mem::Event;
+using bf_mem::HostArray;
+using bf_mem::MappedArray;
+using bf_mem::Stream;
 
 // Contexts alive per device in this process (defined in bf_context.cpp).  The persistent loop kernel needs every one of its
 // work-groups resident at once; two such kernels from two contexts could each hold part of the CUs and wait for the rest,
@@ -34,11 +43,12 @@ using namespace bf;
 extern std::atomic<int> g_live_ctx[64];
 
 struct GlobalSearch;   // bf_global_search.cpp: the exhaustive search's window, scratch and per-event state
+struct GlobalSearchFree { void operator()(GlobalSearch* g) const; };   // (defined where the type is complete)
 
 namespace {
 
 struct ProfRec {
-    hipEvent_t a, b;
+    Event a, b;
     int cat;
     long long nev;
 };
@@ -54,8 +64,7 @@ constexpr int kFusedMargin = 8;    // one-kernel loops: D on top of the stencil 
 
 struct bf_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    Stream stream;                   // created, or the caller's (bf_create)
 
     long long cap_events = 0;   // padded
     long long n = 0, n_pad = 0;
@@ -63,11 +72,11 @@ struct bf_ctx {
     int cap_blocks = 0;
 
     // two event sets: the tile-binned mode ping-pongs between them on every re-bin
-    struct EvSet { uint32_t* xy = nullptr; int32_t* t = nullptr; float2* p = nullptr; uint32_t* perm = nullptr; float2* p2 = nullptr; };
+    struct EvSet { DevArray<uint32_t> xy; DevArray<int32_t> t; DevArray<float2> p; DevArray<uint32_t> perm; DevArray<float2> p2; };
     EvSet set[2];
     int cs = 0;                      // set holding the live events
     bool has_perm = false;           // set[cs] is permuted; perm[] gives the upload index
-    uint8_t* d_noise = nullptr;
+    DevArray<uint8_t> d_noise;
     // tile-binned scatter
     int opt_binned = 1;              // 0 never, 1 when it pays (dense enough), 2 whenever possible
     bool opt_bin_predict = true;
@@ -82,16 +91,14 @@ struct bf_ctx {
     bool fused_ok = false;           // decided per slice in bf_set_cloud
     bool fused_shared = false;       // ... and it is also the loop to take when the context shares the GPU ("co_schedule")
     BinGrid fgrid;                   // its sort grid: keys = (tile, zone)
-    uint32_t* d_ftab = nullptr;      // FusedTab per tile
-    int ftab_alloc = 0;
+    DevArray<uint32_t> d_ftab;       // FusedTab per tile
     // persistent form of that loop (k_fused_loop, bf_loop.hip): a context ALONE on the GPU keeps the work-groups resident
     bool counted = false;            // in g_live_ctx
     int opt_persist = 1;             // 0 never, 1 for warm-started runs of the one-kernel loop on a context that is not co-scheduled, 2 cold runs too
-    unsigned long long *d_xrec = nullptr, *d_xred = nullptr;   // exchange records of the sub-tiles / of the reducers (two parities each)
-    unsigned long long* d_verdict = nullptr;   // (launch id << 2) | COMMIT / ABORT of the persistent kernel's current launch (bf_loop.hip)
-    int* h_broken = nullptr;         // pinned: set by the device if a committed launch could not be read back (never observed)
-    int xrec_alloc = 0;              // records per parity d_xrec holds
-    float2* d_xscratch[4] = {nullptr, nullptr, nullptr, nullptr};       // private product arrays of the strips' readers
+    DevArray<unsigned long long> d_xrec, d_xred;   // exchange records of the sub-tiles / of the reducers (two parities each)
+    DevArray<unsigned long long> d_verdict;   // (launch id << 2) | COMMIT / ABORT of the persistent kernel's current launch (bf_loop.hip)
+    HostArray<int> h_broken;         // set by the device if a committed launch could not be read back (never observed)
+    DevArray<float2> d_xscratch[4];  // private product arrays of the strips' readers
     // a launch that gave up (something else holds part of the GPU) costs 0.2 s: the context then leaves the persistent kernel
     // alone for persist_backoff runs (1, 2, 4, ... 64; a launch that completes resets it)
     int persist_skip = 0, persist_backoff = 0;
@@ -99,55 +106,47 @@ struct bf_ctx {
     // test hooks, read from the environment ONCE at bf_create (BF_DEBUG_PERSIST_ABORT / _MUTE / _SPLIT=<pass>[,late])
     int dbg_persist_abort = -1, dbg_persist_mute = -1, dbg_persist_split = -1, dbg_persist_split_late = 0;
     int dbg_margin = 0;              // BF_DEBUG_MARGIN=<n>: both loops' margin (tests: margins of 1 .. 4 pixels make events outrun their bins)
-    uint16_t* d_binid = nullptr;
-    uint32_t *d_hist_cnt = nullptr, *d_bin_start = nullptr, *d_cursor = nullptr;
-    uint32_t* d_armed = nullptr;
-    unsigned long long* d_slabs = nullptr;
-    uint16_t* d_cidx = nullptr;      // compact lists: pixel index per entry (same slot count as d_slabs)
-    uint32_t* d_chdr = nullptr;      // compact lists: entries per bin
+    DevArray<uint16_t> d_binid;
+    DevArray<uint32_t> d_hist_cnt, d_bin_start, d_cursor;
+    DevArray<uint32_t> d_armed;
+    DevArray<unsigned long long> d_slabs;
+    DevArray<uint16_t> d_cidx;       // compact lists: pixel index per entry (same slot count as d_slabs)
+    DevArray<uint32_t> d_chdr;       // compact lists: entries per bin
     int fmt = 0;                     // what this slice's scatter hands to the stencil: 0 dense slabs, 2 event lists, 3 own pixels + margin plane (bf_set_cloud)
     int opt_bin_compact = 1;         // 0 never, 1 when the image is sparse (decided per iteration on the device), 2 always
     // interior + margin format of a dense slice (fmt 3, bf_scatter.hip: flush_split): 0 never, 1 when it is the faster one, 2 always
     int opt_bin_split = 1;
-    unsigned long long* d_mplane[2] = {nullptr, nullptr};   // margin planes (cap_px words each), double buffered like d_plane
-    uint32_t* d_mlist = nullptr;     // per bin: the pixels of the margin plane it added to in its last executed launch
-    uint32_t* d_mcount = nullptr;    // per bin: entries of that list
-    size_t mlist_alloc = 0;
-    int mcount_alloc = 0;
+    DevArray<unsigned long long> d_mplane[2];   // margin planes (cap_px words each), double buffered like d_plane
+    DevArray<uint32_t> d_mlist;      // per bin: the pixels of the margin plane it added to in its last executed launch
+    DevArray<uint32_t> d_mcount;     // per bin: entries of that list
     int m_nbins = 0, m_cap = 0;      // geometry the lists were written with
     int m_dirty_plane = -1;          // the margin plane the lists describe (-1: both planes are clean, the lists empty)
     bool m_unknown = false;          // a run did not complete: clear everything before the next use
-    uint32_t* d_ovf_bits[2] = {nullptr, nullptr};   // per plane buffer: one bit per image pixel an overflow event touched (tile-binned loop)
-    size_t ovf_bits_words = 0;
+    DevArray<uint32_t> d_ovf_bits[2];   // per plane buffer: one bit per image pixel an overflow event touched (tile-binned loop)
     int ovf_pitch = 0;               // words per image row: ceil(C / 32) + 3 (one spare word left, two right: the stencil tile's window)
-    int bins_alloc = 0;
-    size_t slabs_alloc = 0;
     bool bin_setup_done = false;
     // per-tile optimizers (bf_run_tiles)
-    uint32_t *d_tile_hist = nullptr, *d_tile_start = nullptr, *d_tile_cursor = nullptr;
-    DevState* d_tile_states = nullptr;
-    int tiles_alloc = 0;
-    void* d_ltile = nullptr;         // bf_local_run_tiles: the windows' states, then their return codes
-    int ltile_alloc = 0;
-    void* d_many_args = nullptr;     // bf_run_tiles_many (lead context): the slices' launch arguments + the claim counter
-    void* h_many_args = nullptr;     // ... and their pinned staging copy
-    int many_alloc = 0;
-    int32_t *d_in_x = nullptr, *d_in_y = nullptr, *d_in_t = nullptr;
+    DevArray<uint32_t> d_tile_hist, d_tile_start, d_tile_cursor;
+    DevArray<DevState> d_tile_states;
+    DevArray<uint8_t> d_ltile;       // bf_local_run_tiles: the windows' states, then their return codes
+    DevArray<uint8_t> d_many_args;   // bf_run_tiles_many (lead context): the slices' launch arguments + the claim counter
+    HostArray<TileArgs> h_many_args; // ... and their pinned staging copy
+    DevArray<int32_t> d_in_x, d_in_y, d_in_t;
     // streaming: a second staging slot, a copy stream and one event per slot
-    int32_t* d_in2[3] = {nullptr, nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t copy_done[2] = {nullptr, nullptr};
-    hipEvent_t staged[2] = {nullptr, nullptr};   // the staging kernels that read a slot have run (compute stream)
+    DevArray<int32_t> d_in2[3];
+    Stream copy_stream;
+    Event copy_done[2];
+    Event staged[2];                 // the staging kernels that read a slot have run (compute stream)
     bool staged_valid[2] = {false, false};
     long long pending_n[2] = {0, 0};
     bool pending_ts64[2] = {false, false};       // slot holds absolute 64-bit timestamps (ring hand-off)
     bool pending_ts32[2] = {false, false};       // ... of which only the low 32 bits were sent (bf_upload_ring16t32_async)
     bool pending_addr16[2] = {false, false};     // ... and 16-bit addresses in d_in16 (bf_upload_ring16_async)
     bool pending_noise[2] = {false, false};      // ... and Event::noise flags in d_in_noise
-    uint16_t* d_in16[2] = {nullptr, nullptr};    // row[cap_events] then col[cap_events]
-    uint8_t* d_in_noise[2] = {nullptr, nullptr};
+    DevArray<uint16_t> d_in16[2];                // row[cap_events] then col[cap_events]
+    DevArray<uint8_t> d_in_noise[2];
     unsigned long long pending_t0[2] = {0, 0};
-    unsigned long long* d_in_ts[2] = {nullptr, nullptr};
+    DevArray<unsigned long long> d_in_ts[2];
     int pend_head = 0, pend_count = 0;   // FIFO of pending async uploads (slot = index & 1)
     // Early staging (round 6): an asynchronous upload WITHOUT a noise ring runs its staging kernels (widening, k_prepare)
     // on the COPY stream, right behind its copies, into the slot's own event arrays and its own pinned statistics record --
@@ -155,9 +154,9 @@ struct bf_ctx {
     // compute stream wait for the slot's `prepared` event: no staging kernel and no statistics round trip are left on a
     // warm-started chain's critical path (~35 us of a ~230 us slice at 346x260).
     EvSet inc[2];                                 // xy, t, p of the slice staged in slot i
-    SliceStats* h_stats_slot[2] = {nullptr, nullptr};   // pinned: k_prepare's per-work-group records of slot i
-    hipEvent_t prepared[2] = {nullptr, nullptr};  // slot i's staging kernels have run (copy stream)
-    hipEvent_t inc_free[2] = {nullptr, nullptr};  // the arrays swapped INTO inc[i] at a commit are free (compute stream is past that commit)
+    HostArray<SliceStats> h_stats_slot[2];        // k_prepare's per-work-group records of slot i
+    Event prepared[2];                            // slot i's staging kernels have run (copy stream)
+    Event inc_free[2];                            // the arrays swapped INTO inc[i] at a commit are free (compute stream is past that commit)
     bool inc_free_valid[2] = {false, false};
     bool pending_early[2] = {false, false};
     // "defer_uploads": an asynchronous upload only takes its slot and remembers what to copy; its HIP calls (three copies, the
@@ -169,48 +168,47 @@ struct bf_ctx {
     std::function<int()> deferred[2];
     std::mutex stats_mu;                          // fold_stats: bf_set_cloud's thread and an uploading thread (stage_early's guard) may both fold
     const SliceStats* stats_src = nullptr;        // where fold_stats reads (h_stats, or the committed slot's record)
-    hipEvent_t stats_event = nullptr;             // ... once this event has completed (null: the compute stream)
-    double2 *d_nxny = nullptr, *d_uv = nullptr;
-    unsigned long long* d_plane[2] = {nullptr, nullptr};
-    uint32_t* d_cplane[2] = {nullptr, nullptr};
-    float *d_time = nullptr, *d_gx = nullptr, *d_gy = nullptr, *d_img = nullptr;
-    uint32_t* d_count = nullptr;
-    MomentAcc* d_acc = nullptr;      // 3 x kAccGroups exact moment accumulators (two-kernel loop: parity of the iteration in the
+    hipEvent_t stats_event = nullptr;             // ... once this event has completed (null: the compute stream); one of prepared[], not owned
+    DevArray<double2> d_nxny, d_uv;
+    DevArray<unsigned long long> d_plane[2];
+    DevArray<uint32_t> d_cplane[2];
+    DevArray<float> d_time, d_gx, d_gy, d_img;
+    DevArray<uint32_t> d_count;
+    DevArray<MomentAcc> d_acc;       // 3 x kAccGroups exact moment accumulators (two-kernel loop: parity of the iteration in the
                                      // first two; one-kernel loop: launch number mod 3) + one line whose first word is `lost`
     bool acc_dirty = false;          // a head-update loop leaves its last iteration's sums behind: whoever uses the
                                      // accumulators next without a loop_init of its own (a ticket-mode stencil) clears them
-    uint32_t* d_ovf = nullptr;       // tile-binned loop: overflow events of iteration j in slot j % 3
-    unsigned int* d_ticket = nullptr;
-    unsigned long long* d_tl = nullptr;   // debug timeline (BF_TIMELINE=<file>, `make tl` build)
+    DevArray<uint32_t> d_ovf;        // tile-binned loop: overflow events of iteration j in slot j % 3
+    DevArray<unsigned int> d_ticket;
+    DevArray<unsigned long long> d_tl;    // debug timeline (BF_TIMELINE=<file>, `make tl` build)
     const char* tl_path = nullptr;
-    DevState* d_state = nullptr;     // 2 buffers: the tile-binned loop ping-pongs, everything else uses [0]
-    SliceStats* d_stats = nullptr;
-    bf_trace_rec* d_trace = nullptr;
-    int trace_alloc = 0;
+    DevArray<DevState> d_state;      // 2 buffers: the tile-binned loop ping-pongs, everything else uses [0]
+    SliceStats* d_stats = nullptr;   // = h_stats (not owned)
+    DevArray<bf_trace_rec> d_trace;
     int trace_valid = 0;
 
     // contrast-score optimiser (bf_local.hip)
-    uint32_t* d_lplane[2] = {nullptr, nullptr};   // point planes, double buffered
-    unsigned long long* d_lscore = nullptr;       // non-zero sum / count of the blurred image
-    uint8_t* d_limg = nullptr;                    // project_img
-    void* d_col_planes = nullptr;                 // colour time image: sum cos, sum sin (i64), count (u32) point planes
-    uint8_t* d_col_img = nullptr;                    // ... and its B, G, R bytes
-    unsigned long long* h_lscore = nullptr;       // pinned
+    DevArray<uint32_t> d_lplane[2];               // point planes, double buffered
+    DevArray<unsigned long long> d_lscore;        // non-zero sum / count of the blurred image
+    DevArray<uint8_t> d_limg;                     // project_img
+    DevArray<uint8_t> d_col_planes;               // colour time image: sum cos, sum sin (i64), count (u32) point planes
+    DevArray<uint8_t> d_col_img;                  // ... and its B, G, R bytes
+    HostArray<unsigned long long> h_lscore;
     bf_local_window lwin;
     bool have_lwin = false;
     int lcur = 0;
     // exhaustive search (bf_global.hip / bf_global_search.cpp)
-    GlobalSearch* glob = nullptr;
+    std::unique_ptr<GlobalSearch, GlobalSearchFree> glob;
     bool glob_valid = false;         // bf_global_set_window ran on the slice uploaded now (every upload clears it)
     SliceStats stats;                // folded k_prepare statistics of the uploaded slice
     bool stats_valid = false;
 
-    DevState* h_state = nullptr;     // pinned, D2H target only: 2 slots (pipelined polling)
-    unsigned long long* h_seq = nullptr;   // pinned: "snapshot complete" sequence number of a warm start's batch (k_finish_update)
+    HostArray<DevState> h_state;     // D2H target only: 2 slots (pipelined polling), then h_seq
+    unsigned long long* h_seq = nullptr;   // in h_state (not owned): "snapshot complete" sequence number of a warm start's batch (k_finish_update)
     unsigned long long seq_counter = 0;
-    hipEvent_t poll_ev[2] = {nullptr, nullptr};
+    Event poll_ev[2];
     double opt_watchdog_s = 40.0;    // a cold run whose device iteration counter stands still this long is declared hung
-    SliceStats* h_stats = nullptr;   // pinned, D2H target only
+    HostArray<SliceStats> h_stats;   // D2H target only
 
     DevState hst;                    // authoritative host mirror outside bf_run
     bf_window win;
@@ -225,7 +223,7 @@ struct bf_ctx {
     int warm_iters_hint = 6;         // iterations the previous warm-started run needed
     bool p_clean = false;            // p is all zero (Event::reset state): set by the upload, cleared by any warp
     bool out_sorted = false;         // d_nxny (and d_uv) are in slot order: un-permute with set[cs].perm before reading back
-    double2* d_out_tmp = nullptr;    // second buffer for that un-permutation
+    DevArray<double2> d_out_tmp;     // second buffer for that un-permutation
     bool uv_valid = false;           // d_uv holds compute_uv of that n (fused into bf_run's final warp)
     int cur = 0;                     // plane buffer that is guaranteed all-zero
     bool planes_unknown = true;      // both buffers must be cleared before use
@@ -233,15 +231,13 @@ struct bf_ctx {
 
     int prof_mode = 0;
     std::vector<ProfRec> prof_pending;
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event> ev_pool;
     bf_profile prof;
 
     char err[512];
     std::mutex err_mu;   // fail() may be called from the uploading thread and the solving thread at once (see bf_accel.h: threading)
 };
 
-// frees what bf_global_search.cpp allocated for ctx (bf_destroy)
-void global_free(bf_ctx* c);
 // the live slice's per-event flow in upload order on the device, or null (bf_operators.cpp)
 extern "C" int ctx_device_uv(bf_ctx* c, const double2** uv);
 
@@ -268,14 +264,14 @@ int fail(bf_ctx* c, int code, const char* fmt, ...) {
                         __FILE__, __LINE__);                                                  \
     } while (0)
 
-hipEvent_t get_event(bf_ctx* c) {
-    if (!c->ev_pool.empty()) {
-        hipEvent_t e = c->ev_pool.back();
+Event get_event(bf_ctx* c) {
+    Event e;
+    if (c->ev_pool.empty()) {
+        (void)e.create();
+    } else {
+        e = std::move(c->ev_pool.back());
         c->ev_pool.pop_back();
-        return e;
     }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
     return e;
 }
 
@@ -301,7 +297,7 @@ struct ProfScope {
         if (!t.consumed) (void)hipEventRecord(r.b, c->stream);
         t.start = t.stop = nullptr;
         t.consumed = false;
-        c->prof_pending.push_back(r);
+        c->prof_pending.push_back(std::move(r));
     }
 };
 
@@ -318,8 +314,8 @@ int prof_fold(bf_ctx* c) {
             case 2: c->prof.update_ms += ms; c->prof.update_launches++; break;
             default: c->prof.other_ms += ms; c->prof.other_launches++; break;
         }
-        c->ev_pool.push_back(r.a);
-        c->ev_pool.push_back(r.b);
+        c->ev_pool.push_back(std::move(r.a));
+        c->ev_pool.push_back(std::move(r.b));
     }
     c->prof_pending.clear();
     return BF_OK;
@@ -395,10 +391,10 @@ StencilArgs st_args(bf_ctx* c, int buf, int check_done) {
 int stencil_src(const bf_ctx* c, bool binned_pass) { return binned_pass ? 3 : (c->packed ? 0 : 1); }
 
 int ensure_cplanes(bf_ctx* c) {
-    if (c->d_cplane[0]) return BF_OK;
     for (int i = 0; i < 2; ++i) {
-        HIP_TRY(c, hipMalloc(&c->d_cplane[i], c->cap_px * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->d_cplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
+        bool fresh;
+        HIP_TRY(c, c->d_cplane[i].grow(c->cap_px, &fresh));
+        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_cplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
     }
     return BF_OK;
 }
@@ -409,7 +405,7 @@ int clear_planes(bf_ctx* c) {
         if (c->d_cplane[i])
             HIP_TRY(c, hipMemsetAsync(c->d_cplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
         if (c->d_ovf_bits[i])
-            HIP_TRY(c, hipMemsetAsync(c->d_ovf_bits[i], 0, c->ovf_bits_words * sizeof(uint32_t), c->stream));
+            HIP_TRY(c, hipMemsetAsync(c->d_ovf_bits[i], 0, c->d_ovf_bits[i].size() * sizeof(uint32_t), c->stream));
     }
     c->planes_unknown = false;
     c->cur = 0;
@@ -421,17 +417,24 @@ int clear_planes(bf_ctx* c) {
 int ensure_ovf_bits(bf_ctx* c, int R, int C) {
     const int pitch = (C + 31) / 32 + 3;
     const size_t need = (size_t)R * (size_t)pitch;
-    if (need > c->ovf_bits_words) {
-        for (int i = 0; i < 2; ++i) {
-            if (c->d_ovf_bits[i]) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(c->d_ovf_bits[i])); }
-            c->d_ovf_bits[i] = nullptr;
-            HIP_TRY(c, hipMalloc(&c->d_ovf_bits[i], need * sizeof(uint32_t)));
-        }
-        c->ovf_bits_words = need;
-        c->planes_unknown = true;   // (fresh bitmaps: cleared with the planes below)
+    for (int i = 0; i < 2; ++i) {
+        bool fresh;
+        HIP_TRY(c, c->d_ovf_bits[i].grow(need, &fresh));
+        if (fresh) c->planes_unknown = true;   // (fresh bitmaps: cleared with the planes below)
     }
     if (pitch != c->ovf_pitch) c->planes_unknown = true;   // (bits set under another row pitch mean other pixels)
     c->ovf_pitch = pitch;
+    return BF_OK;
+}
+
+// The second event set and both permutations, shared by the tile-binned loops and bf_run_tiles: whichever comes first allocates
+// them, and the other finds them (with the slice's events possibly IN the second set).
+int ensure_second_set(bf_ctx* c) {
+    const size_t ne = (size_t)c->cap_events;
+    HIP_TRY(c, c->set[1].xy.grow(ne));
+    HIP_TRY(c, c->set[1].t.grow(ne));
+    HIP_TRY(c, c->set[1].p.grow(ne));
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, c->set[i].perm.grow(ne));
     return BF_OK;
 }
 
@@ -440,41 +443,22 @@ int ensure_bin_buffers(bf_ctx* c, const BinGrid& g) {
         if (bin_kernel_setup() != 0) return fail(c, BF_ERR_HIP, "cannot raise the dynamic LDS limit");
         c->bin_setup_done = true;
     }
-    if (!c->d_binid) {
-        HIP_TRY(c, hipMalloc(&c->d_binid, (size_t)c->cap_events * sizeof(uint16_t)));
-        HIP_TRY(c, hipMalloc(&c->d_armed, 64));
-        HIP_TRY(c, hipMemsetAsync(c->d_armed, 0, 64, c->stream));
-    }
-    // (the second event set and the permutations are shared with bf_run_tiles, which may have allocated them -- and may have
-    // left the slice's events IN the second set: replacing the buffers here lost them)
-    for (int i = 0; i < 2; ++i)
-        if (!c->set[i].perm) HIP_TRY(c, hipMalloc(&c->set[i].perm, (size_t)c->cap_events * sizeof(uint32_t)));
-    if (!c->set[1].xy) {
-        HIP_TRY(c, hipMalloc(&c->set[1].xy, (size_t)c->cap_events * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->set[1].t, (size_t)c->cap_events * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->set[1].p, (size_t)c->cap_events * sizeof(float2)));
-    }
-    if (g.nbins > c->bins_alloc) {
-        void* old[] = {c->d_hist_cnt, c->d_bin_start, c->d_cursor, c->d_chdr};
-        for (void* o : old) if (o) HIP_TRY(c, hipFree(o));
-        c->d_hist_cnt = nullptr; c->d_bin_start = nullptr; c->d_cursor = nullptr; c->d_chdr = nullptr;
-        const size_t nb = (size_t)g.nbins + 1;
-        HIP_TRY(c, hipMalloc(&c->d_hist_cnt, kHistCopies * nb * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_bin_start, nb * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_cursor, nb * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_chdr, nb * 580 * sizeof(uint32_t)));   // event lists: 3 LR + 1 <= 577 key offsets per bin ((column zone, row) keys)
-        HIP_TRY(c, hipMemsetAsync(c->d_hist_cnt, 0, kHistCopies * nb * sizeof(uint32_t), c->stream));
-        c->bins_alloc = g.nbins;
-    }
+    const size_t ne = (size_t)c->cap_events;
+    bool fresh;
+    HIP_TRY(c, c->d_binid.grow(ne));
+    HIP_TRY(c, c->d_armed.grow(16, &fresh));
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_armed, 0, 64, c->stream));
+    const int rc = ensure_second_set(c);
+    if (rc != BF_OK) return rc;
+    const size_t nb = (size_t)g.nbins + 1;
+    HIP_TRY(c, c->d_hist_cnt.grow(kHistCopies * nb, &fresh));
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_hist_cnt, 0, kHistCopies * nb * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, c->d_bin_start.grow(nb));
+    HIP_TRY(c, c->d_cursor.grow(nb));
+    HIP_TRY(c, c->d_chdr.grow(nb * 580));   // event lists: 3 LR + 1 <= 577 key offsets per bin ((column zone, row) keys)
     const size_t need = (size_t)g.nbins * (size_t)g.LR * (size_t)g.L;
-    if (need > c->slabs_alloc) {
-        if (c->d_slabs) HIP_TRY(c, hipFree(c->d_slabs));
-        if (c->d_cidx) HIP_TRY(c, hipFree(c->d_cidx));
-        c->d_slabs = nullptr; c->d_cidx = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_slabs, need * sizeof(unsigned long long)));
-        HIP_TRY(c, hipMalloc(&c->d_cidx, need * sizeof(uint16_t)));
-        c->slabs_alloc = need;
-    }
+    HIP_TRY(c, c->d_slabs.grow(need));
+    HIP_TRY(c, c->d_cidx.grow(need));
     return BF_OK;
 }
 
@@ -487,7 +471,7 @@ int margin_reset(bf_ctx* c) {
     if (c->m_unknown) {
         for (int i = 0; i < 2; ++i)
             if (c->d_mplane[i]) HIP_TRY(c, hipMemsetAsync(c->d_mplane[i], 0, c->cap_px * sizeof(unsigned long long), c->stream));
-        if (c->d_mcount) HIP_TRY(c, hipMemsetAsync(c->d_mcount, 0, (size_t)c->mcount_alloc * sizeof(uint32_t), c->stream));
+        if (c->d_mcount) HIP_TRY(c, hipMemsetAsync(c->d_mcount, 0, c->d_mcount.size() * sizeof(uint32_t), c->stream));
         c->m_unknown = false;
     } else if (c->m_dirty_plane >= 0) {
         launch_margin_clean(c->d_mplane[c->m_dirty_plane], c->d_mlist, c->d_mcount, c->m_nbins, c->m_cap, c->stream);
@@ -502,25 +486,14 @@ int ensure_margin_buffers(bf_ctx* c, const BinGrid& g) {
         int rc = margin_reset(c);
         if (rc != BF_OK) return rc;
     }
-    for (int i = 0; i < 2; ++i)
-        if (!c->d_mplane[i]) {
-            HIP_TRY(c, hipMalloc(&c->d_mplane[i], c->cap_px * sizeof(unsigned long long)));
-            HIP_TRY(c, hipMemsetAsync(c->d_mplane[i], 0, c->cap_px * sizeof(unsigned long long), c->stream));
-        }
-    if (g.nbins > c->mcount_alloc) {
-        if (c->d_mcount) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(c->d_mcount)); }
-        c->d_mcount = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_mcount, (size_t)g.nbins * sizeof(uint32_t)));
-        HIP_TRY(c, hipMemsetAsync(c->d_mcount, 0, (size_t)g.nbins * sizeof(uint32_t), c->stream));
-        c->mcount_alloc = g.nbins;
+    bool fresh;
+    for (int i = 0; i < 2; ++i) {
+        HIP_TRY(c, c->d_mplane[i].grow(c->cap_px, &fresh));
+        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_mplane[i], 0, c->cap_px * sizeof(unsigned long long), c->stream));
     }
-    const size_t need = (size_t)g.nbins * (size_t)mcap;
-    if (need > c->mlist_alloc) {
-        if (c->d_mlist) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(c->d_mlist)); }
-        c->d_mlist = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_mlist, need * sizeof(uint32_t)));
-        c->mlist_alloc = need;
-    }
+    HIP_TRY(c, c->d_mcount.grow((size_t)g.nbins, &fresh));
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_mcount, 0, (size_t)g.nbins * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, c->d_mlist.grow((size_t)g.nbins * (size_t)mcap));
     c->m_nbins = g.nbins;
     c->m_cap = mcap;
     return BF_OK;
@@ -528,7 +501,7 @@ int ensure_margin_buffers(bf_ctx* c, const BinGrid& g) {
 
 // Device-conditional counting sort of the live events by the image tile of their current
 // target (runs only when hot.need_rebin is set); no host synchronisation.
-uint32_t* lost_flag(const bf_ctx* c) { return reinterpret_cast<uint32_t*>(c->d_acc + 3 * kAccGroups); }
+uint32_t* lost_flag(const bf_ctx* c) { return reinterpret_cast<uint32_t*>(c->d_acc.get() + 3 * kAccGroups); }
 
 int enqueue_rebin(bf_ctx* c, DevState* st, bool has_perm_at_start, const WarpParams* prewarp = nullptr, bool fused = false, int launch_no = 0) {
     ProfScope ps(c, 3);
@@ -623,15 +596,19 @@ int after_upload(bf_ctx* c, long long n) {
     return BF_OK;
 }
 
-// the HIP side of uploads that were only recorded ("defer_uploads"), oldest first
+// the HIP side of uploads that were only recorded ("defer_uploads"), oldest first.  One that fails is dropped with every upload
+// behind it: the uploads ahead of it stay pending and committable, the failed ones were never taken.
 int issue_deferred_uploads(bf_ctx* c) {
     for (int k = 0; k < c->pend_count; ++k) {
         const int slot = (c->pend_head + k) & 1;
-        if (c->deferred[slot]) {
-            std::function<int()> f;
-            f.swap(c->deferred[slot]);
-            const int rc = f();
-            if (rc != BF_OK) return rc;
+        if (!c->deferred[slot]) continue;
+        std::function<int()> f;
+        f.swap(c->deferred[slot]);
+        const int rc = f();
+        if (rc != BF_OK) {
+            for (int j = k + 1; j < c->pend_count; ++j) c->deferred[(c->pend_head + j) & 1] = nullptr;
+            c->pend_count = k;
+            return rc;
         }
     }
     return BF_OK;
@@ -639,18 +616,15 @@ int issue_deferred_uploads(bf_ctx* c) {
 
 // copy stream, its events and the second staging slot of the asynchronous uploads (created on first use)
 int streaming_setup(bf_ctx* c) {
-    if (c->copy_stream) return BF_OK;
-    HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventCreateWithFlags(&c->copy_done[i], hipEventDisableTiming));
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipEventCreateWithFlags(&c->staged[i], hipEventDisableTiming));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, hipMalloc(&c->d_in2[i], (size_t)c->cap_events * sizeof(int32_t)));
-    for (int i = 0; i < 2; ++i) {   // early staging: the slots' own event arrays, statistics records and events
-        HIP_TRY(c, hipEventCreateWithFlags(&c->prepared[i], hipEventDisableTiming));
-        HIP_TRY(c, hipEventCreateWithFlags(&c->inc_free[i], hipEventDisableTiming));
-        HIP_TRY(c, hipMalloc(&c->inc[i].xy, (size_t)c->cap_events * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->inc[i].t, (size_t)c->cap_events * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->inc[i].p, (size_t)c->cap_events * sizeof(float2)));
-        HIP_TRY(c, hipHostMalloc(&c->h_stats_slot[i], kPrepBlocks * sizeof(SliceStats), hipHostMallocDefault));
+    const size_t ne = (size_t)c->cap_events;
+    HIP_TRY(c, c->copy_stream.create(hipStreamNonBlocking));
+    for (int i = 0; i < 3; ++i) HIP_TRY(c, c->d_in2[i].grow(ne));
+    for (int i = 0; i < 2; ++i) {   // (early staging: the slots' own event arrays, statistics records and events)
+        for (Event* e : {&c->copy_done[i], &c->staged[i], &c->prepared[i], &c->inc_free[i]}) HIP_TRY(c, e->create(hipEventDisableTiming));
+        HIP_TRY(c, c->inc[i].xy.grow(ne));
+        HIP_TRY(c, c->inc[i].t.grow(ne));
+        HIP_TRY(c, c->inc[i].p.grow(ne));
+        HIP_TRY(c, c->h_stats_slot[i].grow(kPrepBlocks));
     }
     return BF_OK;
 }

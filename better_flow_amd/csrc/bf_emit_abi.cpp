@@ -19,23 +19,21 @@ struct bf_emit {
     int device = 0;
     unsigned long long cap = 0;             // ring positions of the covered plane
     int rows = 0, cols = 0;
-    uint8_t* plane = nullptr;
-    unsigned long long *tail_t = nullptr, *tail_g = nullptr;
-    unsigned long long* d_off = nullptr;    // running row offset, two words (slice parity)
-    uint32_t* d_err = nullptr;
-    // scratch for slices of up to m_cap elements (shared by every context: the slices run one after the other on the device)
-    long long m_cap = 0;
-    unsigned long long *t = nullptr, *keys = nullptr, *keys2 = nullptr;
-    uint32_t *rc = nullptr, *pos = nullptr;
-    uint8_t* flag = nullptr;
-    void* temp = nullptr;
-    size_t temp_bytes = 0;
+    DevArray<uint8_t> plane;
+    DevArray<unsigned long long> tail_t, tail_g;
+    DevArray<unsigned long long> d_off;     // running row offset, two words (slice parity)
+    DevArray<uint32_t> d_err;
+    // scratch for slices of up to t.size() elements (shared by every context: the slices run one after the other on the device)
+    DevArray<unsigned long long> t, keys, keys2;
+    DevArray<uint32_t> rc, pos;
+    DevArray<uint8_t> flag;
+    DevArray<uint8_t> temp;                 // the sort's and the scan's temporary storage
     // pinned, device-mapped output ring and per-slice records (first row, rows, error bits, -)
     unsigned long long out_rows = 0;
-    uint64_t* out_t = nullptr;
-    uint16_t *out_row = nullptr, *out_col = nullptr;
-    double *out_u = nullptr, *out_v = nullptr;
-    unsigned long long* recs = nullptr;
+    MappedArray<uint64_t> out_t;
+    MappedArray<uint16_t> out_row, out_col;
+    MappedArray<double> out_u, out_v;
+    MappedArray<unsigned long long> recs;
     // host bookkeeping, under mu
     std::mutex mu;
     unsigned long long prev_end = 0, prev_first = 0;   // events below prev_end have been in an emitted slice
@@ -44,39 +42,30 @@ struct bf_emit {
     unsigned long long known_end = 0;                   // exact row offset after the last waited slice
     unsigned long long pending_bound = 0;               // + at most this many rows from enqueued, not yet waited slices
     long long rec_m[kRecs];                             // elements of each slice in flight (its bound)
-    hipEvent_t done[kRecs];                             // the slice's kernels have finished
+    Event done[kRecs];                                  // the slice's kernels have finished
     bool have_last = false;
-    hipEvent_t last = nullptr;                          // the newest enqueued slice
+    hipEvent_t last = nullptr;                          // the newest enqueued slice (one of done[], not owned)
 };
 
 namespace {
 
-void emit_free_scratch(bf_emit* e) {
-    void* bufs[] = {e->t, e->keys, e->keys2, e->rc, e->pos, e->flag, e->temp};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    e->t = e->keys = e->keys2 = nullptr;
-    e->rc = e->pos = nullptr;
-    e->flag = nullptr;
-    e->temp = nullptr;
-    e->m_cap = 0;
-    e->temp_bytes = 0;
-}
-
+// Scratch for a slice of m elements: an array that holds fewer is replaced by one of k = 1.25 m + 1024 (the slices of a stream
+// vary a little), and the temporary storage is sized for k whenever an array was.
 int emit_reserve(bf_ctx* c, bf_emit* e, long long m) {
-    if (m <= e->m_cap) return BF_OK;
-    if (e->have_last) HIP_TRY(c, hipEventSynchronize(e->last));   // (slices in flight use the scratch)
-    emit_free_scratch(e);
-    const long long k = m + m / 4 + 1024;
-    HIP_TRY(c, hipMalloc(&e->t, (size_t)k * 8));
-    HIP_TRY(c, hipMalloc(&e->keys, (size_t)k * 8));
-    HIP_TRY(c, hipMalloc(&e->keys2, (size_t)k * 8));
-    HIP_TRY(c, hipMalloc(&e->rc, (size_t)k * 4));
-    HIP_TRY(c, hipMalloc(&e->pos, (size_t)k * 4));
-    HIP_TRY(c, hipMalloc(&e->flag, (size_t)k));
-    e->temp_bytes = emit_temp_bytes(k);
-    HIP_TRY(c, hipMalloc(&e->temp, e->temp_bytes ? e->temp_bytes : 1));
-    e->m_cap = k;
+    const size_t k = (size_t)(m + m / 4 + 1024);
+    bool fresh = false;
+    auto reserve = [&](auto& a) {
+        if (a.size() >= (size_t)m) return hipSuccess;
+        fresh = true;
+        return a.grow(k);
+    };
+    HIP_TRY(c, reserve(e->t));
+    HIP_TRY(c, reserve(e->keys));
+    HIP_TRY(c, reserve(e->keys2));
+    HIP_TRY(c, reserve(e->rc));
+    HIP_TRY(c, reserve(e->pos));
+    HIP_TRY(c, reserve(e->flag));
+    if (fresh || !e->temp) HIP_TRY(c, e->temp.grow(std::max<size_t>(emit_temp_bytes((long long)k), 1)));
     return BF_OK;
 }
 
@@ -95,17 +84,8 @@ int emit_clear(bf_ctx* c, bf_emit* e) {
     return BF_OK;
 }
 
-void emit_free(bf_emit* e) {
-    emit_free_scratch(e);
-    void* bufs[] = {e->plane, e->tail_t, e->tail_g, e->d_off, e->d_err};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    void* pinned[] = {e->out_t, e->out_row, e->out_col, e->out_u, e->out_v, e->recs};
-    for (void* b : pinned)
-        if (b) (void)hipHostFree(b);
-    for (int i = 0; i < kRecs; ++i)
-        if (e->done[i]) (void)hipEventDestroy(e->done[i]);
-    delete e;
+int create_failed(bf_ctx* c, hipError_t err, const char* what) {
+    return fail(c, err == hipErrorOutOfMemory ? BF_ERR_CAPACITY : BF_ERR_HIP, "bf_emit_create: %s: %s", what, hipGetErrorString(err));
 }
 
 }  // namespace
@@ -119,37 +99,32 @@ int bf_emit_create(bf_ctx* c, int64_t ring_cap, int32_t rows, int32_t cols, int6
         return fail(c, BF_ERR_ARG, "bf_emit_create: bad ring capacity %lld, sensor %d x %d or output ring %lld", (long long)ring_cap, rows,
                     cols, (long long)out_rows);
     HIP_TRY(c, hipSetDevice(c->device));
-    bf_emit* e = new (std::nothrow) bf_emit;
+    std::unique_ptr<bf_emit> e(new (std::nothrow) bf_emit);   // (a failure below frees what was made)
     if (!e) return fail(c, BF_ERR_CAPACITY, "bf_emit_create: out of host memory");
-    for (int i = 0; i < kRecs; ++i) e->done[i] = nullptr;
     e->device = c->device;
     e->cap = (unsigned long long)ring_cap;
     e->rows = rows;
     e->cols = cols;
     e->out_rows = (unsigned long long)out_rows;
     const size_t px = (size_t)rows * (size_t)cols, R = (size_t)out_rows;
-    auto bad = [&](hipError_t err, const char* what) {
-        emit_free(e);
-        return fail(c, err == hipErrorOutOfMemory ? BF_ERR_CAPACITY : BF_ERR_HIP, "bf_emit_create: %s: %s", what, hipGetErrorString(err));
-    };
     hipError_t err;
-    if ((err = hipMalloc(&e->plane, (size_t)ring_cap)) != hipSuccess) return bad(err, "covered plane");
-    if ((err = hipMalloc(&e->tail_t, px * 8)) != hipSuccess) return bad(err, "tail");
-    if ((err = hipMalloc(&e->tail_g, px * 8)) != hipSuccess) return bad(err, "tail");
-    if ((err = hipMalloc(&e->d_off, 16)) != hipSuccess) return bad(err, "row offset");
-    if ((err = hipMalloc(&e->d_err, 4)) != hipSuccess) return bad(err, "error word");
+    if ((err = e->plane.grow((size_t)ring_cap)) != hipSuccess) return create_failed(c, err, "covered plane");
+    if ((err = e->tail_t.grow(px)) != hipSuccess) return create_failed(c, err, "tail");
+    if ((err = e->tail_g.grow(px)) != hipSuccess) return create_failed(c, err, "tail");
+    if ((err = e->d_off.grow(2)) != hipSuccess) return create_failed(c, err, "row offset");
+    if ((err = e->d_err.grow(1)) != hipSuccess) return create_failed(c, err, "error word");
     // (pinned and mapped: k_emit_rows stores the rows straight into them)
-    if ((err = hipHostMalloc(&e->out_t, R * 8, hipHostMallocMapped)) != hipSuccess) return bad(err, "output ring");
-    if ((err = hipHostMalloc(&e->out_row, R * 2, hipHostMallocMapped)) != hipSuccess) return bad(err, "output ring");
-    if ((err = hipHostMalloc(&e->out_col, R * 2, hipHostMallocMapped)) != hipSuccess) return bad(err, "output ring");
-    if ((err = hipHostMalloc(&e->out_u, R * 8, hipHostMallocMapped)) != hipSuccess) return bad(err, "output ring");
-    if ((err = hipHostMalloc(&e->out_v, R * 8, hipHostMallocMapped)) != hipSuccess) return bad(err, "output ring");
-    if ((err = hipHostMalloc(&e->recs, (size_t)kRecs * 4 * 8, hipHostMallocMapped)) != hipSuccess) return bad(err, "slice records");
+    if ((err = e->out_t.grow(R)) != hipSuccess) return create_failed(c, err, "output ring");
+    if ((err = e->out_row.grow(R)) != hipSuccess) return create_failed(c, err, "output ring");
+    if ((err = e->out_col.grow(R)) != hipSuccess) return create_failed(c, err, "output ring");
+    if ((err = e->out_u.grow(R)) != hipSuccess) return create_failed(c, err, "output ring");
+    if ((err = e->out_v.grow(R)) != hipSuccess) return create_failed(c, err, "output ring");
+    if ((err = e->recs.grow((size_t)kRecs * 4)) != hipSuccess) return create_failed(c, err, "slice records");
     for (int i = 0; i < kRecs; ++i)
-        if ((err = hipEventCreateWithFlags(&e->done[i], hipEventDisableTiming)) != hipSuccess) return bad(err, "events");
-    const int rc = emit_clear(c, e);
-    if (rc != BF_OK) { emit_free(e); return rc; }
-    *out = e;
+        if ((err = e->done[i].create(hipEventDisableTiming)) != hipSuccess) return create_failed(c, err, "events");
+    const int rc = emit_clear(c, e.get());
+    if (rc != BF_OK) return rc;
+    *out = e.release();
     return BF_OK;
 }
 
@@ -157,7 +132,7 @@ int bf_emit_destroy(bf_emit* e) {
     if (!e) return BF_ERR_ARG;
     (void)hipSetDevice(e->device);
     if (e->have_last) (void)hipEventSynchronize(e->last);
-    emit_free(e);
+    delete e;
     return BF_OK;
 }
 
@@ -225,7 +200,7 @@ int bf_emit_slice(bf_ctx* c, bf_emit* e, int64_t n, uint64_t first, uint64_t sta
     a.jbits = bits_for((unsigned long long)m - 1);
     a.kbits = a.jbits + bits_for((unsigned long long)e->rows * (unsigned long long)e->cols - 1);
     a.err = e->d_err;
-    a.out_t = (unsigned long long*)e->out_t; a.out_row = e->out_row; a.out_col = e->out_col; a.out_u = e->out_u; a.out_v = e->out_v;
+    a.out_t = (unsigned long long*)e->out_t.get(); a.out_row = e->out_row; a.out_col = e->out_col; a.out_u = e->out_u; a.out_v = e->out_v;
     a.out_rows = e->out_rows;
     a.off_in = e->d_off + (ticket & 1);
     a.off_out = e->d_off + ((ticket + 1) & 1);
@@ -233,7 +208,7 @@ int bf_emit_slice(bf_ctx* c, bf_emit* e, int64_t n, uint64_t first, uint64_t sta
     // after the previous slice, whichever context enqueued it: it wrote the plane, the tail and the offset this one reads
     if (e->have_last) HIP_TRY(c, hipStreamWaitEvent(c->stream, e->last, 0));
     HIP_TRY(c, hipMemsetAsync(e->d_err, 0, 4, c->stream));
-    HIP_TRY(c, launch_emit(a, e->keys2, e->temp, e->temp_bytes, c->stream));
+    HIP_TRY(c, launch_emit(a, e->keys2, e->temp, e->temp.size(), c->stream));
     HIP_TRY(c, hipEventRecord(e->done[slot], c->stream));
     e->last = e->done[slot];
     e->have_last = true;

@@ -17,26 +17,14 @@ int tiles_prepare(bf_ctx* c, const bf_tile_opts* o, hipStream_t s, TileArgs& a, 
     if (c->has_noise) return fail(c, BF_ERR_ARG, "bf_run_tiles does not take a noise mask");
     HIP_TRY(c, hipSetDevice(c->device));
     const int nt = o->grid_rows * o->grid_cols;
-    // second event set + permutation (shared with the tile-binned scatter)
-    if (!c->set[1].xy) {
-        HIP_TRY(c, hipMalloc(&c->set[1].xy, (size_t)c->cap_events * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->set[1].t, (size_t)c->cap_events * sizeof(int32_t)));
-        HIP_TRY(c, hipMalloc(&c->set[1].p, (size_t)c->cap_events * sizeof(float2)));
-    }
-    for (int i = 0; i < 2; ++i)
-        if (!c->set[i].perm) HIP_TRY(c, hipMalloc(&c->set[i].perm, (size_t)c->cap_events * sizeof(uint32_t)));
-    if (nt > c->tiles_alloc) {
-        void* old[] = {c->d_tile_hist, c->d_tile_start, c->d_tile_cursor, c->d_tile_states};
-        for (void* p : old) if (p) HIP_TRY(c, hipFree(p));
-        c->d_tile_hist = c->d_tile_start = c->d_tile_cursor = nullptr;
-        c->d_tile_states = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_tile_hist, (size_t)(nt + 1) * 4));
-        HIP_TRY(c, hipMalloc(&c->d_tile_start, (size_t)(nt + 1) * 4));
-        HIP_TRY(c, hipMalloc(&c->d_tile_cursor, (size_t)(nt + 1) * 4));
-        HIP_TRY(c, hipMalloc(&c->d_tile_states, (size_t)nt * sizeof(DevState)));
-        HIP_TRY(c, hipMemsetAsync(c->d_tile_hist, 0, (size_t)(nt + 1) * 4, s));
-        c->tiles_alloc = nt;
-    }
+    int rc = ensure_second_set(c);
+    if (rc != BF_OK) return rc;
+    bool fresh;
+    HIP_TRY(c, c->d_tile_hist.grow((size_t)nt + 1, &fresh));
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_tile_hist, 0, (size_t)(nt + 1) * 4, s));
+    HIP_TRY(c, c->d_tile_start.grow((size_t)nt + 1));
+    HIP_TRY(c, c->d_tile_cursor.grow((size_t)nt + 1));
+    HIP_TRY(c, c->d_tile_states.grow((size_t)nt));
     // LDS image capacity: the largest window a tile can have
     const int tr = (o->sensor_res_x + o->grid_rows - 1) / o->grid_rows + 1;
     const int tc = (o->sensor_res_y + o->grid_cols - 1) / o->grid_cols + 1;
@@ -136,17 +124,11 @@ int bf_run_tiles_many(bf_ctx* const* ctxs, int32_t n, const bf_tile_opts* o, bf_
     }
     HIP_TRY(lead, hipSetDevice(lead->device));
     const int nt = o->grid_rows * o->grid_cols;
-    if (n > lead->many_alloc) {
-        if (lead->d_many_args) HIP_TRY(lead, hipFree(lead->d_many_args));
-        if (lead->h_many_args) HIP_TRY(lead, hipHostFree(lead->h_many_args));
-        lead->d_many_args = nullptr; lead->h_many_args = nullptr; lead->many_alloc = 0;
-        HIP_TRY(lead, hipMalloc(&lead->d_many_args, (size_t)n * sizeof(TileArgs) + 64));
-        HIP_TRY(lead, hipHostMalloc(&lead->h_many_args, (size_t)n * sizeof(TileArgs), hipHostMallocDefault));
-        lead->many_alloc = n;
-    }
-    TileArgs* host_args = static_cast<TileArgs*>(lead->h_many_args);
-    TileArgs* dev_args = static_cast<TileArgs*>(lead->d_many_args);
-    uint32_t* counter = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(lead->d_many_args) + (size_t)lead->many_alloc * sizeof(TileArgs));
+    HIP_TRY(lead, lead->d_many_args.grow((size_t)n * sizeof(TileArgs) + 64));
+    HIP_TRY(lead, lead->h_many_args.grow((size_t)n));
+    TileArgs* host_args = lead->h_many_args;
+    TileArgs* dev_args = reinterpret_cast<TileArgs*>(lead->d_many_args.get());
+    uint32_t* counter = reinterpret_cast<uint32_t*>(dev_args + n);   // (not owned: the claim counter behind the arguments)
     // every slice's preparation on the lead's stream, behind whatever its own context's stream still holds for it
     for (int i = 0; i < n; ++i) {
         bf_ctx* c = ctxs[i];
@@ -200,14 +182,9 @@ int bf_local_run_tiles(bf_ctx* c, const bf_local_tile_opts* o, bf_local_state* s
     int rc = tiles_prepare(c, &to, c->stream, ta, false);   // (the counting sort by sensor tile; the rolling optimizers' states are not used)
     if (rc != BF_OK) return rc;
     const int nt = o->grid_rows * o->grid_cols;
-    if (nt > c->ltile_alloc) {
-        if (c->d_ltile) HIP_TRY(c, hipFree(c->d_ltile));
-        c->d_ltile = nullptr; c->ltile_alloc = 0;
-        HIP_TRY(c, hipMalloc(&c->d_ltile, (size_t)nt * (sizeof(bf_local_state) + sizeof(int32_t))));
-        c->ltile_alloc = nt;
-    }
-    bf_local_state* d_states = static_cast<bf_local_state*>(c->d_ltile);
-    int32_t* d_rcs = reinterpret_cast<int32_t*>(d_states + c->ltile_alloc);
+    HIP_TRY(c, c->d_ltile.grow((size_t)nt * (sizeof(bf_local_state) + sizeof(int32_t))));
+    bf_local_state* d_states = reinterpret_cast<bf_local_state*>(c->d_ltile.get());
+    int32_t* d_rcs = reinterpret_cast<int32_t*>(d_states + nt);   // (not owned: behind the states in d_ltile)
     TileGrid g;
     g.rows = o->grid_rows; g.cols = o->grid_cols; g.res_x = o->sensor_res_x; g.res_y = o->sensor_res_y;
     {
@@ -252,6 +229,15 @@ void project_one(int32_t fr_x, int32_t fr_y, int64_t t, float kx, float ky, doub
     *pr_y = (double)(float)fr_y - (double)py / 10000.0;
 }
 
+// point planes, score and image of the contrast-score path (bf_projection_img shares them)
+int ensure_lplanes(bf_ctx* c) {
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, c->d_lplane[i].grow(c->cap_px));
+    HIP_TRY(c, c->d_lscore.grow(2));
+    HIP_TRY(c, c->d_limg.grow(c->cap_px));
+    HIP_TRY(c, c->h_lscore.grow(2));
+    return BF_OK;
+}
+
 int local_step(bf_ctx* c, double nx, double ny, double* score, bool want_img) {
     const bf_local_window& w = c->lwin;
     LocalGeom g;
@@ -268,7 +254,7 @@ int local_step(bf_ctx* c, double nx, double ny, double* score, bool want_img) {
     HIP_TRY(c, hipMemsetAsync(c->d_lscore, 0, 2 * sizeof(unsigned long long), c->stream));
     launch_local_project_count(e.xy, e.t, c->n, g, c->d_lplane[c->lcur], c->stream);
     if (launch_local_blur_score(c->d_lplane[c->lcur], c->d_lplane[c->lcur ^ 1], g, c->d_lscore,
-                                want_img ? c->d_limg : nullptr, c->stream) != 0)
+                                want_img ? c->d_limg.get() : nullptr, c->stream) != 0)
         return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7 (got %d)", w.scale);
     c->lcur ^= 1;
     HIP_TRY(c, hipGetLastError());
@@ -311,12 +297,8 @@ int bf_local_set_window(bf_ctx* c, int32_t scale, int32_t wsz, int32_t c_fr_x, i
     w.scale_img_y = w.metric_wsizey + scale;
     if ((size_t)w.scale_img_x * (size_t)w.scale_img_y > c->cap_px)
         return fail(c, BF_ERR_CAPACITY, "window %d x %d exceeds the image capacity", w.scale_img_x, w.scale_img_y);
-    if (!c->d_lplane[0]) {
-        for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMalloc(&c->d_lplane[i], c->cap_px * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_lscore, 2 * sizeof(unsigned long long)));
-        HIP_TRY(c, hipMalloc(&c->d_limg, c->cap_px));
-        HIP_TRY(c, hipHostMalloc(&c->h_lscore, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-    }
+    int rc = ensure_lplanes(c);
+    if (rc != BF_OK) return rc;
     // a new window lays the planes out afresh
     for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMemsetAsync(c->d_lplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
     c->lcur = 0;
@@ -392,12 +374,7 @@ int bf_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, in
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
     if (rc != BF_OK) return rc;
-    if (!c->d_lplane[0]) {
-        for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMalloc(&c->d_lplane[i], c->cap_px * sizeof(uint32_t)));
-        HIP_TRY(c, hipMalloc(&c->d_lscore, 2 * sizeof(unsigned long long)));
-        HIP_TRY(c, hipMalloc(&c->d_limg, c->cap_px));
-        HIP_TRY(c, hipHostMalloc(&c->h_lscore, 2 * sizeof(unsigned long long), hipHostMallocDefault));
-    }
+    if ((rc = ensure_lplanes(c)) != BF_OK) return rc;
     // the point planes are shared with the contrast-score path: lay them out afresh for this geometry
     for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMemsetAsync(c->d_lplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
     c->have_lwin = false;
@@ -442,13 +419,11 @@ int bf_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, in
     }
     g.x_shift = -double(res_x / 2) * double(scale) + double(g.mx) / 2.0;     // :677-678 with x_min = 0, x_max = RES_X
     g.y_shift = -double(res_y / 2) * double(scale) + double(g.my) / 2.0;
-    if (!c->d_col_planes) {
-        HIP_TRY(c, hipMalloc(&c->d_col_planes, c->cap_px * 20));   // 2 x i64 sums + u32 count per pixel
-        HIP_TRY(c, hipMalloc(&c->d_col_img, c->cap_px * 3));
-    }
+    HIP_TRY(c, c->d_col_planes.grow(c->cap_px * 20));   // 2 x i64 sums + u32 count per pixel
+    HIP_TRY(c, c->d_col_img.grow(c->cap_px * 3));
     HIP_TRY(c, hipMemsetAsync(c->d_col_planes, 0, px * 20, c->stream));
     const bf_ctx::EvSet& e = c->set[c->cs];
-    unsigned long long* sums = reinterpret_cast<unsigned long long*>(c->d_col_planes);
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(c->d_col_planes.get());
     launch_color_time(e.xy, e.t, e.p, c->has_noise ? c->d_noise : nullptr, c->n, g,
                       reinterpret_cast<uint32_t*>(sums + 2 * px), sums, sums + px, c->d_col_img, c->stream);
     HIP_TRY(c, hipGetLastError());

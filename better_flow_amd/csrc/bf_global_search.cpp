@@ -9,38 +9,24 @@ struct GlobalSearch {
     bool have = false;
     long long n = 0;                        // events of the slice the window was set on
     GlobalGeom g;
-    double* d_state = nullptr;              // 6 arrays of state_cap doubles (GlobalEventState)
-    long long state_cap = 0;
-    uint32_t *d_pts = nullptr, *d_win = nullptr;   // batch_cap planes each
-    int batch_cap = 0;
-    long long plane_alloc = 0;              // the plane size they were allocated for
-    GlobalCand* d_cands = nullptr;
-    unsigned long long* d_S = nullptr;
-    long long cand_cap = 0;
-    uint8_t* d_img = nullptr;
-    size_t img_cap = 0;
-    float* d_scores = nullptr;
-    size_t scores_cap = 0;
+    DevArray<double> d_state;               // 6 arrays of d_state.size() / 6 doubles (GlobalEventState)
+    DevArray<uint32_t> d_pts, d_win;        // the point / window planes of one batch of candidates
+    DevArray<GlobalCand> d_cands;
+    DevArray<unsigned long long> d_S;
+    DevArray<uint8_t> d_img;
+    DevArray<float> d_scores;
     std::vector<GlobalCand> h_cands;
 
     GlobalEventState state() const {
         GlobalEventState s;
-        const long long k = state_cap;
+        const long long k = (long long)(d_state.size() / 6);
         s.max_score = d_state; s.best_nx = d_state + k; s.best_ny = d_state + 2 * k; s.best_nz = d_state + 3 * k;
         s.best_pr_x = d_state + 4 * k; s.best_pr_y = d_state + 5 * k;
         return s;
     }
 };
 
-void global_free(bf_ctx* c) {
-    GlobalSearch* gs = c->glob;
-    if (!gs) return;
-    void* bufs[] = {gs->d_state, gs->d_pts, gs->d_win, gs->d_cands, gs->d_S, gs->d_img, gs->d_scores};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    delete gs;
-    c->glob = nullptr;
-}
+void GlobalSearchFree::operator()(GlobalSearch* g) const { delete g; }
 
 extern "C" {
 
@@ -60,27 +46,15 @@ GlobalCand make_cand(double nx, double ny, double nz) {
 
 // buffers for batches of up to `nb` candidates of the current window
 int ensure_batch(bf_ctx* c, GlobalSearch* gs, int nb) {
-    const long long plane = gs->g.plane;
-    if (gs->batch_cap >= nb && gs->plane_alloc == plane) return BF_OK;
-    if (gs->d_pts) HIP_TRY(c, hipFree(gs->d_pts));
-    if (gs->d_win) HIP_TRY(c, hipFree(gs->d_win));
-    gs->d_pts = gs->d_win = nullptr;
-    gs->batch_cap = 0;
-    HIP_TRY(c, hipMalloc(&gs->d_pts, (size_t)nb * (size_t)plane * sizeof(uint32_t)));
-    HIP_TRY(c, hipMalloc(&gs->d_win, (size_t)nb * (size_t)plane * sizeof(uint32_t)));
-    gs->batch_cap = nb;
-    gs->plane_alloc = plane;
+    const size_t need = (size_t)nb * (size_t)gs->g.plane;
+    HIP_TRY(c, gs->d_pts.grow(need));
+    HIP_TRY(c, gs->d_win.grow(need));
     return BF_OK;
 }
 
 int ensure_cands(bf_ctx* c, GlobalSearch* gs, long long k) {
-    if (gs->cand_cap >= k) return BF_OK;
-    if (gs->d_cands) HIP_TRY(c, hipFree(gs->d_cands));
-    if (gs->d_S) HIP_TRY(c, hipFree(gs->d_S));
-    gs->d_cands = nullptr; gs->d_S = nullptr; gs->cand_cap = 0;
-    HIP_TRY(c, hipMalloc(&gs->d_cands, (size_t)k * sizeof(GlobalCand)));
-    HIP_TRY(c, hipMalloc(&gs->d_S, (size_t)k * sizeof(unsigned long long)));
-    gs->cand_cap = k;
+    HIP_TRY(c, gs->d_cands.grow((size_t)k));
+    HIP_TRY(c, gs->d_S.grow((size_t)k));
     return BF_OK;
 }
 
@@ -150,17 +124,11 @@ int bf_global_set_window(bf_ctx* c, int32_t scale, int32_t metric_wsize, bf_glob
     const long long plane = (long long)w.scale_bordered_img_x * w.scale_bordered_img_y;
     if (plane * 8 > kGlobalBatchBytes)
         return fail(c, BF_ERR_CAPACITY, "bordered image %d x %d is too large", w.scale_bordered_img_x, w.scale_bordered_img_y);
-    if (!c->glob) c->glob = new GlobalSearch();
-    GlobalSearch* gs = c->glob;
+    if (!c->glob) c->glob.reset(new GlobalSearch());
+    GlobalSearch* gs = c->glob.get();
     gs->have = false;
     c->glob_valid = false;
-    if (gs->state_cap < (long long)c->n) {
-        if (gs->d_state) HIP_TRY(c, hipFree(gs->d_state));
-        gs->d_state = nullptr; gs->state_cap = 0;
-        const long long cap = std::max((long long)c->n, (long long)c->cap_events);
-        HIP_TRY(c, hipMalloc(&gs->d_state, (size_t)cap * 6 * sizeof(double)));
-        gs->state_cap = cap;
-    }
+    HIP_TRY(c, gs->d_state.grow((size_t)c->cap_events * 6));   // (n <= cap_events: one allocation for every slice)
     GlobalGeom& g = gs->g;
     g.scale = scale; g.mw = metric_wsize;
     g.xs = w.x_min * scale; g.ys = w.y_min * scale;
@@ -184,29 +152,19 @@ int bf_global_project_all(bf_ctx* c, double nx, double ny, double nz, uint8_t* i
     int rc = global_ready(c);
     if (rc != BF_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    GlobalSearch* gs = c->glob;
+    GlobalSearch* gs = c->glob.get();
     const bf_global_window& w = gs->w;
     const size_t img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
     const size_t sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
     if ((rc = ensure_cands(c, gs, 1)) != BF_OK) return rc;
-    if (img_out && gs->img_cap < img_px) {
-        if (gs->d_img) HIP_TRY(c, hipFree(gs->d_img));
-        gs->d_img = nullptr; gs->img_cap = 0;
-        HIP_TRY(c, hipMalloc(&gs->d_img, img_px));
-        gs->img_cap = img_px;
-    }
-    if (scores_out && gs->scores_cap < sc_px) {
-        if (gs->d_scores) HIP_TRY(c, hipFree(gs->d_scores));
-        gs->d_scores = nullptr; gs->scores_cap = 0;
-        HIP_TRY(c, hipMalloc(&gs->d_scores, sc_px * sizeof(float)));
-        gs->scores_cap = sc_px;
-    }
+    if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
+    if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
     gs->h_cands.assign(1, make_cand(nx, ny, nz));
     HIP_TRY(c, hipMemcpyAsync(gs->d_cands, gs->h_cands.data(), sizeof(GlobalCand), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, sizeof(unsigned long long), c->stream));
     if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
     if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
-    if ((rc = run_candidates(c, gs, 0, 1, img_out ? gs->d_img : nullptr, scores_out ? gs->d_scores : nullptr)) != BF_OK)
+    if ((rc = run_candidates(c, gs, 0, 1, img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr)) != BF_OK)
         return rc;
     unsigned long long S = 0;
     HIP_TRY(c, hipMemcpyAsync(&S, gs->d_S, sizeof(S), hipMemcpyDeviceToHost, c->stream));
@@ -243,7 +201,7 @@ int bf_global_search(bf_ctx* c, const bf_global_search_opts* opts, bf_global_res
     if (k > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "%lld candidates (more than 2^26)", k);
     if (surface_out && surface_cap < k) return fail(c, BF_ERR_ARG, "surface buffer holds %lld of %lld", (long long)surface_cap, k);
     HIP_TRY(c, hipSetDevice(c->device));
-    GlobalSearch* gs = c->glob;
+    GlobalSearch* gs = c->glob.get();
     gs->h_cands.resize((size_t)k);
     for (long long i = 0; i < nxc; ++i)
         for (long long j = 0; j < nyc; ++j) gs->h_cands[(size_t)(i * nyc + j)] = make_cand(xs[i], ys[j], o.nz);
@@ -275,7 +233,7 @@ int bf_global_get_events(bf_ctx* c, double* max_score, double* best_nx, double* 
     int rc = global_ready(c);
     if (rc != BF_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    GlobalSearch* gs = c->glob;
+    GlobalSearch* gs = c->glob.get();
     const size_t n = (size_t)gs->n;
     if (n == 0) return BF_OK;
     const GlobalEventState st = gs->state();

@@ -191,15 +191,8 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
                 int rc = ensure_cplanes(c);
                 if (rc == BF_OK) rc = ensure_bin_buffers(c, f);
                 if (rc != BF_OK) return rc;
-                const int nt = f.nbr * f.nbc;
-                if (nt > c->ftab_alloc) {
-                    if (c->d_ftab) HIP_TRY(c, hipFree(c->d_ftab));
-                    c->d_ftab = nullptr;
-                    HIP_TRY(c, hipMalloc(&c->d_ftab, (size_t)nt * sizeof(FusedTab)));
-                    c->ftab_alloc = nt;
-                }
-                for (int i = 0; i < 2; ++i)
-                    if (!c->set[i].p2) HIP_TRY(c, hipMalloc(&c->set[i].p2, (size_t)c->cap_events * sizeof(float2)));
+                HIP_TRY(c, c->d_ftab.grow((size_t)f.nbr * f.nbc * kFusedTabWords));
+                for (int i = 0; i < 2; ++i) HIP_TRY(c, c->set[i].p2.grow((size_t)c->cap_events));
                 c->fgrid = f;
                 c->fused_ok = true;
                 // Contexts that share the GPU: with dense slices the two loop kernels are bandwidth-bound and the tail-update
@@ -418,7 +411,7 @@ int bf_fast_model(bf_ctx* c, const float* img, int32_t rows, int32_t cols, bf_mo
     HIP_TRY(c, hipGetLastError());
     int rc = d2h_state(c);
     if (rc != BF_OK) return rc;
-    const bf_model& m = c->h_state->model;
+    const bf_model& m = c->h_state[0].model;
     model->cx = m.cx; model->cy = m.cy;
     model->dx = m.dx; model->dy = m.dy;
     model->rot = m.rot; model->div = m.div;
@@ -433,7 +426,7 @@ static int materialize_outputs(bf_ctx* c) {
     if (!c->out_sorted) return BF_OK;
     c->out_sorted = false;
     if (!c->has_perm || c->n == 0) return BF_OK;
-    if (!c->d_out_tmp) HIP_TRY(c, hipMalloc(&c->d_out_tmp, (size_t)c->cap_events * sizeof(double2)));
+    HIP_TRY(c, c->d_out_tmp.grow((size_t)c->cap_events));
     const uint32_t* perm = c->set[c->cs].perm;
     launch_unpermute(c->d_nxny, perm, c->d_out_tmp, c->n, c->stream);
     std::swap(c->d_nxny, c->d_out_tmp);

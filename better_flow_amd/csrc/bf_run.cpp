@@ -51,12 +51,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
         return BF_SKIPPED;
     }
 
-    if (o.trace_cap > c->trace_alloc) {
-        if (c->d_trace) HIP_TRY(c, hipFree(c->d_trace));
-        c->d_trace = nullptr;
-        HIP_TRY(c, hipMalloc(&c->d_trace, (size_t)o.trace_cap * sizeof(bf_trace_rec)));
-        c->trace_alloc = o.trace_cap;
-    }
+    if (o.trace_cap > 0) HIP_TRY(c, c->d_trace.grow((size_t)o.trace_cap));
     c->p_clean = false;   // the loop warps the events
     // One slice context alone on the GPU: the one-kernel iteration when the slice qualifies (bf_set_cloud), else the
     // two-kernel tile-binned loop when the slice is dense enough for it, else global atomics.
@@ -198,29 +193,17 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
     // exchange their moment sums through memory -- for a context that has the GPU to itself (two such kernels from two
     // contexts could each hold half of the CUs and wait for the other half).
     if (persist) {
-        const int nsub = c->fgrid.TSR / 16, nrec = c->fgrid.nbr * c->fgrid.nbc * nsub;
-        if (nrec > c->xrec_alloc) {
-            if (c->d_xrec) { HIP_TRY(c, hipStreamSynchronize(c->stream)); HIP_TRY(c, hipFree(c->d_xrec)); }
-            c->d_xrec = nullptr;
-            HIP_TRY(c, hipMalloc(&c->d_xrec, (size_t)2 * (size_t)nrec * 32 * sizeof(unsigned long long)));
-            HIP_TRY(c, hipMemsetAsync(c->d_xrec, 0, (size_t)2 * (size_t)nrec * 32 * sizeof(unsigned long long), c->stream));
-            c->xrec_alloc = nrec;
-        }
-        // (each buffer under its own check: an allocation that fails half-way must not leave the others looking ready)
-        if (!c->d_xred) {
-            HIP_TRY(c, hipMalloc(&c->d_xred, (size_t)2 * 16 * 32 * sizeof(unsigned long long)));
-            HIP_TRY(c, hipMemsetAsync(c->d_xred, 0, (size_t)2 * 16 * 32 * sizeof(unsigned long long), c->stream));
-        }
-        if (!c->d_verdict) {
-            HIP_TRY(c, hipMalloc(&c->d_verdict, 64));
-            HIP_TRY(c, hipMemsetAsync(c->d_verdict, 0, 64, c->stream));
-        }
-        if (!c->h_broken) {
-            HIP_TRY(c, hipHostMalloc(&c->h_broken, 64, hipHostMallocDefault));
-            *c->h_broken = 0;
-        }
-        for (int i = 0; i < 4; ++i)
-            if (!c->d_xscratch[i]) HIP_TRY(c, hipMalloc(&c->d_xscratch[i], (size_t)c->cap_events * sizeof(float2)));
+        const size_t nrec = (size_t)c->fgrid.nbr * c->fgrid.nbc * (c->fgrid.TSR / 16);
+        bool fresh;
+        HIP_TRY(c, c->d_xrec.grow(2 * nrec * 32, &fresh));
+        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_xrec, 0, 2 * nrec * 32 * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, c->d_xred.grow(2 * 16 * 32, &fresh));
+        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_xred, 0, 2 * 16 * 32 * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, c->d_verdict.grow(8, &fresh));
+        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_verdict, 0, 64, c->stream));
+        HIP_TRY(c, c->h_broken.grow(16, &fresh));
+        if (fresh) *c->h_broken = 0;
+        for (int i = 0; i < 4; ++i) HIP_TRY(c, c->d_xscratch[i].grow((size_t)c->cap_events));
     }
     bool want_rebin = false;
     int last_rebin_at = 0;
@@ -304,7 +287,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
         if (host_timing && batch < 40)
             fprintf(stderr, "persist round %d: it %d done %d need_rebin %d redo %d last_j %d rebins %d rc %d launches %d ovf_total %u\n", batch, ws.hot.it,
                     ws.hot.done, ws.hot.need_rebin, ws.hot.redo, ws.last_j, ws.hot.rebins, ws.rc, ws.hot.spare_, ws.ovf_total);
-        if (*reinterpret_cast<volatile int*>(c->h_broken)) {
+        if (*reinterpret_cast<volatile int*>(c->h_broken.get())) {
             *c->h_broken = 0;
             return fail(c, BF_ERR_HIP, "persistent loop kernel: a committed launch could not be read back");
         }
@@ -548,7 +531,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
         // A cold run is polled one batch behind the launches, so its wait can sleep (the wake-up latency hides
         // behind the batch already queued) instead of burning a host core per slice context; a warm start waits
         // for the batch it has just launched and spins.
-        hipEvent_t* pev = c->poll_ev;
+        const Event* pev = c->poll_ev;
         HIP_TRY(c, hipEventRecord(pev[batch & 1], c->stream));
         if (batch == 0 && !quick_warm) continue;
         if (quick_warm) {   // look at this batch straight away

@@ -26,17 +26,17 @@ static int upload_ring(bf_ctx* c, const ADDR* ring_x, const ADDR* ring_y, const 
     const int slot = (c->pend_head + c->pend_count) & 1;
     auto body = [=]() -> int {
     if (c->staged_valid[slot]) HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->staged[slot], 0));
-    if (!c->d_in_ts[slot]) HIP_TRY(c, hipMalloc(&c->d_in_ts[slot], (size_t)c->cap_events * sizeof(unsigned long long)));
+    HIP_TRY(c, c->d_in_ts[slot].grow((size_t)c->cap_events));
     const bool narrow = sizeof(ADDR) == 2;
-    if (narrow && !c->d_in16[slot]) HIP_TRY(c, hipMalloc(&c->d_in16[slot], (size_t)c->cap_events * 2 * sizeof(uint16_t)));
-    if (ring_noise && !c->d_in_noise[slot]) HIP_TRY(c, hipMalloc(&c->d_in_noise[slot], (size_t)c->cap_events));
+    if (narrow) HIP_TRY(c, c->d_in16[slot].grow((size_t)c->cap_events * 2));
+    if (ring_noise) HIP_TRY(c, c->d_in_noise[slot].grow((size_t)c->cap_events));
     // destinations of the two address columns: the slot's int32 staging arrays, or (16-bit form) two halves of d_in16
-    ADDR* dx = narrow ? reinterpret_cast<ADDR*>(c->d_in16[slot]) : reinterpret_cast<ADDR*>(slot ? c->d_in2[0] : c->d_in_x);
-    ADDR* dy = narrow ? reinterpret_cast<ADDR*>(c->d_in16[slot] + c->cap_events) : reinterpret_cast<ADDR*>(slot ? c->d_in2[1] : c->d_in_y);
+    ADDR* dx = narrow ? reinterpret_cast<ADDR*>(c->d_in16[slot].get()) : reinterpret_cast<ADDR*>((slot ? c->d_in2[0] : c->d_in_x).get());
+    ADDR* dy = narrow ? reinterpret_cast<ADDR*>(c->d_in16[slot] + c->cap_events) : reinterpret_cast<ADDR*>((slot ? c->d_in2[1] : c->d_in_y).get());
     const int64_t n0 = (first + n <= cap) ? n : cap - first, n1 = n - n0;   // [first, first + n0) then [0, n1)
     HIP_TRY(c, hipMemcpyAsync(dx, ring_x + first, (size_t)n0 * sizeof(ADDR), hipMemcpyHostToDevice, c->copy_stream));
     HIP_TRY(c, hipMemcpyAsync(dy, ring_y + first, (size_t)n0 * sizeof(ADDR), hipMemcpyHostToDevice, c->copy_stream));
-    TS* dts = reinterpret_cast<TS*>(c->d_in_ts[slot]);   // (cap_events x 8 bytes: the 32-bit form uses half of it)
+    TS* dts = reinterpret_cast<TS*>(c->d_in_ts[slot].get());   // (cap_events x 8 bytes: the 32-bit form uses half of it)
     HIP_TRY(c, hipMemcpyAsync(dts, ring_ts + first, (size_t)n0 * sizeof(TS), hipMemcpyHostToDevice, c->copy_stream));
     if (ring_noise) HIP_TRY(c, hipMemcpyAsync(c->d_in_noise[slot], ring_noise + first, (size_t)n0, hipMemcpyHostToDevice, c->copy_stream));
     if (n1 > 0) {

@@ -713,6 +713,43 @@ def test_staging_slots_are_not_overwritten_early(accel_mod):
     acc.close()
 
 
+def test_close_with_both_upload_slots_pending(accel_mod):
+    """bf_destroy with both slots pending: the first upload issued, its early staging running on the copy stream; the second
+    only recorded ("defer_uploads").  The teardown waits for both streams before anything is freed and drops the recorded
+    upload unrun; a new context on the device then solves a slice to the bits of a reference run.  The pinned inputs belong to
+    a second context, closed after the first (Accel.close frees a context's own pinned buffers before bf_destroy)."""
+    H, W, s = 260, 346, 3
+    sls = [synth.make_slice(600000, H, W, 0.03, seed=120 + i) for i in range(2)]
+    nmax = max(len(sl["t"]) for sl in sls)
+    kw = dict(max_events=nmax, max_rows=s * H + s, max_cols=s * W + s)
+
+    def solve(acc):
+        sl = sls[0]
+        acc.upload_events(sl["fr_x"], sl["fr_y"], sl["t"])
+        acc.set_cloud(s, H, W)
+        o = acc.default_opts()
+        o.res_x, o.res_y, o.max_iter = H, W, 12
+        rc, m, info = acc.run(o)
+        return rc, info.iterations, m.as_dict(), tuple(a.tobytes() for a in acc.compute_uv())
+
+    acc = accel_mod.Accel(**kw)
+    ref = solve(acc)
+    acc.close()
+    feeder = accel_mod.Accel(**kw)
+    pin = [[feeder.pinned_int32(nmax) for _ in range(3)] for _ in range(2)]
+    acc = accel_mod.Accel(**kw)
+    for k, sl in enumerate(sls):
+        n = len(sl["t"])
+        pin[k][0][:n], pin[k][1][:n], pin[k][2][:n] = sl["fr_x"], sl["fr_y"], sl["t"]
+        acc.set_option("defer_uploads", k)   # the first upload goes out at once, the second is only recorded
+        acc.upload_events_async(pin[k][0], pin[k][1], pin[k][2], n)
+    acc.close()
+    feeder.close()
+    acc = accel_mod.Accel(**kw)
+    assert solve(acc) == ref
+    acc.close()
+
+
 def test_full_size_config2(oracle_lib, accel_mod):
     """BASELINE config 2 at full size (1M events, 346x260, scale 3): event-count image bit-exact,
     time image within 1e-6, first iterations of the loop on the oracle's trajectory, binned and
