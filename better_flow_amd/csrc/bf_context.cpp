@@ -197,13 +197,11 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         return BF_OK;
     }
     if (!strcmp(key, "one_kernel")) {
-        *value = (c->fused_ok && (!c->opt_co_schedule || c->fused_shared)) ? 1 : 0;
+        *value = plan_one_kernel(c) ? 1 : 0;
         return BF_OK;
     }
     if (!strcmp(key, "persistent")) {   // would bf_run, called now, take the persistent loop kernel?
-        *value = (c->fused_ok && !c->opt_co_schedule && (c->opt_persist == 2 || (c->opt_persist == 1 && c->pending_warp)) &&
-                  g_live_ctx[c->device & 63].load() == 1 &&
-                  fused_loop_resident(c->win.scale / 2, c->fgrid.TSR, c->n_cus, c->fgrid.nbr * c->fgrid.nbc)) ? 1 : 0;
+        *value = plan_persistent(c) ? 1 : 0;
         return BF_OK;
     }
     if (!strcmp(key, "persist_giveups")) {   // launches of the persistent loop kernel that gave up and undid themselves

@@ -1,4 +1,4 @@
-// bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_run.cpp,
+// bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
 // bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  Nothing here is part
@@ -37,9 +37,8 @@ using bf_mem::HostArray;
 using bf_mem::MappedArray;
 using bf_mem::Stream;
 
-// Contexts alive per device in this process (defined in bf_context.cpp).  The persistent loop kernel needs every one of its
-// work-groups resident at once; two such kernels from two contexts could each hold part of the CUs and wait for the rest,
-// so a context takes it only while it is the one context on its device.
+// Contexts alive per device in this process (defined in bf_context.cpp): the persistent loop kernel is for a context alone on its
+// device (plan_persistent).
 extern std::atomic<int> g_live_ctx[64];
 
 struct GlobalSearch;   // bf_global_search.cpp: the exhaustive search's window, scratch and per-event state
@@ -58,7 +57,7 @@ struct ProfRec {
 // Margins of the tile-binned loops, in scaled pixels: how far an event may drift from where the counting sort found it before
 // its bin must be re-sorted.  Swept flat over 4 .. 8 in rounds 3 and 4 (EXPERIMENTS: 195.9 / 195.1 / 193.1 Mevents/s at 8 / 6 / 4),
 // so no longer an option.  The tile shape, the scatter work-groups' size and their events per thread are chosen per slice
-// (bf_set_cloud, bf_run): the options that overrode them went with it.
+// (bf_plan.cpp): the options that overrode them went with it.
 constexpr int kBinMargin = 8;      // two-kernel loop: D of BinGrid (capped at half the smaller tile side)
 constexpr int kFusedMargin = 8;    // one-kernel loops: D on top of the stencil halo H = scale / 2 + 1
 
@@ -83,12 +82,12 @@ struct bf_ctx {
     bool opt_co_schedule = false;    // several slice contexts share the GPU: the update runs in the stencil kernel's last work-group
     int opt_bin_pack_limit = 64;     // bits available to the per-bin packing (lower only to test the fallback)
     int n_cus = 0;
-    bool use_binned = false;         // decided per slice in bf_set_cloud
+    bool use_binned = false;         // decided per slice (plan_slice)
     BinGrid grid;
     // one-kernel iteration (k_fused_pass): the loop of a context that has the GPU to itself
     int opt_fused = 1;               // 0 never, 1 where it is the faster loop (small slices on small images; sparser ones only when
                                      // the context is co-scheduled with others), 2 whenever possible
-    bool fused_ok = false;           // decided per slice in bf_set_cloud
+    bool fused_ok = false;           // decided per slice (plan_slice)
     bool fused_shared = false;       // ... and it is also the loop to take when the context shares the GPU ("co_schedule")
     BinGrid fgrid;                   // its sort grid: keys = (tile, zone)
     DevArray<uint32_t> d_ftab;       // FusedTab per tile
@@ -112,7 +111,7 @@ struct bf_ctx {
     DevArray<unsigned long long> d_slabs;
     DevArray<uint16_t> d_cidx;       // compact lists: pixel index per entry (same slot count as d_slabs)
     DevArray<uint32_t> d_chdr;       // compact lists: entries per bin
-    int fmt = 0;                     // what this slice's scatter hands to the stencil: 0 dense slabs, 2 event lists, 3 own pixels + margin plane (bf_set_cloud)
+    int fmt = 0;                     // what this slice's scatter hands to the stencil: 0 dense slabs, 2 event lists, 3 own pixels + margin plane (plan_slice)
     int opt_bin_compact = 1;         // 0 never, 1 when the image is sparse (decided per iteration on the device), 2 always
     // interior + margin format of a dense slice (fmt 3, bf_scatter.hip: flush_split): 0 never, 1 when it is the faster one, 2 always
     int opt_bin_split = 1;
@@ -163,7 +162,7 @@ struct bf_ctx {
     // staging kernels, the events: ~25 us of host time) are issued by the next bf_run once that run's first batch of kernels is in
     // the queue -- or by whoever needs the slot sooner (bf_commit_upload, bf_wait_uploads).  For a single-threaded caller
     // driving one warm-started chain those 25 us otherwise sit between two runs, with the GPU idle.
-    int opt_sep_update = 1;          // co-scheduled contexts: the update as a kernel of its own -- 0 never, 1 for event lists, 2 always (bf_run.cpp)
+    int opt_sep_update = 1;          // co-scheduled contexts: the update as a kernel of its own -- 0 never, 1 for event lists, 2 always (plan_run)
     bool opt_defer_uploads = false;
     std::function<int()> deferred[2];
     std::mutex stats_mu;                          // fold_stats: bf_set_cloud's thread and an uploading thread (stage_early's guard) may both fold
@@ -241,9 +240,28 @@ struct bf_ctx {
 // the live slice's per-event flow in upload order on the device, or null (bf_operators.cpp)
 extern "C" int ctx_device_uv(bf_ctx* c, const double2** uv);
 
+// Which loop a slice runs (bf_plan.cpp): plan_slice once per slice, plan_run once per run; nothing else decides it.
+struct SlicePlan {
+    BinGrid grid{}, fgrid{};         // the tile-binned loop's bin grid (zw aside), the one-kernel iteration's sort grid
+    bool binned = false, fused_ok = false, fused_shared = false;   // bf_ctx: use_binned, fused_ok, fused_shared
+    int fmt = 0, zw = 0;             // bf_ctx: fmt, grid.zw
+};
+struct RunPlan {
+    bool fused = false, binned = false, persist = false;   // one-kernel iteration, tile-binned (either loop), persistent kernel
+    bool head_update = false, sep_update = false;   // the update at the next scatter launch's head / in k_finish_update
+    bool split = false;              // the two-kernel loop on own pixels + margin plane (fmt 3)
+    int bin_threads = 0, ev_per_thread = 8;   // the scatter kernel's work-group size and events per thread
+    bool warm_start = false, prewarp = false, first_warp = false;   // bf_set_model's warp: by the first counting sort / iteration
+    bool quick_warm = false, snap_polled = false;   // polled batch by batch (a warm start expected to converge soon) / from the pinned snapshot
+    double drift_limit = 1e300;      // tile-binned loops: the drift since the sort that asks for a re-bin
+    bool head_like() const { return head_update || sep_update; }   // (the stencil kernel only accumulates)
+};
+SlicePlan plan_slice(const bf_ctx* c, const bf_window& w);
+bool plan_one_kernel(const bf_ctx* c);   // (and bf_get_stat)
+bool plan_persistent(const bf_ctx* c);   // (and bf_get_stat: without the back-off after a launch gave up)
+RunPlan plan_run(bf_ctx* c, const bf_run_opts& o);   // (takes one run of that back-off)
+
 namespace {
-
-
 
 int fail(bf_ctx* c, int code, const char* fmt, ...) {
     if (c) {
@@ -327,6 +345,13 @@ int bit_length(unsigned long long v) {
     return b;
 }
 
+// a warp by (dnx, dny) about (cx, cy), divergence div, rotation `angle` (cos / sin evaluated on the host: event.h:91-92,102-103)
+void set_warp(WarpParams& w, double dnx, double dny, double cx, double cy, double div, double angle) {
+    w.dnx = dnx; w.dny = dny; w.cx = cx; w.cy = cy; w.div = div;
+    w.c = std::cos(angle);
+    w.s = std::sin(angle);
+}
+
 WarpParams identity_warp() {
     WarpParams w;
     w.dnx = w.dny = w.cx = w.cy = w.div = 0.0;
@@ -390,12 +415,15 @@ StencilArgs st_args(bf_ctx* c, int buf, int check_done) {
 // which k_stencil instantiation reads the scatter result of the current mode
 int stencil_src(const bf_ctx* c, bool binned_pass) { return binned_pass ? 3 : (c->packed ? 0 : 1); }
 
+// grow(n), and zero the array on the context's stream when that allocated it
+template <class T> hipError_t grow_zeroed(bf_ctx* c, DevArray<T>& a, size_t n) {
+    bool fresh;
+    const hipError_t e = a.grow(n, &fresh);
+    return (e == hipSuccess && fresh) ? hipMemsetAsync(a, 0, n * sizeof(T), c->stream) : e;
+}
+
 int ensure_cplanes(bf_ctx* c) {
-    for (int i = 0; i < 2; ++i) {
-        bool fresh;
-        HIP_TRY(c, c->d_cplane[i].grow(c->cap_px, &fresh));
-        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_cplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
-    }
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, grow_zeroed(c, c->d_cplane[i], c->cap_px));
     return BF_OK;
 }
 
@@ -444,15 +472,12 @@ int ensure_bin_buffers(bf_ctx* c, const BinGrid& g) {
         c->bin_setup_done = true;
     }
     const size_t ne = (size_t)c->cap_events;
-    bool fresh;
     HIP_TRY(c, c->d_binid.grow(ne));
-    HIP_TRY(c, c->d_armed.grow(16, &fresh));
-    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_armed, 0, 64, c->stream));
+    HIP_TRY(c, grow_zeroed(c, c->d_armed, 16));
     const int rc = ensure_second_set(c);
     if (rc != BF_OK) return rc;
     const size_t nb = (size_t)g.nbins + 1;
-    HIP_TRY(c, c->d_hist_cnt.grow(kHistCopies * nb, &fresh));
-    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_hist_cnt, 0, kHistCopies * nb * sizeof(uint32_t), c->stream));
+    HIP_TRY(c, grow_zeroed(c, c->d_hist_cnt, kHistCopies * nb));
     HIP_TRY(c, c->d_bin_start.grow(nb));
     HIP_TRY(c, c->d_cursor.grow(nb));
     HIP_TRY(c, c->d_chdr.grow(nb * 580));   // event lists: 3 LR + 1 <= 577 key offsets per bin ((column zone, row) keys)
@@ -461,7 +486,6 @@ int ensure_bin_buffers(bf_ctx* c, const BinGrid& g) {
     HIP_TRY(c, c->d_cidx.grow(need));
     return BF_OK;
 }
-
 
 // Margin planes and per-bin lists of the interior + margin format.  Iteration j of a run adds to margin plane b0 ^ (j & 1) and
 // clears, bin by bin, what the lists say the previous executed launch left in the other one (flush_split); the host keeps
@@ -486,13 +510,8 @@ int ensure_margin_buffers(bf_ctx* c, const BinGrid& g) {
         int rc = margin_reset(c);
         if (rc != BF_OK) return rc;
     }
-    bool fresh;
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(c, c->d_mplane[i].grow(c->cap_px, &fresh));
-        if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_mplane[i], 0, c->cap_px * sizeof(unsigned long long), c->stream));
-    }
-    HIP_TRY(c, c->d_mcount.grow((size_t)g.nbins, &fresh));
-    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_mcount, 0, (size_t)g.nbins * sizeof(uint32_t), c->stream));
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, grow_zeroed(c, c->d_mplane[i], c->cap_px));
+    HIP_TRY(c, grow_zeroed(c, c->d_mcount, (size_t)g.nbins));
     HIP_TRY(c, c->d_mlist.grow((size_t)g.nbins * (size_t)mcap));
     c->m_nbins = g.nbins;
     c->m_cap = mcap;
@@ -526,13 +545,6 @@ int flush_pending(bf_ctx* c) {
     c->uv_valid = false;
     c->out_sorted = false;
     HIP_TRY(c, hipGetLastError());
-    return BF_OK;
-}
-
-int d2h_state(bf_ctx* c) {
-    HIP_TRY(c, hipMemcpyAsync(c->h_state, c->d_state, sizeof(DevState), hipMemcpyDeviceToHost,
-                              c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BF_OK;
 }
 
@@ -628,6 +640,5 @@ int streaming_setup(bf_ctx* c) {
     }
     return BF_OK;
 }
-
 
 }  // namespace

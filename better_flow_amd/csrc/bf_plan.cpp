@@ -1,0 +1,217 @@
+// bf_plan.cpp -- which loop a slice runs: bin grids and scatter format per slice (plan_slice), loop form, home of the update and
+// scatter sizing per run (plan_run).  Every rule is a measured crossover, and the measurement stands next to it.
+#include "bf_ctx.h"
+
+SlicePlan plan_slice(const bf_ctx* c, const bf_window& w) {
+    SlicePlan p;
+    const int scale = w.scale;
+    // Tile-binned scatter: usable when there is no noise mask and the bin grid fits the kernels' LDS.  Its own
+    // per-bin packing is decided on the device by the counting sort (k_bin_scan), with the overflow path as fallback.
+    BinGrid& g = p.grid;
+    // Tile shape: one work-group per bin.  Cost model of one iteration (calibrated on config 2, in us):
+    //   waves of work-groups x events per tile x 1.7 ns   (the fullest CU sets the length of the scatter kernel)
+    // + slab pixels x 2.3 ps                               (every slab pixel is written and re-read)
+    // over widths {16, 32, 64} (a power of two) and heights {32 .. 128}; ties go to the larger tile.  Small dense
+    // images get small tiles (enough bins to fill the CUs), large images large ones (less margin overhead).
+    // (the margin: kBinMargin, even; BF_DEBUG_MARGIN overrides it for tests)
+    const int bin_margin = c->dbg_margin > 0 ? ((c->dbg_margin + 1) & ~1) : kBinMargin;
+    g.TS = 64;
+    g.TSR = 64;
+    if (c->n_cus > 0) {
+        const double density = (double)c->n / ((double)w.scale_img_x * (double)w.scale_img_y);
+        double best = -1.0;
+        int best_area = 0;
+        for (int cols = 16; cols <= 64; cols *= 2) {
+            for (int rows = 32; rows <= 128; rows += 16) {
+                const int d = bin_margin > cols / 2 ? cols / 2 : bin_margin;
+                if ((size_t)(rows + 2 * d) * (cols + 2 * d) * 8 > 64 * 1024) continue;
+                const int nb = ((w.scale_img_x + rows - 1) / rows) * ((w.scale_img_y + cols - 1) / cols);
+                if (nb > 8192) continue;
+                const double cost = (double)((nb + c->n_cus - 1) / c->n_cus) * rows * cols * density * 1.7e-3 +
+                                    (double)nb * (rows + 2 * d) * (cols + 2 * d) * 2.3e-6;
+                if (best < 0 || cost < best * 0.999 || (cost <= best * 1.001 && rows * cols > best_area)) {
+                    best = cost; best_area = rows * cols; g.TS = cols; g.TSR = rows;
+                }
+            }
+        }
+    }
+    g.lg = 0;
+    while ((1 << g.lg) < g.TS) ++g.lg;
+    g.nbc = (w.scale_img_y + g.TS - 1) / g.TS;
+    const int tmin_ = g.TS < g.TSR ? g.TS : g.TSR;
+    g.D = bin_margin > tmin_ / 2 ? tmin_ / 2 : bin_margin;   // <= 2 x 2 bins per pixel
+    g.L = g.TS + 2 * g.D;
+    g.LR = g.TSR + 2 * g.D;
+    g.mul_r = (uint32_t)(0x100000000ull / (unsigned)g.TSR) + 1u;
+    g.mul_l = (uint32_t)(0x100000000ull / (unsigned)g.L) + 1u;
+    g.mul_h = (uint32_t)(0x100000000ull / (unsigned)(g.L / 2 > 0 ? g.L / 2 : 1)) + 1u;
+    g.nbr = (w.scale_img_x + g.TSR - 1) / g.TSR;
+    g.nbins = g.nbr * g.nbc;
+    // Density rule: every iteration writes and re-reads one slab pixel (8 B x (L / TS)^2) per image pixel, a global
+    // atomic costs ~48 ns per event; below ~1 event per 12 pixels the plain atomic scatter is the faster one
+    // (measured: 300k events on a 3550 x 6350 image, 0.41 vs 0.66 ms per iteration).
+    // ... on an image of tens of megapixels: the event-list form of the binned loop follows the events, and up to the
+    // 8.3 M pixels of a 1280x720 sensor at scale 3 it beats the atomics for sparse slices too (20k .. 500k events:
+    // 640x480 22 .. 28 us per iteration against 31 .. 40, 1280x720 48 .. 64 against 62 .. 86).
+    const bool dense = (double)w.scale_img_x * (double)w.scale_img_y < 12.0 * (double)c->n ||
+                       (double)w.scale_img_x * (double)w.scale_img_y <= 9.0e6;
+    p.binned = (c->opt_binned == 2 || (c->opt_binned == 1 && dense)) && !c->force_split && !c->has_noise && c->n > 0 &&
+               g.nbins <= 8192 && c->cap_events < (1ll << 29) &&   // (32-bit byte offsets into the event arrays: ld_idx)
+               (size_t)g.LR * g.L * 8 <= (size_t)kBinTileLdsMax && w.scale_img_x < (1 << 20);
+    // (<= 8192 bins x <= 156 KB: slabs, tiled image and margin plane stay below 2^31 bytes -- the stencil kernel's buffer loads
+    // carry 32-bit byte offsets, buf_ld_u64)
+
+    // The one-kernel iteration (k_fused_pass; used by bf_run unless the context is co-scheduled with others): image
+    // tiles of 32 x 64 pixels -- 64 x 64 when the nine sort keys per tile would not fit the counting sort -- and a
+    // margin D that keeps a tile's edge strips (H + D wide, H = scale / 2 + 1) from overlapping.
+    // Where it pays (measured on MI355X, one context, cold runs; us per iteration fused / best two-kernel or atomic loop):
+    //   240x180: 50k events 16.1 / 22.0, 200k 17.9 / 19.6, 400k 20.5 / 18.2;   346x260: 20k 16.0 / 17.1, 50k 15.9 / 19.6,
+    //   100k 17.5 / 23.1, 200k 17.8 / 20.2, 400k 19.6 / 20.3, 1M 26.8 / 19.7;   640x480: 20k .. 400k 31 .. 38 / 22 .. 34.
+    // The events of a tile's edge strips are warped by up to four work-groups (2.1 x the events at D = 8) and a
+    // dense slice meets in few LDS words, so "auto" takes it for slices of at most one event per two image pixels on
+    // images up to 1.2 M pixels; a launch chain half as long is what it buys there.
+    const double Pimg = (double)w.scale_img_x * (double)w.scale_img_y;
+    const bool fused_pays = Pimg <= 1.2e6 && 2.0 * (double)c->n <= Pimg;
+    if ((c->opt_fused == 2 || (c->opt_fused == 1 && fused_pays)) && c->opt_binned != 0 && !c->force_split && !c->has_noise && c->n > 0 && scale / 2 <= 4 &&
+        w.scale_img_x < (1 << 20) && (long long)c->n < (1ll << 31)) {
+        BinGrid& f = p.fgrid;
+        const int Hh = scale / 2 + 1;
+        auto tiles = [&](int rows) { return ((w.scale_img_x + rows - 1) / rows) * ((w.scale_img_y + 63) / 64); };
+        const int rows = tiles(32) * kFusedZones <= 8192 ? 32 : 64;
+        int Dm = c->dbg_margin > 0 ? c->dbg_margin : kFusedMargin;
+        if (Dm > rows / 2 - Hh) Dm = rows / 2 - Hh;
+        if (Dm >= 1 && tiles(rows) * kFusedZones <= 8192) {
+            f.TS = 64; f.lg = 6; f.TSR = rows; f.D = Dm; f.fz = Hh + Dm;
+            f.nbc = (w.scale_img_y + 63) / 64;
+            f.nbr = (w.scale_img_x + rows - 1) / rows;
+            f.nbins = f.nbr * f.nbc * kFusedZones;   // sort keys
+            f.mul_r = (uint32_t)(0x100000000ull / (unsigned)f.TSR) + 1u;
+            p.fused_ok = true;
+            // Contexts that share the GPU: with dense slices the two loop kernels are bandwidth-bound and the tail-update
+            // form keeps the CUs full, so the two-kernel loop stays; sparse slices remain launch-bound even with eight
+            // contexts in flight (346x260, 2 / 4 / 8 contexts: 50k events 12.4 / 11.4 / 10.6 us per iteration and slice
+            // against 16.7 / 14.6 / 12.8; 200k events 11.8 / 9.3 / 9.4 against 13.3 / 9.2 / 9.1).
+            p.fused_shared = c->opt_fused == 2 || 8.0 * (double)c->n <= Pimg;
+        }
+    }
+
+    // Dense slabs or event lists.  A dense slice (one event per four pixels or more) merges its events in the bin's LDS
+    // tile and writes the tile.  A sparse one writes lists, work and traffic following the events: one entry per EVENT
+    // and no LDS tile (a 1280x720 sensor with 1M events -- the tile of such a bin would fill the CU's LDS and leave one
+    // work-group per CU).  "auto" decides once per slice: the kernels are compiled per format.  Measured per iteration
+    // (dense / events): 1280x720 scale 3: 90 / 68 us; 640x480 scale 3: 44 / 52.  (A third form -- lists merged per pixel
+    // in the LDS tile, for small sensors at large scales: 346x260 scale 7 61 against 96 / 103 us -- was removed in round 5:
+    // no BASELINE configuration took it, and every form multiplies the bit-identity matrix.)
+    const size_t LLg = (size_t)g.LR * (size_t)g.L;
+    const bool lists_ok = p.binned && LLg <= 65536;                         // 16-bit tile-local pixel indices
+    const int mode = lists_ok ? c->opt_bin_compact : 0;
+    if (mode == 2 || (mode == 1 && 4.0 * (double)c->n < Pimg)) p.fmt = 2;
+    // Dense slices: the bin's own pixels + a margin plane instead of whole-tile slabs (flush_split).  It moves 0.6 x the
+    // slab bytes and a quarter of the stencil kernel's loads; "auto" takes it where that is what the iteration
+    // waits for -- a context that has the GPU to itself (update at the scatter head) on an image of >= 1.5 M
+    // pixels: 640x480 scale 3, 1M events: K1 14.7 -> 11.3 us, iteration 37.2 -> 32.9 us.  At 346x260 the loop is a
+    // latency chain and nothing moves (18.8 us either way); with the update in the stencil tail ("co_schedule") the
+    // lean scatter kernel LOSES 1.7 us per launch (8.0 -> 9.7 us at 346x260, value 196 -> 178 Mevents/s).
+    const bool split_pays = !c->opt_co_schedule && Pimg >= 1.5e6;
+    if (p.fmt == 0 && p.binned && (c->opt_bin_split == 2 || (c->opt_bin_split == 1 && split_pays)) && g.D >= 2 &&
+        (g.D & (g.D - 1)) == 0 && g.TS >= 4)   // (D a power of two)
+        p.fmt = 3;
+    // Event lists on 64-column bins (every sensor of BASELINE.json's configurations): entries sorted by (column zone,
+    // row), so that a stencil tile gathers from the bins beside its own only the zone that faces it (bf_scatter.hip,
+    // "event lists").  zw: the columns of a bin's tile a box sum of the neighbouring stencil tile can reach.
+    if (p.fmt == 2 && g.TS == 64 && g.L >= 2 * (g.D + scale / 2 + 1)) p.zw = g.D + scale / 2 + 1;
+    return p;
+}
+
+bool plan_one_kernel(const bf_ctx* c) {
+    // One slice context alone on the GPU: the one-kernel iteration when the slice qualifies (plan_slice), else the
+    // two-kernel tile-binned loop when the slice is dense enough for it, else global atomics.
+    return c->fused_ok && (!c->opt_co_schedule || c->fused_shared);
+}
+
+bool plan_persistent(const bf_ctx* c) {
+    // The persistent form of the one-kernel loop (bf_loop.hip): the work-groups stay resident over many iterations and
+    // exchange their moment sums through memory -- for a context that has the GPU to itself (two such kernels from two
+    // contexts could each hold half of the CUs and wait for the other half), when all tiles can be resident at once.
+    // A cold run re-bins a dozen times in its first iterations, and every re-bin ends a launch of the persistent kernel with
+    // a host round trip (measured on 50 000 events, 240x180: 25 us per iteration against 17); a warm-started slice of a stream
+    // -- the reference's own mode, ~115 iterations and one or two re-bins -- is where it pays (11.1 against 12.2 us per
+    // iteration all in): "auto" takes it for warm starts.
+    return plan_one_kernel(c) && !c->opt_co_schedule && (c->opt_persist == 2 || (c->opt_persist == 1 && c->pending_warp)) &&
+           g_live_ctx[c->device & 63].load() == 1 &&
+           fused_loop_resident(c->win.scale / 2, c->fgrid.TSR, c->n_cus, c->fgrid.nbr * c->fgrid.nbc);   // (else: one launch per iteration)
+}
+
+RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
+    RunPlan p;
+    p.fused = plan_one_kernel(c);
+    p.binned = c->use_binned || p.fused;
+    p.persist = plan_persistent(c);
+    // (g_live_ctx only knows this process: another process's kernels -- or anything else that keeps work-groups from becoming
+    // resident -- shows as a launch that gives up after 0.2 s.  The context then stays away from the kernel for a while.)
+    if (p.persist && c->persist_skip > 0) { --c->persist_skip; p.persist = false; }
+    // Tile-binned mode sorts the events by the tile of their CURRENT target, so a warm-start
+    // warp (bf_set_model) is applied before the sort rather than inside the first iteration.
+    p.warm_start = c->pending_warp;
+    p.prewarp = p.binned && c->pending_warp;   // fused into the first counting sort (k_bin_count<true>)
+    p.first_warp = c->pending_warp && !p.prewarp;
+    // (the persistent loop re-bins AT the request -- it returns for it --, the other loops one or two batches of launches
+    // after it: the same effective threshold)
+    if (p.binned) p.drift_limit = c->opt_bin_predict ? (p.persist ? 0.85 : 0.6) * (double)(p.fused ? c->fgrid.D : c->grid.D) : 1e300;
+    p.split = c->use_binned && !p.fused && c->fmt == 3;
+    // Where the model / loop update runs.  One slice context alone: at the head of the next warp+scatter launch (every
+    // work-group for itself; shortest iteration).  Several contexts sharing the GPU ("co_schedule"): in the last
+    // work-group of the stencil kernel -- a serial tail on ONE CU that the other contexts' kernels fill, instead of
+    // ~1.5 us on all 256 CUs.
+    p.head_update = p.fused || (p.binned && !c->opt_co_schedule);   // (the one-kernel loop has no other form)
+    // A third home ("sep_update", round 6): contexts that share the GPU run the lean scatter kernel and a stencil kernel that
+    // only ACCUMULATES (no drain of its atomics, no ticket, no serial tail), and the update is a kernel of its own
+    // (k_finish_update: one wave) ahead of every scatter launch, on ONE state buffer (nobody reads the state while that kernel
+    // writes it).  Bookkeeping -- accumulator parities, overflow slots, when a snapshot is behind a re-bin -- is the head
+    // form's.  A stencil work-group that has to see its fifteen atomics acknowledged and then wait for its ticket holds its LDS and a
+    // wave slot ~1 us longer -- 10 % of its life: with thousands of work-groups per launch (event lists: 8100 tiles at 1280x720)
+    // the third launch per iteration is the cheaper way (stencil kernel 42.7 -> 37.9 us under co_schedule, config 5's batch +2.7 %);
+    // with a few hundred (config 2: 752) the launch costs more than the tickets (bench 206.7 -> 200.9): "auto" takes it for event
+    // lists only.  Same bits either way.
+    p.sep_update = p.binned && !p.fused && !p.head_update && (c->opt_sep_update == 2 || (c->opt_sep_update == 1 && c->fmt == 2));
+    const double ev_per_bin = p.binned ? (double)c->n / (double)(c->grid.nbins > 0 ? c->grid.nbins : 1) : 0.0;
+    // Work-group size of the scatter kernel (bin_scatter_threads, bf_scatter.hip).  Dense tiles: 1024 threads for a context that
+    // has the GPU to itself and bins of thousands of events (8.0 against 8.9 us per launch at config 2; at 640x480, bins of
+    // ~1500 events, 512 threads: 11.7 against 17.4 us), 512 for contexts sharing the GPU ("co_schedule": a
+    // 1024-thread work-group with its 51 KB tile needs half a CU's wave slots free at once and waits for them while the other
+    // contexts' kernels hold a few each -- 16.7 instead of 8.0 us under four contexts; with 512 threads 170 -> 190 Mevents/s).
+    // Event lists over thousands of small bins -- 1280x720 at scale 3: 1620 bins of ~600 events, six per CU -- run 256-thread
+    // work-groups (16.6 against 18.6 us per scatter launch there at 1 M events, 8.2 against 13.3 at 100 k); with a couple of
+    // bins per CU -- 640x480, 540 bins -- 512 threads stay ahead (6.3 against 8.2).  (512 rather than 1024 where a bin holds a few
+    // hundred events -- large images --: twice as many bins in flight per CU, 84 instead of 91 us per iteration at 1280x720.)
+    const bool many_small_bins = c->fmt == 2 && c->n_cus > 0 && c->grid.nbins >= 4 * c->n_cus && ev_per_bin < 1024.0;
+    p.bin_threads = bin_scatter_threads(c->fmt, p.head_update, many_small_bins, ev_per_bin);
+    if (p.binned) {
+        // events a scatter thread keeps in flight:
+        // (event lists: registers, not LDS, set the occupancy there -- two events per thread keep four work-groups on a
+        // CU, and a bin above the pass size takes a second pass; measured at 1280x720: 512 x 2 69.8 us, 512 x 4 73.5)
+        // (dense tiles: a pass should cover the AVERAGE bin, fuller bins take a second pass -- sizing it for 1.5 x the
+        // average left half of every thread's slots empty at 640x480: 512 x 8 19.9 us, 512 x 4 15.3 us)
+        const double per_bin = (c->fmt == 2 ? 1.0 : 1.1) * ev_per_bin / (double)p.bin_threads;
+        // (... and between two and four, two up to 2.83 -- the geometric middle: bins of ~2100 events on 1024 threads ran
+        // 15.3 us with four events per thread, half of every thread's slots empty, against 12.1 us with two and a second pass
+        // for the fuller bins; measured at 1M events on 440 / 520 / 560 x 480 sensors)
+        p.ev_per_thread = per_bin <= 1 ? 1 : (per_bin <= 2.83 ? 2 : (per_bin <= 4 ? 4 : 8));
+        // (dense slabs on 512-thread work-groups with bins of thousands of events -- config 2 under "co_schedule": 272 bins, 3673
+        // events on average, 4912 in the fullest -- : the pass covers the FULLEST bin, ~1.35 x the average; with 8 per thread two
+        // thirds of the bins took a second pass: 8.45 -> 8.13 us per launch alone, 8.2 -> 7.8 under four contexts)
+        if (c->fmt == 0 && p.bin_threads == 512 && per_bin > 6.5) p.ev_per_thread = per_bin <= 8.2 ? 10 : 12;
+        // (event lists, update in the stencil tail, thousands of small bins on 256 threads -- 1280x720: 1620 bins, 608 events on average,
+        // 877 in the fullest: four per thread cover every bin in one pass, 14.3-14.6 -> 13.5 us per launch; the head form, whose
+        // registers also hold the update, loses with four: 14.8 -> 16.5)
+        if (c->fmt == 2 && !p.head_update && p.bin_threads == 256 && per_bin > 2.0) p.ev_per_thread = 4;
+    }
+    // A warm start that is expected to converge in a handful of iterations (the previous one did) is polled batch by batch,
+    // the final warp riding along: "quick".  One that is expected to run long -- the reference's own ring: ~115 iterations per
+    // warm-started slice -- is fed and polled like a cold run: two-iteration batches with a blocking poll each cost it a
+    // host round trip every other iteration (22 instead of 14 us per iteration on a 50 000-event slice).
+    p.quick_warm = p.warm_start && c->warm_iters_hint < 3 * o.poll_interval;
+    // A tile-binned run that is not a quick warm start reads its progress from the pinned snapshot (bf_run.cpp: wait_snapshot).
+    p.snap_polled = p.binned && !p.quick_warm;
+    return p;
+}

@@ -207,3 +207,65 @@ def test_forced_form_warm_started_against_the_oracle(accel_mod, warm_case, form)
     print("%s, warm start: %d iterations (oracle %d / %d); valid-pixel counts equal for the first %d; worst relative deviation "
           "before the first crossing %.2e, after it %.2f x the oracle's own spread" %
           (form, info.iterations, len(otr), c["n_r"], k_g, worst[0], worst[1]))
+
+
+CAP = 12
+
+
+@pytest.fixture(scope="module")
+def capped_ref(accel_mod, case):
+    """The global-atomic loop (the other forms' bits are held to it elsewhere) on `case`'s slice: stopped at CAP iterations, and
+    a fresh context's K + 1 iterations."""
+    H, W, s, sl = case["H"], case["W"], case["s"], case["sl"]
+    out = []
+    for capped in (True, False):
+        a = accel_mod.Accel(max_events=len(sl["t"]), max_rows=s * H + s, max_cols=s * W + s)
+        a.set_option("binned", 0)
+        a.set_option("fused", 0)
+        a.upload_events(sl["fr_x"], sl["fr_y"], sl["t"])
+        a.set_cloud(s, H, W)
+        o = a.default_opts()
+        o.res_x, o.res_y = H, W
+        if capped:
+            o.max_iter, o.hard_iter_cap = -1, CAP
+        else:
+            o.max_iter = K
+        m, info = accel_mod.Model(), accel_mod.RunInfo()
+        rc = a.L.bf_run(a.h, accel_mod.C.byref(o), accel_mod.C.byref(m), accel_mod.C.byref(info))
+        a.close()
+        out.append((rc, info.iterations, bytes(m)))
+    assert out[0][0] == accel_mod.BF_ERR_NOCONV and out[1][0] == 0, out
+    return out
+
+
+@pytest.mark.parametrize("form", list(FORMS), ids=lambda f: f.split(" (")[0].replace(" ", "_").replace(",", ""))
+def test_forced_form_at_the_iteration_cap(accel_mod, case, capped_ref, form):
+    """bf_run stopped by hard_iter_cap (max_iter = -1: the loop would not end by itself) returns BF_ERR_NOCONV with the same
+    iteration count and model bits in every form, and leaves the context fit for the next slice: set_cloud + run then give the
+    bits of a fresh context."""
+    options, want_fmt, want_one_kernel = FORMS[form][:3]
+    want_persistent = FORMS[form][3] if len(FORMS[form]) > 3 else 0
+    H, W, s, sl = case["H"], case["W"], case["s"], case["sl"]
+    a = accel_mod.Accel(max_events=len(sl["t"]), max_rows=s * H + s, max_cols=s * W + s)
+    for k, v in options.items():
+        a.set_option(k, v)
+    a.upload_events(sl["fr_x"], sl["fr_y"], sl["t"])
+    a.set_cloud(s, H, W)
+    assert a.get_stat("one_kernel") == want_one_kernel, form
+    assert a.get_stat("persistent") == want_persistent, form
+    if want_fmt is not None:
+        assert a.get_stat("scatter_format") == want_fmt, (form, a.get_stat("scatter_format"))
+    o = a.default_opts()
+    o.res_x, o.res_y, o.max_iter, o.hard_iter_cap = H, W, -1, CAP
+    m, info = accel_mod.Model(), accel_mod.RunInfo()
+    # (Accel.run raises on this return code; bf_run itself still writes the model and the run info)
+    rc = a.L.bf_run(a.h, accel_mod.C.byref(o), accel_mod.C.byref(m), accel_mod.C.byref(info))
+    capped = (rc, info.iterations, bytes(m))
+    assert a.get_stat("persist_giveups") == 0, form   # (the persistent kernel ran to the cap itself)
+    a.set_cloud(s, H, W)
+    o2 = a.default_opts()
+    o2.res_x, o2.res_y, o2.max_iter = H, W, K
+    rc2, m2, info2 = a.run(o2)
+    a.close()
+    assert capped == capped_ref[0], (form, capped[:2], capped_ref[0][:2])
+    assert (rc2, info2.iterations, bytes(m2)) == capped_ref[1], (form, rc2, info2.iterations, capped_ref[1][:2])
