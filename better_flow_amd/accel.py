@@ -150,7 +150,10 @@ EXPORTS = [
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
     "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
+    "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
 ]
+
+BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
 
 _lib = None
 
@@ -305,6 +308,14 @@ def load(path=None):
                                     C.c_int32, C.POINTER(C.c_int64)]
         L.bf_emit_wait.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]
         L.bf_emit_release.argtypes = [C.c_void_p, C.c_uint64]
+        # per-slice frames on the device (include/bf_accel.h: bf_frame_*, bf_render_frame)
+        L.bf_frame_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bf_frame_destroy.argtypes = [C.c_void_p]
+        L.bf_frame_render.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.bf_frame_wait.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.POINTER(C.c_uint8)),
+                                    C.POINTER(C.POINTER(C.c_uint8))]
+        L.bf_frame_release.argtypes = [C.c_void_p, C.c_int64]
+        L.bf_render_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         _libs[path] = L
         if path == LIB_PATH:
             _lib = L
@@ -514,6 +525,16 @@ class Accel:
         img = np.empty((res_x * sc + sc, res_y * sc + sc, 3), dtype=np.uint8)
         self._chk(self.L.bf_color_time_img(self.h, scale, res_x, res_y, 1 if show_final else 0, _ptr(img)))
         return img
+
+    def render_frame(self, res_x, res_y, ppm=True, avi=True):
+        """DVS_flow::render_frame's frame of the live slice, composed on the device (bf_render_frame): returns (ppm, avi),
+        the PPM payload as a (6 res_x, 6 res_y, 3) RGB array, the AVI payload as a (6 res_x, stride) byte array of bottom-up
+        BGR rows padded to a multiple of 4 bytes; None for a layout not asked for."""
+        rows, cols = 6 * res_x, 6 * res_y
+        p = np.empty((rows, cols, 3), dtype=np.uint8) if ppm else None
+        a = np.empty((rows, (cols * 3 + 3) & ~3), dtype=np.uint8) if avi else None
+        self._chk(self.L.bf_render_frame(self.h, res_x, res_y, _ptr(p), _ptr(a)))
+        return p, a
 
     def local_run(self, res_x=180, res_y=240, max_evaluations=100000):
         st = LocalState()

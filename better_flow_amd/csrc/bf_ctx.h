@@ -240,6 +240,13 @@ struct bf_ctx {
 // the live slice's per-event flow in upload order on the device, or null (bf_operators.cpp)
 extern "C" int ctx_device_uv(bf_ctx* c, const double2** uv);
 
+// The two frame tiles of the live slice (bf_extras.cpp), ENQUEUED on the context stream into device memory: the 8-bit projection
+// image, (scale res_x) x (scale res_y), and the colour-coded time image, (scale res_x + scale) x (scale res_y + scale) BGR.  A
+// pending bf_set_model warp is applied first.  bf_projection_img / bf_color_time_img are these, a copy and a sync; bf_frame_render
+// runs them into its own tiles.
+extern "C" int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img);
+extern "C" int render_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_bgr);
+
 // Which loop a slice runs (bf_plan.cpp): plan_slice once per slice, plan_run once per run; nothing else decides it.
 struct SlicePlan {
     BinGrid grid{}, fgrid{};         // the tile-binned loop's bin grid (zw aside), the one-kernel iteration's sort grid

@@ -268,6 +268,60 @@ int local_step(bf_ctx* c, double nx, double ny, double* score, bool want_img) {
 
 }  // namespace
 
+// EventFile::projection_img (event_file.h:460-515) of the live slice into d_img (at least (scale res_x) x (scale res_y) bytes):
+// enqueued on the context stream, nothing copied, nothing waited for.  Arguments checked by the callers.
+int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img) {
+    const size_t px = (size_t)res_x * scale * (size_t)res_y * scale;
+    int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
+    if (rc != BF_OK) return rc;
+    if ((rc = ensure_lplanes(c)) != BF_OK) return rc;
+    // the point planes are shared with the contrast-score path: lay them out afresh for this geometry
+    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMemsetAsync(c->d_lplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
+    c->have_lwin = false;
+    c->lcur = 0;
+    HIP_TRY(c, hipMemsetAsync(c->d_lscore, 0, 2 * sizeof(unsigned long long), c->stream));
+    const bf_ctx::EvSet& e = c->set[c->cs];
+    launch_proj_count(e.xy, e.p, c->has_noise ? c->d_noise : nullptr, c->n, scale, res_x, res_y, show_final ? 1 : 0,
+                      c->d_lplane[0], c->stream);
+    LocalGeom g;
+    memset(&g, 0, sizeof(g));
+    g.scale = scale; g.R = res_x * scale; g.C = res_y * scale;
+    if (launch_local_blur_score(c->d_lplane[0], c->d_lplane[1], g, c->d_lscore, d_img, c->stream) != 0)
+        return fail(c, BF_ERR_ARG, "unsupported scale %d", scale);
+    launch_proj_scale(d_img, (long long)px, c->d_lscore, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return BF_OK;
+}
+
+// EventFile::color_time_img (event_file.h:649-747) of the live slice into d_bgr ((scale res_x + scale) x (scale res_y + scale)
+// x 3 bytes), enqueued on the context stream.  Arguments checked by the callers (scale already mapped from 0 to 11).
+int render_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_bgr) {
+    ColorGeom g;
+    memset(&g, 0, sizeof(g));
+    g.scale = scale; g.show_final = show_final ? 1 : 0;
+    g.mx = scale * res_x; g.my = scale * res_y;
+    g.R = g.mx + scale; g.C = g.my + scale;
+    const size_t px = (size_t)g.R * (size_t)g.C;
+    int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
+    if (rc != BF_OK) return rc;
+    if (c->n > 0) {
+        rc = fold_stats(c);
+        if (rc != BF_OK) return rc;
+        g.t_min = c->stats.tmin;                                             // :659-662: t_max starts at 0
+        g.t_range = std::max<long long>(c->stats.tmax, 0) - g.t_min;
+    }
+    g.x_shift = -double(res_x / 2) * double(scale) + double(g.mx) / 2.0;     // :677-678 with x_min = 0, x_max = RES_X
+    g.y_shift = -double(res_y / 2) * double(scale) + double(g.my) / 2.0;
+    HIP_TRY(c, c->d_col_planes.grow(c->cap_px * 20));   // 2 x i64 sums + u32 count per pixel
+    HIP_TRY(c, hipMemsetAsync(c->d_col_planes, 0, px * 20, c->stream));
+    const bf_ctx::EvSet& e = c->set[c->cs];
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(c->d_col_planes.get());
+    launch_color_time(e.xy, e.t, e.p, c->has_noise ? c->d_noise : nullptr, c->n, g,
+                      reinterpret_cast<uint32_t*>(sums + 2 * px), sums, sums + px, d_bgr, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return BF_OK;
+}
+
 int bf_local_set_window(bf_ctx* c, int32_t scale, int32_t wsz, int32_t c_fr_x, int32_t c_fr_y, int64_t c_t,
                         bf_local_window* window_out) {
     if (!c) return BF_ERR_ARG;
@@ -372,24 +426,9 @@ int bf_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, in
     const size_t px = (size_t)res_x * scale * (size_t)res_y * scale;
     if (px > c->cap_px) return fail(c, BF_ERR_CAPACITY, "image %d x %d exceeds the image capacity", res_x * scale, res_y * scale);
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
+    int rc = ensure_lplanes(c);
     if (rc != BF_OK) return rc;
-    if ((rc = ensure_lplanes(c)) != BF_OK) return rc;
-    // the point planes are shared with the contrast-score path: lay them out afresh for this geometry
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMemsetAsync(c->d_lplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
-    c->have_lwin = false;
-    c->lcur = 0;
-    HIP_TRY(c, hipMemsetAsync(c->d_lscore, 0, 2 * sizeof(unsigned long long), c->stream));
-    const bf_ctx::EvSet& e = c->set[c->cs];
-    launch_proj_count(e.xy, e.p, c->has_noise ? c->d_noise : nullptr, c->n, scale, res_x, res_y, show_final ? 1 : 0,
-                      c->d_lplane[0], c->stream);
-    LocalGeom g;
-    memset(&g, 0, sizeof(g));
-    g.scale = scale; g.R = res_x * scale; g.C = res_y * scale;
-    if (launch_local_blur_score(c->d_lplane[0], c->d_lplane[1], g, c->d_lscore, c->d_limg, c->stream) != 0)
-        return fail(c, BF_ERR_ARG, "unsupported scale %d", scale);
-    launch_proj_scale(c->d_limg, (long long)px, c->d_lscore, c->stream);
-    HIP_TRY(c, hipGetLastError());
+    if ((rc = render_projection_img(c, scale, res_x, res_y, show_final, c->d_limg)) != BF_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(img_out, c->d_limg, px, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BF_OK;
@@ -401,32 +440,12 @@ int bf_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, in
     if (scale == 0) scale = 11;   // event_file.h:650
     if (scale < 1 || scale > 15) return fail(c, BF_ERR_ARG, "scale must be in 1..15 (got %d)", scale);
     if (res_x < 1 || res_y < 1) return fail(c, BF_ERR_ARG, "bad sensor size");
-    ColorGeom g;
-    memset(&g, 0, sizeof(g));
-    g.scale = scale; g.show_final = show_final ? 1 : 0;
-    g.mx = scale * res_x; g.my = scale * res_y;
-    g.R = g.mx + scale; g.C = g.my + scale;
-    const size_t px = (size_t)g.R * (size_t)g.C;
-    if (px > c->cap_px) return fail(c, BF_ERR_CAPACITY, "image %d x %d exceeds the image capacity", g.R, g.C);
+    const size_t px = (size_t)(scale * res_x + scale) * (size_t)(scale * res_y + scale);
+    if (px > c->cap_px) return fail(c, BF_ERR_CAPACITY, "image %d x %d exceeds the image capacity", scale * res_x + scale, scale * res_y + scale);
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
-    if (rc != BF_OK) return rc;
-    if (c->n > 0) {
-        rc = fold_stats(c);
-        if (rc != BF_OK) return rc;
-        g.t_min = c->stats.tmin;                                             // :659-662: t_max starts at 0
-        g.t_range = std::max<long long>(c->stats.tmax, 0) - g.t_min;
-    }
-    g.x_shift = -double(res_x / 2) * double(scale) + double(g.mx) / 2.0;     // :677-678 with x_min = 0, x_max = RES_X
-    g.y_shift = -double(res_y / 2) * double(scale) + double(g.my) / 2.0;
-    HIP_TRY(c, c->d_col_planes.grow(c->cap_px * 20));   // 2 x i64 sums + u32 count per pixel
     HIP_TRY(c, c->d_col_img.grow(c->cap_px * 3));
-    HIP_TRY(c, hipMemsetAsync(c->d_col_planes, 0, px * 20, c->stream));
-    const bf_ctx::EvSet& e = c->set[c->cs];
-    unsigned long long* sums = reinterpret_cast<unsigned long long*>(c->d_col_planes.get());
-    launch_color_time(e.xy, e.t, e.p, c->has_noise ? c->d_noise : nullptr, c->n, g,
-                      reinterpret_cast<uint32_t*>(sums + 2 * px), sums, sums + px, c->d_col_img, c->stream);
-    HIP_TRY(c, hipGetLastError());
+    int rc = render_color_time_img(c, scale, res_x, res_y, show_final, c->d_col_img);
+    if (rc != BF_OK) return rc;
     HIP_TRY(c, hipMemcpyAsync(bgr_out, c->d_col_img, px * 3, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return BF_OK;

@@ -323,4 +323,20 @@ struct EmitSlice {
 size_t emit_temp_bytes(long long m);
 hipError_t launch_emit(const EmitSlice& a, unsigned long long* keys_sorted, void* temp, size_t temp_bytes, hipStream_t s);
 
+// bf_frame.hip -- the 2 x 2 frame mosaic of --img / --video (bf_frame_render): tiles of R x C (grey) and CR x CC BGR (colour,
+// CR = R + 3, CC = C + 3), index 0 the compensated tiles (top row), 1 the raw ones; the colour resize's taps (row0 / row1 / row_w:
+// R entries, col0 / col1 / col_w: C entries).  Out: the PPM payload (ppm_dwords dwords) and / or the AVI payload (avi_dwords
+// dwords, rows of `stride` bytes); a null destination is skipped.
+struct FrameCompose {
+    const uint8_t* gray[2];
+    const uint8_t* colour[2];
+    int R, C, CR, CC;
+    const int32_t *row0, *row1, *col0, *col1;
+    const float *row_w, *col_w;
+    uint8_t *ppm, *avi;
+    long long ppm_dwords, avi_dwords;
+    int stride;
+};
+void launch_frame_compose(const FrameCompose& a, hipStream_t s);
+
 }  // namespace bf

@@ -20,13 +20,6 @@
 #include <chrono>
 #include <unordered_map>
 
-inline std::string f2str(double v) {   // dvs_flow.h:14-19, as written ("1.05" prints as "1.5")
-    int base = int(v * 100);
-    std::string ret = std::to_string(base / 100) + ".";
-    ret += std::to_string(std::abs(base) % 100);
-    return ret;
-}
-
 template <size_t MAX_SZ, sll SPAN> class DVS_flow {
 public:
     // Buffer for incoming events (aka 'slice')
@@ -144,17 +137,9 @@ void DVS_flow<MAX_SZ, SPAN>::render_frame(OptimizerRolling<LinearEventPtrs> &opt
     if (generate_pictures) {
         const std::string base = img_prefix + "/frame_" + std::to_string(frame_count++);
         if (!bf::write_ppm(base + ".ppm", frame) && !quiet) std::cerr << "cannot write " << base << ".ppm\n";
-        if (FILE *f = std::fopen((base + ".txt").c_str(), "w")) {   // what the reference draws with cv::putText, :277-315
-            const ObjectModel &m = last_model;
-            std::fprintf(f, "timestamp: %s\n%%realtime: %s\nTime diff (new): %s\nEvents: %zu\nNew events: %lld\n",
-                         f2str(double(current_slice_time) * 1e-9).c_str(), f2str(double(on_time_change) / double(time_diff)).c_str(),
-                         f2str(double(time_diff) * 1e-9).c_str(), (size_t)ev_buffer.size(), (long long)event_diff);
-            std::fprintf(f, "Model:\nC: (%s, %s)\nShift: (%s, %s); total: (%s, %s)\nRot: %s total: %s\nDiv: %s total: %s\n",
-                         f2str(m.cx).c_str(), f2str(m.cy).c_str(), f2str(m.dx).c_str(), f2str(m.dy).c_str(), f2str(m.total_dx).c_str(),
-                         f2str(m.total_dy).c_str(), f2str(m.rot).c_str(), f2str(m.total_rot).c_str(), f2str(m.div).c_str(),
-                         f2str(m.total_div).c_str());
-            std::fclose(f);
-        }
+        // what the reference draws with cv::putText, :277-315
+        (void)bf::write_text(base + ".txt", bf::frame_sidecar(current_slice_time, on_time_change, time_diff, (size_t)ev_buffer.size(),
+                                                              (long long)event_diff, last_model));
     }
     if (generate_video) {
         if (!outputvideo.is_open() && !outputvideo.open(video_name, frame.rows, frame.cols, video_fps))

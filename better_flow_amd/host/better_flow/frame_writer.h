@@ -18,9 +18,17 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
+
+inline std::string f2str(double v) {   // dvs_flow.h:14-19, as written ("1.05" prints as "1.5")
+    int base = int(v * 100);
+    std::string ret = std::to_string(base / 100) + ".";
+    ret += std::to_string(std::abs(base) % 100);
+    return ret;
+}
 
 namespace bf {
 
@@ -84,6 +92,73 @@ inline FrameBGR mosaic_2x2(const FrameBGR &tl, const FrameBGR &tr, const FrameBG
             for (int r = 0; r < tl.rows; ++r)
                 std::memcpy(m.at(a * tl.rows + r, b * tl.cols), t[a][b]->at(r, 0), (size_t)tl.cols * 3);
     return m;
+}
+
+// DVS_flow::render_frame's frame from its four tiles (dvs_flow.h:256-335): the projection images (rows x cols grey) and the
+// colour-coded time images ((rows + 3) x (cols + 3) BGR) of the slice, motion compensated and as recorded -- at scale 3,
+// rows = 3 RES_X, cols = 3 RES_Y.  The device composes the same bytes (bf_frame_render, csrc/bf_frame.hip).
+inline FrameBGR compose_frame(const uint8_t *gray_comp, const uint8_t *colour_comp, const uint8_t *gray_raw, const uint8_t *colour_raw,
+                              int rows, int cols) {
+    auto gray_tile = [&](const uint8_t *g) { return resize_bilinear(gray_to_bgr(g, rows, cols), rows, cols); };
+    auto colour_tile = [&](const uint8_t *c) {
+        FrameBGR f(rows + 3, cols + 3);
+        std::memcpy(f.px.data(), c, f.px.size());
+        return resize_bilinear(f, rows, cols);
+    };
+    return mosaic_2x2(gray_tile(gray_comp), colour_tile(colour_comp), gray_tile(gray_raw), colour_tile(colour_raw));
+}
+
+// The bytes of the files without their headers.  PPM: top-down RGB, rows x cols x 3 (the bytes write_ppm writes after "P6").
+// AVI: bottom-up BGR rows of avi_stride(cols) bytes, the padding zero (what AviWriter::write stores per frame).
+inline size_t avi_stride(int cols) { return ((size_t)cols * 3 + 3) & ~(size_t)3; }
+inline void ppm_payload(const FrameBGR &f, uint8_t *out) {
+    for (size_t i = 0; i < (size_t)f.rows * f.cols; ++i) {
+        out[3 * i] = f.px[3 * i + 2]; out[3 * i + 1] = f.px[3 * i + 1]; out[3 * i + 2] = f.px[3 * i];
+    }
+}
+inline void avi_payload(const FrameBGR &f, uint8_t *out) {
+    const size_t stride = avi_stride(f.cols);
+    for (int r = 0; r < f.rows; ++r) {
+        uint8_t *d = out + (size_t)(f.rows - 1 - r) * stride;
+        std::memcpy(d, f.at(r, 0), (size_t)f.cols * 3);
+        std::memset(d + (size_t)f.cols * 3, 0, stride - (size_t)f.cols * 3);
+    }
+}
+
+// The side-car frame_N.txt of a frame: what the reference draws with cv::putText (dvs_flow.h:277-315).  trigger_time /
+// time_diff / on_time_change in ns; ring_size = the ring's size at the trigger; M: an ObjectModel.
+template <class M>
+std::string frame_sidecar(unsigned long long trigger_time, unsigned long long on_time_change, long long time_diff, size_t ring_size,
+                          long long new_events, const M &m) {
+    char buf[2048];
+    std::string out;
+    std::snprintf(buf, sizeof(buf), "timestamp: %s\n%%realtime: %s\nTime diff (new): %s\nEvents: %zu\nNew events: %lld\n",
+                  f2str(double(trigger_time) * 1e-9).c_str(), f2str(double(on_time_change) / double(time_diff)).c_str(),
+                  f2str(double(time_diff) * 1e-9).c_str(), ring_size, new_events);
+    out += buf;
+    std::snprintf(buf, sizeof(buf), "Model:\nC: (%s, %s)\nShift: (%s, %s); total: (%s, %s)\nRot: %s total: %s\nDiv: %s total: %s\n",
+                  f2str(m.cx).c_str(), f2str(m.cy).c_str(), f2str(m.dx).c_str(), f2str(m.dy).c_str(), f2str(m.total_dx).c_str(),
+                  f2str(m.total_dy).c_str(), f2str(m.rot).c_str(), f2str(m.total_rot).c_str(), f2str(m.div).c_str(),
+                  f2str(m.total_div).c_str());
+    out += buf;
+    return out;
+}
+
+inline bool write_text(const std::string &path, const std::string &text) {
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) return false;
+    const bool w = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+    return std::fclose(f) == 0 && w;
+}
+
+// A PPM file from its payload (ppm_payload's layout): the header, then the bytes in one write
+inline bool write_ppm_raw(const std::string &path, int rows, int cols, const uint8_t *payload) {
+    FILE *fp = std::fopen(path.c_str(), "wb");
+    if (!fp) return false;
+    std::fprintf(fp, "P6\n%d %d\n255\n", cols, rows);
+    const size_t n = (size_t)rows * (size_t)cols * 3;
+    const bool w = std::fwrite(payload, 1, n, fp) == n;
+    return std::fclose(fp) == 0 && w;
 }
 
 inline bool write_ppm(const std::string &path, const FrameBGR &f) {
@@ -151,15 +226,21 @@ public:
 
     bool write(const FrameBGR &f) {
         if (!fp || f.rows != rows || f.cols != cols) return false;
+        for (int r = 0; r < rows; ++r) std::memcpy(&buf[(size_t)(rows - 1 - r) * stride], f.at(r, 0), (size_t)cols * 3);
+        return write_raw(buf.data());
+    }
+
+    // One frame given as its payload: rows x stride bytes, bottom-up BGR, the padding zero (avi_payload's layout)
+    bool write_raw(const uint8_t *payload) {
+        if (!fp) return false;
         // RIFF sizes are 32 bit: stop before the file would pass 4 GB
         if ((uint64_t)(frames + 1) * (frame_bytes + 8 + 16) + 4096 > 0xffffffffull) {
             if (!full) std::fprintf(stderr, "AviWriter: 4 GB container limit reached after %u frames\n", frames);
             full = true;
             return false;
         }
-        for (int r = 0; r < rows; ++r) std::memcpy(&buf[(size_t)(rows - 1 - r) * stride], f.at(r, 0), (size_t)cols * 3);
         tag("00db"); u32(frame_bytes);
-        std::fwrite(buf.data(), 1, buf.size(), fp);
+        std::fwrite(payload, 1, frame_bytes, fp);
         frames++;
         return true;
     }

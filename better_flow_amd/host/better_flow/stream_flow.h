@@ -23,6 +23,11 @@
 //     no per-slice flow block, no history, no walk at the end; memory grows with the output rows only.  The solving worker
 //     only enqueues the emit kernels; they store the rows in a pinned output ring, and deliver() -- in slice order, after
 //     the solve -- waits for them and moves the rows into blocks of the table.
+//   * set_frames: DVS_flow's --img / --video frame of every slice (dvs_flow.h render_frame), the same bytes.  The solving
+//     worker enqueues the render and compose (bf_frame_render) into a pinned frame slot before its context takes the next
+//     slice; deliver() waits for it in slice order and hands it to a writer thread, which writes the files and frees the slot.
+//     A C-ABI library without the bf_frame_* entries (the CPU stand-in of the tests) gets the frame composed on the host
+//     from bf_projection_img / bf_color_time_img (frame_writer.h): the same bytes again.
 //
 // Semantics: those of DVS_flow, element for element --
 //   * ring of at most MAX_SZ events spanning at most SPAN ns (push_back :31-44, fix_span :46-59);
@@ -43,6 +48,7 @@
 
 #include <better_flow/accel_lib.h>
 #include <better_flow/common.h>
+#include <better_flow/frame_writer.h>
 #include <better_flow/object_model.h>
 #include <better_flow/slice_farm.h>
 
@@ -60,6 +66,12 @@ int bf_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_
                   int32_t lead_row, int32_t lead_col, int64_t *ticket_out) __attribute__((weak));
 int bf_emit_wait(bf_ctx *ctx, bf_emit *emit, int64_t ticket, uint64_t *first_row, int64_t *rows) __attribute__((weak));
 int bf_emit_release(bf_emit *emit, uint64_t upto_row) __attribute__((weak));
+// (weak for the same reason: without them set_frames composes on the host)
+int bf_frame_create(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t slots, int32_t layouts, bf_frame **out) __attribute__((weak));
+int bf_frame_destroy(bf_frame *frame) __attribute__((weak));
+int bf_frame_render(bf_ctx *ctx, bf_frame *frame, int64_t *ticket_out) __attribute__((weak));
+int bf_frame_wait(bf_ctx *ctx, bf_frame *frame, int64_t ticket, const uint8_t **ppm, const uint8_t **avi) __attribute__((weak));
+int bf_frame_release(bf_frame *frame, int64_t ticket) __attribute__((weak));
 }
 
 namespace bf {
@@ -115,6 +127,8 @@ public:
     virtual ~StreamEngine() {
         if (farm) {
             try { farm->drain(); } catch (...) {}
+            stop_frame_writer();
+            for (bf_frame *f : frame_state) if (f) (void)bf_frame_destroy(f);
             bf_ctx *c = farm->context(0);
             if (ts) (void)bf_host_free(c, ts);
             if (row_) (void)bf_host_free(c, row_);
@@ -146,6 +160,14 @@ public:
     void set_lookahead(size_t n) { lookahead = n; }          // ring slots beyond MAX_SZ (default: 2 MAX_SZ, at least 65536)
     void set_devices(const std::vector<int> &d, int contexts = 1) { devices = d; contexts_per_device = contexts; }
     void on_slice(SliceFn fn) { slice_fn = std::move(fn); }
+    // DVS_flow's frames (set_generate_pictures / set_generate_video): one per slice, in slice order.  pictures: frame_N.ppm and
+    // the side-car frame_N.txt under `prefix`; a non-empty video_name: every frame appended to that AVI at video_fps.  The
+    // frames are rendered at scale 3 whatever set_scale says, so the contexts get that image capacity too.
+    void set_frames(const std::string &prefix, bool pictures, const std::string &video_name = "", int video_fps = 30, int slots = 4) {
+        frame_prefix = prefix; frame_pictures = pictures; frame_video_name = video_name; frame_video_fps = video_fps;
+        frame_slots = slots < 1 ? 1 : slots;
+        frames_on = pictures || !video_name.empty();
+    }
 
     // Create the workers, their device contexts and the pinned ring now (otherwise: at the first event).
     void warm_up() { ensure_ring(); }
@@ -312,7 +334,11 @@ public:
             t.want_uv = true;
             t.on_solved = [this, idx, first, n, st, lead, lt, lr, lc](bf_ctx *ctx, SliceFarm::Result &r) {
                 emit_slice(idx, ctx, r, first, n, st, lead, lt, lr, lc);
+                if (frames_on) frame_slice(idx, ctx, r);
             };
+        } else if (frames_on) {
+            const uint64_t idx = p.index;
+            t.on_solved = [this, idx](bf_ctx *ctx, SliceFarm::Result &r) { frame_slice(idx, ctx, r); };
         }
         if ((accumulate || (want_flow && farm->workers() > 1)) && p.n > 0) {
             // A private block per slice, copied into the ring by deliver() -- which runs in SLICE order.  Needed for
@@ -327,11 +353,15 @@ public:
             t.uv_ring = uv; t.uv_cap = (int64_t)cap; t.uv_first = t.first;
         }
         t.user = p.index;
+        bool flag_after = false;
         if (farm->workers() > 1 && p.n > 0 && window_guard_on_host(p)) {   // see slice_farm.h: uploads run ahead
             // (earlier slices overlap this one in the ring and their workers may not have read it yet: in the reference's
             // order they do not see this slice's flags -- wait for them first.  The guard stops a slice once in a long while.)
             farm->drain();
-            flag_noise(p);
+            // With frames, the slice itself must not see its own flags either: DVS_flow renders it as uploaded, before
+            // OptimizerRolling::run flagged it -- flag once it has been solved and rendered.
+            if (frames_on) flag_after = true;
+            else flag_noise(p);
         }
         {
             std::lock_guard<std::mutex> g(mu);
@@ -342,12 +372,20 @@ public:
         event_diff = 0;
         last_slice_time = current_slice_time;
         farm->submit(t);
+        if (flag_after) {
+            farm->drain();
+            flag_noise(p);
+        }
         if (!pipelined) drain();
     }
 
     // Wait for every slice triggered so far (pipelined mode); rethrows a failure of a slice as bf::AccelError.
     void drain() {
         if (farm) farm->drain();
+        if (frames_on) {   // every frame delivered so far is in its files
+            std::unique_lock<std::mutex> g(frame_mu);
+            frame_cv.wait(g, [&] { return frame_queue.empty() && !frame_writing; });
+        }
         rethrow_failure();
     }
 
@@ -368,6 +406,9 @@ public:
     sll get_time_diff() const { return time_diff; }
     ull events_seen() const { return head; }
     double seconds_blocked() const { return blocked_s; }   // the producer waited this long in reserve() for slices in flight
+    uint64_t frames_delivered() { std::lock_guard<std::mutex> g(frame_mu); return frames_handed; }
+    // time the engine waited for frames: a free frame slot, a render to finish, room at the writer
+    double seconds_frame_wait() { std::lock_guard<std::mutex> g(frame_mu); return frame_wait_s; }
 
     // DVS_flow::get_accumulated (dvs_flow.h:351-389): the events of all slices, each once, with the flow of the first
     // slice that solved it.  The marking rule is the reference's: walking the slices in order and, inside a slice, the
@@ -484,6 +525,29 @@ protected:
     uint64_t emit_released = 0;              // rows of the output ring read so far
     std::vector<RowBlock> dev_blocks;
     size_t dev_rows = 0;
+    // frames (set_frames)
+    struct FrameJob {             // one slice's frame, from its worker to the writer
+        int worker = -1;
+        int64_t ticket = -1;                  // device composition: the frame slot's ticket
+        std::vector<uint8_t> host_ppm, host_avi;   // host composition: the payloads
+        const uint8_t *ppm = nullptr, *avi = nullptr;
+        std::string text;                     // the side-car
+        uint64_t number = 0;                  // frame_<number>
+    };
+    bool frames_on = false, frame_pictures = false;
+    std::string frame_prefix, frame_video_name;
+    int frame_video_fps = 30, frame_slots = 4;
+    std::vector<bf_frame *> frame_state;     // per worker (device composition); empty: host composition
+    std::mutex frame_mu;                     // everything below
+    std::condition_variable frame_cv;
+    std::map<uint64_t, FrameJob> frame_ready;   // slice index -> its frame, from the worker's hook to deliver()
+    std::vector<int> frame_held;             // per worker: slots rendered and not yet released
+    std::deque<FrameJob> frame_queue;        // delivered, in slice order, for the writer
+    bool frame_writing = false, frame_stop = false;
+    uint64_t frames_handed = 0, frame_number = 0;
+    double frame_wait_s = 0;
+    std::thread frame_writer;
+    AviWriter video;                         // (the writer's)
 
     // the emit step of slice `idx`, on the worker that solved it (SliceFarm::Task::on_solved): enqueue only
     void emit_slice(uint64_t idx, bf_ctx *ctx, SliceFarm::Result &r, uint64_t first, uint64_t n, ull start, bool lead, ull lead_t,
@@ -549,6 +613,170 @@ protected:
         emit_cv.notify_all();
     }
 
+    size_t worker_of(bf_ctx *ctx) const {
+        for (size_t w = 0; w < farm->workers(); ++w)
+            if (farm->context(w) == ctx) return w;
+        return 0;
+    }
+
+    void start_frames() {
+        frame_held.assign(farm->workers(), 0);
+        if (bf_frame_create) {
+            const int layouts = (frame_pictures ? BF_FRAME_PPM : 0) | (frame_video_name.empty() ? 0 : BF_FRAME_AVI);
+            for (size_t w = 0; w < farm->workers(); ++w) {
+                bf_frame *f = nullptr;
+                const int rc = bf_frame_create(farm->context(w), RES_X, RES_Y, frame_slots, layouts, &f);
+                if (rc < 0) throw AccelError(rc, std::string("StreamEngine: bf_frame_create failed: ") + bf_last_error(farm->context(w)));
+                frame_state.push_back(f);
+            }
+        }
+        frame_writer = std::thread([this] { write_frames(); });
+    }
+
+    void stop_frame_writer() {
+        if (!frame_writer.joinable()) return;
+        {
+            std::lock_guard<std::mutex> g(frame_mu);
+            frame_stop = true;
+        }
+        frame_cv.notify_all();
+        frame_writer.join();
+        video.close();
+    }
+
+    // the frame of slice `idx`, on the worker that solved it (SliceFarm::Task::on_solved), before its context takes the next
+    // slice: enqueued into a frame slot (waiting for one if all are taken), or composed here on the host
+    void frame_slice(uint64_t idx, bf_ctx *ctx, SliceFarm::Result &r) {
+        FrameJob job;
+        job.worker = (int)worker_of(ctx);
+        if (r.rc >= 0 && !frame_state.empty()) {
+            bf_frame *f = frame_state[(size_t)job.worker];
+            bool retried = false;   // (only this worker renders into f, so a slot counted free here is free in f)
+            for (;;) {
+                const int rc = bf_frame_render(ctx, f, &job.ticket);
+                if (rc == BF_ERR_CAPACITY) {
+                    std::unique_lock<std::mutex> g(frame_mu);
+                    if (frame_held[(size_t)job.worker] >= frame_slots) {   // every slot holds a frame not yet written: wait for one
+                        const auto t0 = std::chrono::steady_clock::now();
+                        frame_cv.wait(g, [&] { return frame_held[(size_t)job.worker] < frame_slots || failed.load(); });
+                        frame_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+                        retried = false;
+                        if (!failed) continue;
+                    } else if (!retried) {   // the writer freed a slot since the call: once more
+                        retried = true;
+                        continue;
+                    }
+                }
+                if (rc < 0) { r.rc = rc; r.error = std::string("SliceFarm: frame render failed (") + std::to_string(rc) + "): " + bf_last_error(ctx); job.ticket = -1; }
+                else { std::lock_guard<std::mutex> g(frame_mu); ++frame_held[(size_t)job.worker]; }
+                break;
+            }
+        } else if (r.rc >= 0) {   // host composition: the four tiles through the synchronous renderers
+            const int R = 3 * RES_X, C = 3 * RES_Y;
+            std::vector<uint8_t> gray[2], colour[2];
+            for (int i = 0; i < 2 && r.rc >= 0; ++i) {
+                gray[i].resize((size_t)R * C);
+                colour[i].resize((size_t)(R + 3) * (C + 3) * 3);
+                int rc = bf_projection_img(ctx, 3, RES_X, RES_Y, i == 0 ? 1 : 0, gray[i].data());
+                if (rc >= 0) rc = bf_color_time_img(ctx, 3, RES_X, RES_Y, i == 0 ? 1 : 0, colour[i].data());
+                if (rc < 0) { r.rc = rc; r.error = std::string("SliceFarm: frame tiles failed (") + std::to_string(rc) + "): " + bf_last_error(ctx); }
+            }
+            if (r.rc >= 0) {
+                const FrameBGR fr = compose_frame(gray[0].data(), colour[0].data(), gray[1].data(), colour[1].data(), R, C);
+                if (frame_pictures) { job.host_ppm.resize(fr.px.size()); ppm_payload(fr, job.host_ppm.data()); }
+                if (!frame_video_name.empty()) { job.host_avi.resize(avi_stride(fr.cols) * (size_t)fr.rows); avi_payload(fr, job.host_avi.data()); }
+            }
+        }
+        std::lock_guard<std::mutex> g(frame_mu);
+        frame_ready[idx] = std::move(job);
+    }
+
+    // deliver(), in slice order: wait for the slice's frame and hand it to the writer
+    void deliver_frame(const Pending &p, const SliceFarm::Result &r) {
+        FrameJob job;
+        {
+            std::lock_guard<std::mutex> g(frame_mu);
+            auto it = frame_ready.find(p.index);
+            if (it == frame_ready.end()) return;
+            job = std::move(it->second);
+            frame_ready.erase(it);
+        }
+        if (r.rc < 0) {   // (failed: nothing to write; the slot goes back)
+            if (job.ticket >= 0) {
+                (void)bf_frame_release(frame_state[(size_t)job.worker], job.ticket);
+                std::lock_guard<std::mutex> g(frame_mu);
+                --frame_held[(size_t)job.worker];
+            }
+            frame_cv.notify_all();
+            return;
+        }
+        const auto t0 = std::chrono::steady_clock::now();
+        if (job.ticket >= 0) {
+            bf_ctx *ctx = farm->context((size_t)job.worker);
+            const int rc = bf_frame_wait(ctx, frame_state[(size_t)job.worker], job.ticket, &job.ppm, &job.avi);
+            if (rc < 0) {
+                {
+                    std::lock_guard<std::mutex> g(mu);
+                    if (!failed) { fail_code = rc; fail_text = "StreamEngine: slice " + std::to_string(p.index) + ": frame: " + bf_last_error(ctx); failed = true; }
+                }
+                (void)bf_frame_release(frame_state[(size_t)job.worker], job.ticket);
+                {
+                    std::lock_guard<std::mutex> g(frame_mu);
+                    --frame_held[(size_t)job.worker];
+                }
+                frame_cv.notify_all();
+                return;
+            }
+        } else {
+            job.ppm = job.host_ppm.empty() ? nullptr : job.host_ppm.data();
+            job.avi = job.host_avi.empty() ? nullptr : job.host_avi.data();
+        }
+        if (frame_pictures)
+            job.text = frame_sidecar(p.trigger_time, on_time_change, p.time_diff, (size_t)p.ring_size, (long long)p.new_events, ObjectModel(r.model));
+        std::unique_lock<std::mutex> g(frame_mu);
+        if (frame_pictures) job.number = frame_number++;
+        // (host composition holds its frames in the queue: keep it short)
+        if (frame_state.empty()) frame_cv.wait(g, [&] { return frame_queue.size() < (size_t)frame_slots || frame_stop; });
+        frame_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        frame_queue.push_back(std::move(job));
+        ++frames_handed;
+        g.unlock();
+        frame_cv.notify_all();
+    }
+
+    // the writer thread: the files of every delivered frame, in slice order; then the frame's slot is free again
+    void write_frames() {
+        const int rows = 6 * RES_X, cols = 6 * RES_Y;
+        for (;;) {
+            FrameJob job;
+            {
+                std::unique_lock<std::mutex> g(frame_mu);
+                frame_cv.wait(g, [&] { return frame_stop || !frame_queue.empty(); });
+                if (frame_queue.empty()) return;
+                job = std::move(frame_queue.front());
+                frame_queue.pop_front();
+                frame_writing = true;
+            }
+            if (frame_pictures && job.ppm) {
+                const std::string base = frame_prefix + "/frame_" + std::to_string(job.number);
+                if (!write_ppm_raw(base + ".ppm", rows, cols, job.ppm)) std::cerr << "cannot write " << base << ".ppm\n";
+                (void)write_text(base + ".txt", job.text);
+            }
+            if (!frame_video_name.empty() && job.avi) {
+                if (!video.is_open() && !video.open(frame_video_name, rows, cols, frame_video_fps))
+                    std::cout << "Could not open the output video for write" << std::endl;
+                if (video.is_open()) video.write_raw(job.avi);
+            }
+            if (job.ticket >= 0) (void)bf_frame_release(frame_state[(size_t)job.worker], job.ticket);
+            {
+                std::lock_guard<std::mutex> g(frame_mu);
+                if (job.ticket >= 0) --frame_held[(size_t)job.worker];
+                frame_writing = false;
+            }
+            frame_cv.notify_all();
+        }
+    }
+
     static uint16_t narrow(uint32_t v) {
         if (v > 65535u) throw AccelError(BF_ERR_ARG, "StreamEngine: event address " + std::to_string(v) + " does not fit 16 bits");
         return (uint16_t)v;
@@ -604,8 +832,12 @@ protected:
         if (chained && devices.size() * (size_t)contexts_per_device != 1)
             throw AccelError(BF_ERR_ARG, "StreamEngine: several devices / contexts need independent slices (set_stm_disable): a warm-start "
                                          "chain is sequential");
-        farm.reset(new SliceFarm(devices, contexts_per_device, (long long)max_sz, scale * RES_X + scale, scale * RES_Y + scale,
-                                 [this](const SliceFarm::Result &r) { deliver(r); }, chained));
+        if (frames_on && max_sz < 2)   // (a slice of a one-event ring is empty: the context would still hold the previous one)
+            throw AccelError(BF_ERR_ARG, "StreamEngine: frames need a ring of at least 2 events");
+        // (frames are rendered at scale 3: the colour tile is (3 RES_X + 3) x (3 RES_Y + 3), as DVS_flow reserves it)
+        const int fs = frames_on ? 3 : 0;
+        farm.reset(new SliceFarm(devices, contexts_per_device, (long long)max_sz, std::max(scale * RES_X + scale, fs * RES_X + fs),
+                                 std::max(scale * RES_Y + scale, fs * RES_Y + fs), [this](const SliceFarm::Result &r) { deliver(r); }, chained));
         size_t extra = lookahead ? lookahead : (2 * max_sz > 65536 ? 2 * max_sz : 65536);   // the producer may run two slices ahead
         cap = max_sz + extra;
         if (accumulate_device) {
@@ -635,6 +867,7 @@ protected:
             const int rc = bf_emit_create(c, (int64_t)cap, RES_X, RES_Y, (int64_t)cap, &emit_state);
             if (rc < 0) throw AccelError(rc, std::string("StreamEngine: bf_emit_create failed: ") + bf_last_error(c));
         }
+        if (frames_on) start_frames();
     }
 
     void archive(uint64_t g, uint64_t end) {   // (two contiguous pieces of the ring, appended in bulk)
@@ -692,6 +925,7 @@ protected:
             if (p.zero_excluded && uv) { const size_t s = (size_t)((p.first - 1) % cap); uv[2 * s] = uv[2 * s + 1] = 0.0; }
         }
         if (accumulate_device) collect_rows(farm->context((size_t)r.worker), p.index);
+        if (frames_on) deliver_frame(p, r);
         SliceRecord rec;
         rec.index = p.index; rec.first_event = p.first; rec.events = p.n; rec.ring_size = p.ring_size; rec.new_events = p.new_events;
         rec.start_time = p.start_time; rec.trigger_time = p.trigger_time; rec.time_diff = p.time_diff;

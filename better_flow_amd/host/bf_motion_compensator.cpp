@@ -13,9 +13,10 @@
 // Two slice managers sit behind the same flags and give the same results (tests/test_host_cli.py holds one to the
 // other): bf::StreamEngine (better_flow/stream_flow.h) -- events enter a pinned structure-of-arrays ring in bulk, a
 // binary input is read straight into that ring, slices are solved on a worker thread while the next block is read,
-// --devices= spreads independent slices (--stm-disable) over several GPUs, per-event flow is fetched only for -o -- and
-// DVS_flow (better_flow/dvs_flow.h), the reference's array-of-Event ring, which --img / --video / -i need (the frame
-// renderer works on its optimizer object) and --engine=ring selects.
+// --devices= spreads independent slices (--stm-disable) over several GPUs, per-event flow is fetched only for -o, the
+// --img / --video frames are composed on the device and written by a thread of their own -- and DVS_flow
+// (better_flow/dvs_flow.h), the reference's array-of-Event ring, which -i needs, --engine=ring selects, and --img / --video
+// still select by default.
 #include <better_flow/common.h>
 #include <better_flow/dvs_flow.h>
 #include <better_flow/stream_flow.h>
@@ -126,7 +127,7 @@ const std::vector<Flag> &flag_table() {
         {"--span", Arg::Inline, [](Options &o, const char *v) { o.span_sec = atof(v); o.ring_flags = true; }, "<seconds>",
          "time span of the event ring = longest slice (the reference compiles in 0.2)"},
         {"--engine", Arg::Inline, [](Options &o, const char *v) { o.engine = v; }, "stream|ring",
-         "slice manager: structure-of-arrays stream engine (default) or the reference's array-of-Event ring"},
+         "slice manager: structure-of-arrays stream engine (default) or the reference's array-of-Event ring (the default with --img / --video / -i)"},
         {"--devices", Arg::Inline, [](Options &o, const char *v) { o.devices = parse_device_list(v); if (o.devices.empty()) o.devices.push_back(-1); },
          "<list>", "HIP devices for independent slices (needs --stm-disable), e.g. 0-7 or 0,2"},
         {"--contexts", Arg::Inline, [](Options &o, const char *v) { o.contexts = atoi(v); }, "<n>", "slice contexts (worker threads) per device"},
@@ -197,9 +198,10 @@ int parse(int argc, char **argv, Options &o) {
     if (!o.have_input) { std::fprintf(stderr, "no input file\n"); return 1; }
     if (o.scale < 1 || o.scale % 2 == 0) { std::fprintf(stderr, "--scale must be odd\n"); return 1; }
     if (!o.engine.empty() && o.engine != "stream" && o.engine != "ring") { std::fprintf(stderr, "--engine must be stream or ring\n"); return 1; }
+    // (--img / --video run on both engines; without --engine they keep the reference ring)
     const bool needs_ring = o.frames || o.video || o.interactive;
     if (o.engine.empty()) o.engine = needs_ring ? "ring" : "stream";
-    if (o.engine == "stream" && needs_ring) { std::fprintf(stderr, "--img / --video / -i work on the reference ring: drop --engine=stream\n"); return 1; }
+    if (o.engine == "stream" && o.interactive) { std::fprintf(stderr, "-i works on the reference ring: drop --engine=stream\n"); return 1; }
     if (o.have_output_bin && o.output_bin.empty()) { std::fprintf(stderr, "--outfile-bin needs a file name: --outfile-bin=<file>\n"); return 1; }
     if (o.engine == "ring" && o.have_output_bin) {
         std::fprintf(stderr, "--outfile-bin belongs to the stream engine (the reference ring writes only the -o text)\n");
@@ -210,7 +212,7 @@ int parse(int argc, char **argv, Options &o) {
                      kMaxEvents, kMaxSpanSec);
         return 1;
     }
-    if (!o.more_inputs.empty() && (o.engine != "stream" || !o.to_bin.empty())) {
+    if (!o.more_inputs.empty() && (o.engine != "stream" || !o.to_bin.empty() || o.frames || o.video)) {
         std::fprintf(stderr, "several input files are independent streams of the stream engine: not with --engine=ring / --img / --video / -i / --to-bin\n");
         return 1;
     }
@@ -323,6 +325,7 @@ int run_stream(const Options &o) {
     if (o.have_output_bin) engine.set_accumulate_device();   // (-o then writes the same table)
     else if (o.have_output) engine.set_accumulate();
     engine.set_pipelined(!o.sync && !o.bufferize);
+    if (o.frames || o.video) engine.set_frames(o.frame_prefix, o.frames, o.video ? o.video_name : std::string(), o.video_fps);
     if (!o.devices.empty() || o.contexts > 1)
         engine.set_devices(o.devices.empty() ? std::vector<int>{bf::DeviceContext::device()} : o.devices, o.contexts);
     FILE *slice_log = nullptr;
@@ -443,10 +446,11 @@ int run_stream(const Options &o) {
     if (o.timing)
         std::fprintf(stderr, "{\"engine\": \"stream\", \"events\": %llu, \"slices\": %llu, \"iterations\": %llu, \"init_s\": %.6f, "
                              "\"stream_s\": %.6f, \"read_s\": %.6f, \"blocked_s\": %.6f, \"output_s\": %.6f, \"total_s\": %.6f, \"mevents_per_s\": %.3f, "
-                             "\"steady_s\": %.6f, \"steady_mevents_per_s\": %.3f, \"output_bin_s\": %.6f}\n",
+                             "\"steady_s\": %.6f, \"steady_mevents_per_s\": %.3f, \"output_bin_s\": %.6f, \"frames\": %llu, \"frame_wait_s\": %.6f}\n",
                      n_events, (unsigned long long)engine.get_slices_done(), (unsigned long long)engine.get_iterations_total(), s_init,
                      s_stream, s_read, engine.seconds_blocked(), s_output, seconds_since(t_start), s_stream > 0 ? n_events / s_stream * 1e-6 : 0.0,
-                     s_steady, s_steady > 0 ? (n_events - events_first_slice) / s_steady * 1e-6 : 0.0, s_output_bin);
+                     s_steady, s_steady > 0 ? (n_events - events_first_slice) / s_steady * 1e-6 : 0.0, s_output_bin,
+                     (unsigned long long)engine.frames_delivered(), engine.seconds_frame_wait());
     if (slice_log) std::fclose(slice_log);
     return 0;
 }

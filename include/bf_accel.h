@@ -604,6 +604,37 @@ int bf_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_
 int bf_emit_wait(bf_ctx *ctx, bf_emit *emit, int64_t ticket, uint64_t *first_row, int64_t *rows);
 int bf_emit_release(bf_emit *emit, uint64_t upto_row);
 
+/* ---- per-slice frames on the device: DVS_flow::render_frame (dvs_flow.h) -----------------------------------------------
+ * The frame of --img / --video: the 2 x 2 mosaic of the context's live slice -- projection image (grey) and colour-coded time
+ * image, motion compensated on top, as recorded below -- at scale 3 whatever scale the slice was solved at, every tile
+ * (3 res_x) x (3 res_y), so the frame is (6 res_x) x (6 res_y) pixels.  It is composed on the device in the byte layouts of the
+ * files: BF_FRAME_PPM, the PPM payload (top-down RGB, the bytes after the "P6" header), and BF_FRAME_AVI, the AVI payload
+ * (bottom-up BGR rows padded with zeros to a multiple of 4 bytes), both byte for byte those of host/better_flow/frame_writer.h.
+ * A bf_frame owns `slots` frames per layout in pinned, device-mapped host memory, which the compose kernel writes directly; it
+ * lives on the device of the context it was created with, and its contexts need an image capacity of
+ * (3 res_x + 3) x (3 res_y + 3) (bf_create's max_rows / max_cols).
+ *   bf_frame_create   state for a res_x x res_y sensor; layouts: a mask of BF_FRAME_PPM and BF_FRAME_AVI.
+ *   bf_frame_destroy  waits for the renders in flight, then frees everything.
+ *   bf_frame_render   ENQUEUES the frame of ctx's live slice -- as it stands after bf_run, a pending bf_set_model warp applied
+ *                     first, like bf_projection_img -- on ctx's stream into a free slot and returns at once with a ticket
+ *                     (0, 1, 2, ...).  The context may upload and solve its next slice at once: the frame sees the slice it
+ *                     was rendered from.  BF_ERR_CAPACITY when every slot is taken (checked first: nothing runs).
+ *   bf_frame_wait     waits for frame `ticket` and gives its payloads (NULL for a layout not created); valid until released.
+ *                     BF_ERR_ARG for a ticket released or never issued.
+ *   bf_frame_release  the slot of `ticket` may be reused.
+ *   bf_render_frame   the synchronous form: one frame of ctx's live slice into ppm_out (res_x * res_y * 108 bytes) and / or
+ *                     avi_out (6 res_x rows of ((18 res_y + 3) & ~3) bytes); either may be NULL, not both.
+ * The kernel is in bf_frame.hip; DESIGN.md, section 11, states what is bit-exact against what. */
+#define BF_FRAME_PPM 1
+#define BF_FRAME_AVI 2
+typedef struct bf_frame bf_frame;
+int bf_frame_create(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t slots, int32_t layouts, bf_frame **out);
+int bf_frame_destroy(bf_frame *frame);
+int bf_frame_render(bf_ctx *ctx, bf_frame *frame, int64_t *ticket_out);
+int bf_frame_wait(bf_ctx *ctx, bf_frame *frame, int64_t ticket, const uint8_t **ppm, const uint8_t **avi);
+int bf_frame_release(bf_frame *frame, int64_t ticket);
+int bf_render_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, uint8_t *ppm_out, uint8_t *avi_out);
+
 /* NUMA placement of a feeder thread (no reference counterpart: the reference is single-threaded, SURVEY 8(b) "Threading"; the
  * 8-GPU farm of SURVEY 8(e) wants one feeder thread per GPU with NUMA-local pinned buffers).
  *   bf_device_numa_node          host NUMA node of HIP device `device` (sysfs numa_node of its PCI function); -1: unknown.
