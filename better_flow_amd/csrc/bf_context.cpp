@@ -55,8 +55,7 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
         (void)hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, device);
         if (hip_stream) c->stream.borrow((hipStream_t)hip_stream);
         else HIP_TRY(c, c->stream.create(hipStreamNonBlocking));
-        const long long gran = (long long)kThreads * kEvPerThread;
-        c->cap_events = ((long long)max_events + gran - 1) / gran * gran;
+        c->cap_events = pad_events(max_events);
         c->cap_px = (size_t)max_rows * (size_t)max_cols;
         int gx, gy;
         stencil_grid(max_rows, max_cols, &gx, &gy);
@@ -67,9 +66,7 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
         HIP_TRY(c, c->set[0].t.grow(ne));
         HIP_TRY(c, c->set[0].p.grow(ne));
         HIP_TRY(c, c->d_noise.grow(ne));
-        HIP_TRY(c, c->d_in_x.grow(ne));
-        HIP_TRY(c, c->d_in_y.grow(ne));
-        HIP_TRY(c, c->d_in_t.grow(ne));
+        for (DevArray<int32_t>* a : {&c->up.slot[0].x, &c->up.slot[0].y, &c->up.slot[0].t}) HIP_TRY(c, a->grow(ne));   // (bf_upload_events)
         HIP_TRY(c, c->d_nxny.grow(ne));
         HIP_TRY(c, c->d_uv.grow(ne));
         for (int i = 0; i < 2; ++i) HIP_TRY(c, c->d_plane[i].grow(c->cap_px));
@@ -160,14 +157,14 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
 }
 
 // Teardown in one order: uncount, device, wait for BOTH streams (early staging writes the slots' arrays and pinned records on the
-// copy stream), drop uploads that were only recorded, dump the debug timeline; the handles then free everything.
+// copy stream), drop the pending uploads (those only RECORDED go unrun), dump the debug timeline; the handles then free everything.
 void bf_destroy(bf_ctx* c) {
     if (!c) return;
     if (c->counted) g_live_ctx[c->device & 63].fetch_sub(1);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    for (auto& f : c->deferred) f = nullptr;
+    if (c->up.stream) (void)hipStreamSynchronize(c->up.stream);
+    drop_uploads(c, 0);
     if (c->d_tl) {   // debug timeline dump: launch group slot ticks(100 MHz)
         std::vector<unsigned long long> tl(3 * 64 * 2 * 16);   // [kernel][launch][group][slot]
         (void)hipMemcpy(tl.data(), c->d_tl, tl.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
@@ -236,10 +233,10 @@ int bf_set_option(bf_ctx* c, const char* key, int64_t value) {
         HIP_TRY(c, hipSetDevice(c->device));
         const int rc = streaming_setup(c);
         if (rc != BF_OK) return rc;
-        for (int slot = 0; slot < 2; ++slot) {
-            HIP_TRY(c, c->d_in_ts[slot].grow((size_t)c->cap_events));
-            HIP_TRY(c, c->d_in16[slot].grow((size_t)c->cap_events * 2));
-            HIP_TRY(c, c->d_in_noise[slot].grow((size_t)c->cap_events));   // (else: first use, possibly in the middle of a solve)
+        for (bf_ctx::UploadSlot& s : c->up.slot) {
+            HIP_TRY(c, s.ts.grow((size_t)c->cap_events));
+            HIP_TRY(c, s.in16.grow((size_t)c->cap_events * 2));
+            HIP_TRY(c, s.noise.grow((size_t)c->cap_events));   // (else: first use, possibly in the middle of a solve)
         }
         return BF_OK;
     }

@@ -1,11 +1,11 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
 // bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
-// context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  Nothing here is part
-// of the ABI (include/bf_accel.h).
+// context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
+// uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
+// (bf_ctx::UploadSlot).  Nothing here is part of the ABI (include/bf_accel.h).
 #pragma once
 #pragma clang diagnostic ignored "-Wunused-function"   // (every file uses its own subset of the helpers below)
-#include <functional>
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -130,44 +130,56 @@ struct bf_ctx {
     DevArray<uint8_t> d_ltile;       // bf_local_run_tiles: the windows' states, then their return codes
     DevArray<uint8_t> d_many_args;   // bf_run_tiles_many (lead context): the slices' launch arguments + the claim counter
     HostArray<TileArgs> h_many_args; // ... and their pinned staging copy
-    DevArray<int32_t> d_in_x, d_in_y, d_in_t;
-    // streaming: a second staging slot, a copy stream and one event per slot
-    DevArray<int32_t> d_in2[3];
-    Stream copy_stream;
-    Event copy_done[2];
-    Event staged[2];                 // the staging kernels that read a slot have run (compute stream)
-    bool staged_valid[2] = {false, false};
-    long long pending_n[2] = {0, 0};
-    bool pending_ts64[2] = {false, false};       // slot holds absolute 64-bit timestamps (ring hand-off)
-    bool pending_ts32[2] = {false, false};       // ... of which only the low 32 bits were sent (bf_upload_ring16t32_async)
-    bool pending_addr16[2] = {false, false};     // ... and 16-bit addresses in d_in16 (bf_upload_ring16_async)
-    bool pending_noise[2] = {false, false};      // ... and Event::noise flags in d_in_noise
-    DevArray<uint16_t> d_in16[2];                // row[cap_events] then col[cap_events]
-    DevArray<uint8_t> d_in_noise[2];
-    unsigned long long pending_t0[2] = {0, 0};
-    DevArray<unsigned long long> d_in_ts[2];
-    int pend_head = 0, pend_count = 0;   // FIFO of pending async uploads (slot = index & 1)
-    // Early staging (round 6): an asynchronous upload WITHOUT a noise ring runs its staging kernels (widening, k_prepare)
-    // on the COPY stream, right behind its copies, into the slot's own event arrays and its own pinned statistics record --
-    // under the previous slice's solve.  bf_commit_upload then only swaps those arrays with set[0]'s (pointers) and makes the
-    // compute stream wait for the slot's `prepared` event: no staging kernel and no statistics round trip are left on a
-    // warm-started chain's critical path (~35 us of a ~230 us slice at 346x260).
-    EvSet inc[2];                                 // xy, t, p of the slice staged in slot i
-    HostArray<SliceStats> h_stats_slot[2];        // k_prepare's per-work-group records of slot i
-    Event prepared[2];                            // slot i's staging kernels have run (copy stream)
-    Event inc_free[2];                            // the arrays swapped INTO inc[i] at a commit are free (compute stream is past that commit)
-    bool inc_free_valid[2] = {false, false};
-    bool pending_early[2] = {false, false};
-    // "defer_uploads": an asynchronous upload only takes its slot and remembers what to copy; its HIP calls (three copies, the
+    // One staging slot of the asynchronous uploads (bf_upload.cpp).  Its state:
+    //   FREE      not taken;
+    //   RECORDED  taken, `src` describes what to copy, no HIP call issued yet ("defer_uploads");
+    //   ISSUED    the copies are on the copy stream; the staging kernels run on the compute stream at the commit;
+    //   EARLY     the copies and, behind them on the copy stream, the staging kernels (widening, k_prepare) into the slot's own
+    //             event arrays and pinned statistics record -- under the previous slice's solve.  The commit then only swaps
+    //             those arrays with set[0]'s and makes the compute stream wait for `prepared`: no staging kernel and no
+    //             statistics round trip on a warm-started chain's critical path (~35 us of a ~230 us slice at 346x260).
+    struct UploadSlot {
+        enum State { FREE, RECORDED, ISSUED, EARLY };
+        // what the host columns hold: int32 addresses and slice-local int32 times / int32 addresses and absolute 64-bit
+        // nanoseconds / 16-bit addresses and absolute nanoseconds / 16-bit addresses and the low 32 bits of those
+        enum Format { LOCAL32, TS64, ADDR16_TS64, ADDR16_TS32 };
+        struct Source {                   // [first, first + n) of host rings of cap entries (a flat array: first 0, cap n)
+            const void *x, *y, *ts;
+            const uint8_t* noise;         // Event::noise ring, or null
+            long long cap, first, n;
+            unsigned long long t0;        // slice start of the absolute timestamps
+            Format fmt;
+        };
+        State state = FREE;
+        Source src{};
+        DevArray<int32_t> x, y, t;        // what k_prepare reads (slot 0's: also the blocking upload's, allocated at bf_create)
+        DevArray<unsigned long long> ts;  // absolute timestamps (the 32-bit form uses half)
+        DevArray<uint16_t> in16;          // 16-bit addresses: row[cap_events] then col[cap_events]
+        DevArray<uint8_t> noise;
+        EvSet inc;                        // EARLY: xy, t, p of the slice
+        HostArray<SliceStats> stats;      // EARLY: k_prepare's per-work-group records
+        Event copy_done;                  // the copies have landed (copy stream)
+        Event staged;                     // the staging kernels that read x / y / t have run (compute stream)
+        Event prepared;                   // EARLY: the staging kernels have run (copy stream)
+        Event inc_free;                   // the arrays swapped INTO inc at a commit are free (compute stream is past that commit)
+        bool staged_valid = false, inc_free_valid = false;
+    };
+    // Everything an uploading second thread touches (bf_accel.h: threading) -- and, through fold_stats, the statistics.
+    struct Uploads {
+        Stream stream;                    // the copy stream
+        UploadSlot slot[2];
+        int head = 0, count = 0;          // FIFO of taken slots: the k-th oldest is slot[(head + k) & 1]
+        UploadSlot& at(int k) { return slot[(head + k) & 1]; }
+    } up;
+    // "defer_uploads": an asynchronous upload only takes its slot and records what to copy; its HIP calls (three copies, the
     // staging kernels, the events: ~25 us of host time) are issued by the next bf_run once that run's first batch of kernels is in
     // the queue -- or by whoever needs the slot sooner (bf_commit_upload, bf_wait_uploads).  For a single-threaded caller
     // driving one warm-started chain those 25 us otherwise sit between two runs, with the GPU idle.
     int opt_sep_update = 1;          // co-scheduled contexts: the update as a kernel of its own -- 0 never, 1 for event lists, 2 always (plan_run)
     bool opt_defer_uploads = false;
-    std::function<int()> deferred[2];
-    std::mutex stats_mu;                          // fold_stats: bf_set_cloud's thread and an uploading thread (stage_early's guard) may both fold
+    std::mutex stats_mu;                          // fold_stats: bf_set_cloud's thread and an uploading thread (stage_early) may both fold
     const SliceStats* stats_src = nullptr;        // where fold_stats reads (h_stats, or the committed slot's record)
-    hipEvent_t stats_event = nullptr;             // ... once this event has completed (null: the compute stream); one of prepared[], not owned
+    hipEvent_t stats_event = nullptr;             // ... once this event has completed (null: the compute stream); a slot's `prepared`, not owned
     DevArray<double2> d_nxny, d_uv;
     DevArray<unsigned long long> d_plane[2];
     DevArray<uint32_t> d_cplane[2];
@@ -268,6 +280,13 @@ bool plan_one_kernel(const bf_ctx* c);   // (and bf_get_stat)
 bool plan_persistent(const bf_ctx* c);   // (and bf_get_stat: without the back-off after a launch gave up)
 RunPlan plan_run(bf_ctx* c, const bf_run_opts& o);   // (takes one run of that back-off)
 
+// The asynchronous uploads (bf_upload.cpp): the copy stream, the slots' events and arrays (on first use); the HIP side of the
+// RECORDED uploads, oldest first (one that fails is dropped with every upload behind it); every taken slot from FIFO position k
+// on returned to FREE.
+int streaming_setup(bf_ctx* c);
+int issue_deferred_uploads(bf_ctx* c);
+void drop_uploads(bf_ctx* c, int k);
+
 namespace {
 
 int fail(bf_ctx* c, int code, const char* fmt, ...) {
@@ -344,6 +363,12 @@ int prof_fold(bf_ctx* c) {
     }
     c->prof_pending.clear();
     return BF_OK;
+}
+
+// n events padded to whole k_prepare work-groups (the event arrays' granule)
+long long pad_events(long long n) {
+    constexpr long long gran = (long long)kThreads * kEvPerThread;
+    return (n + gran - 1) / gran * gran;
 }
 
 int bit_length(unsigned long long v) {
@@ -572,12 +597,14 @@ int wait_event_sleeping(bf_ctx* c, hipEvent_t ev) {
 }
 
 // Folds the per-work-group min / max / sum records k_prepare wrote for the uploaded slice (one
-// device-to-host copy per slice, cached).
-int fold_stats(bf_ctx* c) {
+// device-to-host copy per slice, cached).  With `overwritten`, a record about to be reused: only if the slice's statistics are
+// still unread in that record.
+int fold_stats(bf_ctx* c, const SliceStats* overwritten = nullptr) {
     // (one folder at a time: with early staging the thread that uploads the NEXT slice into this record's slot folds the current
     // slice's statistics first if nobody has -- bf_upload.cpp: stage_early -- while bf_set_cloud may be doing the same)
     std::lock_guard<std::mutex> lk(c->stats_mu);
     if (c->stats_valid) return BF_OK;
+    if (overwritten && (!c->uploaded || c->stats_src != overwritten)) return BF_OK;
     // (the records are in pinned host memory once k_prepare has completed: on the compute stream, or -- early staging -- on the
     // copy stream, usually long ago)
     if (c->stats_event) HIP_TRY(c, hipEventSynchronize(c->stats_event));
@@ -612,39 +639,6 @@ int after_upload(bf_ctx* c, long long n) {
     c->n_valid = false;
     c->uv_valid = false;
     c->out_sorted = false;
-    return BF_OK;
-}
-
-// the HIP side of uploads that were only recorded ("defer_uploads"), oldest first.  One that fails is dropped with every upload
-// behind it: the uploads ahead of it stay pending and committable, the failed ones were never taken.
-int issue_deferred_uploads(bf_ctx* c) {
-    for (int k = 0; k < c->pend_count; ++k) {
-        const int slot = (c->pend_head + k) & 1;
-        if (!c->deferred[slot]) continue;
-        std::function<int()> f;
-        f.swap(c->deferred[slot]);
-        const int rc = f();
-        if (rc != BF_OK) {
-            for (int j = k + 1; j < c->pend_count; ++j) c->deferred[(c->pend_head + j) & 1] = nullptr;
-            c->pend_count = k;
-            return rc;
-        }
-    }
-    return BF_OK;
-}
-
-// copy stream, its events and the second staging slot of the asynchronous uploads (created on first use)
-int streaming_setup(bf_ctx* c) {
-    const size_t ne = (size_t)c->cap_events;
-    HIP_TRY(c, c->copy_stream.create(hipStreamNonBlocking));
-    for (int i = 0; i < 3; ++i) HIP_TRY(c, c->d_in2[i].grow(ne));
-    for (int i = 0; i < 2; ++i) {   // (early staging: the slots' own event arrays, statistics records and events)
-        for (Event* e : {&c->copy_done[i], &c->staged[i], &c->prepared[i], &c->inc_free[i]}) HIP_TRY(c, e->create(hipEventDisableTiming));
-        HIP_TRY(c, c->inc[i].xy.grow(ne));
-        HIP_TRY(c, c->inc[i].t.grow(ne));
-        HIP_TRY(c, c->inc[i].p.grow(ne));
-        HIP_TRY(c, c->h_stats_slot[i].grow(kPrepBlocks));
-    }
     return BF_OK;
 }
 

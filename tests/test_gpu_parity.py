@@ -587,11 +587,18 @@ def test_tile_grid_matches_per_tile_oracle(oracle_lib, accel_mod):
 
 def test_streaming_upload_matches_blocking(accel_mod):
     """Config 3 plumbing: the copy-stream upload (two staging slots) must give exactly the
-    results of the blocking upload over an STM chain of slices."""
+    results of the blocking upload over an STM chain of slices -- on a context alone on the GPU (early staging on the copy
+    stream) and on a co-scheduled one (staging on the compute stream at the commit)."""
+    for co in (0, 1):
+        _streaming_matches_blocking(accel_mod, co)
+
+
+def _streaming_matches_blocking(accel_mod, co):
     H, W, s = 180, 240, 3
     sls = [synth.make_slice(30000, H, W, 0.03, seed=60 + i) for i in range(4)]
     nmax = max(len(sl["t"]) for sl in sls)
     acc = accel_mod.Accel(max_events=nmax, max_rows=s * H + s, max_cols=s * W + s)
+    acc.set_option("co_schedule", co)   # (before the reference: both chains solve in the same loop form)
 
     def chain(upload):
         prev, out = None, []
@@ -621,7 +628,7 @@ def test_streaming_upload_matches_blocking(accel_mod):
             put(i + 1)
 
     got = chain(up)
-    assert got == ref
+    assert got == ref, co
     with pytest.raises(accel_mod.BfError):
         acc.commit_upload()                       # nothing pending
     # ... TWO uploads ahead of the slice being solved (the staging kernels of slice i + 1 run on the copy stream, into the slot's own
@@ -650,14 +657,14 @@ def test_streaming_upload_matches_blocking(accel_mod):
                 acc.commit_upload()
                 if i + 2 < len(sls):
                     put2(i + 2)
-            assert chain(up2) == ref, (defer, pins is pin16)
+            assert chain(up2) == ref, (co, defer, pins is pin16)
             # cold slices with a per-event read-back each, same pattern
             put2(0); put2(1)
             for i in range(len(sls)):
                 up2(i, sls[i])
                 acc.set_cloud(s, H, W)
                 acc.run()
-                assert tuple(a.tobytes() for a in acc.compute_uv()) == want_uv[i], (defer, i)
+                assert tuple(a.tobytes() for a in acc.compute_uv()) == want_uv[i], (co, defer, i)
     acc.set_option("defer_uploads", 1)
     put2(0)                                        # recorded only ...
     acc.set_option("defer_uploads", 0)             # ... goes out when the mode ends
@@ -665,18 +672,26 @@ def test_streaming_upload_matches_blocking(accel_mod):
     acc.commit_upload()
     acc.set_cloud(s, H, W)
     rc, m0, info0 = acc.run()
-    assert (rc, info0.iterations) == ref[0][:2]
+    assert (rc, info0.iterations) == ref[0][:2], co
     acc.close()
 
 
 def test_staging_slots_are_not_overwritten_early(accel_mod):
     """Two uploads in flight, then a third into the slot of the first as soon as that one is committed (legal: "at most
     two pending"): the third copy must wait until the staging kernel of the first has read the slot.  Large slices and a
-    busy compute stream make the window wide.  A blocking upload while asynchronous ones are pending is refused."""
+    busy compute stream make the window wide.  A blocking upload while asynchronous ones are pending is refused.  Both
+    staging paths: early, on the copy stream (a context alone on the GPU), and at the commit, on the compute stream (a
+    co-scheduled context: the slot's reuse waits for its `staged` event)."""
+    for co in (0, 1):
+        _staging_slots_not_overwritten_early(accel_mod, co)
+
+
+def _staging_slots_not_overwritten_early(accel_mod, co):
     H, W, s = 260, 346, 3
     sls = [synth.make_slice(600000, H, W, 0.03, seed=90 + i) for i in range(4)]
     nmax = max(len(sl["t"]) for sl in sls)
     acc = accel_mod.Accel(max_events=nmax, max_rows=s * H + s, max_cols=s * W + s)
+    acc.set_option("co_schedule", co)   # (before the reference: both solve in the same loop form)
     o = acc.default_opts()
     o.res_x, o.res_y, o.max_iter = H, W, 12
 
@@ -709,7 +724,7 @@ def test_staging_slots_are_not_overwritten_early(accel_mod):
     got.append(solve())
     acc.commit_upload(); got.append(solve())
     acc.commit_upload(); got.append(solve())
-    assert got == ref
+    assert got == ref, co
     acc.close()
 
 
@@ -1286,6 +1301,18 @@ def test_ring16_hand_off_with_noise_and_flow_ring(oracle_lib, accel_mod):
             assert np.isnan(uv[0::2][rest]).all()                  # nothing outside the slice's ring positions was written
         else:
             assert int(got[0].sum()) > int(want[0].sum())          # without the mask the flagged events count again
+    # the no-noise ring on a co-scheduled context (staged on the compute stream at the commit, not early on the copy stream):
+    # identical to the blocking upload of the same slice in the same loop form
+    acc.set_option("co_schedule", 1)
+    acc.upload_events(sl["fr_x"], sl["fr_y"], sl["t"])
+    want_co = solve(acc)
+    want_co_uv = acc.compute_uv()
+    acc.upload_ring_async(ring_row, ring_col, ring_ts, first, n, t0)
+    acc.commit_upload()
+    got = solve(acc)
+    assert np.array_equal(got[0], want_co[0]) and got[1:] == want_co[1:]
+    assert all(np.array_equal(a, b) for a, b in zip(acc.compute_uv(), want_co_uv))
+    acc.set_option("co_schedule", 0)
     # the int32 ring form carries the same noise ring
     acc.upload_ring_async(ring_row.astype(np.int32), ring_col.astype(np.int32), ring_ts, first, n, t0, ring_noise)
     acc.commit_upload()
