@@ -1,7 +1,7 @@
 """Two numpy-level restatements of the -o table's marking rule (DVS_flow::get_accumulated, dvs_flow.h:351-389).
 
-host_rows: StreamEngine::get_accumulated (stream_flow.h) literally -- per-pixel prev / next chains over the whole history,
-  a mark array per slice, an emitted event marking its later copies, same-pixel predecessors less than 0.1 ms before it and
+host_rows: StreamEngine::get_accumulated (HostFlowAccumulator::table, flow_table.h) literally -- per-pixel prev / next
+  chains over the whole history, a mark array per slice, an emitted event marking its later copies, same-pixel predecessors less than 0.1 ms before it and
   same-instant successors in every later slice.
 device_rows: the form bf_emit.hip computes -- a covered byte per ring position read before the slice and written after
   it, the slice sorted by (pixel, arrival) and walked from each element (the pull form), and a per-pixel tail for marks

@@ -88,3 +88,18 @@ def test_stream_engine_and_slice_farm_under_thread_sanitizer(tmp_path):
     r = subprocess.run(pre + [exe, txt], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1800)
     assert r.returncode == 0 and b"ThreadSanitizer" not in r.stderr, r.stderr.decode()[-4000:]
     assert r.stdout.decode().count("\nOK ") + r.stdout.decode().startswith("OK ") == 8
+
+
+def test_failure_latch_under_thread_sanitizer(tmp_path):
+    """The failure seam of the stream engine and its components (better_flow/failure_latch.h) on its own, without a device
+    or a C-ABI library -- tests/cpp/test_failure_latch.cpp: two reporters and two waiters per round; first failure wins,
+    rethrow() throws it, every waiter is woken.  Any data-race report fails the run (halt_on_error)."""
+    exe = str(tmp_path / "test_failure_latch_tsan")
+    subprocess.check_call(["g++", "-O1", "-std=c++14", "-pthread", "-fsanitize=thread", "-g", "-fno-omit-frame-pointer",
+                           "-I" + os.path.join(ROOT, "better_flow_amd", "host"), "-I" + os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "test_failure_latch.cpp"), "-o", exe])
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:second_deadlock_stack=1")
+    pre = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []   # (as above)
+    r = subprocess.run(pre + [exe], cwd=str(tmp_path), env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0 and b"ThreadSanitizer" not in r.stderr, (r.stdout.decode()[-2000:], r.stderr.decode()[-4000:])
+    assert r.stdout.decode().startswith("OK failure latch: 300 rounds")
