@@ -151,9 +151,13 @@ EXPORTS = [
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
     "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
     "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
+    "bf_flow_field", "bf_color_flow_img", "bf_flow_frame_create", "bf_flow_frame_destroy", "bf_flow_frame_render",
+    "bf_flow_frame_wait", "bf_flow_frame_release", "bf_render_flow_frame",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
+BF_FLOW_FRAME_FLO = 4               # ... and bf_flow_frame_create's third
+BF_FLOW_LAST_UPLOADED, BF_FLOW_FIRST_UPLOADED = 0, 1   # owner_rule of the per-pixel flow
 
 _lib = None
 
@@ -316,6 +320,16 @@ def load(path=None):
                                     C.POINTER(C.POINTER(C.c_uint8))]
         L.bf_frame_release.argtypes = [C.c_void_p, C.c_int64]
         L.bf_render_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        # per-pixel flow (include/bf_accel.h: bf_flow_field, bf_color_flow_img, bf_flow_frame_*, bf_render_flow_frame)
+        L.bf_flow_field.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bf_color_flow_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        L.bf_flow_frame_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+        L.bf_flow_frame_destroy.argtypes = [C.c_void_p]
+        L.bf_flow_frame_render.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
+        L.bf_flow_frame_wait.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.POINTER(C.c_uint8)),
+                                         C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_float))]
+        L.bf_flow_frame_release.argtypes = [C.c_void_p, C.c_int64]
+        L.bf_render_flow_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         _libs[path] = L
         if path == LIB_PATH:
             _lib = L
@@ -535,6 +549,33 @@ class Accel:
         a = np.empty((rows, (cols * 3 + 3) & ~3), dtype=np.uint8) if avi else None
         self._chk(self.L.bf_render_frame(self.h, res_x, res_y, _ptr(p), _ptr(a)))
         return p, a
+
+    def flow_field(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED):
+        """The per-pixel flow field of the live slice (bf_flow_field): (owner, u, v), each (res_x, res_y) -- the upload index
+        of the event that owns the pixel (-1: none) and its (best_u, best_v) as bf_compute_uv returns them (0: none)."""
+        owner = np.empty((res_x, res_y), dtype=np.int32)
+        u, v = np.empty((res_x, res_y)), np.empty((res_x, res_y))
+        self._chk(self.L.bf_flow_field(self.h, res_x, res_y, owner_rule, _ptr(owner), _ptr(u), _ptr(v)))
+        return owner, u, v
+
+    def color_flow_img(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, want_hs=False):
+        """EventFile::color_flow_img (event_file.h:318-350): the (res_x, res_y, 3) B, G, R colour-coded flow of the live
+        slice; with want_hs also the (res_x, res_y, 2) H and S bytes before the conversion."""
+        bgr = np.empty((res_x, res_y, 3), dtype=np.uint8)
+        hs = np.empty((res_x, res_y, 2), dtype=np.uint8) if want_hs else None
+        self._chk(self.L.bf_color_flow_img(self.h, res_x, res_y, owner_rule, _ptr(bgr), _ptr(hs)))
+        return (bgr, hs) if want_hs else bgr
+
+    def render_flow_frame(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, ppm=True, avi=True, flo=True):
+        """The flow frame of the live slice, composed on the device (bf_render_flow_frame): compensated events | colour-coded
+        flow | raw events.  Returns (ppm, avi, flo): the PPM payload as a (res_x, 3 res_y, 3) RGB array, the AVI payload as a
+        (res_x, stride) byte array of bottom-up BGR rows, the .flo payload as (res_x, res_y, 2) float32 (horizontal = v,
+        vertical = u; 1e9 without an event); None for a layout not asked for."""
+        p = np.empty((res_x, 3 * res_y, 3), dtype=np.uint8) if ppm else None
+        a = np.empty((res_x, (9 * res_y + 3) & ~3), dtype=np.uint8) if avi else None
+        f = np.empty((res_x, res_y, 2), dtype=np.float32) if flo else None
+        self._chk(self.L.bf_render_flow_frame(self.h, res_x, res_y, owner_rule, _ptr(p), _ptr(a), _ptr(f)))
+        return p, a, f
 
     def local_run(self, res_x=180, res_y=240, max_evaluations=100000):
         st = LocalState()

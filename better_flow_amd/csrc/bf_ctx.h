@@ -1,5 +1,5 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
@@ -204,6 +204,7 @@ struct bf_ctx {
     DevArray<uint8_t> d_limg;                     // project_img
     DevArray<uint8_t> d_col_planes;               // colour time image: sum cos, sum sin (i64), count (u32) point planes
     DevArray<uint8_t> d_col_img;                  // ... and its B, G, R bytes
+    DevArray<uint8_t> d_flow;                     // flow field / colour-coded flow / flow frame scratch (bf_flow_abi.cpp: FlowScratch)
     HostArray<unsigned long long> h_lscore;
     bf_local_window lwin;
     bool have_lwin = false;
@@ -251,6 +252,10 @@ struct bf_ctx {
 
 // the live slice's per-event flow in upload order on the device, or null (bf_operators.cpp)
 extern "C" int ctx_device_uv(bf_ctx* c, const double2** uv);
+
+// the live slice's per-event (nx, ny) in upload order on the device, a pending bf_set_model warp applied first; null when no
+// warp has run (Event::reset: n = 0) or the window is degenerate (bf_operators.cpp)
+extern "C" int ctx_device_nxny(bf_ctx* c, const double2** nxny);
 
 // The two frame tiles of the live slice (bf_extras.cpp), ENQUEUED on the context stream into device memory: the 8-bit projection
 // image, (scale res_x) x (scale res_y), and the colour-coded time image, (scale res_x + scale) x (scale res_y + scale) BGR.  A

@@ -5,6 +5,7 @@
 
 #include "bf_device.h"
 #include "bf_kernels.h"
+#include "../../include/bf_flow_color.h"
 #include <math.h>
 #include <math.h>
 
@@ -12,9 +13,8 @@ namespace bf {
 
 // `int x = <double>` on x86-64 is cvttsd2si: NaN / out-of-range -> INT_MIN (then rejected by
 // the bounds test of accel_lib.h:157).  v_cvt_i32_f64 would saturate / give 0 instead.
-__device__ __forceinline__ int trunc_x86(double v) {
-    return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-}
+// (the rule itself is stated once, for device and host: bf_double_to_int_x86, include/bf_flow_color.h)
+__device__ __forceinline__ int trunc_x86(double v) { return bf_double_to_int_x86(v); }
 
 // The same for a scatter position, whose only consumer is the window test of accel_lib.h:157: anything out of int
 // range is rejected there whichever end it saturates to (the window is far inside the int range), so the hardware's
@@ -57,6 +57,17 @@ __device__ __forceinline__ double div_1e9(double x) {
     const double q0 = x * R;
     const double r = fma(-q0, 1000000000.0, x);
     return fma(r, R, q0);   // (x is a finite integer; x == 0 gives 0 either way)
+}
+
+// Event::compute_uv, event.h:135-142 -- the ONE place this arithmetic lives (k_compute_uv, the final warp of bf_run, and the
+// per-pixel flow field of bf_flowimg.hip give the same bits).
+__device__ __forceinline__ double2 uv_from_n(double2 v) {
+    const double len = hypot(v.x, v.y);
+    const double speed = len / (127.0 / (double)(1000000000 / (1 * 10000)));
+    double2 o;
+    o.x = (len == 0) ? 0 : speed * v.x / len;
+    o.y = (len == 0) ? 0 : speed * v.y / len;
+    return o;
 }
 
 // Previous / new projected position from the stored f32 product (event.h:167-168):

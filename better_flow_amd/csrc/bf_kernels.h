@@ -339,4 +339,31 @@ struct FrameCompose {
 };
 void launch_frame_compose(const FrameCompose& a, hipStream_t s);
 
+// bf_flowimg.hip -- the per-pixel flow field and EventFile::color_flow_img (event_file.h:318-350) of a slice on a res_x x res_y
+// sensor (pixel (x, y) at x * res_y + y).  The event sources are plain pointers: address word and f32 products in slot order,
+// `perm` the upload index of a slot (null: the identity), `noise` flags and `nxny` in upload order (null: no flag / zero flow).
+struct FlowSources {
+    const uint32_t* xy; const float2* p; const uint32_t* perm; const uint8_t* noise; const double2* nxny;
+    long long n;
+};
+// owner: res_x * res_y words, every one 0xffffffff ("none") on entry; first != 0: the smallest upload index that lands on a
+// pixel owns it, else the largest
+void launch_flow_owner(const FlowSources& e, int res_x, int res_y, int first, uint32_t* owner, hipStream_t s);
+// per pixel, every destination optional: owner index or -1, (u, v) of the owner (0 without one), the .flo pair (float v, float
+// u; 1e9 twice without an owner), the H and S bytes, the B, G, R bytes
+struct FlowFieldOut {
+    int32_t* owner; double *u, *v; float2* flo; uint8_t *hs, *bgr;
+};
+void launch_flow_field(const uint32_t* owner, const double2* nxny, long long px, const FlowFieldOut& o, hipStream_t s);
+// The flow frame: three R x C tiles side by side -- grey | B, G, R | grey -- as PPM payload (top-down RGB, ppm_dwords dwords
+// cover its 9 R C bytes) and / or AVI payload (bottom-up BGR rows of `stride` bytes, zero padding); a null destination is skipped.
+struct FlowFrameCompose {
+    const uint8_t *left, *flow, *right;
+    int R, C;
+    uint8_t *ppm, *avi;
+    long long ppm_dwords, avi_dwords;
+    int stride;
+};
+void launch_flow_frame_compose(const FlowFrameCompose& a, hipStream_t s);
+
 }  // namespace bf

@@ -26,16 +26,6 @@
 
 namespace bf {
 
-// Event::compute_uv, event.h:135-142.
-__device__ __forceinline__ double2 uv_from_n(double2 v) {
-    const double len = hypot(v.x, v.y);
-    const double speed = len / (127.0 / (double)(1000000000 / (1 * 10000)));
-    double2 o;
-    o.x = (len == 0) ? 0 : speed * v.x / len;
-    o.y = (len == 0) ? 0 : speed * v.y / len;
-    return o;
-}
-
 template <bool WARP, bool SCATTER, bool WRITE_N, bool PACKED>
 __device__ __forceinline__ void event_body(uint32_t xy, int32_t t, float2& p, bool live,
                                            bool noise, double2* nxny, double2* uv, const uint32_t* perm,

@@ -409,42 +409,6 @@ __global__ __launch_bounds__(kThreads) void k_color_point(const uint32_t* __rest
     atomicAdd(&ps[at], (unsigned long long)llrint(sin((double)angle) * 4294967296.0));
 }
 
-__device__ __forceinline__ uint8_t unit_to_u8(float x) {
-    const float v = x * 255.0f;
-    return (uint8_t)(v <= 0.0f ? 0 : (v >= 255.0f ? 255 : (int)rintf(v)));
-}
-
-// HSV (H in [0, 180), S, V in [0, 255]) -> B, G, R; float32, no contraction.
-__device__ __forceinline__ void hsv_to_bgr_u8(int H, int S, int V, uint8_t* bgr) {
-    const float s = (float)S * (1.0f / 255.0f), v = (float)V * (1.0f / 255.0f);
-    float h = (float)H * (6.0f / 180.0f);
-    int sector = (int)floorf(h);
-    h -= (float)sector;
-    sector = ((sector % 6) + 6) % 6;
-    float tab[4];
-    tab[0] = v;
-    tab[1] = v * (1.0f - s);
-    tab[2] = v * (1.0f - s * h);
-    tab[3] = v * (1.0f - s * (1.0f - h));
-    int ib, ig, ir;
-    switch (sector) {
-        case 0: ib = 1; ig = 3; ir = 0; break;
-        case 1: ib = 1; ig = 0; ir = 2; break;
-        case 2: ib = 3; ig = 0; ir = 1; break;
-        case 3: ib = 0; ig = 2; ir = 1; break;
-        case 4: ib = 0; ig = 1; ir = 3; break;
-        default: ib = 2; ig = 1; ir = 0; break;
-    }
-    float b = tab[0], gg = tab[0], r = tab[0];
-#pragma unroll
-    for (int k = 1; k < 4; ++k) {
-        b = ib == k ? tab[k] : b;
-        gg = ig == k ? tab[k] : gg;
-        r = ir == k ? tab[k] : r;
-    }
-    bgr[0] = unit_to_u8(b); bgr[1] = unit_to_u8(gg); bgr[2] = unit_to_u8(r);
-}
-
 __global__ __launch_bounds__(kThreads) void k_color_final(const uint32_t* __restrict__ cnt,
                                                           const unsigned long long* __restrict__ pc,
                                                           const unsigned long long* __restrict__ ps, ColorGeom g,
@@ -474,7 +438,7 @@ __global__ __launch_bounds__(kThreads) void k_color_final(const uint32_t* __rest
         if (speed != 0) angle = (atan2((double)vy, (double)vx) + 3.1416) * 180 / 3.1416;   // :717-718
         const int H = (int)(unsigned char)trunc_x86(angle / 2);           // :720-722 (double -> uchar)
         const int S = (int)(unsigned char)trunc_x86(speed * 255);
-        hsv_to_bgr_u8(H, S, 255, out);
+        bf_hsv_to_bgr_u8(H, S, 255, out);   // include/bf_flow_color.h
     }
     bgr[3 * i + 0] = out[0]; bgr[3 * i + 1] = out[1]; bgr[3 * i + 2] = out[2];
 }

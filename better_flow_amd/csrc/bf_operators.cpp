@@ -339,6 +339,19 @@ int ctx_device_uv(bf_ctx* c, const double2** uv) {
     return BF_OK;
 }
 
+// The per-event (nx, ny) of the live slice in upload order on the device; null when no warp has run or the window is
+// degenerate.  For the flow field (bf_flow_abi.cpp), which forms (u, v) at the owning events only.
+int ctx_device_nxny(bf_ctx* c, const double2** nxny) {
+    *nxny = nullptr;
+    int rc = flush_pending(c);
+    if (rc != BF_OK) return rc;
+    if (c->n == 0 || !c->n_valid || !c->have_window || c->degenerate) return BF_OK;
+    rc = materialize_outputs(c);
+    if (rc != BF_OK) return rc;
+    *nxny = c->d_nxny;
+    return BF_OK;
+}
+
 // (d_src null: zeros -- Event::reset leaves nx = ny = 0, event.h:57)
 static int copy_pairs(bf_ctx* c, const double2* d_src, double* a, double* b) {
     std::vector<double2> tmp((size_t)c->n);

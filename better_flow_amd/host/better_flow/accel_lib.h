@@ -13,6 +13,7 @@
 #define BF_HOST_ACCEL_LIB_H
 
 #include <better_flow/event.h>
+#include <better_flow/flow_field.h>
 #include <better_flow/object_model.h>
 #include <bf_accel.h>
 
@@ -87,6 +88,7 @@ private:
     bf_ctx *ctx;
     size_t size;   // number of events staged
     bool staged;
+    std::vector<uint8_t> noise_staged;   // Event::noise as uploaded (empty: none) -- the host composition of the flow field reads it
 
     void check(int rc, const char *what) const {
         if (rc < 0)
@@ -139,6 +141,8 @@ private:
         check(bf_upload_events(ctx, fx.data(), fy.data(), ft.data(), any_noise ? noise.data() : nullptr,
                                (int64_t)size), "init_gpu");
         this->staged = true;
+        if (!any_noise) noise.clear();
+        this->noise_staged.swap(noise);
     }
 
 public:
@@ -245,6 +249,25 @@ public:
         *rows = RES_X * sc + sc; *cols = RES_Y * sc + sc;
         std::vector<uint8_t> img((size_t)*rows * (size_t)*cols * 3);
         check(bf_color_time_img(ctx, scale, RES_X, RES_Y, show_final ? 1 : 0, img.data()), "color_time_img");
+        return img;
+    }
+
+    // The per-pixel flow field of the staged slice (bf_flow_field): RES_X x RES_Y owner indices and (best_u, best_v).  The
+    // events were uploaded in the cloud's iteration order, which is the order EventFile::color_flow_img walks them in
+    // (event_file.h:321), so the last uploaded event on a pixel owns it: BF_FLOW_LAST_UPLOADED.
+    bf::FlowField flow_field() {
+        bf::FlowField f(RES_X, RES_Y);
+        if (bf_flow_field) check(bf_flow_field(ctx, RES_X, RES_Y, BF_FLOW_LAST_UPLOADED, f.owner.data(), f.u.data(), f.v.data()), "flow_field");
+        else check(bf::flow_field_from_readbacks(ctx, size, noise_staged.empty() ? nullptr : noise_staged.data(), RES_X, RES_Y,
+                                                 BF_FLOW_LAST_UPLOADED, f), "flow_field");
+        return f;
+    }
+
+    // EventFile::color_flow_img (event_file.h:318-350) of the staged slice: RES_X x RES_Y pixels of B, G, R bytes
+    std::vector<uint8_t> color_flow_img() {
+        if (!bf_color_flow_img) return bf::color_flow_img_of(flow_field());
+        std::vector<uint8_t> img((size_t)RES_X * (size_t)RES_Y * 3);
+        check(bf_color_flow_img(ctx, RES_X, RES_Y, BF_FLOW_LAST_UPLOADED, img.data(), nullptr), "color_flow_img");
         return img;
     }
 

@@ -49,6 +49,10 @@ protected:
     bf::AviWriter outputvideo;
     bool generate_pictures;
     std::string img_prefix;
+    bool generate_flow_img = false, generate_flow_field = false;   // --flow-img / --flow-field: flow_N.ppm / flow_N.flo
+    std::string flow_prefix;
+    bf::AviWriter flowvideo;
+    ull flow_count = 0;
     bool stm_disable;
     bool quiet;
     ull slices_done, slices_skipped, iterations_total;
@@ -57,6 +61,7 @@ protected:
 
     ull slice_origin();
     void render_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
+    void render_flow_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
 
 public:
     DVS_flow(ull on_ev_change_, ull on_time_change_, ull start_time = 0)
@@ -85,6 +90,11 @@ public:
     }
     void set_generate_pictures(bool val = true, std::string img_prefix_ = "./") {
         generate_pictures = val; img_prefix = img_prefix_;
+    }
+    // the flow frame (compensated events | colour-coded flow | raw events: flow_N.ppm) and the per-pixel flow field
+    // (flow_N.flo) of every slice under `prefix`; with set_generate_video, the flow frames also go to bf::flow_video_name
+    void set_generate_flow(bool img, bool field, std::string prefix = "./") {
+        generate_flow_img = img; generate_flow_field = field; flow_prefix = prefix;
     }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
@@ -148,6 +158,29 @@ void DVS_flow<MAX_SZ, SPAN>::render_frame(OptimizerRolling<LinearEventPtrs> &opt
     }
 }
 
+// The flow frame and the flow field of the slice (include/bf_accel.h, "per-pixel flow"): the three images the reference's
+// visualiser publishes per recompute() (bf_visualizer.cpp:249-265), rendered synchronously beside render_frame.  The slice was
+// uploaded in the ring's iteration order, newest -> oldest, which is the order color_flow_img walks it in: AccelLib asks for
+// BF_FLOW_LAST_UPLOADED, and the owner of a pixel is the oldest event that lands on it.
+template <size_t MAX_SZ, sll SPAN>
+void DVS_flow<MAX_SZ, SPAN>::render_flow_frame(OptimizerRolling<LinearEventPtrs> &optimizer) {
+    const std::string base = flow_prefix + "/flow_" + std::to_string(flow_count++);
+    if (generate_flow_field) {
+        const std::vector<float> flo = bf::flo_payload(optimizer.get_flow_field());
+        if (!bf::write_flo(base + ".flo", RES_X, RES_Y, flo.data()) && !quiet) std::cerr << "cannot write " << base << ".flo\n";
+    }
+    if (!generate_flow_img) return;
+    bf::Image2D<uint8_t> comp = optimizer.get_projection_img(1, false), raw = optimizer.get_projection_img(1, true);
+    const std::vector<uint8_t> flow = optimizer.get_color_flow_img();
+    const bf::FrameBGR frame = bf::compose_flow_frame(comp.ptr(0), flow.data(), raw.ptr(0), RES_X, RES_Y);
+    if (!bf::write_ppm(base + ".ppm", frame) && !quiet) std::cerr << "cannot write " << base << ".ppm\n";
+    if (generate_video) {
+        if (!flowvideo.is_open() && !flowvideo.open(bf::flow_video_name(video_name), frame.rows, frame.cols, video_fps))
+            std::cout << "Could not open the output video for write" << std::endl;
+        if (flowvideo.is_open()) flowvideo.write(frame);
+    }
+}
+
 // One slice: the events now in the ring, their times made relative to the slice origin, one OptimizerRolling run --
 // warm-started from the previous slice's model unless --stm-disable (the "short-term memory", dvs_flow.h:218-224) --,
 // per-event flow fetched from the device, optional frame, bookkeeping (dvs_flow.h:185-347).
@@ -174,6 +207,7 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::recompute() {
         last_model = optimizer.get_model();
         optimizer.fetch_uv();                  // "compute the actual u and v after minimizations are done", :233-235
         if (frames) render_frame(optimizer);
+        if (generate_flow_img || generate_flow_field) render_flow_frame(optimizer);
         info = optimizer.get_run_info();
     }
     ++slices_done;

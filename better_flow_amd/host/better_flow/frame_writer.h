@@ -108,6 +108,28 @@ inline FrameBGR compose_frame(const uint8_t *gray_comp, const uint8_t *colour_co
     return mosaic_2x2(gray_tile(gray_comp), colour_tile(colour_comp), gray_tile(gray_raw), colour_tile(colour_raw));
 }
 
+// The flow frame of --flow-img: the three images the reference's live front end publishes after every recompute()
+// (bf_visualizer.cpp:249-265), side by side and not transposed -- projection_img(1) of the compensated events (grey),
+// color_flow_img (B G R), projection_img(1) of the events as recorded (grey) --, every tile rows x cols = RES_X x RES_Y.
+// The device composes the same bytes (bf_flow_frame_render, csrc/bf_flowimg.hip).
+inline FrameBGR compose_flow_frame(const uint8_t *gray_comp, const uint8_t *flow_bgr, const uint8_t *gray_raw, int rows, int cols) {
+    FrameBGR m(rows, 3 * cols);
+    const FrameBGR left = gray_to_bgr(gray_comp, rows, cols), right = gray_to_bgr(gray_raw, rows, cols);
+    for (int r = 0; r < rows; ++r) {
+        std::memcpy(m.at(r, 0), left.at(r, 0), (size_t)cols * 3);
+        std::memcpy(m.at(r, cols), flow_bgr + (size_t)r * cols * 3, (size_t)cols * 3);
+        std::memcpy(m.at(r, 2 * cols), right.at(r, 0), (size_t)cols * 3);
+    }
+    return m;
+}
+
+// The flow frames' video next to `name`: "_flow" before the extension ("out.avi" -> "out_flow.avi")
+inline std::string flow_video_name(const std::string &name) {
+    const size_t slash = name.find_last_of('/'), dot = name.find_last_of('.');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return name + "_flow";
+    return name.substr(0, dot) + "_flow" + name.substr(dot);
+}
+
 // The bytes of the files without their headers.  PPM: top-down RGB, rows x cols x 3 (the bytes write_ppm writes after "P6").
 // AVI: bottom-up BGR rows of avi_stride(cols) bytes, the padding zero (what AviWriter::write stores per frame).
 inline size_t avi_stride(int cols) { return ((size_t)cols * 3 + 3) & ~(size_t)3; }

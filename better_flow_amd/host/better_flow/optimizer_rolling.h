@@ -123,6 +123,10 @@ public:
         return accel.color_time_img(sc, show_final, rows, cols);
     }
 
+    // EventFile::color_flow_img of this optimizer's events (event_file.h:318-350), and the per-pixel field behind it
+    std::vector<uint8_t> get_color_flow_img() { this->stage(); return accel.color_flow_img(); }
+    bf::FlowField get_flow_field() { this->stage(); return accel.flow_field(); }
+
     const bf_run_info &get_run_info() const { return last_info; }
     int get_scale_img_x() { this->stage(); return scale_img_x; }
     int get_scale_img_y() { this->stage(); return scale_img_y; }

@@ -30,6 +30,7 @@
 #include <deque>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -66,6 +67,9 @@ public:
         // without uv_ring (the hook reads it there).
         std::function<void(bf_ctx *, Result &)> on_solved;
         bool want_uv = false;
+        // keep a copy of the noise flags the slice is uploaded with (Result::noise_uploaded): for a hook that rebuilds
+        // per-event products on the host and must see the flags the device saw, not the ring's later state
+        bool keep_noise = false;
     };
 
     struct Result {
@@ -78,6 +82,8 @@ public:
         int worker = 0, device = 0;
         double ms = 0;                                   // upload issue -> results on the host
         std::string error;
+        // Task::keep_noise: the slice's flags as read when its copy was issued, oldest -> newest (null: none was uploaded)
+        std::shared_ptr<const std::vector<uint8_t>> noise_uploaded;
     };
 
     typedef std::function<void(const Result &)> ResultFn;
@@ -140,7 +146,7 @@ public:
                 can = waiting_for_slot_ == 0 && wk.slots < 2;
             }
             if (can) {
-                job.upload_rc = issue_upload(wk.ctx, t);
+                job.upload_rc = issue_upload(wk.ctx, t, job);
                 job.uploaded = true;
                 if (job.upload_rc >= 0) ++wk.slots;
             }
@@ -173,6 +179,7 @@ private:
         Task task;
         bool uploaded = false;     // its copy has been issued (or it has no events)
         int upload_rc = 0;         // < 0: issuing the copy failed; reported when the task's turn comes
+        std::shared_ptr<const std::vector<uint8_t>> noise_uploaded;   // Task::keep_noise (issue_upload)
         std::chrono::steady_clock::time_point t_issue;
     };
     struct Worker {
@@ -197,9 +204,15 @@ private:
     int waiting_for_slot_ = 0;              // queued tasks whose copy has not been issued yet (single-worker farms)
     bool stopping_ = false;
 
-    static int issue_upload(bf_ctx *ctx, const Task &t) {
+    static int issue_upload(bf_ctx *ctx, const Task &t, Job &job) {
+        job.noise_uploaded.reset();
         if (t.ring_ts) {
             const bool noise = t.ring_noise && (!t.noise_live || t.noise_live->load(std::memory_order_acquire) > t.first_global);
+            if (noise && t.keep_noise) {
+                auto flags = std::make_shared<std::vector<uint8_t>>((size_t)t.n);
+                for (int64_t i = 0; i < t.n; ++i) (*flags)[(size_t)i] = t.ring_noise[(t.first + i) % t.cap];
+                job.noise_uploaded = flags;
+            }
             return bf_upload_ring16_async(ctx, t.ring_row, t.ring_col, t.ring_ts, noise ? t.ring_noise : nullptr, t.cap, t.first, t.n, t.t0);
         }
         return bf_upload_events_async(ctx, t.fr_x, t.fr_y, t.t_ns, t.n);
@@ -225,6 +238,7 @@ private:
         const Task &t = s.task;
         Result r;
         r.id = s.id; r.user = t.user; r.worker = wk.index; r.device = wk.device;
+        r.noise_uploaded = s.noise_uploaded;
         std::memset(&r.info, 0, sizeof(r.info));
         std::memset(&r.model, 0, sizeof(r.model));
         std::memset(&r.window, 0, sizeof(r.window));
@@ -313,7 +327,7 @@ private:
                     }
                     if (!job.uploaded) {
                         job.t_issue = std::chrono::steady_clock::now();
-                        job.upload_rc = issue_upload(wk.ctx, job.task);
+                        job.upload_rc = issue_upload(wk.ctx, job.task, job);
                         job.uploaded = true;
                         if (job.upload_rc >= 0) ++wk.slots;
                     }
@@ -342,7 +356,7 @@ private:
                 for (Staged &p : staged) if (p.task.n > 0 && p.upload_rc >= 0) held.push_back(&p);
                 for (Staged *p : held) { (void)p; (void)bf_commit_upload(wk.ctx); }
                 for (Staged *p : held) {
-                    p->upload_rc = issue_upload(wk.ctx, p->task);
+                    p->upload_rc = issue_upload(wk.ctx, p->task, *p);
                     if (p->upload_rc < 0) --wk.slots;   // (a failed re-issue holds no slot)
                 }
             }

@@ -124,7 +124,13 @@ public:
     void set_frames(const std::string &prefix, bool pictures, const std::string &video_name = "", int video_fps = 30, int slots = 4) {
         frame_cfg.prefix = prefix; frame_cfg.pictures = pictures; frame_cfg.video_name = video_name; frame_cfg.video_fps = video_fps;
         frame_cfg.slots = slots < 1 ? 1 : slots;
-        frames_on = pictures || !video_name.empty();
+        frames_on = frame_cfg.mosaic() || frame_cfg.flow();
+    }
+    // DVS_flow's flow frames and flow fields (set_generate_flow): flow_N.ppm / flow_N.flo under `prefix`, one per slice, in
+    // slice order; with a video name set by set_frames, the flow frames also go to bf::flow_video_name of it.
+    void set_flow_frames(const std::string &prefix, bool pictures, bool field) {
+        frame_cfg.flow_prefix = prefix; frame_cfg.flow_pictures = pictures; frame_cfg.flow_field = field;
+        frames_on = frame_cfg.mosaic() || frame_cfg.flow();
     }
 
     // Create the workers, their device contexts and the pinned ring now (otherwise: at the first event).
@@ -284,9 +290,13 @@ public:
                 t.want_uv = true;
             }
             const uint64_t idx = p.index;
-            t.on_solved = [this, idx, e](bf_ctx *ctx, SliceFarm::Result &r) {
+            // (the host composition of the flow field -- a library without bf_flow_frame_* -- rebuilds the field from per-event
+            // read-backs and needs the noise flags the slice was uploaded with: the farm keeps a copy of them for the hook)
+            t.keep_noise = frames && frames->flow_on_device() == 0;
+            const size_t n_events = (size_t)p.n;
+            t.on_solved = [this, idx, e, n_events](bf_ctx *ctx, SliceFarm::Result &r) {
                 if (device_table) device_table->enqueue(idx, ctx, r, e);
-                if (frames) frames->render(idx, (int)worker_of(ctx), ctx, r);
+                if (frames) frames->render(idx, (int)worker_of(ctx), ctx, r, n_events);
             };
         }
         if ((accumulate || (want_flow && farm->workers() > 1)) && p.n > 0) {
@@ -353,6 +363,8 @@ public:
     ull events_seen() const { return head; }
     double seconds_blocked() const { return blocked_s; }   // the producer waited this long in reserve() for slices in flight
     uint64_t frames_delivered() { return frames ? frames->delivered() : 0; }
+    // 1: the flow frames are composed on the device (bf_flow_frame_*), 0: on the host from read-backs, -1: no flow frames
+    int flow_frames_on_device() { return frames ? frames->flow_on_device() : -1; }
     // time the engine waited for frames: a free frame slot, a render to finish, room at the writer
     double seconds_frame_wait() { return frames ? frames->seconds_waiting() : 0.0; }
 
@@ -480,7 +492,7 @@ private:
         if (frames_on && max_sz < 2)   // (a slice of a one-event ring is empty: the context would still hold the previous one)
             throw AccelError(BF_ERR_ARG, "StreamEngine: frames need a ring of at least 2 events");
         // (frames are rendered at scale 3: the colour tile is (3 RES_X + 3) x (3 RES_Y + 3), as DVS_flow reserves it)
-        const int fs = frames_on ? 3 : 0;
+        const int fs = frame_cfg.mosaic() ? 3 : 0;
         std::unique_ptr<SliceFarm> f(new SliceFarm(devices, contexts_per_device, (long long)max_sz, std::max(scale * RES_X + scale, fs * RES_X + fs),
                                                    std::max(scale * RES_Y + scale, fs * RES_Y + fs), [this](const SliceFarm::Result &r) { deliver(r); }, chained));
         const size_t extra = lookahead ? lookahead : (2 * max_sz > 65536 ? 2 * max_sz : 65536);   // the producer may run two slices ahead

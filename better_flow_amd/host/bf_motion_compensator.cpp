@@ -35,6 +35,7 @@ struct Options {
     unsigned long long refresh_events = 20000;   // ... or new events, whichever comes first
     bool interactive = false, quiet = false, gpu_flag = false, stm_disable = false, bufferize = false;
     bool frames = false, video = false;
+    bool flow_img = false, flow_field = false;   // --flow-img / --flow-field: flow_N.ppm / flow_N.flo per slice
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
     int scale = 3, max_iter = -1;
@@ -99,7 +100,11 @@ const std::vector<Flag> &flag_table() {
         {"--stm-disable", Arg::None, [](Options &o, const char *) { o.stm_disable = true; }, "",
          "start every slice from the zero model instead of the previous slice's estimate"},
         {"--img", Arg::None, [](Options &o, const char *) { o.frames = true; }, "", "write one frame (PPM + text side-car) per slice"},
-        {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames"},
+        {"--flow-img", Arg::None, [](Options &o, const char *) { o.flow_img = true; }, "",
+         "write one flow frame per slice (flow_N.ppm): compensated events | colour-coded flow | raw events; with --video, also <video-name>_flow"},
+        {"--flow-field", Arg::None, [](Options &o, const char *) { o.flow_field = true; }, "",
+         "write the per-pixel flow field of every slice (flow_N.flo, Middlebury layout: horizontal = column flow, 1e9 = no event)"},
+        {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
         {"--video", Arg::None, [](Options &o, const char *) { o.video = true; }, "", "write the frames to a video (uncompressed AVI)"},
         {"--video-name", Arg::Next, [](Options &o, const char *v) { o.video_name = v; }, "<file>", "name of that video"},
         {"--video-fps", Arg::Inline, [](Options &o, const char *v) { o.video_fps = atoi(v); }, "<n>", "its frame rate"},
@@ -198,8 +203,8 @@ int parse(int argc, char **argv, Options &o) {
     if (!o.have_input) { std::fprintf(stderr, "no input file\n"); return 1; }
     if (o.scale < 1 || o.scale % 2 == 0) { std::fprintf(stderr, "--scale must be odd\n"); return 1; }
     if (!o.engine.empty() && o.engine != "stream" && o.engine != "ring") { std::fprintf(stderr, "--engine must be stream or ring\n"); return 1; }
-    // (--img / --video run on both engines; without --engine they keep the reference ring)
-    const bool needs_ring = o.frames || o.video || o.interactive;
+    // (--img / --video / --flow-img / --flow-field run on both engines; without --engine they keep the reference ring)
+    const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive;
     if (o.engine.empty()) o.engine = needs_ring ? "ring" : "stream";
     if (o.engine == "stream" && o.interactive) { std::fprintf(stderr, "-i works on the reference ring: drop --engine=stream\n"); return 1; }
     if (o.have_output_bin && o.output_bin.empty()) { std::fprintf(stderr, "--outfile-bin needs a file name: --outfile-bin=<file>\n"); return 1; }
@@ -212,7 +217,7 @@ int parse(int argc, char **argv, Options &o) {
                      kMaxEvents, kMaxSpanSec);
         return 1;
     }
-    if (!o.more_inputs.empty() && (o.engine != "stream" || !o.to_bin.empty() || o.frames || o.video)) {
+    if (!o.more_inputs.empty() && (o.engine != "stream" || !o.to_bin.empty() || o.frames || o.video || o.flow_img || o.flow_field)) {
         std::fprintf(stderr, "several input files are independent streams of the stream engine: not with --engine=ring / --img / --video / -i / --to-bin\n");
         return 1;
     }
@@ -262,6 +267,7 @@ int run_ring(const Options &o) {
     if (o.interactive) estimator.set_manual_mode(true);
     if (o.frames) estimator.set_generate_pictures(true, o.frame_prefix);
     if (o.video) estimator.set_generate_video(true, o.video_name, o.video_fps);
+    if (o.flow_img || o.flow_field) estimator.set_generate_flow(o.flow_img, o.flow_field, o.frame_prefix);
     if (o.stm_disable) estimator.set_stm_disable(true);
     if (!o.slice_log.empty() && !estimator.open_slice_log(o.slice_log)) {
         std::fprintf(stderr, "cannot write '%s'\n", o.slice_log.c_str());
@@ -326,6 +332,7 @@ int run_stream(const Options &o) {
     else if (o.have_output) engine.set_accumulate();
     engine.set_pipelined(!o.sync && !o.bufferize);
     if (o.frames || o.video) engine.set_frames(o.frame_prefix, o.frames, o.video ? o.video_name : std::string(), o.video_fps);
+    if (o.flow_img || o.flow_field) engine.set_flow_frames(o.frame_prefix, o.flow_img, o.flow_field);
     if (!o.devices.empty() || o.contexts > 1)
         engine.set_devices(o.devices.empty() ? std::vector<int>{bf::DeviceContext::device()} : o.devices, o.contexts);
     FILE *slice_log = nullptr;
@@ -446,11 +453,11 @@ int run_stream(const Options &o) {
     if (o.timing)
         std::fprintf(stderr, "{\"engine\": \"stream\", \"events\": %llu, \"slices\": %llu, \"iterations\": %llu, \"init_s\": %.6f, "
                              "\"stream_s\": %.6f, \"read_s\": %.6f, \"blocked_s\": %.6f, \"output_s\": %.6f, \"total_s\": %.6f, \"mevents_per_s\": %.3f, "
-                             "\"steady_s\": %.6f, \"steady_mevents_per_s\": %.3f, \"output_bin_s\": %.6f, \"frames\": %llu, \"frame_wait_s\": %.6f}\n",
+                             "\"steady_s\": %.6f, \"steady_mevents_per_s\": %.3f, \"output_bin_s\": %.6f, \"frames\": %llu, \"frame_wait_s\": %.6f, \"flow_frames_device\": %d}\n",
                      n_events, (unsigned long long)engine.get_slices_done(), (unsigned long long)engine.get_iterations_total(), s_init,
                      s_stream, s_read, engine.seconds_blocked(), s_output, seconds_since(t_start), s_stream > 0 ? n_events / s_stream * 1e-6 : 0.0,
                      s_steady, s_steady > 0 ? (n_events - events_first_slice) / s_steady * 1e-6 : 0.0, s_output_bin,
-                     (unsigned long long)engine.frames_delivered(), engine.seconds_frame_wait());
+                     (unsigned long long)engine.frames_delivered(), engine.seconds_frame_wait(), engine.flow_frames_on_device());
     if (slice_log) std::fclose(slice_log);
     return 0;
 }

@@ -635,6 +635,68 @@ int bf_frame_wait(bf_ctx *ctx, bf_frame *frame, int64_t ticket, const uint8_t **
 int bf_frame_release(bf_frame *frame, int64_t ticket);
 int bf_render_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, uint8_t *ppm_out, uint8_t *avi_out);
 
+/* ---- per-pixel flow: EventFile::color_flow_img (event_file.h:318-350) and the field behind it ---------------------------------
+ * The picture of the flow that the reference's live front end publishes after every recompute() (bf_visualizer.cpp:249-265),
+ * and the same scatter stopped before the colour step: the per-pixel flow field.  On a res_x x res_y sensor, pixel (x, y) at
+ * index x * res_y + y (x the row):
+ *   - every non-noise event of the live slice lands on pixel (x, y) = ((int)pr_x, (int)pr_y) -- C truncation toward zero of the
+ *     double, so pr = -0.7 lands on 0, INSIDE; NaN and anything outside the int range give INT_MIN, as on x86 -- and is left
+ *     out unless 0 <= x < res_x and 0 <= y < res_y (:324-328).  pr is the event's current projected position, what
+ *     bf_writeout_events returns (a pending bf_set_model warp applied first, as by every renderer);
+ *   - the reference assigns (:337-338), so the LAST event of its loop that lands on a pixel owns it.  Ownership is defined here
+ *     on the UPLOAD index -- not on where an event sits after the device has re-binned the slice -- and `owner_rule` says which
+ *     end wins: BF_FLOW_LAST_UPLOADED, the largest upload index (a container the reference iterates in upload order: DVS_flow
+ *     here uploads its ring in iteration order, newest -> oldest), or BF_FLOW_FIRST_UPLOADED, the smallest (a slice uploaded
+ *     oldest -> newest, bf_upload_ring*_async, that the reference iterates newest -> oldest, datastructures.h:66-76).  Either
+ *     way the owner of a pixel in the command line is the OLDEST non-noise event that lands on it;
+ *   - the field of a pixel is its owner's (best_u, best_v) = Event::compute_uv (event.h:135-142): bit for bit what bf_compute_uv
+ *     returns at that upload index (0 when no warp has run);
+ *   - colour (:330-338, all double): speed = hypot(u, v); angle = speed != 0 ? (atan2(v, u) + 3.1416) * 180 / 3.1416 : 0;
+ *     log_spd = std::min(255.0, log(speed) / log(1.025)); H = uchar(angle / 2), S = uchar(log_spd), V = 255; a pixel without an
+ *     event is HSV (0, 0, 255): white.  double -> uchar is what the reference's x86-64 build does: truncate to int32
+ *     (cvttsd2si: NaN and out-of-range values give INT_MIN), keep the low byte.  So a speed below 1 px/s, whose log_spd is
+ *     negative, wraps (0.5 px/s: -28.07 -> -28 -> 228); speed == 0 gives log_spd = -inf -> INT_MIN -> S = 0 (and H = 0);
+ *     a NaN flow gives H = 0 (NaN -> INT_MIN) and S = 255 (std::min(255.0, NaN) is 255.0); speeds from 1.025^255 = 543 px/s
+ *     up saturate at S = 255.  include/bf_flow_color.h holds this arithmetic for the device and the host alike;
+ *   - HSV -> BGR is the float formula stated at bf_color_time_img (the same function); parity with the reference's
+ *     un-versioned cv::cvtColor stays unpinned for that stage, as there.  atan2 / log / hypot are the device library's,
+ *     which may differ from a host libm in the last place: a pixel whose angle / 2 or log_spd lies within an ulp of an
+ *     integer may differ by one H or S step between the two.
+ * One deliberate deviation: the reference paints best_pr / best_u / best_v, which a slice stopped by
+ * a guard of run() (optimizer_rolling.h:49-58) never assumes; this build paints such a slice's own current state.
+ *   bf_flow_field      owner_out[x * res_y + y]: upload index of the owning event, -1 without one; u_out / v_out: its flow,
+ *                      0 without one.  Any output may be NULL.
+ *   bf_color_flow_img  bgr_out: res_x * res_y * 3 bytes, B, G, R; hs_out (may be NULL): res_x * res_y * 2 bytes, the H and S
+ *                      of every pixel before the conversion.
+ * Both enqueue on the context stream, copy and synchronise.  BF_ERR_STATE before an upload; BF_ERR_ARG for an unknown rule or
+ * a sensor of more pixels than the context's image capacity (bf_create's max_rows x max_cols).
+ *
+ * The flow frame of --flow-img: three res_x x res_y tiles side by side, left to right bf_projection_img(scale 1, show_final 0)
+ * grey -> BGR, bf_color_flow_img, bf_projection_img(scale 1, show_final 1) grey -> BGR -- the visualiser's three topics, not
+ * transposed --, res_x x (3 res_y) pixels.  Composed on the device in the byte layouts of the files, byte for byte
+ * host/better_flow/frame_writer.h's compose_flow_frame: BF_FRAME_PPM (top-down RGB) and BF_FRAME_AVI (bottom-up BGR rows padded
+ * with zeros to a multiple of 4 bytes); BF_FLOW_FRAME_FLO adds the field as the payload of a Middlebury .flo file: per pixel,
+ * row-major, two float32 -- horizontal = (float)v, vertical = (float)u, the swap -o makes (event_file.h:274-275) -- and 1e9 in
+ * both for a pixel without an event.  A bf_flow_frame owns `slots` frames per layout in pinned, device-mapped host memory;
+ * the calls are bf_frame_*'s (tickets 0, 1, 2, ...; BF_ERR_CAPACITY with every slot taken, checked first; BF_ERR_ARG for a ticket
+ * released or never issued); every context renders into its own scratch, so contexts of one device may share a bf_flow_frame.
+ *   bf_render_flow_frame  the synchronous form: ppm_out (res_x * res_y * 9 bytes), avi_out (res_x rows of ((9 res_y + 3) & ~3)
+ *                         bytes), flo_out (res_x * res_y * 2 floats); any may be NULL, not all.
+ * The kernels are in bf_flowimg.hip. */
+#define BF_FLOW_LAST_UPLOADED 0
+#define BF_FLOW_FIRST_UPLOADED 1
+#define BF_FLOW_FRAME_FLO 4
+typedef struct bf_flow_frame bf_flow_frame;
+int bf_flow_field(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, int32_t *owner_out, double *u_out, double *v_out);
+int bf_color_flow_img(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, uint8_t *bgr_out, uint8_t *hs_out);
+int bf_flow_frame_create(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t slots, int32_t layouts, bf_flow_frame **out);
+int bf_flow_frame_destroy(bf_flow_frame *frame);
+int bf_flow_frame_render(bf_ctx *ctx, bf_flow_frame *frame, int32_t owner_rule, int64_t *ticket_out);
+int bf_flow_frame_wait(bf_ctx *ctx, bf_flow_frame *frame, int64_t ticket, const uint8_t **ppm, const uint8_t **avi, const float **flo);
+int bf_flow_frame_release(bf_flow_frame *frame, int64_t ticket);
+int bf_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, uint8_t *ppm_out, uint8_t *avi_out,
+                         float *flo_out);
+
 /* NUMA placement of a feeder thread (no reference counterpart: the reference is single-threaded, SURVEY 8(b) "Threading"; the
  * 8-GPU farm of SURVEY 8(e) wants one feeder thread per GPU with NUMA-local pinned buffers).
  *   bf_device_numa_node          host NUMA node of HIP device `device` (sysfs numa_node of its PCI function); -1: unknown.
