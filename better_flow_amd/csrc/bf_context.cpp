@@ -205,6 +205,18 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         *value = c->persist_giveups;
         return BF_OK;
     }
+    // The kernel variants the last bf_run launched of the two-kernel tile-binned loop (-1: it launched none) ...
+    const struct { const char* name; int v; } launched[] = {
+        {"k1_threads", c->launched.k1_threads}, {"k1_events_per_thread", c->launched.k1_per_thread}, {"k1_head", c->launched.k1_head},
+        {"k3_half_scale", c->launched.k3_half_scale}, {"k3_mode", c->launched.k3_mode}, {"k3_capped", c->launched.k3_capped},
+        // ... and the bin grid bf_set_cloud planned for it (0: the slice does not take that loop)
+        {"bin_rows", c->use_binned ? c->grid.TSR : 0}, {"bin_cols", c->use_binned ? c->grid.TS : 0},
+        {"bin_margin", c->use_binned ? c->grid.D : 0}, {"bins", c->use_binned ? c->grid.nbins : 0}};
+    for (const auto& e : launched)
+        if (!strcmp(key, e.name)) {
+            *value = e.v;
+            return BF_OK;
+        }
     return fail(c, BF_ERR_ARG, "unknown statistic '%s'", key);
 }
 

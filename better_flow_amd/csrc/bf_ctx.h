@@ -54,12 +54,10 @@ struct ProfRec {
 
 }  // namespace
 
-// Margins of the tile-binned loops, in scaled pixels: how far an event may drift from where the counting sort found it before
-// its bin must be re-sorted.  Swept flat over 4 .. 8 in rounds 3 and 4 (EXPERIMENTS: 195.9 / 195.1 / 193.1 Mevents/s at 8 / 6 / 4),
-// so no longer an option.  The tile shape, the scatter work-groups' size and their events per thread are chosen per slice
-// (bf_plan.cpp): the options that overrode them went with it.
-constexpr int kBinMargin = 8;      // two-kernel loop: D of BinGrid (capped at half the smaller tile side)
-constexpr int kFusedMargin = 8;    // one-kernel loops: D on top of the stencil halo H = scale / 2 + 1
+// Margins of the tile-binned loops (bf_plan_rules.h).  The tile shape, the scatter work-groups' size and their events per thread
+// are chosen per slice (bf_plan.cpp, by the rules of bf_plan_rules.h): the options that overrode them went in round 5.
+using bf_rules::kBinMargin;
+using bf_rules::kFusedMargin;
 
 struct bf_ctx {
     int device = 0;
@@ -240,6 +238,14 @@ struct bf_ctx {
     int cur = 0;                     // plane buffer that is guaranteed all-zero
     bool planes_unknown = true;      // both buffers must be cleared before use
     int last_R = 0, last_C = 0;
+
+    // What the last bf_run launched of the two-kernel tile-binned loop (bf_get_stat "k1_*" / "k3_*"; -1: that run launched no
+    // such kernel): the scatter kernel's work-group size, events per thread and form, the stencil kernel's HS, MODE and build.
+    // Host integers written next to the launches they describe (bf_run.cpp: enqueue_iteration).
+    struct Launched {
+        int k1_threads = -1, k1_per_thread = -1, k1_head = -1;
+        int k3_half_scale = -1, k3_mode = -1, k3_capped = -1;
+    } launched;
 
     int prof_mode = 0;
     std::vector<ProfRec> prof_pending;

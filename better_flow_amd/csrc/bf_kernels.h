@@ -6,11 +6,13 @@
 #include <stdint.h>
 
 #include "bf_device.h"
+#include "bf_plan_rules.h"
 
 namespace bf {
 
 constexpr int kHistCopies = 8;   // copies of the re-bin's global histogram (work-group b adds to copy b % 8: contention)
-constexpr int kBinTileLdsMax = 156 * 1024;   // dynamic LDS of a scatter work-group (160 KiB per CU minus its static part)
+using bf_rules::kBinTileLdsMax;   // dynamic LDS of a scatter work-group
+static_assert(bf_rules::kStencilTileR == kTileR && bf_rules::kStencilTileC == kTileC, "the rules count the stencil kernel's own tiles");
 constexpr int kPrepBlocks = 1024;   // work-groups of k_prepare == SliceStats records it writes
 
 // min / max / sum statistics of one staged slice (k_prepare), one record per work-group.
@@ -151,7 +153,7 @@ void launch_fill_states(DevState* states, const DevState& tmpl, int nt, hipStrea
 
 // bf_rebin.hip / bf_scatter.hip / bf_stencil.hip / bf_fused.hip (the tile-binned loops)
 int bin_kernel_setup();
-void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n_cus);
+void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n_cus);   // (the build: bf_rules::stencil_capped)
 // interior + margin format: clear what the bins' lists name in `mplane`, empty the lists (a run that cannot rely on the
 // loop's own clean-up: the dirty margin plane is the one its first iteration adds to, or the bin grid changes)
 void launch_margin_clean(unsigned long long* mplane, const uint32_t* mlist, uint32_t* mcount, int nbins, int mcap, hipStream_t s);
@@ -189,9 +191,8 @@ struct BinScatterArgs {
     uint32_t* mcount;                // per bin: entries of its list
     int mcap;
 };
-// work-group size of the scatter kernel for a slice: format (0 dense slabs, 2 event lists, 3 own pixels + margin plane), where the
-// update runs, -- lists -- whether the grid is thousands of small bins, and -- dense tiles -- the events per bin
-int bin_scatter_threads(int fmt, bool head, bool many_small_bins, double events_per_bin);
+// `threads`, `per_thread`: bf_rules::scatter_size()'s answer for this slice, taken as it is -- a tuple that is not one of the
+// compiled instantiations (bf_rules::scatter_compiled) is refused with hipErrorInvalidValue, never rounded to a neighbour.
 hipError_t launch_bin_warp_scatter(const BinScatterArgs& a, bool warp, int threads, int per_thread, hipStream_t s);
 // The one-kernel iteration (k_fused_pass, bf_fused.hip): warp + scatter + stencil + moments of one image tile per work-group.
 struct FusedArgs {

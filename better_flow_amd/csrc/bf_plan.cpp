@@ -14,39 +14,21 @@ SlicePlan plan_slice(const bf_ctx* c, const bf_window& w) {
     // over widths {16, 32, 64} (a power of two) and heights {32 .. 128}; ties go to the larger tile.  Small dense
     // images get small tiles (enough bins to fill the CUs), large images large ones (less margin overhead).
     // (the margin: kBinMargin, even; BF_DEBUG_MARGIN overrides it for tests)
-    const int bin_margin = c->dbg_margin > 0 ? ((c->dbg_margin + 1) & ~1) : kBinMargin;
-    g.TS = 64;
-    g.TSR = 64;
-    if (c->n_cus > 0) {
-        const double density = (double)c->n / ((double)w.scale_img_x * (double)w.scale_img_y);
-        double best = -1.0;
-        int best_area = 0;
-        for (int cols = 16; cols <= 64; cols *= 2) {
-            for (int rows = 32; rows <= 128; rows += 16) {
-                const int d = bin_margin > cols / 2 ? cols / 2 : bin_margin;
-                if ((size_t)(rows + 2 * d) * (cols + 2 * d) * 8 > 64 * 1024) continue;
-                const int nb = ((w.scale_img_x + rows - 1) / rows) * ((w.scale_img_y + cols - 1) / cols);
-                if (nb > 8192) continue;
-                const double cost = (double)((nb + c->n_cus - 1) / c->n_cus) * rows * cols * density * 1.7e-3 +
-                                    (double)nb * (rows + 2 * d) * (cols + 2 * d) * 2.3e-6;
-                if (best < 0 || cost < best * 0.999 || (cost <= best * 1.001 && rows * cols > best_area)) {
-                    best = cost; best_area = rows * cols; g.TS = cols; g.TSR = rows;
-                }
-            }
-        }
-    }
+    const int bin_margin = bf_rules::bin_margin(c->dbg_margin);
+    const bf_rules::BinShape shape = bf_rules::bin_shape(c->n, w.scale_img_x, w.scale_img_y, c->n_cus, bin_margin);
+    g.TS = shape.TS;
+    g.TSR = shape.TSR;
     g.lg = 0;
     while ((1 << g.lg) < g.TS) ++g.lg;
-    g.nbc = (w.scale_img_y + g.TS - 1) / g.TS;
-    const int tmin_ = g.TS < g.TSR ? g.TS : g.TSR;
-    g.D = bin_margin > tmin_ / 2 ? tmin_ / 2 : bin_margin;   // <= 2 x 2 bins per pixel
+    g.nbc = shape.nbc;
+    g.D = shape.D;   // <= 2 x 2 bins per pixel
     g.L = g.TS + 2 * g.D;
     g.LR = g.TSR + 2 * g.D;
     g.mul_r = (uint32_t)(0x100000000ull / (unsigned)g.TSR) + 1u;
     g.mul_l = (uint32_t)(0x100000000ull / (unsigned)g.L) + 1u;
     g.mul_h = (uint32_t)(0x100000000ull / (unsigned)(g.L / 2 > 0 ? g.L / 2 : 1)) + 1u;
-    g.nbr = (w.scale_img_x + g.TSR - 1) / g.TSR;
-    g.nbins = g.nbr * g.nbc;
+    g.nbr = shape.nbr;
+    g.nbins = shape.nbins;
     // Density rule: every iteration writes and re-reads one slab pixel (8 B x (L / TS)^2) per image pixel, a global
     // atomic costs ~48 ns per event; below ~1 event per 12 pixels the plain atomic scatter is the faster one
     // (measured: 300k events on a 3550 x 6350 image, 0.41 vs 0.66 ms per iteration).
@@ -56,8 +38,8 @@ SlicePlan plan_slice(const bf_ctx* c, const bf_window& w) {
     const bool dense = (double)w.scale_img_x * (double)w.scale_img_y < 12.0 * (double)c->n ||
                        (double)w.scale_img_x * (double)w.scale_img_y <= 9.0e6;
     p.binned = (c->opt_binned == 2 || (c->opt_binned == 1 && dense)) && !c->force_split && !c->has_noise && c->n > 0 &&
-               g.nbins <= 8192 && c->cap_events < (1ll << 29) &&   // (32-bit byte offsets into the event arrays: ld_idx)
-               (size_t)g.LR * g.L * 8 <= (size_t)kBinTileLdsMax && w.scale_img_x < (1 << 20);
+               c->cap_events < (1ll << 29) &&   // (32-bit byte offsets into the event arrays: ld_idx)
+               bf_rules::bin_grid_ok(shape, w.scale_img_x);
     // (<= 8192 bins x <= 156 KB: slabs, tiled image and margin plane stay below 2^31 bytes -- the stencil kernel's buffer loads
     // carry 32-bit byte offsets, buf_ld_u64)
 
@@ -102,8 +84,7 @@ SlicePlan plan_slice(const bf_ctx* c, const bf_window& w) {
     // (dense / events): 1280x720 scale 3: 90 / 68 us; 640x480 scale 3: 44 / 52.  (A third form -- lists merged per pixel
     // in the LDS tile, for small sensors at large scales: 346x260 scale 7 61 against 96 / 103 us -- was removed in round 5:
     // no BASELINE configuration took it, and every form multiplies the bit-identity matrix.)
-    const size_t LLg = (size_t)g.LR * (size_t)g.L;
-    const bool lists_ok = p.binned && LLg <= 65536;                         // 16-bit tile-local pixel indices
+    const bool lists_ok = p.binned && bf_rules::bin_format_ok(shape, 2);    // 16-bit tile-local pixel indices
     const int mode = lists_ok ? c->opt_bin_compact : 0;
     if (mode == 2 || (mode == 1 && 4.0 * (double)c->n < Pimg)) p.fmt = 2;
     // Dense slices: the bin's own pixels + a margin plane instead of whole-tile slabs (flush_split).  It moves 0.6 x the
@@ -113,8 +94,8 @@ SlicePlan plan_slice(const bf_ctx* c, const bf_window& w) {
     // latency chain and nothing moves (18.8 us either way); with the update in the stencil tail ("co_schedule") the
     // lean scatter kernel LOSES 1.7 us per launch (8.0 -> 9.7 us at 346x260, value 196 -> 178 Mevents/s).
     const bool split_pays = !c->opt_co_schedule && Pimg >= 1.5e6;
-    if (p.fmt == 0 && p.binned && (c->opt_bin_split == 2 || (c->opt_bin_split == 1 && split_pays)) && g.D >= 2 &&
-        (g.D & (g.D - 1)) == 0 && g.TS >= 4)   // (D a power of two)
+    if (p.fmt == 0 && p.binned && (c->opt_bin_split == 2 || (c->opt_bin_split == 1 && split_pays)) &&
+        bf_rules::bin_format_ok(shape, 3))   // (D a power of two)
         p.fmt = 3;
     // Event lists on 64-column bins (every sensor of BASELINE.json's configurations): entries sorted by (column zone,
     // row), so that a stencil tile gathers from the bins beside its own only the zone that faces it (bf_scatter.hip,
@@ -174,8 +155,7 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     // with a few hundred (config 2: 752) the launch costs more than the tickets (bench 206.7 -> 200.9): "auto" takes it for event
     // lists only.  Same bits either way.
     p.sep_update = p.binned && !p.fused && !p.head_update && (c->opt_sep_update == 2 || (c->opt_sep_update == 1 && c->fmt == 2));
-    const double ev_per_bin = p.binned ? (double)c->n / (double)(c->grid.nbins > 0 ? c->grid.nbins : 1) : 0.0;
-    // Work-group size of the scatter kernel (bin_scatter_threads, bf_scatter.hip).  Dense tiles: 1024 threads for a context that
+    // Work-group size of the scatter kernel (bf_rules::scatter_size).  Dense tiles: 1024 threads for a context that
     // has the GPU to itself and bins of thousands of events (8.0 against 8.9 us per launch at config 2; at 640x480, bins of
     // ~1500 events, 512 threads: 11.7 against 17.4 us), 512 for contexts sharing the GPU ("co_schedule": a
     // 1024-thread work-group with its 51 KB tile needs half a CU's wave slots free at once and waits for them while the other
@@ -184,27 +164,25 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     // work-groups (16.6 against 18.6 us per scatter launch there at 1 M events, 8.2 against 13.3 at 100 k); with a couple of
     // bins per CU -- 640x480, 540 bins -- 512 threads stay ahead (6.3 against 8.2).  (512 rather than 1024 where a bin holds a few
     // hundred events -- large images --: twice as many bins in flight per CU, 84 instead of 91 us per iteration at 1280x720.)
-    const bool many_small_bins = c->fmt == 2 && c->n_cus > 0 && c->grid.nbins >= 4 * c->n_cus && ev_per_bin < 1024.0;
-    p.bin_threads = bin_scatter_threads(c->fmt, p.head_update, many_small_bins, ev_per_bin);
     if (p.binned) {
         // events a scatter thread keeps in flight:
         // (event lists: registers, not LDS, set the occupancy there -- two events per thread keep four work-groups on a
         // CU, and a bin above the pass size takes a second pass; measured at 1280x720: 512 x 2 69.8 us, 512 x 4 73.5)
         // (dense tiles: a pass should cover the AVERAGE bin, fuller bins take a second pass -- sizing it for 1.5 x the
         // average left half of every thread's slots empty at 640x480: 512 x 8 19.9 us, 512 x 4 15.3 us)
-        const double per_bin = (c->fmt == 2 ? 1.0 : 1.1) * ev_per_bin / (double)p.bin_threads;
         // (... and between two and four, two up to 2.83 -- the geometric middle: bins of ~2100 events on 1024 threads ran
         // 15.3 us with four events per thread, half of every thread's slots empty, against 12.1 us with two and a second pass
         // for the fuller bins; measured at 1M events on 440 / 520 / 560 x 480 sensors)
-        p.ev_per_thread = per_bin <= 1 ? 1 : (per_bin <= 2.83 ? 2 : (per_bin <= 4 ? 4 : 8));
         // (dense slabs on 512-thread work-groups with bins of thousands of events -- config 2 under "co_schedule": 272 bins, 3673
         // events on average, 4912 in the fullest -- : the pass covers the FULLEST bin, ~1.35 x the average; with 8 per thread two
         // thirds of the bins took a second pass: 8.45 -> 8.13 us per launch alone, 8.2 -> 7.8 under four contexts)
-        if (c->fmt == 0 && p.bin_threads == 512 && per_bin > 6.5) p.ev_per_thread = per_bin <= 8.2 ? 10 : 12;
         // (event lists, update in the stencil tail, thousands of small bins on 256 threads -- 1280x720: 1620 bins, 608 events on average,
         // 877 in the fullest: four per thread cover every bin in one pass, 14.3-14.6 -> 13.5 us per launch; the head form, whose
         // registers also hold the update, loses with four: 14.8 -> 16.5)
-        if (c->fmt == 2 && !p.head_update && p.bin_threads == 256 && per_bin > 2.0) p.ev_per_thread = 4;
+        // (the arithmetic of all of the above: bf_plan_rules.h)
+        const bf_rules::ScatterSize k1 = bf_rules::scatter_size(c->fmt, p.head_update, c->grid.nbins, c->n, c->n_cus);
+        p.bin_threads = k1.threads;
+        p.ev_per_thread = k1.per_thread;
     }
     // A warm start that is expected to converge in a handful of iterations (the previous one did) is polled batch by batch,
     // the final warp riding along: "quick".  One that is expected to run long -- the reference's own ring: ~115 iterations per

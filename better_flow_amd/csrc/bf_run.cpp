@@ -247,6 +247,7 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
             ba.mlist = c->d_mlist; ba.mcount = c->d_mcount; ba.mcap = c->m_cap;
             ProfScope ps(c, 0, c->n);
             HIP_TRY(c, launch_bin_warp_scatter(ba, warp, p.bin_threads, p.ev_per_thread, c->stream));
+            c->launched.k1_threads = p.bin_threads; c->launched.k1_per_thread = p.ev_per_thread; c->launched.k1_head = p.head_update ? 1 : 0;
         } else {
             ProfScope ps(c, 0, c->n);
             launch_warp_scatter(ws_args(c, buf, 1), warp, true, false, c->stream);
@@ -285,7 +286,13 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
         // the GPU by itself keep the plain build: config 2 with four contexts 208.3 against 206.5, round 5 -- since its
         // instruction diet the kernel gains less from two more work-groups per CU than it loses to the spills.)
         const bool shared_lists = c->opt_co_schedule && c->fmt == 2 && g_live_ctx[c->device & 63].load() > 1;
-        launch_stencil(a, stencil_src(c, p.binned), c->stream, shared_lists ? 1 : c->n_cus);
+        const int k3_cus = shared_lists ? 1 : c->n_cus;
+        launch_stencil(a, stencil_src(c, p.binned), c->stream, k3_cus);
+        if (p.binned) {   // (launch_stencil_binned picks its build by the same rule from the same numbers)
+            c->launched.k3_half_scale = bf_rules::stencil_half_scale(a.scale);
+            c->launched.k3_mode = bf_rules::stencil_mode(a.compact);
+            c->launched.k3_capped = bf_rules::stencil_capped(bf_rules::stencil_tiles(a.R, a.C), k3_cus) ? 1 : 0;
+        }
         L.inf.launches += 2;
     }
     L.first = false;
@@ -552,6 +559,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
 
     if (o.trace_cap > 0) HIP_TRY(c, c->d_trace.grow((size_t)o.trace_cap));
     const RunPlan p = plan_run(c, o);
+    c->launched = bf_ctx::Launched{};
     RunLoop L{c, p};
     int rc = run_begin(c, o, p, L);
     if (rc == BF_OK && p.persist) rc = run_persistent(c, o, p, L);

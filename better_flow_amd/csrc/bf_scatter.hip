@@ -673,15 +673,19 @@ __global__ __launch_bounds__(64) void k_finish_update(DevState* st, MomentAcc* a
     }
 }
 
-// The scatter kernel's instantiations are the ones the host really picks (bf_run), not the full product: the update's home
-// fixes the form -- HEAD: every work-group applies the pending update itself (a context that has the GPU to itself), lean: the
-// stencil kernel's last work-group did ("co_schedule") -- and form + format fix the work-group sizes:
-//     dense slabs / own pixels + margin plane:  head 1024 threads (bins of >= 1536 events) or 512, lean 512
-//     event lists:                              256 (thousands of small bins) or 512, either form
-// times 1, 2, 4 or 8 events per thread (dense slabs on 512 threads: also 10 and 12) and warp / no warp (the first pass of a cold run): 88 kernels, where the full product
-// of the knobs that used to be options (3 sizes x 4 formats, both forms) was 192.  (The 512-thread head form is what a
-// context alone runs at 640x480 -- BASELINE config 3: 540-690 bins of ~1500 events -- 11.7 us per launch against 17.4 with
-// 1024 threads: measured when round 5's pruning first took it out.)
+// The scatter kernel's instantiations are the ones the host really picks (bf_rules::scatter_size), not the full product: the
+// update's home fixes the form -- HEAD: every work-group applies the pending update itself (a context that has the GPU to itself),
+// lean: the stencil kernel's last work-group did ("co_schedule") -- and form + format fix the work-group sizes and, with them, the
+// events per thread that can occur (a 512-thread head form is chosen only below 1536 events per bin: at most 4 per thread; the
+// 1024-thread form only above: at least 2; 256 threads only below 1024 events per bin: at most 4):
+//     dense slabs / own pixels + margin plane:  head 1024 threads x 2, 4, 8;  head 512 x 1, 2, 4;  lean 512 x 1, 2, 4, 8
+//     dense slabs only:                         lean 512 x 10, 12
+//     event lists:                              256 (thousands of small bins) x 1, 2, 4;  512 x 1, 2, 4, 8;  either form
+// -- 36 tuples (tests/variants_reachable.txt; tests/cpp/test_plan.cpp sweeps the rules and holds them to it), each with and
+// without the warp (the first pass of a cold run): 72 kernels, where the full product of the knobs that used to be options
+// (3 sizes x 4 formats, both forms) was 192.  (The 512-thread head form is what a context alone runs at 640x480 -- BASELINE
+// config 3: 540-690 bins of ~1500 events -- 11.7 us per launch against 17.4 with 1024 threads: measured when round 5's pruning
+// first took it out.)
 template <bool HEAD, int THREADS, int U, int FMT>
 static hipError_t launch_bws2(const BinScatterArgs& a, bool warp, hipStream_t s) {
     // dynamic LDS: the bin's tile; event lists: none
@@ -713,37 +717,41 @@ static hipError_t launch_bws2(const BinScatterArgs& a, bool warp, hipStream_t s)
     }
     return hipSuccess;
 }
+// `threads`, `per_thread`: bf_rules::scatter_size()'s answer for this slice.  a.acc != NULL: the head form (the pending update's
+// sums), else the lean one.  A tuple outside bf_rules::scatter_compiled() -- the plan never asks for one: tests/cpp/test_plan.cpp --
+// is an error, not a request for the nearest kernel.
 template <bool HEAD, int THREADS, int FMT>
 static hipError_t launch_bws(const BinScatterArgs& a, bool warp, int per_thread, hipStream_t s) {
-    if (per_thread <= 1) return launch_bws2<HEAD, THREADS, 1, FMT>(a, warp, s);
-    if (per_thread <= 2) return launch_bws2<HEAD, THREADS, 2, FMT>(a, warp, s);
-    if (per_thread <= 4) return launch_bws2<HEAD, THREADS, 4, FMT>(a, warp, s);
-    return launch_bws2<HEAD, THREADS, 8, FMT>(a, warp, s);
+    constexpr bool kWide = THREADS == 1024;          // (head form, bins of >= 1536 events: 2, 4 or 8 per thread)
+    constexpr bool kEight = FMT == 2 ? THREADS == 512 : (kWide || !HEAD);
+    switch (per_thread) {
+        case 1: if constexpr (!kWide) return launch_bws2<HEAD, THREADS, 1, FMT>(a, warp, s); else break;
+        case 2: return launch_bws2<HEAD, THREADS, 2, FMT>(a, warp, s);
+        case 4: return launch_bws2<HEAD, THREADS, 4, FMT>(a, warp, s);
+        case 8: if constexpr (kEight) return launch_bws2<HEAD, THREADS, 8, FMT>(a, warp, s); else break;
+        // Dense bins of several thousand events on the lean kernel's 512 threads: a pass that covers the FULLEST bin, not the
+        // average one (config 2: 272 bins, 3673 events on average, 4912 at most -- with 8 per thread two thirds of the bins took
+        // a second pass)
+        case 10: if constexpr (FMT == 0 && !HEAD) return launch_bws2<HEAD, THREADS, 10, FMT>(a, warp, s); else break;
+        case 12: if constexpr (FMT == 0 && !HEAD) return launch_bws2<HEAD, THREADS, 12, FMT>(a, warp, s); else break;
+        default: break;
+    }
+    return hipErrorInvalidValue;
 }
 
-// `threads`: bin_scatter_threads()'s answer for this slice; `per_thread`: events a thread keeps in flight (1, 2, 4 or 8; dense slabs on 512 threads also 10 or 12).
-// a.acc != NULL: the head form (the pending update's sums), else the lean one.
-int bin_scatter_threads(int fmt, bool head, bool many_small_bins, double events_per_bin) {
-    if (fmt == 2) return many_small_bins ? 256 : 512;
-    return (head && events_per_bin >= 1536.0) ? 1024 : 512;
-}
 hipError_t launch_bin_warp_scatter(const BinScatterArgs& a, bool warp, int threads, int per_thread, hipStream_t s) {
     const bool head = a.acc != nullptr;
+    if (!bf_rules::scatter_compiled(head, threads, per_thread, a.compact)) return hipErrorInvalidValue;
     if (a.compact == 2) {
-        if (threads <= 256) return head ? launch_bws<true, 256, 2>(a, warp, per_thread, s) : launch_bws<false, 256, 2>(a, warp, per_thread, s);
+        if (threads == 256) return head ? launch_bws<true, 256, 2>(a, warp, per_thread, s) : launch_bws<false, 256, 2>(a, warp, per_thread, s);
         return head ? launch_bws<true, 512, 2>(a, warp, per_thread, s) : launch_bws<false, 512, 2>(a, warp, per_thread, s);
     }
-    const bool wide = head && threads >= 1024;
-    if (a.compact == 3)
-        return wide ? launch_bws<true, 1024, 3>(a, warp, per_thread, s)
-                    : (head ? launch_bws<true, 512, 3>(a, warp, per_thread, s) : launch_bws<false, 512, 3>(a, warp, per_thread, s));
-    if (a.compact != 0) return hipErrorInvalidValue;
-    // Dense bins of several thousand events on 512 threads: a pass that covers the FULLEST bin, not the average one (config 2:
-    // 272 bins, 3673 events on average, 4912 at most -- with 8 per thread two thirds of the bins took a second pass)
-    if (!wide && per_thread >= 12) return head ? launch_bws2<true, 512, 12, 0>(a, warp, s) : launch_bws2<false, 512, 12, 0>(a, warp, s);
-    if (!wide && per_thread >= 10) return head ? launch_bws2<true, 512, 10, 0>(a, warp, s) : launch_bws2<false, 512, 10, 0>(a, warp, s);
-    return wide ? launch_bws<true, 1024, 0>(a, warp, per_thread, s)
-                : (head ? launch_bws<true, 512, 0>(a, warp, per_thread, s) : launch_bws<false, 512, 0>(a, warp, per_thread, s));
+    if (a.compact == 3) {
+        if (threads == 1024) return launch_bws<true, 1024, 3>(a, warp, per_thread, s);
+        return head ? launch_bws<true, 512, 3>(a, warp, per_thread, s) : launch_bws<false, 512, 3>(a, warp, per_thread, s);
+    }
+    if (threads == 1024) return launch_bws<true, 1024, 0>(a, warp, per_thread, s);
+    return head ? launch_bws<true, 512, 0>(a, warp, per_thread, s) : launch_bws<false, 512, 0>(a, warp, per_thread, s);
 }
 
 

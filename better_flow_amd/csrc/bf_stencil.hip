@@ -487,7 +487,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kStencilSgprs)))
 
 
 void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n_cus) {
-    const bool full = n_cus > 0 && (long long)grid.x * grid.y >= 8ll * n_cus;   // more work-groups than the CUs hold at once
+    const bool full = bf_rules::stencil_capped((long long)grid.x * grid.y, n_cus);   // more work-groups than the CUs hold at once
 #define BF_K3_PRE a.slabs, a.st, a.R, a.C, a.g.D, a.g.lg, a.g.nbc, a.g.nbr, a.g.LR, a.g.L, a.g.TSR, a.g.mul_r
 #define BF_K3(HS_)                                                                                                  \
     if (full) {                                                                                                     \
@@ -497,7 +497,7 @@ void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n
     } else if (a.compact == 3) launch_timed(k_stencil_binned<HS_, 2, kThreads>, grid, dim3(kThreads), 0, s, BF_K3_PRE, a);     \
     else if (a.compact) launch_timed(k_stencil_binned<HS_, 1, kThreads>, grid, dim3(kThreads), 0, s, BF_K3_PRE, a);            \
     else launch_timed(k_stencil_binned<HS_, 0, kThreads>, grid, dim3(kThreads), 0, s, BF_K3_PRE, a)
-    switch (a.scale / 2) {
+    switch (bf_rules::stencil_half_scale(a.scale)) {
         case 0: BF_K3(0); break;
         case 1: BF_K3(1); break;
         case 2: BF_K3(2); break;

@@ -224,6 +224,15 @@ int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
  *                     that were not resident: something else holds part of the GPU) and undid themselves; the run they
  *                     belonged to went on with one launch per iteration, and the context leaves the kernel alone for the
  *                     next 1, 2, 4 ... 64 runs.
+ *   "bin_rows", "bin_cols", "bin_margin", "bins"   the bin grid the last bf_set_cloud planned for the two-kernel tile-binned
+ *                     loop: a bin's rows, columns and margin in scaled pixels, and the number of bins; 0 when the slice does
+ *                     not take that loop.
+ *   "k1_threads", "k1_events_per_thread", "k1_head"   the scatter kernel the last bf_run launched in that loop: its work-group
+ *                     size, the events a thread keeps in flight, and 1 when the model update ran at its head (0: the lean
+ *                     kernel); -1 when that run launched none (one-kernel or global-atomics loop, no run yet).
+ *   "k3_half_scale", "k3_mode", "k3_capped"   ... and its stencil kernel: scale / 2 (at most 4), what it read (0 dense slabs,
+ *                     1 event lists, 2 own pixels + margin plane), and 1 for the build with capped scalar registers that a
+ *                     launch of >= 8 tiles per CU takes; -1 as above.
  * BF_ERR_ARG for an unknown key. */
 int bf_get_stat(bf_ctx *ctx, const char *key, int64_t *value);
 
