@@ -136,6 +136,17 @@ class GlobalResult(C.Structure):
     ]
 
 
+class GlobalCells(C.Structure):
+    _fields_ = [("n_cell_x", C.c_int32), ("n_cell_y", C.c_int32)]
+
+
+class GlobalCellResult(C.Structure):
+    _fields_ = [
+        ("best_nx", C.c_double), ("best_ny", C.c_double), ("best_u", C.c_double), ("best_v", C.c_double),
+        ("best_sum", C.c_int64), ("best_index", C.c_int64), ("events", C.c_int64),
+    ]
+
+
 # every symbol include/bf_accel.h declares
 EXPORTS = [
     "bf_device_count", "bf_create", "bf_destroy", "bf_last_error", "bf_version",
@@ -149,6 +160,7 @@ EXPORTS = [
     "bf_upload_ring_async", "bf_upload_ring16_async", "bf_upload_ring16t32_async", "bf_upload_events16_async", "bf_compute_uv_ring", "bf_wait_uploads", "bf_projection_img",
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
+    "bf_global_set_cells", "bf_global_search_cells",
     "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
     "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
     "bf_flow_field", "bf_color_flow_img", "bf_flow_frame_create", "bf_flow_frame_destroy", "bf_flow_frame_render",
@@ -261,6 +273,9 @@ def load(path=None):
                                             C.POINTER(C.c_int64)]
         L.bf_global_search.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(GlobalResult), C.c_void_p, C.c_int64]
         L.bf_global_get_events.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+        L.bf_global_set_cells.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GlobalCells)]
+        L.bf_global_search_cells.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(GlobalResult), C.c_void_p,
+                                             C.c_int64, C.c_void_p, C.c_int64]
         L.bf_projection_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_color_time_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_upload_ring_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
@@ -370,6 +385,7 @@ class Accel:
         self.n = 0
         self.window = None
         self._gwin = None
+        self._gcells = None
 
     def close(self):
         if getattr(self, "h", None):
@@ -486,6 +502,7 @@ class Accel:
         w = GlobalWindow()
         self._chk(self.L.bf_global_set_window(self.h, scale, metric_wsize, C.byref(w)))
         self._gwin = w
+        self._gcells = None   # (the library clears the cells with the window)
         return w
 
     def global_project_all(self, nx, ny, nz=127.0, want_img=True, want_scores=True):
@@ -519,6 +536,36 @@ class Accel:
         if surf is not None:
             surf = surf[:r.n_x * r.n_y].reshape(r.n_x, r.n_y)
         return r, surf
+
+    def global_set_cells(self, res_x, res_y, cell_rows, cell_cols):
+        """A grid of cell_rows x cell_cols-pixel cells over the res_x x res_y sensor, anchored at pixel (0, 0), for
+        global_search_cells; valid until the next global_set_window or upload.  Returns GlobalCells (n_cell_x, n_cell_y)."""
+        g = GlobalCells()
+        self._gcells = None
+        self._chk(self.L.bf_global_set_cells(self.h, res_x, res_y, cell_rows, cell_cols, C.byref(g)))
+        self._gcells = g
+        return g
+
+    def global_search_cells(self, opts=None, want_surface=False, cells_cap=None, surface_cap=None):
+        """global_search with the objective kept per cell.  Returns (GlobalResult of the slice, structured array
+        [n_cell_x, n_cell_y] with best_nx, best_ny, best_u, best_v, best_sum, best_index, events, and the surface
+        S(k, cell) as int64 [n_cell_x, n_cell_y, n_x, n_y] or None)."""
+        r = GlobalResult()
+        o = opts if opts is not None else self.global_search_opts()
+        g = self._gcells   # None before global_set_cells: the library reports BF_ERR_ARG
+        nc = g.n_cell_x * g.n_cell_y if g else 0
+        cells = np.zeros(nc if cells_cap is None else cells_cap, dtype=np.dtype(GlobalCellResult))
+        surf = None
+        if want_surface:
+            k = len(_sweep(o.x_low, o.x_hi, o.x_step)) * len(_sweep(o.y_low, o.y_hi, o.y_step))
+            if surface_cap is None:
+                surface_cap = nc * k if nc * k <= (1 << 27) else 1   # (over the cap: the library refuses before it writes)
+            surf = np.zeros(surface_cap, dtype=np.int64)
+        self._chk(self.L.bf_global_search_cells(self.h, C.byref(o), C.byref(r), _ptr(cells), len(cells), _ptr(surf),
+                                                0 if surf is None else len(surf)))
+        if surf is not None:
+            surf = surf[:nc * r.n_x * r.n_y].reshape(g.n_cell_x, g.n_cell_y, r.n_x, r.n_y)
+        return r, cells[:nc].reshape(g.n_cell_x, g.n_cell_y), surf
 
     def global_get_events(self):
         """Per-event state in upload order: dict of max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v."""

@@ -13,6 +13,9 @@
 //       float like current_scores), apply_score's strict `>` (event.h:113-121) into the running best, and
 //       floor(score * 2^32) = (sum << 32) / count summed per candidate with integer atomics -- S(k), order free.
 //
+//   G3c k_global_fold_cells + k_global_cells_best replace G3 in bf_global_search_cells: the same per-event fold, walked in
+//       cell order, with S(k, cell) summed per work-group on chip ("OptimizerGlobal").
+//
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
 // order in which work-groups run.
 #include <hip/hip_runtime.h>
@@ -199,6 +202,139 @@ __global__ __launch_bounds__(kGT) void k_global_fold(const uint32_t* __restrict_
     }
 }
 
+// ---- the per-cell objective S(k, cell) (include/bf_accel.h) ----
+// Membership is by the event's recorded address; the grid is anchored at sensor pixel (0, 0).
+__device__ __forceinline__ uint32_t cell_of(uint32_t v, const GlobalCellGrid& cg) {
+    return ((v & 0xffffu) / (uint32_t)cg.cell_rows) * (uint32_t)cg.n_cell_y + (v >> 16) / (uint32_t)cg.cell_cols;
+}
+
+__global__ __launch_bounds__(kGT) void k_global_cell_count(const uint32_t* __restrict__ xy, long long n, GlobalCellGrid cg,
+                                                           uint32_t* __restrict__ count) {
+    const long long i = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t c = cell_of(xy[i], cg);
+    if (c < (uint32_t)cg.n_cells) atomicAdd(&count[c], 1u);   // (the host checked the bounding box: always)
+}
+
+// The slot inside a cell is whichever the atomic hands out: the order of a cell's events is arbitrary, and nothing
+// downstream depends on it (per-event state is indexed by upload index, every sum is an integer).
+__global__ __launch_bounds__(kGT) void k_global_cell_order(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
+                                                           const uint32_t* __restrict__ perm, long long n, GlobalCellGrid cg,
+                                                           const uint32_t* __restrict__ cell_start, uint32_t* __restrict__ cursor,
+                                                           uint32_t* __restrict__ cxy, int32_t* __restrict__ ct,
+                                                           uint32_t* __restrict__ cidx) {
+    const long long i = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t v = xy[i];
+    const uint32_t c = cell_of(v, cg);
+    if (c >= (uint32_t)cg.n_cells) return;
+    const uint32_t j = cell_start[c] + atomicAdd(&cursor[c], 1u);
+    if (j >= cell_start[c + 1]) return;   // (never: cell_start is the scan of this very count)
+    cxy[j] = v; ct[j] = t[i];
+    cidx[j] = perm ? perm[i] : (uint32_t)i;
+}
+
+// k_global_fold per event (the same window word, score and strict `>`), over a run of at most T events of ONE cell: the
+// work-group's total of every candidate goes into the batch block [cell][b] with one 64-bit atomic (none when it is 0).
+// T == 64: the wave's total is the work-group's.  T == 256: lane 63 of each wave parks its totals in LDS, and after one
+// barrier thread b adds the four of candidate b.
+template <int T>
+__global__ __launch_bounds__(T) void k_global_fold_cells(GlobalCells cl, GlobalGeom g, const GlobalCand* __restrict__ cands,
+                                                         int nb, const uint32_t* __restrict__ win, GlobalEventState st) {
+    constexpr int kWaves = T / 64;
+    __shared__ unsigned long long s_part[kWaves > 1 ? kGlobalCellStride * kWaves : 1];
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    const bool live = j < cl.cell_start[cell + 1];
+    unsigned long long* out = cl.block + (size_t)cell * kGlobalCellStride;
+    long long e = 0;   // the event's upload index
+    uint32_t v = 0;
+    int32_t ti = 0;
+    double mx = 0, bnx = 0, bny = 0, bnz = 0, bpx = 0, bpy = 0;
+    if (live) {
+        v = cl.xy[j]; ti = cl.t[j]; e = (long long)cl.idx[j];
+        mx = st.max_score[e]; bnx = st.best_nx[e]; bny = st.best_ny[e]; bnz = st.best_nz[e];
+        bpx = st.best_pr_x[e]; bpy = st.best_pr_y[e];
+    }
+    bool changed = false;
+    const int off = g.scale / 2 + g.mw / 2;
+    for (int b = 0; b < nb; ++b) {
+        const GlobalCand c = cands[b];
+        unsigned long long contrib = 0;
+        double pr_x, pr_y;
+        int X, Y;
+        if (live && global_pixel(g, c, v, ti, pr_x, pr_y, X, Y)) {
+            const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
+            const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
+            const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
+            const float f = (float)score;                                        // current_scores (CV_32FC1)
+            if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
+            if ((double)f > mx) {   // apply_score, event.h:113-121
+                mx = f; bnx = c.nx; bny = c.ny; bnz = c.nz; bpx = pr_x; bpy = pr_y;
+                changed = true;
+            }
+        }
+        const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
+        if ((threadIdx.x & 63) == 63) {
+            if (kWaves == 1) {
+                if (tot) atomicAdd(&out[b], tot);
+            } else {
+                s_part[b * kWaves + (threadIdx.x >> 6)] = tot;
+            }
+        }
+    }
+    if (changed) {
+        st.max_score[e] = mx; st.best_nx[e] = bnx; st.best_ny[e] = bny; st.best_nz[e] = bnz;
+        st.best_pr_x[e] = bpx; st.best_pr_y[e] = bpy;
+    }
+    if (kWaves > 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < nb) {
+            unsigned long long tot = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) tot += s_part[threadIdx.x * kWaves + w];
+            if (tot) atomicAdd(&out[threadIdx.x], tot);
+        }
+    }
+}
+
+// One batch's block [cell][b], kGlobalCellStride threads per cell (8 cells per work-group): the first largest of the
+// cell's nb sums (largest value, then lowest b: what folding them in order with strict `>` picks) folds into the
+// cell's running best with strict `>`; the surface gets its copy; the block is left zero for the next batch; and the
+// batch's S(k) = the sum over cells: over the work-group's 8 cells in LDS, then one integer atomic per candidate.
+__global__ __launch_bounds__(kGT) void k_global_cells_best(GlobalCells cl, int nb, unsigned long long* __restrict__ S) {
+    constexpr int kCellsPerGroup = kGT / kGlobalCellStride;
+    __shared__ unsigned long long s_v[kGT];
+    const int b = threadIdx.x % kGlobalCellStride;
+    const long long cell = (long long)blockIdx.x * kCellsPerGroup + threadIdx.x / kGlobalCellStride;
+    const bool live = cell < cl.n_cells && b < nb;
+    unsigned long long v = 0;
+    if (live) {
+        unsigned long long* p = cl.block + (size_t)cell * kGlobalCellStride + b;
+        v = *p;
+        if (v) *p = 0;
+        if (cl.surface) cl.surface[(size_t)cell * (size_t)cl.n_cand + (size_t)(cl.k0 + b)] = (long long)v;
+    }
+    s_v[threadIdx.x] = v;
+    int at = b;
+    for (int d = kGlobalCellStride / 2; d > 0; d >>= 1) {   // (the 32 lanes of a cell are one half of a wave)
+        const unsigned long long ov = __shfl_xor(v, d, kGlobalCellStride);
+        const int oat = __shfl_xor(at, d, kGlobalCellStride);
+        if (ov > v || (ov == v && oat < at)) { v = ov; at = oat; }
+    }
+    if (b == 0 && cell < cl.n_cells && v > cl.best_sum[cell]) {
+        cl.best_sum[cell] = v;
+        cl.best_k[cell] = (uint32_t)(cl.k0 + at);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+        unsigned long long tot = 0;
+#pragma unroll
+        for (int c = 0; c < kCellsPerGroup; ++c) tot += s_v[c * kGlobalCellStride + threadIdx.x];
+        if (tot) atomicAdd(&S[threadIdx.x], tot);
+    }
+}
+
 // Event(x, y, t) of the reference (event.h:31-35): max_score 0, best_pr = fr; best (nx, ny) = 0 (best_u / best_v 0)
 __global__ __launch_bounds__(kGT) void k_global_reset(const uint32_t* __restrict__ xy, const uint32_t* __restrict__ perm,
                                                       long long n, GlobalEventState st) {
@@ -228,9 +364,11 @@ void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, 
 
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
-                        const GlobalEventState& st, unsigned long long* S, float* scores_out, hipStream_t s) {
+                        const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
+                        hipStream_t s) {
     if (nb <= 0 || n <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
     if (g.scale / 2 > 3) return -1;
+    if (cells && nb > kGlobalCellStride) return -1;
     const unsigned eg = (unsigned)((n + kGT - 1) / kGT);
     hipLaunchKernelGGL(k_global_project, dim3(eg, (unsigned)nb), dim3(kGT), 0, s, xy, t, n, g, cands, pts);
     void (*k)(const uint32_t*, GlobalGeom, uint32_t*, uint8_t*) =
@@ -241,8 +379,30 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
         return -2;
     const dim3 grid((unsigned)((g.Cb + kGTC - 1) / kGTC), (unsigned)((g.Rb + kGTR - 1) / kGTR), (unsigned)nb);
     hipLaunchKernelGGL(k, grid, dim3(kGT), lds, s, pts, g, win, img_out);
-    hipLaunchKernelGGL(k_global_fold, dim3(eg), dim3(kGT), 0, s, xy, t, perm, n, g, cands, nb, win, st, S, scores_out);
+    if (!cells) {
+        hipLaunchKernelGGL(k_global_fold, dim3(eg), dim3(kGT), 0, s, xy, t, perm, n, g, cands, nb, win, st, S, scores_out);
+        return 0;
+    }
+    if (cells->run_len == 64)
+        hipLaunchKernelGGL(k_global_fold_cells<64>, dim3((unsigned)cells->n_runs), dim3(64), 0, s, *cells, g, cands, nb, win, st);
+    else
+        hipLaunchKernelGGL(k_global_fold_cells<kGT>, dim3((unsigned)cells->n_runs), dim3(kGT), 0, s, *cells, g, cands, nb, win, st);
+    constexpr int per = kGT / kGlobalCellStride;
+    hipLaunchKernelGGL(k_global_cells_best, dim3((unsigned)((cells->n_cells + per - 1) / per)), dim3(kGT), 0, s, *cells, nb, S);
     return 0;
+}
+
+void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_global_cell_count, dim3((unsigned)((n + kGT - 1) / kGT)), dim3(kGT), 0, s, xy, n, cg, count);
+}
+
+void launch_global_cell_order(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalCellGrid& cg,
+                              const uint32_t* cell_start, uint32_t* cursor, uint32_t* cxy, int32_t* ct, uint32_t* cidx,
+                              hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_global_cell_order, dim3((unsigned)((n + kGT - 1) / kGT)), dim3(kGT), 0, s, xy, t, perm, n, cg, cell_start,
+                       cursor, cxy, ct, cidx);
 }
 
 }  // namespace bf

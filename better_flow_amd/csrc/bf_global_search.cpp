@@ -1,6 +1,7 @@
 // bf_global_search.cpp -- C-ABI of the exhaustive search, OptimizerGlobal (optimizer_global.h / optimizer_global.cpp): the window
-// (update_fields), one project_all, compute_flow_bruteforce over a candidate grid, and the per-event state.  The kernels
-// are in bf_global.hip; the two definitions this build adds (the per-event best candidate, the objective S) are stated in
+// (update_fields), one project_all, compute_flow_bruteforce over a candidate grid (per slice, and per cell of a grid over the
+// sensor), and the per-event state.  The kernels are in bf_global.hip; the definitions this build adds (the per-event best
+// candidate, the objective S, the objective per cell) are stated in
 // include/bf_accel.h and DESIGN.md.
 #include "bf_ctx.h"
 
@@ -16,6 +17,20 @@ struct GlobalSearch {
     DevArray<uint8_t> d_img;
     DevArray<float> d_scores;
     std::vector<GlobalCand> h_cands;
+
+    // the cell grid of bf_global_set_cells (cleared by bf_global_set_window)
+    bool have_cells = false;
+    bf_global_cells cells;
+    GlobalCellGrid cg;
+    int run_len = 0;
+    std::vector<uint32_t> h_cell_count;                                // events per cell
+    DevArray<uint32_t> d_cell_count, d_cell_start, d_cxy, d_cidx;      // (d_cell_count: the sort's counts, then its cursors)
+    DevArray<int32_t> d_ct;
+    DevArray<uint32_t> d_run_cell, d_run_start;
+    long long n_runs = 0;
+    DevArray<unsigned long long> d_cell_block, d_cell_best;
+    DevArray<uint32_t> d_cell_best_k;
+    DevArray<long long> d_cell_surface;
 
     GlobalEventState state() const {
         GlobalEventState s;
@@ -35,6 +50,8 @@ namespace {
 constexpr long long kGlobalBatchBytes = 512ll << 20;   // point + window planes of one batch
 constexpr int kGlobalMaxBatch = 32;
 constexpr long long kGlobalMaxCandidates = 1ll << 26;
+constexpr long long kGlobalMaxCells = 1ll << 16;
+constexpr long long kGlobalMaxCellSurface = 1ll << 27;   // entries: 1 GiB of int64
 
 GlobalCand make_cand(double nx, double ny, double nz) {
     GlobalCand k;
@@ -65,9 +82,12 @@ int global_ready(bf_ctx* c) {
     return BF_OK;
 }
 
-// candidates [k0, k0 + k) of gs->h_cands, already on the device at d_cands + k0: S into d_S + k0, folded into the state
-int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8_t* d_img, float* d_scores) {
+// candidates [k0, k0 + k) of gs->h_cands, already on the device at d_cands + k0: S into d_S + k0, folded into the state.
+// cells (may be null): the per-cell form of the fold, batch after batch in sweep order
+int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8_t* d_img, float* d_scores,
+                   GlobalCells* cells = nullptr) {
     if (gs->n <= 0) return BF_OK;   // no event: every S stays 0
+    static_assert(kGlobalMaxBatch <= kGlobalCellStride, "a batch must fit the cell block");
     const int B = (int)std::max(1ll, std::min((long long)kGlobalMaxBatch, kGlobalBatchBytes / (gs->g.plane * 8)));
     int rc = ensure_batch(c, gs, (int)std::min((long long)B, k));
     if (rc != BF_OK) return rc;
@@ -76,14 +96,61 @@ int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8
     for (long long b0 = 0; b0 < k; b0 += B) {
         const int nb = (int)std::min((long long)B, k - b0);
         HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)nb * (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
+        if (cells) cells->k0 = k0 + b0;
         const int lr = launch_global_batch(e.xy, e.t, perm, gs->n, gs->g, gs->d_cands + k0 + b0, nb, gs->d_pts, gs->d_win,
-                                           d_img, gs->state(), gs->d_S + k0 + b0, d_scores, c->stream);
+                                           d_img, gs->state(), gs->d_S + k0 + b0, d_scores, cells, c->stream);
         if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
         if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
         if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
         HIP_TRY(c, hipGetLastError());
     }
     return BF_OK;
+}
+
+// The checks of a sweep and its candidate values: opts (NULL: the defaults) validated, the window ready, then the
+// reference's loops (:134-135): repeated double addition, ny restarting from y_low on every row
+int sweep_grid(bf_ctx* c, const bf_global_search_opts* opts, std::vector<double>& xs, std::vector<double>& ys, double& nz) {
+    bf_global_search_opts o;
+    bf_global_search_opts_default(&o);
+    if (opts) o = *opts;
+    if (!(o.x_step > 0) || !(o.y_step > 0) || !(o.x_low < o.x_hi) || !(o.y_low < o.y_hi))   // optimizer_global.cpp:110
+        return fail(c, BF_ERR_ARG, "bad search range: need lo < hi and step > 0");
+    if (!(o.nz > 0) || !std::isfinite(o.x_hi) || !std::isfinite(o.y_hi)) return fail(c, BF_ERR_ARG, "bad nz / range");
+    int rc = global_ready(c);
+    if (rc != BF_OK) return rc;
+    for (double v = o.x_low; v < o.x_hi; v += o.x_step) {
+        xs.push_back(v);
+        if ((long long)xs.size() > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "more than 2^26 candidates");
+    }
+    for (double v = o.y_low; v < o.y_hi; v += o.y_step) {
+        ys.push_back(v);
+        if ((long long)ys.size() > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "more than 2^26 candidates");
+    }
+    const long long k = (long long)xs.size() * (long long)ys.size();
+    if (k > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "%lld candidates (more than 2^26)", k);
+    nz = o.nz;
+    return BF_OK;
+}
+
+// the sweep's candidates (nx outer, ny inner) onto the device, their S zeroed
+int upload_cands(bf_ctx* c, GlobalSearch* gs, const std::vector<double>& xs, const std::vector<double>& ys, double nz) {
+    const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), k = nxc * nyc;
+    gs->h_cands.resize((size_t)k);
+    for (long long i = 0; i < nxc; ++i)
+        for (long long j = 0; j < nyc; ++j) gs->h_cands[(size_t)(i * nyc + j)] = make_cand(xs[(size_t)i], ys[(size_t)j], nz);
+    int rc = ensure_cands(c, gs, k);
+    if (rc != BF_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(gs->d_cands, gs->h_cands.data(), (size_t)k * sizeof(GlobalCand), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, (size_t)k * sizeof(unsigned long long), c->stream));
+    return BF_OK;
+}
+
+// Event::compute_uv, event.h:135-142
+void cand_uv(double nx, double ny, double nz, double* u, double* v) {
+    const double xy_len = std::hypot(nx, ny);
+    const double speed = xy_len / (nz / (1000000000 / (1 * 10000)));
+    *u = xy_len == 0 ? 0 : speed * nx / xy_len;
+    *v = xy_len == 0 ? 0 : speed * ny / xy_len;
 }
 
 }  // namespace
@@ -127,6 +194,7 @@ int bf_global_set_window(bf_ctx* c, int32_t scale, int32_t metric_wsize, bf_glob
     if (!c->glob) c->glob.reset(new GlobalSearch());
     GlobalSearch* gs = c->glob.get();
     gs->have = false;
+    gs->have_cells = false;
     c->glob_valid = false;
     HIP_TRY(c, gs->d_state.grow((size_t)c->cap_events * 6));   // (n <= cap_events: one allocation for every slice)
     GlobalGeom& g = gs->g;
@@ -179,35 +247,15 @@ int bf_global_project_all(bf_ctx* c, double nx, double ny, double nz, uint8_t* i
 int bf_global_search(bf_ctx* c, const bf_global_search_opts* opts, bf_global_result* out, int64_t* surface_out,
                      int64_t surface_cap) {
     if (!c) return BF_ERR_ARG;
-    bf_global_search_opts o;
-    bf_global_search_opts_default(&o);
-    if (opts) o = *opts;
-    if (!(o.x_step > 0) || !(o.y_step > 0) || !(o.x_low < o.x_hi) || !(o.y_low < o.y_hi))   // optimizer_global.cpp:110
-        return fail(c, BF_ERR_ARG, "bad search range: need lo < hi and step > 0");
-    if (!(o.nz > 0) || !std::isfinite(o.x_hi) || !std::isfinite(o.y_hi)) return fail(c, BF_ERR_ARG, "bad nz / range");
-    int rc = global_ready(c);
-    if (rc != BF_OK) return rc;
-    // the reference's loops (:134-135): repeated double addition, ny restarting from y_low on every row
     std::vector<double> xs, ys;
-    for (double v = o.x_low; v < o.x_hi; v += o.x_step) {
-        xs.push_back(v);
-        if ((long long)xs.size() > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "more than 2^26 candidates");
-    }
-    for (double v = o.y_low; v < o.y_hi; v += o.y_step) {
-        ys.push_back(v);
-        if ((long long)ys.size() > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "more than 2^26 candidates");
-    }
+    double nz = 0;
+    int rc = sweep_grid(c, opts, xs, ys, nz);
+    if (rc != BF_OK) return rc;
     const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), k = nxc * nyc;
-    if (k > kGlobalMaxCandidates) return fail(c, BF_ERR_ARG, "%lld candidates (more than 2^26)", k);
     if (surface_out && surface_cap < k) return fail(c, BF_ERR_ARG, "surface buffer holds %lld of %lld", (long long)surface_cap, k);
     HIP_TRY(c, hipSetDevice(c->device));
     GlobalSearch* gs = c->glob.get();
-    gs->h_cands.resize((size_t)k);
-    for (long long i = 0; i < nxc; ++i)
-        for (long long j = 0; j < nyc; ++j) gs->h_cands[(size_t)(i * nyc + j)] = make_cand(xs[i], ys[j], o.nz);
-    if ((rc = ensure_cands(c, gs, k)) != BF_OK) return rc;
-    HIP_TRY(c, hipMemcpyAsync(gs->d_cands, gs->h_cands.data(), (size_t)k * sizeof(GlobalCand), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, (size_t)k * sizeof(unsigned long long), c->stream));
+    if ((rc = upload_cands(c, gs, xs, ys, nz)) != BF_OK) return rc;
     if ((rc = run_candidates(c, gs, 0, k, nullptr, nullptr)) != BF_OK) return rc;
     std::vector<unsigned long long> S((size_t)k);
     HIP_TRY(c, hipMemcpyAsync(S.data(), gs->d_S, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -223,6 +271,149 @@ int bf_global_search(bf_ctx* c, const bf_global_search_opts* opts, bf_global_res
         out->best_sum = (int64_t)S[(size_t)best];
         out->n_x = nxc;
         out->n_y = nyc;
+    }
+    return BF_OK;
+}
+
+int bf_global_set_cells(bf_ctx* c, int32_t res_x, int32_t res_y, int32_t cell_rows, int32_t cell_cols, bf_global_cells* out) {
+    if (!c) return BF_ERR_ARG;
+    int rc = global_ready(c);
+    if (rc != BF_OK) return rc;
+    GlobalSearch* gs = c->glob.get();
+    gs->have_cells = false;
+    if (res_x <= 0 || res_y <= 0 || cell_rows <= 0 || cell_cols <= 0)
+        return fail(c, BF_ERR_ARG, "sensor %d x %d, cells %d x %d: every size must be positive", res_x, res_y, cell_rows, cell_cols);
+    if (gs->n > 0 && (gs->w.x_max >= res_x || gs->w.y_max >= res_y))   // (addresses are unsigned: x_min, y_min >= 0)
+        return fail(c, BF_ERR_ARG, "an event at (%d, %d) lies outside the %d x %d sensor", gs->w.x_max, gs->w.y_max, res_x, res_y);
+    bf_global_cells gc;
+    gc.n_cell_x = (int32_t)(((long long)res_x + cell_rows - 1) / cell_rows);
+    gc.n_cell_y = (int32_t)(((long long)res_y + cell_cols - 1) / cell_cols);
+    const long long nc = (long long)gc.n_cell_x * gc.n_cell_y;
+    if (nc > kGlobalMaxCells) return fail(c, BF_ERR_ARG, "%lld cells (more than 65536)", nc);
+    HIP_TRY(c, hipSetDevice(c->device));
+    GlobalCellGrid& cg = gs->cg;
+    cg.cell_rows = cell_rows; cg.cell_cols = cell_cols; cg.n_cell_y = gc.n_cell_y; cg.n_cells = (int32_t)nc;
+    gs->h_cell_count.assign((size_t)nc, 0u);
+    gs->n_runs = 0;
+    gs->run_len = 64;
+    HIP_TRY(c, gs->d_cell_block.grow((size_t)nc * kGlobalCellStride));
+    HIP_TRY(c, gs->d_cell_best.grow((size_t)nc));
+    HIP_TRY(c, gs->d_cell_best_k.grow((size_t)nc));
+    if (gs->n > 0) {
+        const size_t n = (size_t)gs->n;
+        const bf_ctx::EvSet& e = c->set[c->cs];
+        HIP_TRY(c, gs->d_cell_count.grow((size_t)nc));
+        HIP_TRY(c, gs->d_cell_start.grow((size_t)nc + 1));
+        HIP_TRY(c, gs->d_cxy.grow(n));
+        HIP_TRY(c, gs->d_ct.grow(n));
+        HIP_TRY(c, gs->d_cidx.grow(n));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_count, 0, (size_t)nc * sizeof(uint32_t), c->stream));
+        launch_global_cell_count(e.xy, gs->n, cg, gs->d_cell_count, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(gs->h_cell_count.data(), gs->d_cell_count, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        // the scan, and the runs: a cell of m events is cut into ceil(m / run_len) work-groups.  Work-groups of one wave
+        // unless the occupied cells hold 256 events or more on average (a 256-wide group on a 75-event cell idles 3 waves)
+        std::vector<uint32_t> start((size_t)nc + 1, 0u);
+        long long occupied = 0;
+        for (long long i = 0; i < nc; ++i) {
+            start[(size_t)i + 1] = start[(size_t)i] + gs->h_cell_count[(size_t)i];
+            occupied += gs->h_cell_count[(size_t)i] != 0u;
+        }
+        if ((long long)start[(size_t)nc] != gs->n) return fail(c, BF_ERR_HIP, "bf_global_set_cells: the cell counts do not add up");
+        gs->run_len = gs->n >= 256 * occupied ? 256 : 64;
+        std::vector<uint32_t> run_cell, run_start;
+        for (long long i = 0; i < nc; ++i)
+            for (uint32_t s = start[(size_t)i]; s < start[(size_t)i + 1]; s += (uint32_t)gs->run_len) {
+                run_cell.push_back((uint32_t)i);
+                run_start.push_back(s);
+            }
+        gs->n_runs = (long long)run_cell.size();
+        HIP_TRY(c, gs->d_run_cell.grow(run_cell.size()));
+        HIP_TRY(c, gs->d_run_start.grow(run_start.size()));
+        HIP_TRY(c, hipMemcpyAsync(gs->d_cell_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(gs->d_run_cell, run_cell.data(), run_cell.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(gs->d_run_start, run_start.data(), run_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_count, 0, (size_t)nc * sizeof(uint32_t), c->stream));
+        launch_global_cell_order(e.xy, e.t, c->has_perm ? e.perm : nullptr, gs->n, cg, gs->d_cell_start, gs->d_cell_count, gs->d_cxy,
+                                 gs->d_ct, gs->d_cidx, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host vectors above are read until here)
+    }
+    gs->cells = gc;
+    gs->have_cells = true;
+    if (out) *out = gc;
+    return BF_OK;
+}
+
+int bf_global_search_cells(bf_ctx* c, const bf_global_search_opts* opts, bf_global_result* slice_out,
+                           bf_global_cell_result* cells_out, int64_t cells_cap, int64_t* cell_surface_out,
+                           int64_t cell_surface_cap) {
+    if (!c) return BF_ERR_ARG;
+    std::vector<double> xs, ys;
+    double nz = 0;
+    int rc = sweep_grid(c, opts, xs, ys, nz);
+    if (rc != BF_OK) return rc;
+    GlobalSearch* gs = c->glob.get();
+    if (!gs->have_cells) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), k = nxc * nyc;
+    const long long nc = gs->cg.n_cells;
+    if (cells_out && cells_cap < nc) return fail(c, BF_ERR_ARG, "cell buffer holds %lld of %lld", (long long)cells_cap, nc);
+    if (cell_surface_out) {
+        if (nc * k > kGlobalMaxCellSurface)
+            return fail(c, BF_ERR_CAPACITY, "a surface of %lld cells x %lld candidates has more than 2^27 entries", nc, k);
+        if (cell_surface_cap < nc * k)
+            return fail(c, BF_ERR_ARG, "cell surface buffer holds %lld of %lld", (long long)cell_surface_cap, nc * k);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = upload_cands(c, gs, xs, ys, nz)) != BF_OK) return rc;
+    std::vector<unsigned long long> S((size_t)k, 0ull), cell_best((size_t)nc, 0ull);
+    std::vector<uint32_t> cell_k((size_t)nc, 0u);
+    if (gs->n > 0) {   // (no event: nothing is launched, every S(k, cell) is 0)
+        if (cell_surface_out) HIP_TRY(c, gs->d_cell_surface.grow((size_t)(nc * k)));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_block, 0, (size_t)nc * kGlobalCellStride * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best_k, 0, (size_t)nc * sizeof(uint32_t), c->stream));
+        GlobalCells cl;
+        cl.xy = gs->d_cxy; cl.t = gs->d_ct; cl.idx = gs->d_cidx;
+        cl.cell_start = gs->d_cell_start; cl.run_cell = gs->d_run_cell; cl.run_start = gs->d_run_start;
+        cl.n_runs = (int32_t)gs->n_runs; cl.run_len = gs->run_len; cl.n_cells = (int32_t)nc;
+        cl.block = gs->d_cell_block; cl.best_sum = gs->d_cell_best; cl.best_k = gs->d_cell_best_k;
+        cl.surface = cell_surface_out ? gs->d_cell_surface.get() : nullptr;
+        cl.n_cand = k; cl.k0 = 0;
+        if ((rc = run_candidates(c, gs, 0, k, nullptr, nullptr, &cl)) != BF_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(S.data(), gs->d_S, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cell_best.data(), gs->d_cell_best, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cell_k.data(), gs->d_cell_best_k, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (cell_surface_out)
+            HIP_TRY(c, hipMemcpyAsync(cell_surface_out, gs->d_cell_surface, (size_t)(nc * k) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                                      c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    } else if (cell_surface_out) {
+        std::fill(cell_surface_out, cell_surface_out + nc * k, (int64_t)0);
+    }
+    if (slice_out) {
+        long long best = 0;
+        for (long long i = 1; i < k; ++i)
+            if (S[(size_t)i] > S[(size_t)best]) best = i;   // the first of the largest
+        slice_out->best_nx = xs[(size_t)(best / nyc)];
+        slice_out->best_ny = ys[(size_t)(best % nyc)];
+        slice_out->best_sum = (int64_t)S[(size_t)best];
+        slice_out->n_x = nxc;
+        slice_out->n_y = nyc;
+    }
+    for (long long i = 0; cells_out && i < nc; ++i) {
+        bf_global_cell_result& r = cells_out[i];
+        const long long b = (long long)cell_k[(size_t)i];
+        r.best_nx = xs[(size_t)(b / nyc)];
+        r.best_ny = ys[(size_t)(b % nyc)];
+        cand_uv(r.best_nx, r.best_ny, nz, &r.best_u, &r.best_v);
+        r.best_sum = (int64_t)cell_best[(size_t)i];
+        r.best_index = b;
+        r.events = (int64_t)gs->h_cell_count[(size_t)i];
     }
     return BF_OK;
 }
@@ -248,11 +439,10 @@ int bf_global_get_events(bf_ctx* c, double* max_score, double* best_nx, double* 
     for (size_t i = 0; i < n; ++i) {
         if (best_nx) best_nx[i] = nx[i];
         if (best_ny) best_ny[i] = ny[i];
-        // Event::compute_uv, event.h:135-142
-        const double xy_len = std::hypot(nx[i], ny[i]);
-        const double speed = xy_len / (nz[i] / (1000000000 / (1 * 10000)));
-        if (best_u) best_u[i] = xy_len == 0 ? 0 : speed * nx[i] / xy_len;
-        if (best_v) best_v[i] = xy_len == 0 ? 0 : speed * ny[i] / xy_len;
+        double u, v;
+        cand_uv(nx[i], ny[i], nz[i], &u, &v);
+        if (best_u) best_u[i] = u;
+        if (best_v) best_v[i] = v;
     }
     return BF_OK;
 }

@@ -275,12 +275,41 @@ struct GlobalCand {
 struct GlobalEventState {     // per event, upload order
     double *max_score, *best_nx, *best_ny, *best_nz, *best_pr_x, *best_pr_y;
 };
+// The per-cell objective S(k, cell) (include/bf_accel.h): the slice in cell order, cut into runs of at most run_len
+// consecutive events of ONE cell (one work-group each), and where the sums go.
+constexpr int kGlobalCellStride = 32;   // candidates per cell in the batch block (>= the largest batch)
+struct GlobalCellGrid {
+    int32_t cell_rows, cell_cols, n_cell_y, n_cells;
+};
+struct GlobalCells {
+    const uint32_t* xy; const int32_t* t;   // the slice's events, ordered by cell
+    const uint32_t* idx;                    // ... and their upload indices (the order composed with perm)
+    const uint32_t* cell_start;             // n_cells + 1 offsets into the three arrays above
+    const uint32_t *run_cell, *run_start;   // n_runs each: run r holds events [run_start[r], min(+ run_len, end of its cell))
+    int32_t n_runs, run_len;                // run_len 64 or 256: the fold's work-group size
+    int32_t n_cells;
+    unsigned long long* block;              // [n_cells][kGlobalCellStride] sums of one batch; all zero between batches
+    unsigned long long* best_sum;           // per cell: the running largest S(k, cell) ...
+    uint32_t* best_k;                       // ... and the first candidate that reached it
+    long long* surface;                     // null, or [n_cells][n_cand]
+    long long n_cand, k0;                   // candidates of the sweep; the batch's first
+};
 size_t global_tile_lds(int scale, int mw);
 void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, const GlobalEventState& st, hipStream_t s);
-// one batch of nb candidates; `pts` must be all zero (nb planes); < 0: scale above 7 / kernel attributes / LDS
+// one batch of nb candidates; `pts` must be all zero (nb planes); < 0: scale above 7 / kernel attributes / LDS.
+// cells null: k_global_fold adds S(k) into S[0 .. nb).  Otherwise k_global_fold_cells folds the same per-event state and
+// k_global_cells_best leaves S(k) = the sum over the cells in S[0 .. nb) (which must be zero before), with cells->k0 the
+// batch's first candidate; nb <= kGlobalCellStride, img_out and scores_out unused.
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
-                        const GlobalEventState& st, unsigned long long* S, float* scores_out, hipStream_t s);
+                        const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
+                        hipStream_t s);
+// counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
+// events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
+void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);
+void launch_global_cell_order(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalCellGrid& cg,
+                              const uint32_t* cell_start, uint32_t* cursor, uint32_t* cxy, int32_t* ct, uint32_t* cidx,
+                              hipStream_t s);
 
 void launch_proj_count(const uint32_t* xy, const float2* p, const uint8_t* noise, long long n, int scale, int res_x,
                        int res_y, int show_final, uint32_t* plane, hipStream_t s);

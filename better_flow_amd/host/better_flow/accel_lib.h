@@ -301,6 +301,18 @@ public:
         if (surface && !surface->empty()) { sp = surface->data(); cap = (int64_t)surface->size(); }
         check(bf_global_search(ctx, &o, r, sp, cap), "global_search");
     }
+    // the objective per cell of a grid over the sensor (include/bf_accel.h: bf_global_set_cells, bf_global_search_cells)
+    void global_set_cells(int res_x, int res_y, int cell_rows, int cell_cols, bf_global_cells *g) {
+        check(bf_global_set_cells(ctx, res_x, res_y, cell_rows, cell_cols, g), "global_set_cells");
+    }
+    void global_search_cells(const bf_global_search_opts &o, bf_global_result *r, std::vector<bf_global_cell_result> *cells,
+                             std::vector<int64_t> *cell_surface) {
+        int64_t *sp = nullptr;
+        int64_t cap = 0;
+        if (cell_surface && !cell_surface->empty()) { sp = cell_surface->data(); cap = (int64_t)cell_surface->size(); }
+        check(bf_global_search_cells(ctx, &o, r, cells ? cells->data() : nullptr, cells ? (int64_t)cells->size() : 0, sp, cap),
+              "global_search_cells");
+    }
     void global_get_events(double *max_score, double *best_nx, double *best_ny, double *best_pr_x, double *best_pr_y,
                            double *best_u, double *best_v) {
         check(bf_global_get_events(ctx, max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v), "global_get_events");

@@ -8,6 +8,12 @@
 // first candidate in sweep order with the largest S = sum of floor(score * 2^32).  The blur is this build's stated 8-bit
 // Gaussian, not pinned to any OpenCV.
 //
+// A third: the objective per cell of a grid over the sensor (set_cells, compute_flow_cells; include/bf_accel.h), which
+// answers with one candidate per cell where the slice-level search answers with one.  write_cell_flo writes that grid as a
+// Middlebury .flo through bf::flo_payload / bf::write_flo (flow_field.h), with that writer's conventions: width =
+// n_cell_y, height = n_cell_x, per cell float32 horizontal = best_v (columns) then vertical = best_u (rows), and the
+// writer's unknown-flow value 1e9 in both for a cell with events == 0.
+//
 // Each object stages its slice on a device context of its OWN (not the thread's shared one that OptimizerLocal and
 // OptimizerRolling use): the window and the per-event best state live there and accumulate over project_all /
 // compute_flow_bruteforce calls, so no other optimiser on the thread may replace them.  Objects are not copyable.
@@ -18,7 +24,9 @@
 #include <better_flow/common.h>
 #include <better_flow/datastructures.h>
 #include <better_flow/event.h>
+#include <better_flow/flow_field.h>
 
+#include <string>
 #include <vector>
 
 class OptimizerGlobal {
@@ -43,6 +51,11 @@ protected:
     std::vector<int64_t> surface;
     long long last_sum;
 
+    int cells_res_x = 0, cells_res_y = 0, cell_rows = 0, cell_cols = 0;   // set_cells' arguments (0: not called)
+    bool cells_staged = false;
+    bf_global_cells cell_grid;
+    std::vector<bf_global_cell_result> cell_results;                      // [n_cell_x][n_cell_y]
+
     void stage() {   // the slice goes to the device once; the window resets every event's best state
         if (accel.is_staged()) return;
         if (!own.ctx) {
@@ -59,6 +72,7 @@ protected:
         accel.global_set_window(this->scale, this->metric_wsize, &w);
         this->scale_img_x = w.scale_img_x; this->scale_img_y = w.scale_img_y;
         this->scale_bordered_img_x = w.scale_bordered_img_x; this->scale_bordered_img_y = w.scale_bordered_img_y;
+        this->cells_staged = false;   // (a new window clears the cells)
     }
 
     void update_fields() {   // optimizer_global.cpp:187-205 (the device recomputes the same numbers in stage())
@@ -109,6 +123,43 @@ public:
         }
         this->surface.assign(nx * ny > 0 && nx * ny <= (1ll << 26) ? (size_t)(nx * ny) : 0, 0);
         accel.global_search(this->range, &this->result, &this->surface);
+    }
+
+    // A grid of cell_rows x cell_cols-pixel cells over the res_x x res_y sensor, anchored at pixel (0, 0), for
+    // compute_flow_cells.
+    void set_cells(int res_x, int res_y, int cell_rows_, int cell_cols_) {
+        this->cells_res_x = res_x; this->cells_res_y = res_y; this->cell_rows = cell_rows_; this->cell_cols = cell_cols_;
+        this->cells_staged = false;
+        this->cell_results.clear();
+    }
+
+    // compute_flow_bruteforce with the objective kept per cell: the slice's result as there (from the sum over the cells),
+    // one result per cell, and the same per-event state.  No surface is kept.
+    void compute_flow_cells() {
+        this->stage();
+        if (!this->cells_staged) {
+            accel.global_set_cells(cells_res_x, cells_res_y, cell_rows, cell_cols, &this->cell_grid);   // (throws before set_cells)
+            this->cells_staged = true;
+        }
+        this->cell_results.assign((size_t)cell_grid.n_cell_x * (size_t)cell_grid.n_cell_y, bf_global_cell_result());
+        this->surface.clear();
+        accel.global_search_cells(this->range, &this->result, &this->cell_results, nullptr);
+    }
+
+    int get_n_cell_x() const { return cell_results.empty() ? 0 : cell_grid.n_cell_x; }
+    int get_n_cell_y() const { return cell_results.empty() ? 0 : cell_grid.n_cell_y; }
+    const std::vector<bf_global_cell_result> &get_cell_results() const { return cell_results; }   // [n_cell_x][n_cell_y]
+    const bf_global_cell_result &get_cell(int cx, int cy) const { return cell_results[(size_t)cx * cell_grid.n_cell_y + cy]; }
+
+    // The per-cell (best_u, best_v) of the last compute_flow_cells as a .flo (the conventions are at the top of this file).
+    bool write_cell_flo(const std::string &path) const {
+        bf::FlowField f(this->get_n_cell_x(), this->get_n_cell_y());
+        for (size_t i = 0; i < cell_results.size(); ++i) {
+            if (cell_results[i].events == 0) continue;   // owner -1: the writer's unknown flow
+            f.owner[i] = 0; f.u[i] = cell_results[i].best_u; f.v[i] = cell_results[i].best_v;
+        }
+        const std::vector<float> payload = bf::flo_payload(f);
+        return bf::write_flo(path, f.rows, f.cols, payload.data());
     }
 
     // The search range (optimizer_global.cpp:106-108 hard-codes x in [-0.09, 0.09), y in [-0.04, 0.04), step 0.001:

@@ -575,6 +575,45 @@ int bf_global_search(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_r
 int bf_global_get_events(bf_ctx *ctx, double *max_score, double *best_nx, double *best_ny, double *best_pr_x,
                          double *best_pr_y, double *best_u, double *best_v);
 
+/* The objective per region of the sensor: a third definition of this build ("OptimizerGlobal").
+ *   - The grid.  Cells of cell_rows x cell_cols sensor pixels, anchored at sensor pixel (0, 0) -- not at the cloud's
+ *     bounding box -- so a cell means the same pixels in every slice.  n_cell_x = ceil(res_x / cell_rows), n_cell_y =
+ *     ceil(res_y / cell_cols); the last row and column of cells may be ragged.
+ *   - Membership.  An event belongs to the cell of its recorded address, cell = (fr_x / cell_rows) * n_cell_y + fr_y /
+ *     cell_cols, wherever a candidate projects it.
+ *   - The objective.  S(k, cell) = sum of floor(score * 2^32) over the events of `cell` accepted under candidate k, the
+ *     per-event term of S(k) ((sum << 32) / count): an exact int64, order free, and sum over cells of S(k, cell) == S(k).
+ *   - A cell's answer is the first candidate in sweep order (nx outer, ny inner) with the largest S(k, cell): candidate 0
+ *     when every S(k, cell) is 0, an empty cell included -- the slice rule.
+ *   - The per-event best state folds exactly as in bf_global_search. */
+typedef struct bf_global_cells {
+    int32_t n_cell_x, n_cell_y;
+} bf_global_cells;
+
+typedef struct bf_global_cell_result {
+    double best_nx, best_ny;   /* the cell's answer */
+    double best_u, best_v;     /* Event::compute_uv of it, the expression of bf_global_get_events */
+    int64_t best_sum;          /* S(best, cell) */
+    int64_t best_index;        /* its place in the sweep: i_x * n_y + i_y */
+    int64_t events;            /* events of the slice in the cell, accepted or not */
+} bf_global_cell_result;
+
+/* Lays the grid over a res_x x res_y sensor (rows x columns) and orders the slice by cell.  Valid after
+ * bf_global_set_window, and invalidated like the window: BF_ERR_STATE when any upload happened since; setting the window
+ * again clears the cells.  BF_ERR_ARG for a non-positive size, an event address outside res_x x res_y, more than 65536
+ * cells, or no window.  out (may be NULL) reports the grid. */
+int bf_global_set_cells(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t cell_rows, int32_t cell_cols, bf_global_cells *out);
+
+/* bf_global_search with the objective kept per cell, continuing from the current per-event state: afterwards
+ * bf_global_get_events returns what bf_global_search over the same range would have left.  slice_out (may be NULL) is
+ * filled from S(k) = sum over cells, by the slice rule.  cells_out (may be NULL; cells_cap entries) is row-major
+ * [n_cell_x][n_cell_y].  cell_surface_out (may be NULL; cell_surface_cap entries) receives S(k, cell) as
+ * [cell][n_x][n_y]: at most 2^27 entries, else BF_ERR_CAPACITY; without it the device keeps one batch of candidates per
+ * cell only.  BF_ERR_ARG for what bf_global_search refuses, a buffer shorter than the grid, or no cells. */
+int bf_global_search_cells(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_result *slice_out,
+                           bf_global_cell_result *cells_out, int64_t cells_cap, int64_t *cell_surface_out,
+                           int64_t cell_surface_cap);
+
 /* ---- per-event flow table on the device: DVS_flow::get_accumulated (dvs_flow.h:351-389) -----------------------------
  * The -o table (every event once, with the flow of the first slice that solved it) built slice by slice on the device,
  * with the marking rule of bf::StreamEngine::get_accumulated (stream_flow.h), for slices cut from one event ring whose
