@@ -4,6 +4,10 @@ Bars: window / warp state / event-count image / Scharr planes b
 time image <= 1e-6 relative (the reference's own f32 accumulation-order noise) and
 bit-exact where a single event hit the pixel; moments <= 1e-9 relative; converged
 (u, v) <= 1e-4 relative or 0.02 px/s, iteration count within +-1.
+
+The 1e-6 and 1e-9 bars are the oracle's order noise.  The exact bar -- count and time image bit for bit on every pixel
+against an order-free integer reference, the moments within a derived rounding bound -- is held by tests/test_gpu_exact.py
+(reference: tests/exact_ref.py).
 """
 import os
 
