@@ -147,6 +147,17 @@ class GlobalCellResult(C.Structure):
     ]
 
 
+class GlobalPyramidOpts(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("factor", C.c_int32), ("radius", C.c_int32)]
+
+
+class GlobalPyramidInfo(C.Structure):
+    _fields_ = [
+        ("n_x", C.c_int64), ("n_y", C.c_int64), ("evaluated", C.c_int64), ("level_count", C.c_int64 * 8),
+        ("levels_run", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 # every symbol include/bf_accel.h declares
 EXPORTS = [
     "bf_device_count", "bf_create", "bf_destroy", "bf_last_error", "bf_version",
@@ -160,7 +171,7 @@ EXPORTS = [
     "bf_upload_ring_async", "bf_upload_ring16_async", "bf_upload_ring16t32_async", "bf_upload_events16_async", "bf_compute_uv_ring", "bf_wait_uploads", "bf_projection_img",
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
-    "bf_global_set_cells", "bf_global_search_cells",
+    "bf_global_set_cells", "bf_global_search_cells", "bf_global_search_cells_pyramid",
     "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
     "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
     "bf_flow_field", "bf_color_flow_img", "bf_flow_frame_create", "bf_flow_frame_destroy", "bf_flow_frame_render",
@@ -276,6 +287,9 @@ def load(path=None):
         L.bf_global_set_cells.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GlobalCells)]
         L.bf_global_search_cells.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(GlobalResult), C.c_void_p,
                                              C.c_int64, C.c_void_p, C.c_int64]
+        L.bf_global_search_cells_pyramid.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(GlobalPyramidOpts),
+                                                     C.c_void_p, C.POINTER(GlobalResult), C.c_void_p, C.c_int64, C.c_void_p,
+                                                     C.c_int64, C.c_void_p, C.c_int64, C.POINTER(GlobalPyramidInfo)]
         L.bf_projection_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_color_time_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_upload_ring_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
@@ -566,6 +580,38 @@ class Accel:
         if surf is not None:
             surf = surf[:nc * r.n_x * r.n_y].reshape(g.n_cell_x, g.n_cell_y, r.n_x, r.n_y)
         return r, cells[:nc].reshape(g.n_cell_x, g.n_cell_y), surf
+
+    def global_search_cells_pyramid(self, opts=None, levels=1, factor=2, radius=1, seeds=None, want_surface=False,
+                                    cells_cap=None, evaluated_cap=None, surface_cap=None):
+        """global_search_cells over a candidate set decided on the device (bf_global_search_cells_pyramid): a strided pass
+        over the lattice of opts and `levels - 1` refinements around every cell's own best, or, with seeds (one lattice index
+        or -1 per cell, any shape of n_cell_x * n_cell_y entries: usually the previous slice's best_index), `levels`
+        refinements around them.  evaluated_cap None: room for the whole lattice.  Returns (GlobalResult of the slice, the
+        structured cell array of global_search_cells, the evaluated lattice indices in evaluation order (int64),
+        S(k, cell) as int64 [n_cell_x, n_cell_y, n_evaluated] or None, GlobalPyramidInfo)."""
+        r, info = GlobalResult(), GlobalPyramidInfo()
+        o = opts if opts is not None else self.global_search_opts()
+        p = GlobalPyramidOpts(levels, factor, radius)
+        g = self._gcells   # None before global_set_cells: the library reports BF_ERR_ARG
+        nc = g.n_cell_x * g.n_cell_y if g else 0
+        cells = np.zeros(nc if cells_cap is None else cells_cap, dtype=np.dtype(GlobalCellResult))
+        k = len(_sweep(o.x_low, o.x_hi, o.x_step)) * len(_sweep(o.y_low, o.y_hi, o.y_step)) if o.x_step > 0 and o.y_step > 0 else 0
+        ev = np.zeros(k if evaluated_cap is None else evaluated_cap, dtype=np.int64)
+        sd = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.int64).reshape(-1))
+        if sd is not None and len(sd) != nc:
+            raise ValueError("seeds: %d entries for %d cells" % (len(sd), nc))
+        surf = None
+        if want_surface:
+            if surface_cap is None:
+                surface_cap = min(nc * k, 1 << 27)
+            surf = np.zeros(max(surface_cap, 1), dtype=np.int64)
+        self._chk(self.L.bf_global_search_cells_pyramid(self.h, C.byref(o), C.byref(p), _ptr(sd), C.byref(r), _ptr(cells),
+                                                        len(cells), _ptr(ev), len(ev), _ptr(surf),
+                                                        0 if surf is None else surface_cap, C.byref(info)))
+        ne = info.evaluated
+        if surf is not None:
+            surf = surf[:nc * ne].reshape(g.n_cell_x, g.n_cell_y, ne)
+        return r, cells[:nc].reshape(g.n_cell_x, g.n_cell_y), ev[:ne].copy(), surf, info
 
     def global_get_events(self):
         """Per-event state in upload order: dict of max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v."""

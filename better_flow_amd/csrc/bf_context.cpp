@@ -16,12 +16,15 @@ int bf_device_count(int32_t* count) {
 }
 
 int bf_abi_struct_sizes(int32_t* out, int32_t n) {
-    const int32_t sz[8] = {(int32_t)sizeof(bf_model),     (int32_t)sizeof(bf_window),
-                           (int32_t)sizeof(bf_run_opts),  (int32_t)sizeof(bf_run_info),
-                           (int32_t)sizeof(bf_trace_rec), (int32_t)sizeof(bf_profile),
-                           (int32_t)sizeof(bf_local_window), (int32_t)sizeof(bf_local_state)};
-    for (int i = 0; out && i < n && i < 8; ++i) out[i] = sz[i];
-    return 8;
+    const int32_t sz[10] = {(int32_t)sizeof(bf_model),     (int32_t)sizeof(bf_window),
+                            (int32_t)sizeof(bf_run_opts),  (int32_t)sizeof(bf_run_info),
+                            (int32_t)sizeof(bf_trace_rec), (int32_t)sizeof(bf_profile),
+                            (int32_t)sizeof(bf_local_window), (int32_t)sizeof(bf_local_state),
+                            (int32_t)sizeof(bf_global_pyramid_opts), (int32_t)sizeof(bf_global_pyramid_info)};
+    if (!out) return 10;
+    const int32_t m = n < 0 ? 0 : (n < 10 ? n : 10);
+    for (int i = 0; i < m; ++i) out[i] = sz[i];
+    return m;
 }
 
 void bf_run_opts_default(bf_run_opts* o) {

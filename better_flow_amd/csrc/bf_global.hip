@@ -15,11 +15,19 @@
 //
 //   G3c k_global_fold_cells + k_global_cells_best replace G3 in bf_global_search_cells: the same per-event fold, walked in
 //       cell order, with S(k, cell) summed per work-group on chip ("OptimizerGlobal").
+//   P   bf_global_search_cells_pyramid: the candidates of a level are chosen on the device from the per-cell bests
+//       (k_global_stride_mark / k_global_seed_mark into a bitmap of the lattice, a popcount-scan-write compaction into the
+//       ascending list of k, k_global_cands_from_lattice), scored by the unchanged G1, G2 and G3c fold, and
+//       k_global_cells_best_lattice keeps each cell's best by (largest S, lowest lattice k).
 //
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
 // order in which work-groups run.
 #include <hip/hip_runtime.h>
 #include <limits.h>
+
+#include <cstring>   // (rocprim's headers call memset without including it)
+
+#include <rocprim/rocprim.hpp>
 
 #include "bf_device.h"
 #include "bf_device_fns.h"
@@ -335,6 +343,125 @@ __global__ __launch_bounds__(kGT) void k_global_cells_best(GlobalCells cl, int n
     }
 }
 
+// k_global_cells_best for a batch whose slots are arbitrary lattice points (ks[b] = the lattice k of slot b): the cell's
+// best of the batch is its largest sum, lowest k among equals, and it replaces the running best when it is larger, or as
+// large with a lower k -- the exhaustive rule over whatever has been evaluated, in any order.  best_k starts at
+// kGlobalNoCand, so the first batch always sets it.  The surface column goes to [cell][k0 + b] of a surface n_cand wide
+// (the level's list), the block is zeroed and S summed as in k_global_cells_best.
+__global__ __launch_bounds__(kGT) void k_global_cells_best_lattice(GlobalCells cl, int nb, const uint32_t* __restrict__ ks,
+                                                                   unsigned long long* __restrict__ S) {
+    constexpr int kCellsPerGroup = kGT / kGlobalCellStride;
+    __shared__ unsigned long long s_v[kGT];
+    const int b = threadIdx.x % kGlobalCellStride;
+    const long long cell = (long long)blockIdx.x * kCellsPerGroup + threadIdx.x / kGlobalCellStride;
+    const bool live = cell < cl.n_cells && b < nb;
+    unsigned long long v = 0;
+    uint32_t k = kGlobalNoCand;
+    if (live) {
+        unsigned long long* p = cl.block + (size_t)cell * kGlobalCellStride + b;
+        v = *p;
+        if (v) *p = 0;
+        k = ks[b];
+        if (cl.surface) cl.surface[(size_t)cell * (size_t)cl.n_cand + (size_t)(cl.k0 + b)] = (long long)v;
+    }
+    s_v[threadIdx.x] = v;
+    for (int d = kGlobalCellStride / 2; d > 0; d >>= 1) {   // (the 32 lanes of a cell are one half of a wave)
+        const unsigned long long ov = __shfl_xor(v, d, kGlobalCellStride);
+        const uint32_t ok = __shfl_xor(k, d, kGlobalCellStride);
+        if (ov > v || (ov == v && ok < k)) { v = ov; k = ok; }
+    }
+    if (b == 0 && cell < cl.n_cells && k != kGlobalNoCand) {
+        const unsigned long long bv = cl.best_sum[cell];
+        if (v > bv || (v == bv && k < cl.best_k[cell])) {
+            cl.best_sum[cell] = v;
+            cl.best_k[cell] = k;
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nb) {
+        unsigned long long tot = 0;
+#pragma unroll
+        for (int c = 0; c < kCellsPerGroup; ++c) tot += s_v[c * kGlobalCellStride + threadIdx.x];
+        if (tot) atomicAdd(&S[threadIdx.x], tot);
+    }
+}
+
+// ---- the candidate set of a pyramid level (include/bf_accel.h) ----
+// One thread per strided lattice point; the OR is a vector atomic, so the bitmap does not depend on the order.
+__global__ __launch_bounds__(kGT) void k_global_stride_mark(GlobalLattice lt, long long stride, long long m_x, long long m_y,
+                                                            uint32_t* __restrict__ level) {
+    const long long q = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (q >= m_x * m_y) return;
+    const long long k = (q / m_y) * stride * lt.n_y + (q % m_y) * stride;   // (i, j) < (n_x, n_y): m = ceil(n / stride)
+    atomicOr(&level[k >> 5], 1u << (k & 31));
+}
+
+// One thread per (cell, a, b), |a|, |b| <= radius.
+__global__ __launch_bounds__(kGT) void k_global_seed_mark(GlobalLattice lt, long long stride, int radius, long long total,
+                                                          const uint32_t* __restrict__ cell_start,
+                                                          const unsigned long long* __restrict__ best_sum,
+                                                          const uint32_t* __restrict__ best_k, const int32_t* __restrict__ seed,
+                                                          const uint32_t* __restrict__ evaluated, uint32_t* __restrict__ level) {
+    const long long q = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (q >= total) return;
+    const int w = 2 * radius + 1;
+    const long long cell = q / (w * w);
+    const int ab = (int)(q - cell * (w * w));
+    const int a = ab / w - radius, b = ab % w - radius;
+    if (cell_start[cell + 1] == cell_start[cell]) return;   // no event
+    long long kc;
+    if (best_sum[cell] > 0) {
+        kc = (long long)best_k[cell];
+    } else {
+        if (!seed || seed[cell] < 0) return;
+        kc = (long long)seed[cell];
+    }
+    const long long i = kc / lt.n_y + (long long)a * stride, j = kc % lt.n_y + (long long)b * stride;
+    if (i < 0 || i >= lt.n_x || j < 0 || j >= lt.n_y) return;   // clipped
+    const long long k = i * lt.n_y + j;
+    const uint32_t bit = 1u << (k & 31);
+    if (evaluated[k >> 5] & bit) return;
+    atomicOr(&level[k >> 5], bit);
+}
+
+__global__ __launch_bounds__(kGT) void k_global_bitmap_count(const uint32_t* __restrict__ level, long long n_words,
+                                                             uint32_t* __restrict__ cnt) {
+    const long long w = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (w > n_words) return;
+    cnt[w] = w < n_words ? (uint32_t)__popc(level[w]) : 0u;   // (entry n_words: the scan leaves the total there)
+}
+
+// One thread per word, which it alone reads and writes.
+__global__ __launch_bounds__(kGT) void k_global_bitmap_list(uint32_t* __restrict__ level, uint32_t* __restrict__ evaluated,
+                                                            long long n_words, const uint32_t* __restrict__ offs,
+                                                            uint32_t* __restrict__ list) {
+    const long long w = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (w >= n_words) return;
+    uint32_t bits = level[w];
+    if (!bits) return;
+    evaluated[w] |= bits;
+    level[w] = 0u;
+    uint32_t at = offs[w];
+    while (bits) {
+        const int bit = __ffs((int)bits) - 1;
+        list[at++] = (uint32_t)(w * 32 + bit);
+        bits &= bits - 1u;
+    }
+}
+
+__global__ __launch_bounds__(kGT) void k_global_cands_from_lattice(GlobalLattice lt, const uint32_t* __restrict__ list,
+                                                                   long long m, const GlobalAxis* __restrict__ tab_x,
+                                                                   const GlobalAxis* __restrict__ tab_y, double nz,
+                                                                   GlobalCand* __restrict__ cands) {
+    const long long q = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (q >= m) return;
+    const long long k = (long long)list[q];
+    const GlobalAxis x = tab_x[k / lt.n_y], y = tab_y[k % lt.n_y];
+    GlobalCand c;
+    c.nx = x.n; c.ny = y.n; c.nz = nz; c.kx = x.k; c.ky = y.k;
+    cands[q] = c;
+}
+
 // Event(x, y, t) of the reference (event.h:31-35): max_score 0, best_pr = fr; best (nx, ny) = 0 (best_u / best_v 0)
 __global__ __launch_bounds__(kGT) void k_global_reset(const uint32_t* __restrict__ xy, const uint32_t* __restrict__ perm,
                                                       long long n, GlobalEventState st) {
@@ -365,7 +492,7 @@ void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, 
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
-                        hipStream_t s) {
+                        hipStream_t s, const uint32_t* lattice_k) {
     if (nb <= 0 || n <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
     if (g.scale / 2 > 3) return -1;
     if (cells && nb > kGlobalCellStride) return -1;
@@ -388,8 +515,55 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
     else
         hipLaunchKernelGGL(k_global_fold_cells<kGT>, dim3((unsigned)cells->n_runs), dim3(kGT), 0, s, *cells, g, cands, nb, win, st);
     constexpr int per = kGT / kGlobalCellStride;
-    hipLaunchKernelGGL(k_global_cells_best, dim3((unsigned)((cells->n_cells + per - 1) / per)), dim3(kGT), 0, s, *cells, nb, S);
+    const dim3 cgrid((unsigned)((cells->n_cells + per - 1) / per));
+    if (lattice_k)
+        hipLaunchKernelGGL(k_global_cells_best_lattice, cgrid, dim3(kGT), 0, s, *cells, nb, lattice_k, S);
+    else
+        hipLaunchKernelGGL(k_global_cells_best, cgrid, dim3(kGT), 0, s, *cells, nb, S);
     return 0;
+}
+
+void launch_global_stride_mark(const GlobalLattice& lt, long long stride, uint32_t* level, hipStream_t s) {
+    const long long m_x = (lt.n_x + stride - 1) / stride, m_y = (lt.n_y + stride - 1) / stride;
+    if (m_x * m_y <= 0) return;
+    hipLaunchKernelGGL(k_global_stride_mark, dim3((unsigned)((m_x * m_y + kGT - 1) / kGT)), dim3(kGT), 0, s, lt, stride, m_x, m_y,
+                       level);
+}
+
+void launch_global_seed_mark(const GlobalLattice& lt, long long stride, int radius, int n_cells, const uint32_t* cell_start,
+                             const unsigned long long* best_sum, const uint32_t* best_k, const int32_t* seed,
+                             const uint32_t* evaluated, uint32_t* level, hipStream_t s) {
+    const long long w = 2 * radius + 1, total = (long long)n_cells * w * w;   // <= 2^16 * 129^2: the grid fits 32 bits
+    if (total <= 0) return;
+    hipLaunchKernelGGL(k_global_seed_mark, dim3((unsigned)((total + kGT - 1) / kGT)), dim3(kGT), 0, s, lt, stride, radius, total,
+                       cell_start, best_sum, best_k, seed, evaluated, level);
+}
+
+size_t global_scan_temp_bytes(long long n_words) {
+    size_t b = 0;
+    (void)rocprim::exclusive_scan(nullptr, b, (const uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)(n_words + 1),
+                                  rocprim::plus<uint32_t>());
+    return b;
+}
+
+hipError_t launch_global_bitmap_scan(const uint32_t* level, long long n_words, uint32_t* cnt, uint32_t* offs, void* temp,
+                                     size_t temp_bytes, hipStream_t s) {
+    hipLaunchKernelGGL(k_global_bitmap_count, dim3((unsigned)((n_words + 1 + kGT - 1) / kGT)), dim3(kGT), 0, s, level, n_words, cnt);
+    return rocprim::exclusive_scan(temp, temp_bytes, (const uint32_t*)cnt, offs, 0u, (size_t)(n_words + 1),
+                                   rocprim::plus<uint32_t>(), s);
+}
+
+void launch_global_bitmap_list(uint32_t* level, uint32_t* evaluated, long long n_words, const uint32_t* offs, uint32_t* list,
+                               hipStream_t s) {
+    hipLaunchKernelGGL(k_global_bitmap_list, dim3((unsigned)((n_words + kGT - 1) / kGT)), dim3(kGT), 0, s, level, evaluated, n_words,
+                       offs, list);
+}
+
+void launch_global_cands_from_lattice(const GlobalLattice& lt, const uint32_t* list, long long m, const GlobalAxis* tab_x,
+                                      const GlobalAxis* tab_y, double nz, GlobalCand* cands, hipStream_t s) {
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_global_cands_from_lattice, dim3((unsigned)((m + kGT - 1) / kGT)), dim3(kGT), 0, s, lt, list, m, tab_x, tab_y,
+                       nz, cands);
 }
 
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s) {

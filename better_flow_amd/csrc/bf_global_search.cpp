@@ -32,6 +32,14 @@ struct GlobalSearch {
     DevArray<uint32_t> d_cell_best_k;
     DevArray<long long> d_cell_surface;
 
+    // bf_global_search_cells_pyramid: the lattice bitmaps (one bit per k), the compaction's scratch, the level's list of k,
+    // the axis tables and the seeds; d_state_save holds the per-event state while a call may still fail for a short buffer
+    DevArray<uint32_t> d_bm_eval, d_bm_level, d_bm_cnt, d_bm_offs, d_level_k;
+    DevArray<uint8_t> d_scan_tmp;
+    DevArray<GlobalAxis> d_tab_x, d_tab_y;
+    DevArray<int32_t> d_seed;
+    DevArray<double> d_state_save;
+
     GlobalEventState state() const {
         GlobalEventState s;
         const long long k = (long long)(d_state.size() / 6);
@@ -84,8 +92,9 @@ int global_ready(bf_ctx* c) {
 
 // candidates [k0, k0 + k) of gs->h_cands, already on the device at d_cands + k0: S into d_S + k0, folded into the state.
 // cells (may be null): the per-cell form of the fold, batch after batch in sweep order
+// lattice_k (with cells): the lattice index of each of the k candidates, on the device (the pyramid's best-of-batch rule)
 int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8_t* d_img, float* d_scores,
-                   GlobalCells* cells = nullptr) {
+                   GlobalCells* cells = nullptr, const uint32_t* lattice_k = nullptr) {
     if (gs->n <= 0) return BF_OK;   // no event: every S stays 0
     static_assert(kGlobalMaxBatch <= kGlobalCellStride, "a batch must fit the cell block");
     const int B = (int)std::max(1ll, std::min((long long)kGlobalMaxBatch, kGlobalBatchBytes / (gs->g.plane * 8)));
@@ -98,7 +107,8 @@ int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8
         HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)nb * (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
         if (cells) cells->k0 = k0 + b0;
         const int lr = launch_global_batch(e.xy, e.t, perm, gs->n, gs->g, gs->d_cands + k0 + b0, nb, gs->d_pts, gs->d_win,
-                                           d_img, gs->state(), gs->d_S + k0 + b0, d_scores, cells, c->stream);
+                                           d_img, gs->state(), gs->d_S + k0 + b0, d_scores, cells, c->stream,
+                                           lattice_k ? lattice_k + k0 + b0 : nullptr);
         if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
         if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
         if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
@@ -414,6 +424,216 @@ int bf_global_search_cells(bf_ctx* c, const bf_global_search_opts* opts, bf_glob
         r.best_sum = (int64_t)cell_best[(size_t)i];
         r.best_index = b;
         r.events = (int64_t)gs->h_cell_count[(size_t)i];
+    }
+    return BF_OK;
+}
+
+int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts, const bf_global_pyramid_opts* pyramid,
+                                   const int64_t* seed_index, bf_global_result* slice_out, bf_global_cell_result* cells_out,
+                                   int64_t cells_cap, int64_t* evaluated_out, int64_t evaluated_cap, int64_t* cell_surface_out,
+                                   int64_t cell_surface_cap, bf_global_pyramid_info* info) {
+    if (!c) return BF_ERR_ARG;
+    bf_global_pyramid_opts po;
+    po.levels = 1; po.factor = 2; po.radius = 1;
+    if (pyramid) po = *pyramid;
+    if (po.levels < 1 || po.levels > 8) return fail(c, BF_ERR_ARG, "levels must be 1..8 (got %d)", po.levels);
+    if (po.factor < 2) return fail(c, BF_ERR_ARG, "factor must be >= 2 (got %d)", po.factor);
+    if (po.radius < 1 || po.radius > 64) return fail(c, BF_ERR_ARG, "radius must be 1..64 (got %d)", po.radius);
+    std::vector<double> xs, ys;
+    double nz = 0;
+    int rc = sweep_grid(c, opts, xs, ys, nz);
+    if (rc != BF_OK) return rc;
+    GlobalSearch* gs = c->glob.get();
+    if (!gs->have_cells) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), K = nxc * nyc;
+    const long long nc = gs->cg.n_cells;
+    const int L = po.levels;
+    long long stride[8];
+    stride[L - 1] = 1;
+    for (int l = L - 2; l >= 0; --l) {
+        stride[l] = stride[l + 1] * po.factor;
+        if (stride[l] > std::max(nxc, nyc))
+            return fail(c, BF_ERR_ARG, "the stride of level %d (%d^%d) exceeds the %lld x %lld lattice", l, po.factor, L - 1 - l, nxc, nyc);
+    }
+    if (cells_out && cells_cap < nc) return fail(c, BF_ERR_ARG, "cell buffer holds %lld of %lld", (long long)cells_cap, nc);
+    const bool seeded = seed_index != nullptr;
+    std::vector<int32_t> h_seed;
+    if (seeded) {
+        h_seed.resize((size_t)nc);
+        bool any = false;
+        for (long long i = 0; i < nc; ++i) {
+            if (seed_index[i] < -1 || seed_index[i] >= K)
+                return fail(c, BF_ERR_ARG, "seed %lld of cell %lld is outside the lattice of %lld", (long long)seed_index[i], i, K);
+            h_seed[(size_t)i] = (int32_t)seed_index[i];
+            any = any || (seed_index[i] >= 0 && gs->h_cell_count[(size_t)i] != 0u);
+        }
+        if (!any) return fail(c, BF_ERR_ARG, "the seeds leave nothing to evaluate (no cell has both events and a seed)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    std::vector<uint32_t> evaluated;            // lattice k, evaluation order
+    std::vector<unsigned long long> S;          // S(k) of them
+    std::vector<std::vector<int64_t>> surf;     // per level [cell][level_count]
+    std::vector<unsigned long long> cell_best((size_t)nc, 0ull);
+    std::vector<uint32_t> cell_k((size_t)nc, 0u);
+    long long level_count[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // what a level of `cnt` more candidates needs of the caller's buffers
+    auto fits = [&](long long cnt) -> int {
+        const long long tot = (long long)evaluated.size() + cnt;
+        if (evaluated_out && evaluated_cap < tot)
+            return fail(c, BF_ERR_ARG, "evaluated buffer holds %lld of at least %lld", (long long)evaluated_cap, tot);
+        if (cell_surface_out) {
+            if (nc * tot > kGlobalMaxCellSurface)
+                return fail(c, BF_ERR_CAPACITY, "a surface of %lld cells x %lld candidates has more than 2^27 entries", nc, tot);
+            if (cell_surface_cap < nc * tot)
+                return fail(c, BF_ERR_ARG, "cell surface buffer holds %lld of at least %lld", (long long)cell_surface_cap, nc * tot);
+        }
+        return BF_OK;
+    };
+    if (gs->n <= 0) {
+        // no event: nothing is launched.  No cell has a centre, so only the strided pass evaluates, and every S is 0
+        const long long s0 = stride[0];
+        const long long cnt = ((nxc + s0 - 1) / s0) * ((nyc + s0 - 1) / s0);
+        if ((rc = fits(cnt)) != BF_OK) return rc;
+        for (long long i = 0; i < nxc; i += s0)
+            for (long long j = 0; j < nyc; j += s0) evaluated.push_back((uint32_t)(i * nyc + j));
+        S.assign(evaluated.size(), 0ull);
+        level_count[0] = cnt;
+        if (cell_surface_out) surf.emplace_back((size_t)(nc * cnt), (int64_t)0);
+    } else {
+        const long long n_words = (K + 31) / 32;
+        const GlobalLattice lt{nxc, nyc};
+        HIP_TRY(c, gs->d_bm_eval.grow((size_t)n_words));
+        HIP_TRY(c, gs->d_bm_level.grow((size_t)n_words));
+        HIP_TRY(c, gs->d_bm_cnt.grow((size_t)n_words + 1));
+        HIP_TRY(c, gs->d_bm_offs.grow((size_t)n_words + 1));
+        const size_t tmp_bytes = global_scan_temp_bytes(n_words);
+        HIP_TRY(c, gs->d_scan_tmp.grow(tmp_bytes ? tmp_bytes : 1));
+        HIP_TRY(c, gs->d_tab_x.grow((size_t)nxc));
+        HIP_TRY(c, gs->d_tab_y.grow((size_t)nyc));
+        std::vector<GlobalAxis> tx((size_t)nxc), ty((size_t)nyc);
+        for (long long i = 0; i < nxc; ++i) {
+            const GlobalCand k = make_cand(xs[(size_t)i], 0.0, nz);
+            tx[(size_t)i].n = k.nx; tx[(size_t)i].k = k.kx; tx[(size_t)i].pad = 0.f;
+        }
+        for (long long j = 0; j < nyc; ++j) {
+            const GlobalCand k = make_cand(0.0, ys[(size_t)j], nz);
+            ty[(size_t)j].n = k.ny; ty[(size_t)j].k = k.ky; ty[(size_t)j].pad = 0.f;
+        }
+        HIP_TRY(c, hipMemcpyAsync(gs->d_tab_x, tx.data(), tx.size() * sizeof(GlobalAxis), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(gs->d_tab_y, ty.data(), ty.size() * sizeof(GlobalAxis), hipMemcpyHostToDevice, c->stream));
+        if (seeded) {
+            HIP_TRY(c, gs->d_seed.grow((size_t)nc));
+            HIP_TRY(c, hipMemcpyAsync(gs->d_seed, h_seed.data(), (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        }
+        const bool may_fail = evaluated_out || cell_surface_out;   // only a short buffer can stop the levels half way
+        if (may_fail) {
+            HIP_TRY(c, gs->d_state_save.grow(gs->d_state.size()));
+            HIP_TRY(c, hipMemcpyAsync(gs->d_state_save, gs->d_state, gs->d_state.size() * sizeof(double), hipMemcpyDeviceToDevice,
+                                      c->stream));
+        }
+        HIP_TRY(c, hipMemsetAsync(gs->d_bm_eval, 0, (size_t)n_words * sizeof(uint32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_bm_level, 0, (size_t)n_words * sizeof(uint32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_block, 0, (size_t)nc * kGlobalCellStride * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best_k, 0xff, (size_t)nc * sizeof(uint32_t), c->stream));   // kGlobalNoCand
+        GlobalCells cl;
+        cl.xy = gs->d_cxy; cl.t = gs->d_ct; cl.idx = gs->d_cidx;
+        cl.cell_start = gs->d_cell_start; cl.run_cell = gs->d_run_cell; cl.run_start = gs->d_run_start;
+        cl.n_runs = (int32_t)gs->n_runs; cl.run_len = gs->run_len; cl.n_cells = (int32_t)nc;
+        cl.block = gs->d_cell_block; cl.best_sum = gs->d_cell_best; cl.best_k = gs->d_cell_best_k;
+        for (int l = 0; l < L; ++l) {
+            if (l == 0 && !seeded)
+                launch_global_stride_mark(lt, stride[0], gs->d_bm_level, c->stream);
+            else
+                launch_global_seed_mark(lt, stride[l], po.radius, (int)nc, gs->d_cell_start, gs->d_cell_best, gs->d_cell_best_k,
+                                        seeded ? gs->d_seed.get() : nullptr, gs->d_bm_eval, gs->d_bm_level, c->stream);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, launch_global_bitmap_scan(gs->d_bm_level, n_words, gs->d_bm_cnt, gs->d_bm_offs, gs->d_scan_tmp, tmp_bytes,
+                                                 c->stream));
+            uint32_t cnt32 = 0;   // the one value a level brings back: the launches below need it
+            HIP_TRY(c, hipMemcpyAsync(&cnt32, gs->d_bm_offs + n_words, sizeof(cnt32), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));   // (also: the previous level's copies into the vectors below are done)
+            const long long cnt = (long long)cnt32;
+            level_count[l] = cnt;
+            if (cnt == 0) continue;
+            if ((rc = fits(cnt)) != BF_OK) {
+                if (!evaluated.empty()) {   // levels ran: the state goes back to what the call found
+                    HIP_TRY(c, hipMemcpyAsync(gs->d_state, gs->d_state_save, gs->d_state.size() * sizeof(double),
+                                              hipMemcpyDeviceToDevice, c->stream));
+                    HIP_TRY(c, hipStreamSynchronize(c->stream));
+                }
+                return rc;
+            }
+            HIP_TRY(c, gs->d_level_k.grow((size_t)cnt));
+            if ((rc = ensure_cands(c, gs, cnt)) != BF_OK) return rc;
+            launch_global_bitmap_list(gs->d_bm_level, gs->d_bm_eval, n_words, gs->d_bm_offs, gs->d_level_k, c->stream);
+            launch_global_cands_from_lattice(lt, gs->d_level_k, cnt, gs->d_tab_x, gs->d_tab_y, nz, gs->d_cands, c->stream);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, (size_t)cnt * sizeof(unsigned long long), c->stream));
+            if (cell_surface_out) HIP_TRY(c, gs->d_cell_surface.grow((size_t)(nc * cnt)));
+            cl.surface = cell_surface_out ? gs->d_cell_surface.get() : nullptr;
+            cl.n_cand = cnt; cl.k0 = 0;
+            if ((rc = run_candidates(c, gs, 0, cnt, nullptr, nullptr, &cl, gs->d_level_k)) != BF_OK) return rc;
+            const size_t at = evaluated.size();
+            evaluated.resize(at + (size_t)cnt);
+            S.resize(at + (size_t)cnt);
+            HIP_TRY(c, hipMemcpyAsync(evaluated.data() + at, gs->d_level_k, (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(S.data() + at, gs->d_S, (size_t)cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                      c->stream));
+            if (cell_surface_out) {
+                surf.emplace_back((size_t)(nc * cnt));
+                HIP_TRY(c, hipMemcpyAsync(surf.back().data(), gs->d_cell_surface, (size_t)(nc * cnt) * sizeof(int64_t),
+                                          hipMemcpyDeviceToHost, c->stream));
+                HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the next level grows d_cell_surface)
+            }
+        }
+        HIP_TRY(c, hipMemcpyAsync(cell_best.data(), gs->d_cell_best, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                  c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cell_k.data(), gs->d_cell_best_k, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    const long long ne = (long long)evaluated.size();
+    if (ne == 0) return fail(c, BF_ERR_HIP, "bf_global_search_cells_pyramid: nothing was evaluated");   // (never: checked above)
+    long long best = 0;   // the largest S, the lowest k among equals
+    for (long long m = 1; m < ne; ++m)
+        if (S[(size_t)m] > S[(size_t)best] || (S[(size_t)m] == S[(size_t)best] && evaluated[(size_t)m] < evaluated[(size_t)best])) best = m;
+    if (gs->n <= 0) std::fill(cell_k.begin(), cell_k.end(), evaluated[(size_t)best]);
+    if (slice_out) {
+        const long long b = (long long)evaluated[(size_t)best];
+        slice_out->best_nx = xs[(size_t)(b / nyc)];
+        slice_out->best_ny = ys[(size_t)(b % nyc)];
+        slice_out->best_sum = (int64_t)S[(size_t)best];
+        slice_out->n_x = nxc;
+        slice_out->n_y = nyc;
+    }
+    for (long long i = 0; cells_out && i < nc; ++i) {
+        bf_global_cell_result& r = cells_out[i];
+        const long long b = (long long)cell_k[(size_t)i];
+        r.best_nx = xs[(size_t)(b / nyc)];
+        r.best_ny = ys[(size_t)(b % nyc)];
+        cand_uv(r.best_nx, r.best_ny, nz, &r.best_u, &r.best_v);
+        r.best_sum = (int64_t)cell_best[(size_t)i];
+        r.best_index = b;
+        r.events = (int64_t)gs->h_cell_count[(size_t)i];
+    }
+    for (long long m = 0; evaluated_out && m < ne; ++m) evaluated_out[m] = (int64_t)evaluated[(size_t)m];
+    if (cell_surface_out) {   // the levels side by side: [cell][ne]
+        long long at = 0;
+        for (size_t l = 0; l < surf.size(); ++l) {
+            const long long cnt = (long long)surf[l].size() / nc;
+            for (long long i = 0; i < nc; ++i)
+                std::copy(surf[l].begin() + i * cnt, surf[l].begin() + (i + 1) * cnt, cell_surface_out + i * ne + at);
+            at += cnt;
+        }
+    }
+    if (info) {
+        memset(info, 0, sizeof(*info));
+        info->n_x = nxc; info->n_y = nyc;
+        info->evaluated = ne;
+        for (int l = 0; l < L; ++l) info->level_count[l] = level_count[l];
+        info->levels_run = L;
     }
     return BF_OK;
 }

@@ -299,17 +299,47 @@ void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, 
 // one batch of nb candidates; `pts` must be all zero (nb planes); < 0: scale above 7 / kernel attributes / LDS.
 // cells null: k_global_fold adds S(k) into S[0 .. nb).  Otherwise k_global_fold_cells folds the same per-event state and
 // k_global_cells_best leaves S(k) = the sum over the cells in S[0 .. nb) (which must be zero before), with cells->k0 the
-// batch's first candidate; nb <= kGlobalCellStride, img_out and scores_out unused.
+// batch's first candidate; nb <= kGlobalCellStride, img_out and scores_out unused.  lattice_k (with cells only): the
+// lattice index of each of the nb slots; k_global_cells_best_lattice then takes k_global_cells_best's place.
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
-                        hipStream_t s);
+                        hipStream_t s, const uint32_t* lattice_k = nullptr);
 // counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
 // events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);
 void launch_global_cell_order(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalCellGrid& cg,
                               const uint32_t* cell_start, uint32_t* cursor, uint32_t* cxy, int32_t* ct, uint32_t* cidx,
                               hipStream_t s);
+// The candidate set of one level of bf_global_search_cells_pyramid (include/bf_accel.h), decided on the device.  The
+// lattice is n_x x n_y points, k = i * n_y + j; a bitmap holds one bit per k (bit k & 31 of word k >> 5).
+struct GlobalLattice {
+    long long n_x, n_y;
+};
+struct GlobalAxis {           // one axis value of the lattice: make_cand's n and k of it
+    double n;
+    float k, pad;
+};
+constexpr uint32_t kGlobalNoCand = 0xffffffffu;   // best_k of a cell before anything was evaluated
+// level 0 without seeds: every (i, j) with i % stride == 0 and j % stride == 0 into `level`
+void launch_global_stride_mark(const GlobalLattice& lt, long long stride, uint32_t* level, hipStream_t s);
+// a window of (2 * radius + 1)^2 points, `stride` lattice steps apart and clipped to the lattice, around the centre of every
+// cell that has events: its running best when best_sum > 0, else its seed (seed null or < 0: none).  Bits of `evaluated`
+// are skipped.
+void launch_global_seed_mark(const GlobalLattice& lt, long long stride, int radius, int n_cells, const uint32_t* cell_start,
+                             const unsigned long long* best_sum, const uint32_t* best_k, const int32_t* seed,
+                             const uint32_t* evaluated, uint32_t* level, hipStream_t s);
+// The level's bitmap into the ascending list of its k, in two steps around the host's read of the count: offs[w] = the
+// bits set below word w (offs has n_words + 1 entries: the last is the count; cnt the same size), then the list, with
+// `evaluated` |= `level` and `level` left zero.  temp: global_scan_temp_bytes(n_words) bytes.
+size_t global_scan_temp_bytes(long long n_words);
+hipError_t launch_global_bitmap_scan(const uint32_t* level, long long n_words, uint32_t* cnt, uint32_t* offs, void* temp,
+                                     size_t temp_bytes, hipStream_t s);
+void launch_global_bitmap_list(uint32_t* level, uint32_t* evaluated, long long n_words, const uint32_t* offs, uint32_t* list,
+                               hipStream_t s);
+// cands[m] = the candidate at lattice point list[m], from the two axis tables (the bits make_cand gives)
+void launch_global_cands_from_lattice(const GlobalLattice& lt, const uint32_t* list, long long m, const GlobalAxis* tab_x,
+                                      const GlobalAxis* tab_y, double nz, GlobalCand* cands, hipStream_t s);
 
 void launch_proj_count(const uint32_t* xy, const float2* p, const uint8_t* noise, long long n, int scale, int res_x,
                        int res_y, int show_final, uint32_t* plane, hipStream_t s);

@@ -313,6 +313,21 @@ public:
         check(bf_global_search_cells(ctx, &o, r, cells ? cells->data() : nullptr, cells ? (int64_t)cells->size() : 0, sp, cap),
               "global_search_cells");
     }
+    // ... over a candidate set decided on the device (bf_global_search_cells_pyramid); seeds: empty, or one lattice index
+    // (or -1) per cell.  evaluated (may be null) is resized to what was evaluated.
+    void global_search_cells_pyramid(const bf_global_search_opts &o, const bf_global_pyramid_opts &p,
+                                     const std::vector<int64_t> &seeds, bf_global_result *r,
+                                     std::vector<bf_global_cell_result> *cells, std::vector<int64_t> *evaluated,
+                                     bf_global_pyramid_info *info) {
+        bf_global_pyramid_info local;
+        if (!info) info = &local;
+        check(bf_global_search_cells_pyramid(ctx, &o, &p, seeds.empty() ? nullptr : seeds.data(), r,
+                                             cells ? cells->data() : nullptr, cells ? (int64_t)cells->size() : 0,
+                                             evaluated ? evaluated->data() : nullptr, evaluated ? (int64_t)evaluated->size() : 0,
+                                             nullptr, 0, info),
+              "global_search_cells_pyramid");
+        if (evaluated) evaluated->resize((size_t)info->evaluated);
+    }
     void global_get_events(double *max_score, double *best_nx, double *best_ny, double *best_pr_x, double *best_pr_y,
                            double *best_u, double *best_v) {
         check(bf_global_get_events(ctx, max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v), "global_get_events");

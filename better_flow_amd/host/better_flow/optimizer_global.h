@@ -14,6 +14,12 @@
 // n_cell_y, height = n_cell_x, per cell float32 horizontal = best_v (columns) then vertical = best_u (rows), and the
 // writer's unknown-flow value 1e9 in both for a cell with events == 0.
 //
+// A fourth: the per-cell search over a candidate set chosen on the device (compute_flow_cells_pyramid: a strided pass over
+// the range's lattice, then windows around every cell's own best; compute_flow_cells_seeded: windows around the previous
+// call's per-cell answers).  The seeds are lattice indices, so they carry from one OptimizerGlobal to the next only through
+// get_seeds / set_seeds, and only over the same search range and cell grid: the grid is anchored at sensor pixel (0, 0), so
+// a cell means the same pixels in every slice.
+//
 // Each object stages its slice on a device context of its OWN (not the thread's shared one that OptimizerLocal and
 // OptimizerRolling use): the window and the per-event best state live there and accumulate over project_all /
 // compute_flow_bruteforce calls, so no other optimiser on the thread may replace them.  Objects are not copyable.
@@ -55,6 +61,28 @@ protected:
     bool cells_staged = false;
     bf_global_cells cell_grid;
     std::vector<bf_global_cell_result> cell_results;                      // [n_cell_x][n_cell_y]
+    std::vector<int64_t> seeds;                                           // per cell: a lattice index or -1 (empty: none)
+    bf_global_pyramid_info pyramid_info;
+
+    void stage_cells() {
+        this->stage();
+        if (!this->cells_staged) {
+            accel.global_set_cells(cells_res_x, cells_res_y, cell_rows, cell_cols, &this->cell_grid);   // (throws before set_cells)
+            this->cells_staged = true;
+        }
+        this->cell_results.assign((size_t)cell_grid.n_cell_x * (size_t)cell_grid.n_cell_y, bf_global_cell_result());
+        this->surface.clear();
+    }
+    void keep_seeds() {   // the answers of the cells that have events seed the next call
+        this->seeds.assign(cell_results.size(), (int64_t)-1);
+        for (size_t i = 0; i < cell_results.size(); ++i)
+            if (cell_results[i].events > 0) this->seeds[i] = cell_results[i].best_index;
+    }
+    void search_pyramid(const bf_global_pyramid_opts &pyramid, const std::vector<int64_t> &from) {   // (after stage_cells)
+        accel.global_search_cells_pyramid(this->range, pyramid, from, &this->result, &this->cell_results, nullptr,
+                                          &this->pyramid_info);
+        this->keep_seeds();
+    }
 
     void stage() {   // the slice goes to the device once; the window resets every event's best state
         if (accel.is_staged()) return;
@@ -80,6 +108,7 @@ protected:
         assert(this->metric_wsize % 2 != 0);
         bf_global_search_opts_default(&this->range);
         memset(&this->result, 0, sizeof(this->result));
+        memset(&this->pyramid_info, 0, sizeof(this->pyramid_info));
         this->last_sum = 0;
         const bool empty = this->events->size() == 0;
         this->scale_img_x = empty ? 0 : (this->events->x_max - this->events->x_min + 1) * this->scale;
@@ -136,15 +165,32 @@ public:
     // compute_flow_bruteforce with the objective kept per cell: the slice's result as there (from the sum over the cells),
     // one result per cell, and the same per-event state.  No surface is kept.
     void compute_flow_cells() {
-        this->stage();
-        if (!this->cells_staged) {
-            accel.global_set_cells(cells_res_x, cells_res_y, cell_rows, cell_cols, &this->cell_grid);   // (throws before set_cells)
-            this->cells_staged = true;
-        }
-        this->cell_results.assign((size_t)cell_grid.n_cell_x * (size_t)cell_grid.n_cell_y, bf_global_cell_result());
-        this->surface.clear();
+        this->stage_cells();
         accel.global_search_cells(this->range, &this->result, &this->cell_results, nullptr);
     }
+
+    // compute_flow_cells over a strided pass and pyramid.levels - 1 refinements (bf_global_search_cells_pyramid without
+    // seeds).  Its answers become the seeds of compute_flow_cells_seeded.
+    void compute_flow_cells_pyramid(const bf_global_pyramid_opts &pyramid) {
+        this->stage_cells();
+        this->search_pyramid(pyramid, std::vector<int64_t>());
+    }
+
+    // pyramid.levels windows around the seeds (the last pyramid / seeded call's per-cell best_index, or set_seeds); without
+    // a seed, the unseeded pyramid.  Keeps its answers as the next seeds.  Throws (BF_ERR_ARG) when no seeded cell has an
+    // event in this slice: clear_seeds() and call again.
+    void compute_flow_cells_seeded(const bf_global_pyramid_opts &pyramid) {
+        this->stage_cells();
+        bool any = false;
+        if (this->seeds.size() == this->cell_results.size())
+            for (size_t i = 0; i < seeds.size(); ++i) any = any || seeds[i] >= 0;
+        this->search_pyramid(pyramid, any ? this->seeds : std::vector<int64_t>());
+    }
+
+    void clear_seeds() { this->seeds.clear(); }
+    const std::vector<int64_t> &get_seeds() const { return seeds; }
+    void set_seeds(const std::vector<int64_t> &s) { this->seeds = s; }   // e.g. the previous slice's OptimizerGlobal::get_seeds
+    const bf_global_pyramid_info &get_pyramid_info() const { return pyramid_info; }
 
     int get_n_cell_x() const { return cell_results.empty() ? 0 : cell_grid.n_cell_x; }
     int get_n_cell_y() const { return cell_results.empty() ? 0 : cell_grid.n_cell_y; }

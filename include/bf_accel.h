@@ -140,8 +140,9 @@ void bf_run_opts_default(bf_run_opts *opts);
 
 /* No reference counterpart (the reference has no foreign-language boundary).
  * sizeof() of bf_model, bf_window, bf_run_opts, bf_run_info, bf_trace_rec, bf_profile,
- * bf_local_window, bf_local_state (in that order) as this library was compiled -- lets a
- * foreign-language binding verify its struct layouts.  Writes min(n, 8) entries; returns 8. */
+ * bf_local_window, bf_local_state, bf_global_pyramid_opts, bf_global_pyramid_info (in that order; later versions add at
+ * the end) as this library was compiled -- lets a foreign-language binding verify its struct layouts.  Writes and returns
+ * min(n, 10) entries: a caller that asks for the first 8 gets 8, as before the last two were added.  out NULL: returns 10. */
 int bf_abi_struct_sizes(int32_t *out, int32_t n);
 
 /* Tuning / test knobs that have no counterpart in the reference (each takes effect at the
@@ -613,6 +614,54 @@ int bf_global_set_cells(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t cell_
 int bf_global_search_cells(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_result *slice_out,
                            bf_global_cell_result *cells_out, int64_t cells_cap, int64_t *cell_surface_out,
                            int64_t cell_surface_cap);
+
+/* Coarse-to-fine and seeded forms of bf_global_search_cells: the candidate set is decided on the device from the per-cell
+ * results instead of being the whole grid.  Definitions of this build ("OptimizerGlobal"):
+ *   - The lattice is what opts describes: x_vals[i], y_vals[j] built by the reference's repeated double addition, n_x x n_y
+ *     points, candidate index k = i * n_y + j (the best_index of bf_global_search_cells), at most 2^26 points.  The value
+ *     of candidate k, and everything computed from it, is exactly what bf_global_search_cells uses for that k; so every
+ *     S(k, cell) computed here is bit for bit an entry of the exhaustive surface over the same opts.
+ *   - levels L in 1..8, factor f >= 2, radius r in 1..64.  Level l has the stride s_l = f^(L-1-l) lattice steps; s_0 must
+ *     not exceed max(n_x, n_y).
+ *   - Level 0 without seeds evaluates every (i, j) with i % s_0 == 0 and j % s_0 == 0.
+ *   - Every other level (and level 0 with seeds) takes each cell that has events and a centre: the cell's running best if
+ *     that best has S > 0, else its seed.  It evaluates the window (i* + a s_l, j* + b s_l), |a|, |b| <= r, clipped to the
+ *     lattice; the level's set is the union over the cells minus everything evaluated before.  A cell without events, a
+ *     cell whose best S is 0 and that has no seed, and a cell seeded -1 contribute nothing.
+ *   - seed_index (may be NULL; one entry per cell, row-major like cells_out) is a lattice k or -1.  With seeds the strided
+ *     pass is skipped: L levels of windows with strides s_0 .. 1.  levels == 1 with seeds is the streaming form: one window
+ *     of +-r lattice steps around the previous slice's best_index.
+ *   - Evaluation order: level by level, ascending k within a level, in batches of at most 32.  The per-event state folds
+ *     in exactly that order with apply_score's strict `>` (evaluation order, not sweep order), continuing from the current
+ *     state.  Every evaluated candidate is folded for every cell and for the slice's S(k).
+ *   - A cell's answer is the evaluated candidate with the largest S(k, cell), the lowest k among equals (the lowest
+ *     evaluated k when all are 0): the exhaustive rule restricted to the evaluated set, whatever the order of the levels.
+ *     The slice's answer comes from the sum over cells by the same rule.
+ *   - levels == 1 without seeds gives every output of bf_global_search_cells over the same opts, bit for bit. */
+typedef struct bf_global_pyramid_opts {
+    int32_t levels, factor, radius;
+} bf_global_pyramid_opts;
+
+typedef struct bf_global_pyramid_info {
+    int64_t n_x, n_y;          /* the lattice */
+    int64_t evaluated;         /* candidates evaluated: the sum of level_count */
+    int64_t level_count[8];    /* candidates of level l (0 beyond levels_run) */
+    int32_t levels_run;
+    int32_t reserved;
+} bf_global_pyramid_info;
+
+/* pyramid NULL: levels 1 (the exhaustive sweep).  Outputs, any of which may be NULL: slice_out; cells_out (cells_cap
+ * entries, [n_cell_x][n_cell_y]); evaluated_out (evaluated_cap entries): the evaluated k in evaluation order;
+ * cell_surface_out (cell_surface_cap entries): S(k, cell) as [cell][info->evaluated], columns in the order of evaluated_out,
+ * at most 2^27 entries; info.  Preconditions and invalidation are those of bf_global_search_cells.  BF_ERR_ARG for what
+ * bf_global_search_cells refuses, levels / factor / radius out of range, a stride beyond the lattice, a seed outside
+ * [-1, n_x * n_y), seeds that leave nothing to evaluate (all -1, or only on cells without events), or a buffer too short
+ * for what a level adds; BF_ERR_CAPACITY for a surface beyond 2^27 entries.  After either code the per-event state is what
+ * it was before the call (a short evaluated_out or surface is found out level by level: the state is put back). */
+int bf_global_search_cells_pyramid(bf_ctx *ctx, const bf_global_search_opts *opts, const bf_global_pyramid_opts *pyramid,
+                                   const int64_t *seed_index, bf_global_result *slice_out, bf_global_cell_result *cells_out,
+                                   int64_t cells_cap, int64_t *evaluated_out, int64_t evaluated_cap, int64_t *cell_surface_out,
+                                   int64_t cell_surface_cap, bf_global_pyramid_info *info);
 
 /* ---- per-event flow table on the device: DVS_flow::get_accumulated (dvs_flow.h:351-389) -----------------------------
  * The -o table (every event once, with the flow of the first slice that solved it) built slice by slice on the device,
