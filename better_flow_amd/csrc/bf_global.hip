@@ -17,8 +17,8 @@
 //       cell order, with S(k, cell) summed per work-group on chip ("OptimizerGlobal").
 //   P   bf_global_search_cells_pyramid: the candidates of a level are chosen on the device from the per-cell bests
 //       (k_global_stride_mark / k_global_seed_mark into a bitmap of the lattice, a popcount-scan-write compaction into the
-//       ascending list of k, k_global_cands_from_lattice), scored by the unchanged G1, G2 and G3c fold, and
-//       k_global_cells_best_lattice keeps each cell's best by (largest S, lowest lattice k).
+//       ascending list of k, k_global_cands_from_lattice), scored by the unchanged G1, G2 and G3c; the batch carries the
+//       lattice k of each slot (GlobalCells::ks), by which k_global_cells_best breaks ties.
 //
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
 // order in which work-groups run.
@@ -166,6 +166,45 @@ __global__ __launch_bounds__(kGT) void k_global_tile(const uint32_t* __restrict_
     }
 }
 
+// The running best of one event (apply_score, event.h:113-121), in registers while a batch is folded.
+struct GlobalBest {
+    double mx = 0, nx = 0, ny = 0, nz = 0, pr_x = 0, pr_y = 0;
+    bool changed = false;
+    __device__ __forceinline__ void load(const GlobalEventState& st, long long e) {
+        mx = st.max_score[e]; nx = st.best_nx[e]; ny = st.best_ny[e]; nz = st.best_nz[e];
+        pr_x = st.best_pr_x[e]; pr_y = st.best_pr_y[e];
+    }
+    __device__ __forceinline__ void store(const GlobalEventState& st, long long e) const {
+        if (!changed) return;
+        st.max_score[e] = mx; st.best_nx[e] = nx; st.best_ny[e] = ny; st.best_nz[e] = nz;
+        st.best_pr_x[e] = pr_x; st.best_pr_y[e] = pr_y;
+    }
+};
+
+// One event (v, ti) under candidate c, slot b of the batch: its window word, the score into the running best, and its
+// return value, the event's share of S: floor(score * 2^32), 0 when the candidate rejects the event.
+__device__ __forceinline__ unsigned long long global_fold_event(const GlobalGeom& g, const GlobalCand& c, int b, uint32_t v,
+                                                                int32_t ti, const uint32_t* __restrict__ win,
+                                                                float* __restrict__ scores_out, GlobalBest& best) {
+    const int off = g.scale / 2 + g.mw / 2;
+    unsigned long long contrib = 0;
+    double pr_x, pr_y;
+    int X, Y;
+    if (global_pixel(g, c, v, ti, pr_x, pr_y, X, Y)) {
+        const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
+        const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
+        const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
+        const float f = (float)score;                                        // current_scores (CV_32FC1)
+        if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
+        if (scores_out) scores_out[(size_t)X * (size_t)g.sy + (size_t)Y] = f;   // the same value from every event there
+        if ((double)f > best.mx) {   // apply_score, event.h:113-121
+            best.mx = f; best.nx = c.nx; best.ny = c.ny; best.nz = c.nz; best.pr_x = pr_x; best.pr_y = pr_y;
+            best.changed = true;
+        }
+    }
+    return contrib;
+}
+
 __global__ __launch_bounds__(kGT) void k_global_fold(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
                                                      const uint32_t* __restrict__ perm, long long n, GlobalGeom g,
                                                      const GlobalCand* __restrict__ cands, int nb,
@@ -176,38 +215,17 @@ __global__ __launch_bounds__(kGT) void k_global_fold(const uint32_t* __restrict_
     const long long e = live ? (perm ? (long long)perm[i] : i) : 0;   // the event's upload index
     uint32_t v = 0;
     int32_t ti = 0;
-    double mx = 0, bnx = 0, bny = 0, bnz = 0, bpx = 0, bpy = 0;
+    GlobalBest best;
     if (live) {
         v = xy[i]; ti = t[i];
-        mx = st.max_score[e]; bnx = st.best_nx[e]; bny = st.best_ny[e]; bnz = st.best_nz[e];
-        bpx = st.best_pr_x[e]; bpy = st.best_pr_y[e];
+        best.load(st, e);
     }
-    bool changed = false;
-    const int off = g.scale / 2 + g.mw / 2;
     for (int b = 0; b < nb; ++b) {
-        const GlobalCand c = cands[b];
-        unsigned long long contrib = 0;
-        double pr_x, pr_y;
-        int X, Y;
-        if (live && global_pixel(g, c, v, ti, pr_x, pr_y, X, Y)) {
-            const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
-            const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
-            const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
-            const float f = (float)score;                                        // current_scores (CV_32FC1)
-            if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
-            if (scores_out) scores_out[(size_t)X * (size_t)g.sy + (size_t)Y] = f;   // the same value from every event there
-            if ((double)f > mx) {   // apply_score, event.h:113-121
-                mx = f; bnx = c.nx; bny = c.ny; bnz = c.nz; bpx = pr_x; bpy = pr_y;
-                changed = true;
-            }
-        }
+        const unsigned long long contrib = live ? global_fold_event(g, cands[b], b, v, ti, win, scores_out, best) : 0;
         const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
         if ((threadIdx.x & 63) == 63 && tot) atomicAdd(&S[b], tot);
     }
-    if (changed) {
-        st.max_score[e] = mx; st.best_nx[e] = bnx; st.best_ny[e] = bny; st.best_nz[e] = bnz;
-        st.best_pr_x[e] = bpx; st.best_pr_y[e] = bpy;
-    }
+    best.store(st, e);
 }
 
 // ---- the per-cell objective S(k, cell) (include/bf_accel.h) ----
@@ -242,7 +260,7 @@ __global__ __launch_bounds__(kGT) void k_global_cell_order(const uint32_t* __res
     cidx[j] = perm ? perm[i] : (uint32_t)i;
 }
 
-// k_global_fold per event (the same window word, score and strict `>`), over a run of at most T events of ONE cell: the
+// k_global_fold per event (the same global_fold_event), over a run of at most T events of ONE cell: the
 // work-group's total of every candidate goes into the batch block [cell][b] with one 64-bit atomic (none when it is 0).
 // T == 64: the wave's total is the work-group's.  T == 256: lane 63 of each wave parks its totals in LDS, and after one
 // barrier thread b adds the four of candidate b.
@@ -258,30 +276,13 @@ __global__ __launch_bounds__(T) void k_global_fold_cells(GlobalCells cl, GlobalG
     long long e = 0;   // the event's upload index
     uint32_t v = 0;
     int32_t ti = 0;
-    double mx = 0, bnx = 0, bny = 0, bnz = 0, bpx = 0, bpy = 0;
+    GlobalBest best;
     if (live) {
         v = cl.xy[j]; ti = cl.t[j]; e = (long long)cl.idx[j];
-        mx = st.max_score[e]; bnx = st.best_nx[e]; bny = st.best_ny[e]; bnz = st.best_nz[e];
-        bpx = st.best_pr_x[e]; bpy = st.best_pr_y[e];
+        best.load(st, e);
     }
-    bool changed = false;
-    const int off = g.scale / 2 + g.mw / 2;
     for (int b = 0; b < nb; ++b) {
-        const GlobalCand c = cands[b];
-        unsigned long long contrib = 0;
-        double pr_x, pr_y;
-        int X, Y;
-        if (live && global_pixel(g, c, v, ti, pr_x, pr_y, X, Y)) {
-            const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
-            const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
-            const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
-            const float f = (float)score;                                        // current_scores (CV_32FC1)
-            if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
-            if ((double)f > mx) {   // apply_score, event.h:113-121
-                mx = f; bnx = c.nx; bny = c.ny; bnz = c.nz; bpx = pr_x; bpy = pr_y;
-                changed = true;
-            }
-        }
+        const unsigned long long contrib = live ? global_fold_event(g, cands[b], b, v, ti, win, nullptr, best) : 0;
         const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
         if ((threadIdx.x & 63) == 63) {
             if (kWaves == 1) {
@@ -291,10 +292,7 @@ __global__ __launch_bounds__(T) void k_global_fold_cells(GlobalCells cl, GlobalG
             }
         }
     }
-    if (changed) {
-        st.max_score[e] = mx; st.best_nx[e] = bnx; st.best_ny[e] = bny; st.best_nz[e] = bnz;
-        st.best_pr_x[e] = bpx; st.best_pr_y[e] = bpy;
-    }
+    best.store(st, e);
     if (kWaves > 1) {
         __syncthreads();
         if ((int)threadIdx.x < nb) {
@@ -306,50 +304,21 @@ __global__ __launch_bounds__(T) void k_global_fold_cells(GlobalCells cl, GlobalG
     }
 }
 
-// One batch's block [cell][b], kGlobalCellStride threads per cell (8 cells per work-group): the first largest of the
-// cell's nb sums (largest value, then lowest b: what folding them in order with strict `>` picks) folds into the
-// cell's running best with strict `>`; the surface gets its copy; the block is left zero for the next batch; and the
-// batch's S(k) = the sum over cells: over the work-group's 8 cells in LDS, then one integer atomic per candidate.
+// One batch's block [cell][b], kGlobalCellStride threads per cell (8 cells per work-group).  Slot b is lattice point
+// k = ks[b], or k0 + b without a list.  The cell's best of the batch is its largest sum, lowest k among equals, and it
+// replaces the running best when it is larger, or as large with a lower k: the exhaustive rule (largest S, then lowest k)
+// over whatever has been evaluated, in any order.  The surface column [cell][k0 + b] gets its copy, the block is left
+// zero for the next batch, and the batch's S(k) = the sum over cells: over the work-group's 8 cells in LDS, then one
+// integer atomic per candidate.
+//
+// On an ascending sweep (bf_global_search_cells: k0 = 0, 32, ...) this is folding the sums in order with strict `>`:
+//   - inside a batch k rises with b, so "lowest k among equals" is the first largest.  A lane past nb carries sum 0 and
+//     kGlobalNoCand, above every k (< 2^26): it loses a tie against any live lane, and lane 0 is always live (nb >= 1),
+//     so the winner's k is a candidate's;
+//   - every k of a later batch exceeds the running best_k, so an equal sum never replaces it: only a larger one does;
+//   - best_k starts at kGlobalNoCand and best_sum at 0, so the first batch always sets best_k: to its first largest, which
+//     for a cell without events, or whose sums are all zero, is k 0 -- and all later zeros leave it there.
 __global__ __launch_bounds__(kGT) void k_global_cells_best(GlobalCells cl, int nb, unsigned long long* __restrict__ S) {
-    constexpr int kCellsPerGroup = kGT / kGlobalCellStride;
-    __shared__ unsigned long long s_v[kGT];
-    const int b = threadIdx.x % kGlobalCellStride;
-    const long long cell = (long long)blockIdx.x * kCellsPerGroup + threadIdx.x / kGlobalCellStride;
-    const bool live = cell < cl.n_cells && b < nb;
-    unsigned long long v = 0;
-    if (live) {
-        unsigned long long* p = cl.block + (size_t)cell * kGlobalCellStride + b;
-        v = *p;
-        if (v) *p = 0;
-        if (cl.surface) cl.surface[(size_t)cell * (size_t)cl.n_cand + (size_t)(cl.k0 + b)] = (long long)v;
-    }
-    s_v[threadIdx.x] = v;
-    int at = b;
-    for (int d = kGlobalCellStride / 2; d > 0; d >>= 1) {   // (the 32 lanes of a cell are one half of a wave)
-        const unsigned long long ov = __shfl_xor(v, d, kGlobalCellStride);
-        const int oat = __shfl_xor(at, d, kGlobalCellStride);
-        if (ov > v || (ov == v && oat < at)) { v = ov; at = oat; }
-    }
-    if (b == 0 && cell < cl.n_cells && v > cl.best_sum[cell]) {
-        cl.best_sum[cell] = v;
-        cl.best_k[cell] = (uint32_t)(cl.k0 + at);
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < nb) {
-        unsigned long long tot = 0;
-#pragma unroll
-        for (int c = 0; c < kCellsPerGroup; ++c) tot += s_v[c * kGlobalCellStride + threadIdx.x];
-        if (tot) atomicAdd(&S[threadIdx.x], tot);
-    }
-}
-
-// k_global_cells_best for a batch whose slots are arbitrary lattice points (ks[b] = the lattice k of slot b): the cell's
-// best of the batch is its largest sum, lowest k among equals, and it replaces the running best when it is larger, or as
-// large with a lower k -- the exhaustive rule over whatever has been evaluated, in any order.  best_k starts at
-// kGlobalNoCand, so the first batch always sets it.  The surface column goes to [cell][k0 + b] of a surface n_cand wide
-// (the level's list), the block is zeroed and S summed as in k_global_cells_best.
-__global__ __launch_bounds__(kGT) void k_global_cells_best_lattice(GlobalCells cl, int nb, const uint32_t* __restrict__ ks,
-                                                                   unsigned long long* __restrict__ S) {
     constexpr int kCellsPerGroup = kGT / kGlobalCellStride;
     __shared__ unsigned long long s_v[kGT];
     const int b = threadIdx.x % kGlobalCellStride;
@@ -361,7 +330,7 @@ __global__ __launch_bounds__(kGT) void k_global_cells_best_lattice(GlobalCells c
         unsigned long long* p = cl.block + (size_t)cell * kGlobalCellStride + b;
         v = *p;
         if (v) *p = 0;
-        k = ks[b];
+        k = cl.ks ? cl.ks[b] : (uint32_t)(cl.k0 + b);
         if (cl.surface) cl.surface[(size_t)cell * (size_t)cl.n_cand + (size_t)(cl.k0 + b)] = (long long)v;
     }
     s_v[threadIdx.x] = v;
@@ -370,7 +339,7 @@ __global__ __launch_bounds__(kGT) void k_global_cells_best_lattice(GlobalCells c
         const uint32_t ok = __shfl_xor(k, d, kGlobalCellStride);
         if (ov > v || (ov == v && ok < k)) { v = ov; k = ok; }
     }
-    if (b == 0 && cell < cl.n_cells && k != kGlobalNoCand) {
+    if (b == 0 && cell < cl.n_cells) {
         const unsigned long long bv = cl.best_sum[cell];
         if (v > bv || (v == bv && k < cl.best_k[cell])) {
             cl.best_sum[cell] = v;
@@ -492,7 +461,7 @@ void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, 
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
-                        hipStream_t s, const uint32_t* lattice_k) {
+                        hipStream_t s) {
     if (nb <= 0 || n <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
     if (g.scale / 2 > 3) return -1;
     if (cells && nb > kGlobalCellStride) return -1;
@@ -516,10 +485,7 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
         hipLaunchKernelGGL(k_global_fold_cells<kGT>, dim3((unsigned)cells->n_runs), dim3(kGT), 0, s, *cells, g, cands, nb, win, st);
     constexpr int per = kGT / kGlobalCellStride;
     const dim3 cgrid((unsigned)((cells->n_cells + per - 1) / per));
-    if (lattice_k)
-        hipLaunchKernelGGL(k_global_cells_best_lattice, cgrid, dim3(kGT), 0, s, *cells, nb, lattice_k, S);
-    else
-        hipLaunchKernelGGL(k_global_cells_best, cgrid, dim3(kGT), 0, s, *cells, nb, S);
+    hipLaunchKernelGGL(k_global_cells_best, cgrid, dim3(kGT), 0, s, *cells, nb, S);
     return 0;
 }
 

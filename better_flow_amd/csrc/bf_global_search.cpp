@@ -6,6 +6,7 @@
 #include "bf_ctx.h"
 
 struct GlobalSearch {
+    // the window of bf_global_set_window, the per-event state and the buffers of one batch of candidates
     bf_global_window w;
     bool have = false;
     long long n = 0;                        // events of the slice the window was set on
@@ -18,27 +19,31 @@ struct GlobalSearch {
     DevArray<float> d_scores;
     std::vector<GlobalCand> h_cands;
 
-    // the cell grid of bf_global_set_cells (cleared by bf_global_set_window)
-    bool have_cells = false;
-    bf_global_cells cells;
-    GlobalCellGrid cg;
-    int run_len = 0;
-    std::vector<uint32_t> h_cell_count;                                // events per cell
-    DevArray<uint32_t> d_cell_count, d_cell_start, d_cxy, d_cidx;      // (d_cell_count: the sort's counts, then its cursors)
-    DevArray<int32_t> d_ct;
-    DevArray<uint32_t> d_run_cell, d_run_start;
-    long long n_runs = 0;
-    DevArray<unsigned long long> d_cell_block, d_cell_best;
-    DevArray<uint32_t> d_cell_best_k;
-    DevArray<long long> d_cell_surface;
+    // the cell grid of bf_global_set_cells: valid while `have` (bf_global_set_window clears it)
+    struct Cells {
+        bool have = false;
+        GlobalCellGrid cg;
+        int run_len = 0;
+        long long n_runs = 0;
+        std::vector<uint32_t> h_count;                         // events per cell
+        DevArray<uint32_t> d_count, d_start, d_cxy, d_cidx;    // (d_count: the sort's counts, then its cursors)
+        DevArray<int32_t> d_ct;
+        DevArray<uint32_t> d_run_cell, d_run_start;
+        DevArray<unsigned long long> d_block, d_best;
+        DevArray<uint32_t> d_best_k;
+        DevArray<long long> d_surface;
+    } cells;
 
-    // bf_global_search_cells_pyramid: the lattice bitmaps (one bit per k), the compaction's scratch, the level's list of k,
-    // the axis tables and the seeds; d_state_save holds the per-event state while a call may still fail for a short buffer
-    DevArray<uint32_t> d_bm_eval, d_bm_level, d_bm_cnt, d_bm_offs, d_level_k;
-    DevArray<uint8_t> d_scan_tmp;
-    DevArray<GlobalAxis> d_tab_x, d_tab_y;
-    DevArray<int32_t> d_seed;
-    DevArray<double> d_state_save;
+    // scratch of one bf_global_search_cells_pyramid call: the lattice bitmaps (one bit per k), the compaction's scratch,
+    // the level's list of k, the axis tables and the seeds; d_state_save holds the per-event state while the call may
+    // still fail for a short buffer
+    struct Pyramid {
+        DevArray<uint32_t> d_bm_eval, d_bm_level, d_bm_cnt, d_bm_offs, d_level_k;
+        DevArray<uint8_t> d_scan_tmp;
+        DevArray<GlobalAxis> d_tab_x, d_tab_y;
+        DevArray<int32_t> d_seed;
+        DevArray<double> d_state_save;
+    } pyr;
 
     GlobalEventState state() const {
         GlobalEventState s;
@@ -90,11 +95,9 @@ int global_ready(bf_ctx* c) {
     return BF_OK;
 }
 
-// candidates [k0, k0 + k) of gs->h_cands, already on the device at d_cands + k0: S into d_S + k0, folded into the state.
-// cells (may be null): the per-cell form of the fold, batch after batch in sweep order
-// lattice_k (with cells): the lattice index of each of the k candidates, on the device (the pyramid's best-of-batch rule)
-int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8_t* d_img, float* d_scores,
-                   GlobalCells* cells = nullptr, const uint32_t* lattice_k = nullptr) {
+// the k candidates at d_cands: S into d_S, folded into the per-event state.
+// cells (may be null): the per-cell form of the fold, batch after batch; its k0 and ks advance with the batches
+int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k, uint8_t* d_img, float* d_scores, GlobalCells* cells = nullptr) {
     if (gs->n <= 0) return BF_OK;   // no event: every S stays 0
     static_assert(kGlobalMaxBatch <= kGlobalCellStride, "a batch must fit the cell block");
     const int B = (int)std::max(1ll, std::min((long long)kGlobalMaxBatch, kGlobalBatchBytes / (gs->g.plane * 8)));
@@ -105,16 +108,62 @@ int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k0, long long k, uint8
     for (long long b0 = 0; b0 < k; b0 += B) {
         const int nb = (int)std::min((long long)B, k - b0);
         HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)nb * (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
-        if (cells) cells->k0 = k0 + b0;
-        const int lr = launch_global_batch(e.xy, e.t, perm, gs->n, gs->g, gs->d_cands + k0 + b0, nb, gs->d_pts, gs->d_win,
-                                           d_img, gs->state(), gs->d_S + k0 + b0, d_scores, cells, c->stream,
-                                           lattice_k ? lattice_k + k0 + b0 : nullptr);
+        const int lr = launch_global_batch(e.xy, e.t, perm, gs->n, gs->g, gs->d_cands + b0, nb, gs->d_pts, gs->d_win, d_img,
+                                           gs->state(), gs->d_S + b0, d_scores, cells, c->stream);
         if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
         if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
         if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
         HIP_TRY(c, hipGetLastError());
+        if (cells) {
+            cells->k0 += nb;
+            if (cells->ks) cells->ks += nb;
+        }
     }
     return BF_OK;
+}
+
+// The device's view of the cell grid for a sweep of n_cand candidates, at its first batch.
+// surface: null, or [n_cells][n_cand] on the device; ks: null, or the lattice k of each candidate
+GlobalCells cells_view(const GlobalSearch* gs, long long* surface, long long n_cand, const uint32_t* ks = nullptr) {
+    const GlobalSearch::Cells& cs = gs->cells;
+    GlobalCells cl;
+    cl.xy = cs.d_cxy; cl.t = cs.d_ct; cl.idx = cs.d_cidx;
+    cl.cell_start = cs.d_start; cl.run_cell = cs.d_run_cell; cl.run_start = cs.d_run_start;
+    cl.n_runs = (int32_t)cs.n_runs; cl.run_len = cs.run_len; cl.n_cells = cs.cg.n_cells;
+    cl.block = cs.d_block; cl.best_sum = cs.d_best; cl.best_k = cs.d_best_k;
+    cl.surface = surface; cl.n_cand = n_cand; cl.k0 = 0; cl.ks = ks;
+    return cl;
+}
+
+// before a search: the batch block zero, no cell has a best
+int reset_cell_bests(bf_ctx* c, GlobalSearch* gs) {
+    const size_t nc = (size_t)gs->cells.cg.n_cells;
+    HIP_TRY(c, hipMemsetAsync(gs->cells.d_block, 0, nc * kGlobalCellStride * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(gs->cells.d_best, 0, nc * sizeof(unsigned long long), c->stream));
+    HIP_TRY(c, hipMemsetAsync(gs->cells.d_best_k, 0xff, nc * sizeof(uint32_t), c->stream));   // kGlobalNoCand
+    return BF_OK;
+}
+
+// The caller's buffers (each may be null: not checked) against nc cells and a surface of nc x k entries.
+// at_least: more candidates may follow (the levels of the pyramid)
+int check_cell_buffers(bf_ctx* c, long long nc, long long k, const void* cells_out, int64_t cells_cap, const void* surface_out,
+                       int64_t surface_cap, const char* at_least = "") {
+    if (cells_out && cells_cap < nc) return fail(c, BF_ERR_ARG, "cell buffer holds %lld of %lld", (long long)cells_cap, nc);
+    if (surface_out) {
+        if (nc * k > kGlobalMaxCellSurface)
+            return fail(c, BF_ERR_CAPACITY, "a surface of %lld cells x %lld candidates has more than 2^27 entries", nc, k);
+        if (surface_cap < nc * k)
+            return fail(c, BF_ERR_ARG, "cell surface buffer holds %lld of %s%lld", (long long)surface_cap, at_least, nc * k);
+    }
+    return BF_OK;
+}
+
+// the largest S; among equals the lowest key (null: the index itself, so the first of the largest)
+long long best_of_S(const std::vector<unsigned long long>& S, const uint32_t* key = nullptr) {
+    long long best = 0;
+    for (long long m = 1; m < (long long)S.size(); ++m)
+        if (S[(size_t)m] > S[(size_t)best] || (key && S[(size_t)m] == S[(size_t)best] && key[m] < key[best])) best = m;
+    return best;
 }
 
 // The checks of a sweep and its candidate values: opts (NULL: the defaults) validated, the window ready, then the
@@ -163,6 +212,33 @@ void cand_uv(double nx, double ny, double nz, double* u, double* v) {
     *v = xy_len == 0 ? 0 : speed * ny / xy_len;
 }
 
+// lattice point k (nx outer, ny inner) and its S as the slice's answer
+void write_result(bf_global_result* out, const std::vector<double>& xs, const std::vector<double>& ys, long long k,
+                  unsigned long long sum) {
+    if (!out) return;
+    const long long nyc = (long long)ys.size();
+    out->best_nx = xs[(size_t)(k / nyc)];
+    out->best_ny = ys[(size_t)(k % nyc)];
+    out->best_sum = (int64_t)sum;
+    out->n_x = (int64_t)xs.size();
+    out->n_y = nyc;
+}
+
+void write_cells(bf_global_cell_result* out, const GlobalSearch* gs, const std::vector<double>& xs, const std::vector<double>& ys,
+                 double nz, const std::vector<uint32_t>& cell_k, const std::vector<unsigned long long>& cell_best) {
+    const long long nyc = (long long)ys.size();
+    for (size_t i = 0; out && i < cell_k.size(); ++i) {
+        bf_global_cell_result& r = out[i];
+        const long long b = (long long)cell_k[i];
+        r.best_nx = xs[(size_t)(b / nyc)];
+        r.best_ny = ys[(size_t)(b % nyc)];
+        cand_uv(r.best_nx, r.best_ny, nz, &r.best_u, &r.best_v);
+        r.best_sum = (int64_t)cell_best[i];
+        r.best_index = b;
+        r.events = (int64_t)gs->cells.h_count[i];
+    }
+}
+
 }  // namespace
 
 void bf_global_search_opts_default(bf_global_search_opts* o) {
@@ -204,7 +280,7 @@ int bf_global_set_window(bf_ctx* c, int32_t scale, int32_t metric_wsize, bf_glob
     if (!c->glob) c->glob.reset(new GlobalSearch());
     GlobalSearch* gs = c->glob.get();
     gs->have = false;
-    gs->have_cells = false;
+    gs->cells.have = false;
     c->glob_valid = false;
     HIP_TRY(c, gs->d_state.grow((size_t)c->cap_events * 6));   // (n <= cap_events: one allocation for every slice)
     GlobalGeom& g = gs->g;
@@ -242,7 +318,7 @@ int bf_global_project_all(bf_ctx* c, double nx, double ny, double nz, uint8_t* i
     HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, sizeof(unsigned long long), c->stream));
     if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
     if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
-    if ((rc = run_candidates(c, gs, 0, 1, img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr)) != BF_OK)
+    if ((rc = run_candidates(c, gs, 1, img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr)) != BF_OK)
         return rc;
     unsigned long long S = 0;
     HIP_TRY(c, hipMemcpyAsync(&S, gs->d_S, sizeof(S), hipMemcpyDeviceToHost, c->stream));
@@ -261,27 +337,19 @@ int bf_global_search(bf_ctx* c, const bf_global_search_opts* opts, bf_global_res
     double nz = 0;
     int rc = sweep_grid(c, opts, xs, ys, nz);
     if (rc != BF_OK) return rc;
-    const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), k = nxc * nyc;
+    const long long k = (long long)xs.size() * (long long)ys.size();
     if (surface_out && surface_cap < k) return fail(c, BF_ERR_ARG, "surface buffer holds %lld of %lld", (long long)surface_cap, k);
     HIP_TRY(c, hipSetDevice(c->device));
     GlobalSearch* gs = c->glob.get();
     if ((rc = upload_cands(c, gs, xs, ys, nz)) != BF_OK) return rc;
-    if ((rc = run_candidates(c, gs, 0, k, nullptr, nullptr)) != BF_OK) return rc;
+    if ((rc = run_candidates(c, gs, k, nullptr, nullptr)) != BF_OK) return rc;
     std::vector<unsigned long long> S((size_t)k);
     HIP_TRY(c, hipMemcpyAsync(S.data(), gs->d_S, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    long long best = 0;
-    for (long long i = 1; i < k; ++i)
-        if (S[(size_t)i] > S[(size_t)best]) best = i;   // the first of the largest
     if (surface_out)
         for (long long i = 0; i < k; ++i) surface_out[i] = (int64_t)S[(size_t)i];
-    if (out) {
-        out->best_nx = xs[(size_t)(best / nyc)];
-        out->best_ny = ys[(size_t)(best % nyc)];
-        out->best_sum = (int64_t)S[(size_t)best];
-        out->n_x = nxc;
-        out->n_y = nyc;
-    }
+    const long long best = best_of_S(S);
+    write_result(out, xs, ys, best, S[(size_t)best]);
     return BF_OK;
 }
 
@@ -290,7 +358,8 @@ int bf_global_set_cells(bf_ctx* c, int32_t res_x, int32_t res_y, int32_t cell_ro
     int rc = global_ready(c);
     if (rc != BF_OK) return rc;
     GlobalSearch* gs = c->glob.get();
-    gs->have_cells = false;
+    GlobalSearch::Cells& cs = gs->cells;
+    cs.have = false;
     if (res_x <= 0 || res_y <= 0 || cell_rows <= 0 || cell_cols <= 0)
         return fail(c, BF_ERR_ARG, "sensor %d x %d, cells %d x %d: every size must be positive", res_x, res_y, cell_rows, cell_cols);
     if (gs->n > 0 && (gs->w.x_max >= res_x || gs->w.y_max >= res_y))   // (addresses are unsigned: x_min, y_min >= 0)
@@ -301,26 +370,26 @@ int bf_global_set_cells(bf_ctx* c, int32_t res_x, int32_t res_y, int32_t cell_ro
     const long long nc = (long long)gc.n_cell_x * gc.n_cell_y;
     if (nc > kGlobalMaxCells) return fail(c, BF_ERR_ARG, "%lld cells (more than 65536)", nc);
     HIP_TRY(c, hipSetDevice(c->device));
-    GlobalCellGrid& cg = gs->cg;
+    GlobalCellGrid& cg = cs.cg;
     cg.cell_rows = cell_rows; cg.cell_cols = cell_cols; cg.n_cell_y = gc.n_cell_y; cg.n_cells = (int32_t)nc;
-    gs->h_cell_count.assign((size_t)nc, 0u);
-    gs->n_runs = 0;
-    gs->run_len = 64;
-    HIP_TRY(c, gs->d_cell_block.grow((size_t)nc * kGlobalCellStride));
-    HIP_TRY(c, gs->d_cell_best.grow((size_t)nc));
-    HIP_TRY(c, gs->d_cell_best_k.grow((size_t)nc));
+    cs.h_count.assign((size_t)nc, 0u);
+    cs.n_runs = 0;
+    cs.run_len = 64;
+    HIP_TRY(c, cs.d_block.grow((size_t)nc * kGlobalCellStride));
+    HIP_TRY(c, cs.d_best.grow((size_t)nc));
+    HIP_TRY(c, cs.d_best_k.grow((size_t)nc));
     if (gs->n > 0) {
         const size_t n = (size_t)gs->n;
         const bf_ctx::EvSet& e = c->set[c->cs];
-        HIP_TRY(c, gs->d_cell_count.grow((size_t)nc));
-        HIP_TRY(c, gs->d_cell_start.grow((size_t)nc + 1));
-        HIP_TRY(c, gs->d_cxy.grow(n));
-        HIP_TRY(c, gs->d_ct.grow(n));
-        HIP_TRY(c, gs->d_cidx.grow(n));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_count, 0, (size_t)nc * sizeof(uint32_t), c->stream));
-        launch_global_cell_count(e.xy, gs->n, cg, gs->d_cell_count, c->stream);
+        HIP_TRY(c, cs.d_count.grow((size_t)nc));
+        HIP_TRY(c, cs.d_start.grow((size_t)nc + 1));
+        HIP_TRY(c, cs.d_cxy.grow(n));
+        HIP_TRY(c, cs.d_ct.grow(n));
+        HIP_TRY(c, cs.d_cidx.grow(n));
+        HIP_TRY(c, hipMemsetAsync(cs.d_count, 0, (size_t)nc * sizeof(uint32_t), c->stream));
+        launch_global_cell_count(e.xy, gs->n, cg, cs.d_count, c->stream);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(gs->h_cell_count.data(), gs->d_cell_count, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost,
+        HIP_TRY(c, hipMemcpyAsync(cs.h_count.data(), cs.d_count, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                   c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         // the scan, and the runs: a cell of m events is cut into ceil(m / run_len) work-groups.  Work-groups of one wave
@@ -328,32 +397,31 @@ int bf_global_set_cells(bf_ctx* c, int32_t res_x, int32_t res_y, int32_t cell_ro
         std::vector<uint32_t> start((size_t)nc + 1, 0u);
         long long occupied = 0;
         for (long long i = 0; i < nc; ++i) {
-            start[(size_t)i + 1] = start[(size_t)i] + gs->h_cell_count[(size_t)i];
-            occupied += gs->h_cell_count[(size_t)i] != 0u;
+            start[(size_t)i + 1] = start[(size_t)i] + cs.h_count[(size_t)i];
+            occupied += cs.h_count[(size_t)i] != 0u;
         }
         if ((long long)start[(size_t)nc] != gs->n) return fail(c, BF_ERR_HIP, "bf_global_set_cells: the cell counts do not add up");
-        gs->run_len = gs->n >= 256 * occupied ? 256 : 64;
+        cs.run_len = gs->n >= 256 * occupied ? 256 : 64;
         std::vector<uint32_t> run_cell, run_start;
         for (long long i = 0; i < nc; ++i)
-            for (uint32_t s = start[(size_t)i]; s < start[(size_t)i + 1]; s += (uint32_t)gs->run_len) {
+            for (uint32_t s = start[(size_t)i]; s < start[(size_t)i + 1]; s += (uint32_t)cs.run_len) {
                 run_cell.push_back((uint32_t)i);
                 run_start.push_back(s);
             }
-        gs->n_runs = (long long)run_cell.size();
-        HIP_TRY(c, gs->d_run_cell.grow(run_cell.size()));
-        HIP_TRY(c, gs->d_run_start.grow(run_start.size()));
-        HIP_TRY(c, hipMemcpyAsync(gs->d_cell_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(gs->d_run_cell, run_cell.data(), run_cell.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(gs->d_run_start, run_start.data(), run_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
+        cs.n_runs = (long long)run_cell.size();
+        HIP_TRY(c, cs.d_run_cell.grow(run_cell.size()));
+        HIP_TRY(c, cs.d_run_start.grow(run_start.size()));
+        HIP_TRY(c, hipMemcpyAsync(cs.d_start, start.data(), start.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cs.d_run_cell, run_cell.data(), run_cell.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cs.d_run_start, run_start.data(), run_start.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
                                   c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_count, 0, (size_t)nc * sizeof(uint32_t), c->stream));
-        launch_global_cell_order(e.xy, e.t, c->has_perm ? e.perm : nullptr, gs->n, cg, gs->d_cell_start, gs->d_cell_count, gs->d_cxy,
-                                 gs->d_ct, gs->d_cidx, c->stream);
+        HIP_TRY(c, hipMemsetAsync(cs.d_count, 0, (size_t)nc * sizeof(uint32_t), c->stream));
+        launch_global_cell_order(e.xy, e.t, c->has_perm ? e.perm : nullptr, gs->n, cg, cs.d_start, cs.d_count, cs.d_cxy,
+                                 cs.d_ct, cs.d_cidx, c->stream);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the host vectors above are read until here)
     }
-    gs->cells = gc;
-    gs->have_cells = true;
+    cs.have = true;
     if (out) *out = gc;
     return BF_OK;
 }
@@ -367,64 +435,33 @@ int bf_global_search_cells(bf_ctx* c, const bf_global_search_opts* opts, bf_glob
     int rc = sweep_grid(c, opts, xs, ys, nz);
     if (rc != BF_OK) return rc;
     GlobalSearch* gs = c->glob.get();
-    if (!gs->have_cells) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
-    const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), k = nxc * nyc;
-    const long long nc = gs->cg.n_cells;
-    if (cells_out && cells_cap < nc) return fail(c, BF_ERR_ARG, "cell buffer holds %lld of %lld", (long long)cells_cap, nc);
-    if (cell_surface_out) {
-        if (nc * k > kGlobalMaxCellSurface)
-            return fail(c, BF_ERR_CAPACITY, "a surface of %lld cells x %lld candidates has more than 2^27 entries", nc, k);
-        if (cell_surface_cap < nc * k)
-            return fail(c, BF_ERR_ARG, "cell surface buffer holds %lld of %lld", (long long)cell_surface_cap, nc * k);
-    }
+    if (!gs->cells.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    const long long k = (long long)xs.size() * (long long)ys.size();
+    const long long nc = gs->cells.cg.n_cells;
+    if ((rc = check_cell_buffers(c, nc, k, cells_out, cells_cap, cell_surface_out, cell_surface_cap)) != BF_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = upload_cands(c, gs, xs, ys, nz)) != BF_OK) return rc;
     std::vector<unsigned long long> S((size_t)k, 0ull), cell_best((size_t)nc, 0ull);
     std::vector<uint32_t> cell_k((size_t)nc, 0u);
     if (gs->n > 0) {   // (no event: nothing is launched, every S(k, cell) is 0)
-        if (cell_surface_out) HIP_TRY(c, gs->d_cell_surface.grow((size_t)(nc * k)));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_block, 0, (size_t)nc * kGlobalCellStride * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best_k, 0, (size_t)nc * sizeof(uint32_t), c->stream));
-        GlobalCells cl;
-        cl.xy = gs->d_cxy; cl.t = gs->d_ct; cl.idx = gs->d_cidx;
-        cl.cell_start = gs->d_cell_start; cl.run_cell = gs->d_run_cell; cl.run_start = gs->d_run_start;
-        cl.n_runs = (int32_t)gs->n_runs; cl.run_len = gs->run_len; cl.n_cells = (int32_t)nc;
-        cl.block = gs->d_cell_block; cl.best_sum = gs->d_cell_best; cl.best_k = gs->d_cell_best_k;
-        cl.surface = cell_surface_out ? gs->d_cell_surface.get() : nullptr;
-        cl.n_cand = k; cl.k0 = 0;
-        if ((rc = run_candidates(c, gs, 0, k, nullptr, nullptr, &cl)) != BF_OK) return rc;
+        DevArray<long long>& d_surface = gs->cells.d_surface;
+        if (cell_surface_out) HIP_TRY(c, d_surface.grow((size_t)(nc * k)));
+        if ((rc = reset_cell_bests(c, gs)) != BF_OK) return rc;
+        GlobalCells cl = cells_view(gs, cell_surface_out ? d_surface.get() : nullptr, k);
+        if ((rc = run_candidates(c, gs, k, nullptr, nullptr, &cl)) != BF_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(S.data(), gs->d_S, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cell_best.data(), gs->d_cell_best, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+        HIP_TRY(c, hipMemcpyAsync(cell_best.data(), gs->cells.d_best, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                   c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cell_k.data(), gs->d_cell_best_k, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cell_k.data(), gs->cells.d_best_k, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if (cell_surface_out)
-            HIP_TRY(c, hipMemcpyAsync(cell_surface_out, gs->d_cell_surface, (size_t)(nc * k) * sizeof(int64_t), hipMemcpyDeviceToHost,
-                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(cell_surface_out, d_surface, (size_t)(nc * k) * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     } else if (cell_surface_out) {
         std::fill(cell_surface_out, cell_surface_out + nc * k, (int64_t)0);
     }
-    if (slice_out) {
-        long long best = 0;
-        for (long long i = 1; i < k; ++i)
-            if (S[(size_t)i] > S[(size_t)best]) best = i;   // the first of the largest
-        slice_out->best_nx = xs[(size_t)(best / nyc)];
-        slice_out->best_ny = ys[(size_t)(best % nyc)];
-        slice_out->best_sum = (int64_t)S[(size_t)best];
-        slice_out->n_x = nxc;
-        slice_out->n_y = nyc;
-    }
-    for (long long i = 0; cells_out && i < nc; ++i) {
-        bf_global_cell_result& r = cells_out[i];
-        const long long b = (long long)cell_k[(size_t)i];
-        r.best_nx = xs[(size_t)(b / nyc)];
-        r.best_ny = ys[(size_t)(b % nyc)];
-        cand_uv(r.best_nx, r.best_ny, nz, &r.best_u, &r.best_v);
-        r.best_sum = (int64_t)cell_best[(size_t)i];
-        r.best_index = b;
-        r.events = (int64_t)gs->h_cell_count[(size_t)i];
-    }
+    const long long best = best_of_S(S);
+    write_result(slice_out, xs, ys, best, S[(size_t)best]);
+    write_cells(cells_out, gs, xs, ys, nz, cell_k, cell_best);
     return BF_OK;
 }
 
@@ -444,9 +481,9 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
     int rc = sweep_grid(c, opts, xs, ys, nz);
     if (rc != BF_OK) return rc;
     GlobalSearch* gs = c->glob.get();
-    if (!gs->have_cells) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    if (!gs->cells.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
     const long long nxc = (long long)xs.size(), nyc = (long long)ys.size(), K = nxc * nyc;
-    const long long nc = gs->cg.n_cells;
+    const long long nc = gs->cells.cg.n_cells;
     const int L = po.levels;
     long long stride[8];
     stride[L - 1] = 1;
@@ -455,7 +492,7 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
         if (stride[l] > std::max(nxc, nyc))
             return fail(c, BF_ERR_ARG, "the stride of level %d (%d^%d) exceeds the %lld x %lld lattice", l, po.factor, L - 1 - l, nxc, nyc);
     }
-    if (cells_out && cells_cap < nc) return fail(c, BF_ERR_ARG, "cell buffer holds %lld of %lld", (long long)cells_cap, nc);
+    if ((rc = check_cell_buffers(c, nc, 0, cells_out, cells_cap, nullptr, 0)) != BF_OK) return rc;
     const bool seeded = seed_index != nullptr;
     std::vector<int32_t> h_seed;
     if (seeded) {
@@ -465,7 +502,7 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
             if (seed_index[i] < -1 || seed_index[i] >= K)
                 return fail(c, BF_ERR_ARG, "seed %lld of cell %lld is outside the lattice of %lld", (long long)seed_index[i], i, K);
             h_seed[(size_t)i] = (int32_t)seed_index[i];
-            any = any || (seed_index[i] >= 0 && gs->h_cell_count[(size_t)i] != 0u);
+            any = any || (seed_index[i] >= 0 && gs->cells.h_count[(size_t)i] != 0u);
         }
         if (!any) return fail(c, BF_ERR_ARG, "the seeds leave nothing to evaluate (no cell has both events and a seed)");
     }
@@ -482,13 +519,7 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
         const long long tot = (long long)evaluated.size() + cnt;
         if (evaluated_out && evaluated_cap < tot)
             return fail(c, BF_ERR_ARG, "evaluated buffer holds %lld of at least %lld", (long long)evaluated_cap, tot);
-        if (cell_surface_out) {
-            if (nc * tot > kGlobalMaxCellSurface)
-                return fail(c, BF_ERR_CAPACITY, "a surface of %lld cells x %lld candidates has more than 2^27 entries", nc, tot);
-            if (cell_surface_cap < nc * tot)
-                return fail(c, BF_ERR_ARG, "cell surface buffer holds %lld of at least %lld", (long long)cell_surface_cap, nc * tot);
-        }
-        return BF_OK;
+        return check_cell_buffers(c, nc, tot, nullptr, 0, cell_surface_out, cell_surface_cap, "at least ");
     };
     if (gs->n <= 0) {
         // no event: nothing is launched.  No cell has a centre, so only the strided pass evaluates, and every S is 0
@@ -503,14 +534,16 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
     } else {
         const long long n_words = (K + 31) / 32;
         const GlobalLattice lt{nxc, nyc};
-        HIP_TRY(c, gs->d_bm_eval.grow((size_t)n_words));
-        HIP_TRY(c, gs->d_bm_level.grow((size_t)n_words));
-        HIP_TRY(c, gs->d_bm_cnt.grow((size_t)n_words + 1));
-        HIP_TRY(c, gs->d_bm_offs.grow((size_t)n_words + 1));
+        GlobalSearch::Pyramid& py = gs->pyr;
+        DevArray<long long>& d_surface = gs->cells.d_surface;
+        HIP_TRY(c, py.d_bm_eval.grow((size_t)n_words));
+        HIP_TRY(c, py.d_bm_level.grow((size_t)n_words));
+        HIP_TRY(c, py.d_bm_cnt.grow((size_t)n_words + 1));
+        HIP_TRY(c, py.d_bm_offs.grow((size_t)n_words + 1));
         const size_t tmp_bytes = global_scan_temp_bytes(n_words);
-        HIP_TRY(c, gs->d_scan_tmp.grow(tmp_bytes ? tmp_bytes : 1));
-        HIP_TRY(c, gs->d_tab_x.grow((size_t)nxc));
-        HIP_TRY(c, gs->d_tab_y.grow((size_t)nyc));
+        HIP_TRY(c, py.d_scan_tmp.grow(tmp_bytes ? tmp_bytes : 1));
+        HIP_TRY(c, py.d_tab_x.grow((size_t)nxc));
+        HIP_TRY(c, py.d_tab_y.grow((size_t)nyc));
         std::vector<GlobalAxis> tx((size_t)nxc), ty((size_t)nyc);
         for (long long i = 0; i < nxc; ++i) {
             const GlobalCand k = make_cand(xs[(size_t)i], 0.0, nz);
@@ -520,104 +553,78 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
             const GlobalCand k = make_cand(0.0, ys[(size_t)j], nz);
             ty[(size_t)j].n = k.ny; ty[(size_t)j].k = k.ky; ty[(size_t)j].pad = 0.f;
         }
-        HIP_TRY(c, hipMemcpyAsync(gs->d_tab_x, tx.data(), tx.size() * sizeof(GlobalAxis), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(gs->d_tab_y, ty.data(), ty.size() * sizeof(GlobalAxis), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(py.d_tab_x, tx.data(), tx.size() * sizeof(GlobalAxis), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(py.d_tab_y, ty.data(), ty.size() * sizeof(GlobalAxis), hipMemcpyHostToDevice, c->stream));
         if (seeded) {
-            HIP_TRY(c, gs->d_seed.grow((size_t)nc));
-            HIP_TRY(c, hipMemcpyAsync(gs->d_seed, h_seed.data(), (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, py.d_seed.grow((size_t)nc));
+            HIP_TRY(c, hipMemcpyAsync(py.d_seed, h_seed.data(), (size_t)nc * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         }
         const bool may_fail = evaluated_out || cell_surface_out;   // only a short buffer can stop the levels half way
         if (may_fail) {
-            HIP_TRY(c, gs->d_state_save.grow(gs->d_state.size()));
-            HIP_TRY(c, hipMemcpyAsync(gs->d_state_save, gs->d_state, gs->d_state.size() * sizeof(double), hipMemcpyDeviceToDevice,
+            HIP_TRY(c, py.d_state_save.grow(gs->d_state.size()));
+            HIP_TRY(c, hipMemcpyAsync(py.d_state_save, gs->d_state, gs->d_state.size() * sizeof(double), hipMemcpyDeviceToDevice,
                                       c->stream));
         }
-        HIP_TRY(c, hipMemsetAsync(gs->d_bm_eval, 0, (size_t)n_words * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_bm_level, 0, (size_t)n_words * sizeof(uint32_t), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_block, 0, (size_t)nc * kGlobalCellStride * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_cell_best_k, 0xff, (size_t)nc * sizeof(uint32_t), c->stream));   // kGlobalNoCand
-        GlobalCells cl;
-        cl.xy = gs->d_cxy; cl.t = gs->d_ct; cl.idx = gs->d_cidx;
-        cl.cell_start = gs->d_cell_start; cl.run_cell = gs->d_run_cell; cl.run_start = gs->d_run_start;
-        cl.n_runs = (int32_t)gs->n_runs; cl.run_len = gs->run_len; cl.n_cells = (int32_t)nc;
-        cl.block = gs->d_cell_block; cl.best_sum = gs->d_cell_best; cl.best_k = gs->d_cell_best_k;
+        HIP_TRY(c, hipMemsetAsync(py.d_bm_eval, 0, (size_t)n_words * sizeof(uint32_t), c->stream));
+        HIP_TRY(c, hipMemsetAsync(py.d_bm_level, 0, (size_t)n_words * sizeof(uint32_t), c->stream));
+        if ((rc = reset_cell_bests(c, gs)) != BF_OK) return rc;
         for (int l = 0; l < L; ++l) {
             if (l == 0 && !seeded)
-                launch_global_stride_mark(lt, stride[0], gs->d_bm_level, c->stream);
+                launch_global_stride_mark(lt, stride[0], py.d_bm_level, c->stream);
             else
-                launch_global_seed_mark(lt, stride[l], po.radius, (int)nc, gs->d_cell_start, gs->d_cell_best, gs->d_cell_best_k,
-                                        seeded ? gs->d_seed.get() : nullptr, gs->d_bm_eval, gs->d_bm_level, c->stream);
+                launch_global_seed_mark(lt, stride[l], po.radius, (int)nc, gs->cells.d_start, gs->cells.d_best, gs->cells.d_best_k,
+                                        seeded ? py.d_seed.get() : nullptr, py.d_bm_eval, py.d_bm_level, c->stream);
             HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, launch_global_bitmap_scan(gs->d_bm_level, n_words, gs->d_bm_cnt, gs->d_bm_offs, gs->d_scan_tmp, tmp_bytes,
+            HIP_TRY(c, launch_global_bitmap_scan(py.d_bm_level, n_words, py.d_bm_cnt, py.d_bm_offs, py.d_scan_tmp, tmp_bytes,
                                                  c->stream));
             uint32_t cnt32 = 0;   // the one value a level brings back: the launches below need it
-            HIP_TRY(c, hipMemcpyAsync(&cnt32, gs->d_bm_offs + n_words, sizeof(cnt32), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(&cnt32, py.d_bm_offs + n_words, sizeof(cnt32), hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));   // (also: the previous level's copies into the vectors below are done)
             const long long cnt = (long long)cnt32;
             level_count[l] = cnt;
             if (cnt == 0) continue;
             if ((rc = fits(cnt)) != BF_OK) {
                 if (!evaluated.empty()) {   // levels ran: the state goes back to what the call found
-                    HIP_TRY(c, hipMemcpyAsync(gs->d_state, gs->d_state_save, gs->d_state.size() * sizeof(double),
+                    HIP_TRY(c, hipMemcpyAsync(gs->d_state, py.d_state_save, gs->d_state.size() * sizeof(double),
                                               hipMemcpyDeviceToDevice, c->stream));
                     HIP_TRY(c, hipStreamSynchronize(c->stream));
                 }
                 return rc;
             }
-            HIP_TRY(c, gs->d_level_k.grow((size_t)cnt));
+            HIP_TRY(c, py.d_level_k.grow((size_t)cnt));
             if ((rc = ensure_cands(c, gs, cnt)) != BF_OK) return rc;
-            launch_global_bitmap_list(gs->d_bm_level, gs->d_bm_eval, n_words, gs->d_bm_offs, gs->d_level_k, c->stream);
-            launch_global_cands_from_lattice(lt, gs->d_level_k, cnt, gs->d_tab_x, gs->d_tab_y, nz, gs->d_cands, c->stream);
+            launch_global_bitmap_list(py.d_bm_level, py.d_bm_eval, n_words, py.d_bm_offs, py.d_level_k, c->stream);
+            launch_global_cands_from_lattice(lt, py.d_level_k, cnt, py.d_tab_x, py.d_tab_y, nz, gs->d_cands, c->stream);
             HIP_TRY(c, hipGetLastError());
             HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, (size_t)cnt * sizeof(unsigned long long), c->stream));
-            if (cell_surface_out) HIP_TRY(c, gs->d_cell_surface.grow((size_t)(nc * cnt)));
-            cl.surface = cell_surface_out ? gs->d_cell_surface.get() : nullptr;
-            cl.n_cand = cnt; cl.k0 = 0;
-            if ((rc = run_candidates(c, gs, 0, cnt, nullptr, nullptr, &cl, gs->d_level_k)) != BF_OK) return rc;
+            if (cell_surface_out) HIP_TRY(c, d_surface.grow((size_t)(nc * cnt)));
+            GlobalCells cl = cells_view(gs, cell_surface_out ? d_surface.get() : nullptr, cnt, py.d_level_k);
+            if ((rc = run_candidates(c, gs, cnt, nullptr, nullptr, &cl)) != BF_OK) return rc;
             const size_t at = evaluated.size();
             evaluated.resize(at + (size_t)cnt);
             S.resize(at + (size_t)cnt);
-            HIP_TRY(c, hipMemcpyAsync(evaluated.data() + at, gs->d_level_k, (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost,
+            HIP_TRY(c, hipMemcpyAsync(evaluated.data() + at, py.d_level_k, (size_t)cnt * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                       c->stream));
             HIP_TRY(c, hipMemcpyAsync(S.data() + at, gs->d_S, (size_t)cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                       c->stream));
             if (cell_surface_out) {
                 surf.emplace_back((size_t)(nc * cnt));
-                HIP_TRY(c, hipMemcpyAsync(surf.back().data(), gs->d_cell_surface, (size_t)(nc * cnt) * sizeof(int64_t),
+                HIP_TRY(c, hipMemcpyAsync(surf.back().data(), d_surface, (size_t)(nc * cnt) * sizeof(int64_t),
                                           hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the next level grows d_cell_surface)
+                HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the next level grows d_surface)
             }
         }
-        HIP_TRY(c, hipMemcpyAsync(cell_best.data(), gs->d_cell_best, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+        HIP_TRY(c, hipMemcpyAsync(cell_best.data(), gs->cells.d_best, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                                   c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cell_k.data(), gs->d_cell_best_k, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cell_k.data(), gs->cells.d_best_k, (size_t)nc * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     const long long ne = (long long)evaluated.size();
     if (ne == 0) return fail(c, BF_ERR_HIP, "bf_global_search_cells_pyramid: nothing was evaluated");   // (never: checked above)
-    long long best = 0;   // the largest S, the lowest k among equals
-    for (long long m = 1; m < ne; ++m)
-        if (S[(size_t)m] > S[(size_t)best] || (S[(size_t)m] == S[(size_t)best] && evaluated[(size_t)m] < evaluated[(size_t)best])) best = m;
+    const long long best = best_of_S(S, evaluated.data());   // the largest S, the lowest k among equals
     if (gs->n <= 0) std::fill(cell_k.begin(), cell_k.end(), evaluated[(size_t)best]);
-    if (slice_out) {
-        const long long b = (long long)evaluated[(size_t)best];
-        slice_out->best_nx = xs[(size_t)(b / nyc)];
-        slice_out->best_ny = ys[(size_t)(b % nyc)];
-        slice_out->best_sum = (int64_t)S[(size_t)best];
-        slice_out->n_x = nxc;
-        slice_out->n_y = nyc;
-    }
-    for (long long i = 0; cells_out && i < nc; ++i) {
-        bf_global_cell_result& r = cells_out[i];
-        const long long b = (long long)cell_k[(size_t)i];
-        r.best_nx = xs[(size_t)(b / nyc)];
-        r.best_ny = ys[(size_t)(b % nyc)];
-        cand_uv(r.best_nx, r.best_ny, nz, &r.best_u, &r.best_v);
-        r.best_sum = (int64_t)cell_best[(size_t)i];
-        r.best_index = b;
-        r.events = (int64_t)gs->h_cell_count[(size_t)i];
-    }
+    write_result(slice_out, xs, ys, (long long)evaluated[(size_t)best], S[(size_t)best]);
+    write_cells(cells_out, gs, xs, ys, nz, cell_k, cell_best);
     for (long long m = 0; evaluated_out && m < ne; ++m) evaluated_out[m] = (int64_t)evaluated[(size_t)m];
     if (cell_surface_out) {   // the levels side by side: [cell][ne]
         long long at = 0;

@@ -278,6 +278,7 @@ struct GlobalEventState {     // per event, upload order
 // The per-cell objective S(k, cell) (include/bf_accel.h): the slice in cell order, cut into runs of at most run_len
 // consecutive events of ONE cell (one work-group each), and where the sums go.
 constexpr int kGlobalCellStride = 32;   // candidates per cell in the batch block (>= the largest batch)
+constexpr uint32_t kGlobalNoCand = 0xffffffffu;   // best_k of a cell before anything was evaluated
 struct GlobalCellGrid {
     int32_t cell_rows, cell_cols, n_cell_y, n_cells;
 };
@@ -290,21 +291,21 @@ struct GlobalCells {
     int32_t n_cells;
     unsigned long long* block;              // [n_cells][kGlobalCellStride] sums of one batch; all zero between batches
     unsigned long long* best_sum;           // per cell: the running largest S(k, cell) ...
-    uint32_t* best_k;                       // ... and the first candidate that reached it
+    uint32_t* best_k;                       // ... and the lowest k that reached it (kGlobalNoCand: nothing evaluated yet)
     long long* surface;                     // null, or [n_cells][n_cand]
     long long n_cand, k0;                   // candidates of the sweep; the batch's first
+    const uint32_t* ks;                     // the lattice k of each slot of the batch; null: slot b is candidate k0 + b
 };
 size_t global_tile_lds(int scale, int mw);
 void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, const GlobalEventState& st, hipStream_t s);
 // one batch of nb candidates; `pts` must be all zero (nb planes); < 0: scale above 7 / kernel attributes / LDS.
 // cells null: k_global_fold adds S(k) into S[0 .. nb).  Otherwise k_global_fold_cells folds the same per-event state and
 // k_global_cells_best leaves S(k) = the sum over the cells in S[0 .. nb) (which must be zero before), with cells->k0 the
-// batch's first candidate; nb <= kGlobalCellStride, img_out and scores_out unused.  lattice_k (with cells only): the
-// lattice index of each of the nb slots; k_global_cells_best_lattice then takes k_global_cells_best's place.
+// batch's first candidate and cells->ks its slots' lattice k; nb <= kGlobalCellStride, img_out and scores_out unused.
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
-                        hipStream_t s, const uint32_t* lattice_k = nullptr);
+                        hipStream_t s);
 // counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
 // events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);
@@ -320,7 +321,6 @@ struct GlobalAxis {           // one axis value of the lattice: make_cand's n an
     double n;
     float k, pad;
 };
-constexpr uint32_t kGlobalNoCand = 0xffffffffu;   // best_k of a cell before anything was evaluated
 // level 0 without seeds: every (i, j) with i % stride == 0 and j % stride == 0 into `level`
 void launch_global_stride_mark(const GlobalLattice& lt, long long stride, uint32_t* level, hipStream_t s);
 // a window of (2 * radius + 1)^2 points, `stride` lattice steps apart and clipped to the lattice, around the centre of every

@@ -99,3 +99,23 @@ def two_motion_subgrid():
         return [vals[i] for i in sorted(keep)]
     return (pick(xs, 6, [TWO_MOTION_TRUTH["left"][0], TWO_MOTION_TRUTH["right"][0]]),
             pick(ys, 4, [TWO_MOTION_TRUTH["left"][1], TWO_MOTION_TRUTH["right"][1]]))
+
+
+# Ties in the per-cell best, at the smallest shapes where the rule can go wrong: 7 x 5 = 35 candidates (a batch of 32 and
+# one of 3), 3 x 3 cells (9: one full group of 8 cells in the best kernel and one cell in the next), the middle cell empty.
+TIE_GRID = (24, 24, 8, 8)
+TIE_EQUAL = (-0.003, 0.0035, -0.002, 0.0025)    # x_low, x_hi, y_low, y_hi at step 0.001
+TIE_ZERO = (5.0, 5.0065, 5.0, 5.0045)           # 39 px/s per ns-tick of t / 10000 and more: far off any motion
+
+
+def tie_slice(equal):
+    """300 events on the 24 x 24 sensor, none in the middle cell, the corners occupied.  equal: every t is 0, so every
+    candidate leaves every event on its own pixel and S(k, cell) is the same non-zero number for all k.  Otherwise t lies
+    in [2e7, 3e7): under TIE_ZERO every event leaves the image (by 78 pixels or more) and every S(k, cell) is 0."""
+    rng = np.random.default_rng(17)
+    fr_x, fr_y = rng.integers(0, 24, 600), rng.integers(0, 24, 600)
+    keep = ~((fr_x // 8 == 1) & (fr_y // 8 == 1))
+    fr_x, fr_y = fr_x[keep][:300], fr_y[keep][:300]
+    fr_x[:2], fr_y[:2] = (0, 23), (0, 23)
+    t = np.zeros(300, dtype=np.int64) if equal else np.sort(rng.integers(20000000, 30000000, 300))
+    return fr_x.astype(np.int64), fr_y.astype(np.int64), t.astype(np.int64)

@@ -108,6 +108,30 @@ def test_one_cell_split_over_several_work_groups(accel_mod, n_a, n_b, n_rest):
         acc.close()
 
 
+@pytest.mark.parametrize("equal", [True, False])
+def test_ties_keep_the_lowest_candidate(accel_mod, equal):
+    """GC.tie_slice: S(k, cell) equal and non-zero for all 35 k of two batches, and all zero.  Every cell, the empty one
+    included, and the slice answer candidate 0; the events are counted either way."""
+    ev = GC.tie_slice(equal)
+    lat = GC.TIE_EQUAL if equal else GC.TIE_ZERO
+    xs, ys = G.sweep_values(lat[0], lat[1], 0.001), G.sweep_values(lat[2], lat[3], 0.001)
+    assert (len(xs), len(ys)) == (7, 5)
+    ref = GC.GlobalCells(*ev, *GC.TIE_GRID, scale=3, metric_wsize=15)
+    rsurf, rcells, rbest = ref.search_cells(xs, ys)
+    assert (rsurf == rsurf[:, :, :1, :1]).all() and rsurf[:, :, 0, 0].astype(bool).sum() == (8 if equal else 0)
+    assert ref.events[4] == 0 and (np.delete(ref.events, 4) > 0).all() and not rcells["best_index"].any()
+    acc = _accel(accel_mod, ev)
+    try:
+        acc.global_set_window(3, 15)
+        g = acc.global_set_cells(*GC.TIE_GRID)
+        assert (g.n_cell_x, g.n_cell_y) == (3, 3)
+        r, cells, surf = acc.global_search_cells(_opts(accel_mod, lat[0], lat[1], lat[2], lat[3]), want_surface=True)
+        _check(acc, r, cells, surf, ref, rsurf, rcells, rbest)
+        assert not cells["best_index"].any() and (r.best_nx, r.best_ny) == (xs[0], ys[0])
+    finally:
+        acc.close()
+
+
 def test_equivalence_with_global_search(accel_mod):
     ev = _golden()
     step = 2.0 ** -9                                  # exact in binary: the half grids hold the union's values

@@ -94,6 +94,29 @@ def test_one_level_is_the_exhaustive_search(accel_mod, rows, cols):
         acc.close()
 
 
+# GC.tie_slice on 7 x 5 candidates and 3 x 3 cells: S(k, cell) equal and non-zero for every k (one level: batches of 32 and
+# 3; two levels: 12 strided candidates, then the 3 new ones around candidate 0), and all zero (no cell has a centre: the
+# second level is empty).  Every cell and the slice answer candidate 0.
+@pytest.mark.parametrize("equal,levels,count", [(True, 1, [35]), (True, 2, [12, 3]), (False, 1, [35]), (False, 2, [12, 0])])
+def test_ties_keep_the_lowest_candidate(accel_mod, equal, levels, count):
+    ev = GC.tie_slice(equal)
+    lat = GC.TIE_EQUAL if equal else GC.TIE_ZERO
+    xs, ys = G.sweep_values(lat[0], lat[1], 0.001), G.sweep_values(lat[2], lat[3], 0.001)
+    ref = GC.GlobalCells(*ev, *GC.TIE_GRID, scale=3, metric_wsize=15)
+    want = P.search_pyramid(ref, xs, ys, levels, 2, 1)
+    assert want["level_count"] == count and not want["cells"]["best_index"].any()
+    assert (want["surface"] == want["surface"][:, :1]).all() and want["surface"][:, 0].astype(bool).sum() == (8 if equal else 0)
+    acc = _accel(accel_mod, ev)
+    try:
+        acc.global_set_window(3, 15)
+        acc.global_set_cells(*GC.TIE_GRID)
+        got = acc.global_search_cells_pyramid(_opts(accel_mod, *lat), levels=levels, factor=2, radius=1, want_surface=True)
+        _check(acc, got, ref, want, (7, 5))
+        assert not got[1]["best_index"].any() and (got[0].best_nx, got[0].best_ny) == (xs[0], ys[0])
+    finally:
+        acc.close()
+
+
 # The lattice holds the motion's candidate (0.0381, -0.0254) two steps from its low-x edge and at its high-y edge, so the
 # refinement windows are clipped; 23 x 13 is no multiple of any stride (2, 4, 16).
 LAT = (0.036, 0.0585, -0.0375, -0.0250)
