@@ -171,7 +171,7 @@ EXPORTS = [
     "bf_upload_ring_async", "bf_upload_ring16_async", "bf_upload_ring16t32_async", "bf_upload_events16_async", "bf_compute_uv_ring", "bf_wait_uploads", "bf_projection_img",
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
-    "bf_global_set_cells", "bf_global_search_cells", "bf_global_search_cells_pyramid",
+    "bf_global_set_cells", "bf_global_search_cells", "bf_global_search_cells_pyramid", "bf_global_project_cells",
     "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
     "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
     "bf_flow_field", "bf_color_flow_img", "bf_flow_frame_create", "bf_flow_frame_destroy", "bf_flow_frame_render",
@@ -290,6 +290,8 @@ def load(path=None):
         L.bf_global_search_cells_pyramid.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(GlobalPyramidOpts),
                                                      C.c_void_p, C.POINTER(GlobalResult), C.c_void_p, C.c_int64, C.c_void_p,
                                                      C.c_int64, C.c_void_p, C.c_int64, C.POINTER(GlobalPyramidInfo)]
+        L.bf_global_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int64), C.c_void_p, C.c_int64]
         L.bf_projection_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_color_time_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_upload_ring_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
@@ -612,6 +614,29 @@ class Accel:
         if surf is not None:
             surf = surf[:nc * ne].reshape(g.n_cell_x, g.n_cell_y, ne)
         return r, cells[:nc].reshape(g.n_cell_x, g.n_cell_y), ev[:ne].copy(), surf, info
+
+    def global_project_cells(self, cell_nx, cell_ny, nz=127.0, want_img=True, want_scores=True, want_cell_sums=True):
+        """The piecewise projection (bf_global_project_cells): the slice rendered and scored with every event under its own
+        cell's (nx, ny).  cell_nx / cell_ny: n_cell_x * n_cell_y values in any shape, row-major [n_cell_x, n_cell_y] (for
+        instance global_search_cells' cells["best_nx"], cells["best_ny"]); the entry of a cell without events is not read.
+        The per-event state is not touched.  want_cell_sums False passes no per-cell buffer, like want_img and want_scores
+        for theirs.  Returns (blurred bordered image or None, current_scores or None, S_pw,
+        S_pw(cell) as int64 [n_cell_x, n_cell_y] or None)."""
+        w, g = self._gwin, self._gcells   # None before global_set_window / global_set_cells: the library reports BF_ERR_ARG
+        nc = g.n_cell_x * g.n_cell_y if g else 0
+        cx = np.ascontiguousarray(np.asarray(cell_nx, dtype=np.float64).reshape(-1))
+        cy = np.ascontiguousarray(np.asarray(cell_ny, dtype=np.float64).reshape(-1))
+        if len(cx) != len(cy):
+            raise ValueError("cell_nx has %d entries, cell_ny %d" % (len(cx), len(cy)))
+        img = np.empty((w.scale_bordered_img_x, w.scale_bordered_img_y), dtype=np.uint8) if want_img and w else None
+        sc = np.empty((w.scale_img_x, w.scale_img_y), dtype=np.float32) if want_scores and w else None
+        sums = np.zeros(nc, dtype=np.int64) if want_cell_sums else None
+        S = C.c_int64()
+        self._chk(self.L.bf_global_project_cells(self.h, _ptr(cx), _ptr(cy), len(cx), nz, _ptr(img), _ptr(sc), C.byref(S),
+                                                 _ptr(sums), 0 if sums is None else len(sums)))
+        if sums is not None:
+            sums = sums[:nc].reshape(g.n_cell_x, g.n_cell_y)
+        return img, sc, S.value, sums
 
     def global_get_events(self):
         """Per-event state in upload order: dict of max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v."""

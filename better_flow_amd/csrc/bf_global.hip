@@ -19,6 +19,9 @@
 //       (k_global_stride_mark / k_global_seed_mark into a bitmap of the lattice, a popcount-scan-write compaction into the
 //       ascending list of k, k_global_cands_from_lattice), scored by the unchanged G1, G2 and G3c; the batch carries the
 //       lattice k of each slot (GlobalCells::ks), by which k_global_cells_best breaks ties.
+//   PW  bf_global_project_cells: one image of the slice with every event under its own cell's candidate:
+//       k_global_project_cells (G1 over the cell-ordered runs, all into plane 0), the unchanged G2 on that one plane, and
+//       k_global_score_cells (the score part of G3 per event, summed per cell); no per-event state is touched.
 //
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
 // order in which work-groups run.
@@ -181,22 +184,33 @@ struct GlobalBest {
     }
 };
 
+// An accepted event at pixel (X, Y) of window plane b: its window word, the float score f (into scores_out when asked),
+// and its return value, the event's share of S: floor(score * 2^32).
+__device__ __forceinline__ unsigned long long global_score_pixel(const GlobalGeom& g, int b, int X, int Y,
+                                                                 const uint32_t* __restrict__ win,
+                                                                 float* __restrict__ scores_out, float& f) {
+    const int off = g.scale / 2 + g.mw / 2;
+    unsigned long long contrib = 0;
+    const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
+    const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
+    const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
+    f = (float)score;                                                    // current_scores (CV_32FC1)
+    if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
+    if (scores_out) scores_out[(size_t)X * (size_t)g.sy + (size_t)Y] = f;   // the same value from every event there
+    return contrib;
+}
+
 // One event (v, ti) under candidate c, slot b of the batch: its window word, the score into the running best, and its
 // return value, the event's share of S: floor(score * 2^32), 0 when the candidate rejects the event.
 __device__ __forceinline__ unsigned long long global_fold_event(const GlobalGeom& g, const GlobalCand& c, int b, uint32_t v,
                                                                 int32_t ti, const uint32_t* __restrict__ win,
                                                                 float* __restrict__ scores_out, GlobalBest& best) {
-    const int off = g.scale / 2 + g.mw / 2;
     unsigned long long contrib = 0;
     double pr_x, pr_y;
     int X, Y;
     if (global_pixel(g, c, v, ti, pr_x, pr_y, X, Y)) {
-        const uint32_t w = win[(size_t)b * g.plane + (size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)];
-        const uint32_t sum = w & kSumMask, cnt = w >> kCntShift;
-        const double score = cnt == 0u ? 0.0 : (double)sum / (double)cnt;   // get_event_score, :99
-        const float f = (float)score;                                        // current_scores (CV_32FC1)
-        if (cnt) contrib = ((unsigned long long)sum << 32) / (unsigned long long)cnt;
-        if (scores_out) scores_out[(size_t)X * (size_t)g.sy + (size_t)Y] = f;   // the same value from every event there
+        float f;
+        contrib = global_score_pixel(g, b, X, Y, win, scores_out, f);
         if ((double)f > best.mx) {   // apply_score, event.h:113-121
             best.mx = f; best.nx = c.nx; best.ny = c.ny; best.nz = c.nz; best.pr_x = pr_x; best.pr_y = pr_y;
             best.changed = true;
@@ -300,6 +314,59 @@ __global__ __launch_bounds__(T) void k_global_fold_cells(GlobalCells cl, GlobalG
 #pragma unroll
             for (int w = 0; w < kWaves; ++w) tot += s_part[threadIdx.x * kWaves + w];
             if (tot) atomicAdd(&out[threadIdx.x], tot);
+        }
+    }
+}
+
+// ---- the piecewise projection (include/bf_accel.h, bf_global_project_cells): every event under its own cell's candidate ----
+// G1 over the runs of k_global_fold_cells: one work-group per run, so the cell -- and with it the candidate, read from the
+// [n_cells] table through a wave-uniform address -- is the same for every lane.  All cells splat into plane 0.
+template <int T>
+__global__ __launch_bounds__(T) void k_global_project_cells(GlobalCells cl, GlobalGeom g,
+                                                            const GlobalCand* __restrict__ cell_cands,
+                                                            uint32_t* __restrict__ pts) {
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    if (j >= cl.cell_start[cell + 1]) return;
+    const GlobalCand c = cell_cands[cell];
+    double pr_x, pr_y;
+    int X, Y;
+    if (!global_pixel(g, c, cl.xy[j], cl.t[j], pr_x, pr_y, X, Y)) return;
+    const int off = g.scale / 2 + g.mw / 2;   // the splat's centre, as in k_global_project
+    atomicAdd(&pts[(size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)], 1u);
+}
+
+// G3 of the piecewise projection over the same runs: per event global_score_pixel at its pixel under its cell's candidate
+// (window plane 0), then the work-group's total into cell_sums[cell] with one 64-bit atomic (none when it is 0), summed as
+// in k_global_fold_cells.  The per-event state is neither read nor written.
+template <int T>
+__global__ __launch_bounds__(T) void k_global_score_cells(GlobalCells cl, GlobalGeom g,
+                                                          const GlobalCand* __restrict__ cell_cands,
+                                                          const uint32_t* __restrict__ win, float* __restrict__ scores_out,
+                                                          unsigned long long* __restrict__ cell_sums) {
+    constexpr int kWaves = T / 64;
+    __shared__ unsigned long long s_part[kWaves];
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    unsigned long long contrib = 0;
+    if (j < cl.cell_start[cell + 1]) {
+        double pr_x, pr_y;
+        int X, Y;
+        float f;
+        if (global_pixel(g, cell_cands[cell], cl.xy[j], cl.t[j], pr_x, pr_y, X, Y))
+            contrib = global_score_pixel(g, 0, X, Y, win, scores_out, f);
+    }
+    const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
+    if (kWaves == 1) {
+        if (threadIdx.x == 63 && tot) atomicAdd(&cell_sums[cell], tot);
+    } else {
+        if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = tot;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long all = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) all += s_part[w];
+            if (all) atomicAdd(&cell_sums[cell], all);
         }
     }
 }
@@ -458,6 +525,21 @@ void launch_global_reset(const uint32_t* xy, const uint32_t* perm, long long n, 
     hipLaunchKernelGGL(k_global_reset, dim3((unsigned)((n + kGT - 1) / kGT)), dim3(kGT), 0, s, xy, perm, n, st);
 }
 
+namespace {
+// G2 over nb point planes (scale <= 7: the caller checked); < 0 as launch_global_batch
+int launch_global_tile(const GlobalGeom& g, int nb, const uint32_t* pts, uint32_t* win, uint8_t* img_out, hipStream_t s) {
+    void (*k)(const uint32_t*, GlobalGeom, uint32_t*, uint8_t*) =
+        g.scale / 2 == 0 ? k_global_tile<0> : (g.scale / 2 == 1 ? k_global_tile<1> : (g.scale / 2 == 2 ? k_global_tile<2> : k_global_tile<3>));
+    const size_t lds = global_tile_lds(g.scale, g.mw);
+    if (lds > 160 * 1024) return -3;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+        return -2;
+    const dim3 grid((unsigned)((g.Cb + kGTC - 1) / kGTC), (unsigned)((g.Rb + kGTR - 1) / kGTR), (unsigned)nb);
+    hipLaunchKernelGGL(k, grid, dim3(kGT), lds, s, pts, g, win, img_out);
+    return 0;
+}
+}  // namespace
+
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
@@ -467,14 +549,8 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
     if (cells && nb > kGlobalCellStride) return -1;
     const unsigned eg = (unsigned)((n + kGT - 1) / kGT);
     hipLaunchKernelGGL(k_global_project, dim3(eg, (unsigned)nb), dim3(kGT), 0, s, xy, t, n, g, cands, pts);
-    void (*k)(const uint32_t*, GlobalGeom, uint32_t*, uint8_t*) =
-        g.scale / 2 == 0 ? k_global_tile<0> : (g.scale / 2 == 1 ? k_global_tile<1> : (g.scale / 2 == 2 ? k_global_tile<2> : k_global_tile<3>));
-    const size_t lds = global_tile_lds(g.scale, g.mw);
-    if (lds > 160 * 1024) return -3;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return -2;
-    const dim3 grid((unsigned)((g.Cb + kGTC - 1) / kGTC), (unsigned)((g.Rb + kGTR - 1) / kGTR), (unsigned)nb);
-    hipLaunchKernelGGL(k, grid, dim3(kGT), lds, s, pts, g, win, img_out);
+    const int tr = launch_global_tile(g, nb, pts, win, img_out, s);
+    if (tr != 0) return tr;
     if (!cells) {
         hipLaunchKernelGGL(k_global_fold, dim3(eg), dim3(kGT), 0, s, xy, t, perm, n, g, cands, nb, win, st, S, scores_out);
         return 0;
@@ -486,6 +562,24 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
     constexpr int per = kGT / kGlobalCellStride;
     const dim3 cgrid((unsigned)((cells->n_cells + per - 1) / per));
     hipLaunchKernelGGL(k_global_cells_best, cgrid, dim3(kGT), 0, s, *cells, nb, S);
+    return 0;
+}
+
+int launch_global_piecewise(const GlobalCells& cells, const GlobalGeom& g, const GlobalCand* cell_cands, uint32_t* pts,
+                            uint32_t* win, uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s) {
+    if (cells.n_runs <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
+    if (g.scale / 2 > 3) return -1;
+    const dim3 runs((unsigned)cells.n_runs);
+    if (cells.run_len == 64)
+        hipLaunchKernelGGL(k_global_project_cells<64>, runs, dim3(64), 0, s, cells, g, cell_cands, pts);
+    else
+        hipLaunchKernelGGL(k_global_project_cells<kGT>, runs, dim3(kGT), 0, s, cells, g, cell_cands, pts);
+    const int tr = launch_global_tile(g, 1, pts, win, img_out, s);
+    if (tr != 0) return tr;
+    if (cells.run_len == 64)
+        hipLaunchKernelGGL(k_global_score_cells<64>, runs, dim3(64), 0, s, cells, g, cell_cands, win, scores_out, cell_sums);
+    else
+        hipLaunchKernelGGL(k_global_score_cells<kGT>, runs, dim3(kGT), 0, s, cells, g, cell_cands, win, scores_out, cell_sums);
     return 0;
 }
 

@@ -1,8 +1,8 @@
 // bf_global_search.cpp -- C-ABI of the exhaustive search, OptimizerGlobal (optimizer_global.h / optimizer_global.cpp): the window
 // (update_fields), one project_all, compute_flow_bruteforce over a candidate grid (per slice, and per cell of a grid over the
 // sensor), and the per-event state.  The kernels are in bf_global.hip; the definitions this build adds (the per-event best
-// candidate, the objective S, the objective per cell) are stated in
-// include/bf_accel.h and DESIGN.md.
+// candidate, the objective S, the objective per cell, the candidate set of a pyramid level, the piecewise projection) are
+// stated in include/bf_accel.h and DESIGN.md.
 #include "bf_ctx.h"
 
 struct GlobalSearch {
@@ -32,6 +32,10 @@ struct GlobalSearch {
         DevArray<unsigned long long> d_block, d_best;
         DevArray<uint32_t> d_best_k;
         DevArray<long long> d_surface;
+        // bf_global_project_cells: one candidate per cell and the per-cell sums S_pw(cell)
+        std::vector<GlobalCand> h_pw_cands;
+        DevArray<GlobalCand> d_pw_cands;
+        DevArray<unsigned long long> d_pw_sums;
     } cells;
 
     // scratch of one bf_global_search_cells_pyramid call: the lattice bitmaps (one bit per k), the compaction's scratch,
@@ -642,6 +646,71 @@ int bf_global_search_cells_pyramid(bf_ctx* c, const bf_global_search_opts* opts,
         for (int l = 0; l < L; ++l) info->level_count[l] = level_count[l];
         info->levels_run = L;
     }
+    return BF_OK;
+}
+
+int bf_global_project_cells(bf_ctx* c, const double* cell_nx, const double* cell_ny, int64_t cells_cap, double nz,
+                            uint8_t* img_out, float* scores_out, int64_t* sum_out, int64_t* cell_sums_out,
+                            int64_t cell_sums_cap) {
+    if (!c) return BF_ERR_ARG;
+    int rc = global_ready(c);
+    if (rc != BF_OK) return rc;
+    GlobalSearch* gs = c->glob.get();
+    GlobalSearch::Cells& cs = gs->cells;
+    if (!cs.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    const long long nc = cs.cg.n_cells;
+    if (!cell_nx || !cell_ny) return fail(c, BF_ERR_ARG, "bf_global_project_cells: no candidate grid");
+    if (cells_cap < nc) return fail(c, BF_ERR_ARG, "candidate grid holds %lld of %lld cells", (long long)cells_cap, nc);
+    if (cell_sums_out && cell_sums_cap < nc)
+        return fail(c, BF_ERR_ARG, "cell sum buffer holds %lld of %lld", (long long)cell_sums_cap, nc);
+    if (!(nz > 0)) return fail(c, BF_ERR_ARG, "bad nz");
+    // one candidate per cell that has events (kx, ky once per cell, here); the entry of any other cell is not read
+    // (finite means finite in the float form the projection uses, kx and ky: 1e39 is as infinite there as inf and NaN are)
+    std::vector<GlobalCand> cands((size_t)nc, make_cand(0.0, 0.0, nz));
+    for (long long i = 0; i < nc; ++i) {
+        if (cs.h_count[(size_t)i] == 0u) continue;
+        cands[(size_t)i] = make_cand(cell_nx[i], cell_ny[i], nz);
+        if (!std::isfinite(cands[(size_t)i].kx) || !std::isfinite(cands[(size_t)i].ky))
+            return fail(c, BF_ERR_ARG, "the candidate of cell %lld, which has events, is not finite as a float", i);
+    }
+    cs.h_pw_cands.swap(cands);   // (nothing of this object is written before every check has passed)
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bf_global_window& w = gs->w;
+    const size_t img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
+    const size_t sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
+    if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
+    if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
+    if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
+    if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
+    std::vector<unsigned long long> sums((size_t)nc, 0ull);
+    if (gs->n > 0) {   // (no event: nothing is launched, every sum is 0 and the images are zero)
+        HIP_TRY(c, cs.d_pw_cands.grow((size_t)nc));
+        HIP_TRY(c, cs.d_pw_sums.grow((size_t)nc));
+        if ((rc = ensure_batch(c, gs, 1)) != BF_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(cs.d_pw_cands, cs.h_pw_cands.data(), (size_t)nc * sizeof(GlobalCand), hipMemcpyHostToDevice,
+                                  c->stream));
+        HIP_TRY(c, hipMemsetAsync(cs.d_pw_sums, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
+        const int lr = launch_global_piecewise(cells_view(gs, nullptr, 0), gs->g, cs.d_pw_cands, gs->d_pts, gs->d_win,
+                                               img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr,
+                                               cs.d_pw_sums, c->stream);
+        if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
+        if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
+        if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(sums.data(), cs.d_pw_sums, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                  c->stream));
+    }
+    if (img_out && img_px) HIP_TRY(c, hipMemcpyAsync(img_out, gs->d_img, img_px, hipMemcpyDeviceToHost, c->stream));
+    if (scores_out && sc_px)
+        HIP_TRY(c, hipMemcpyAsync(scores_out, gs->d_scores, sc_px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (h_pw_cands is read until here)
+    unsigned long long S = 0;   // at most 65 536 cell sums: on the host, after the one copy that brought them back
+    for (long long i = 0; i < nc; ++i) {
+        S += sums[(size_t)i];
+        if (cell_sums_out) cell_sums_out[i] = (int64_t)sums[(size_t)i];
+    }
+    if (sum_out) *sum_out = (int64_t)S;
     return BF_OK;
 }
 

@@ -306,6 +306,13 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
                         hipStream_t s);
+// The piecewise projection (include/bf_accel.h, bf_global_project_cells): every event of the cell-ordered slice under
+// cell_cands[its cell] ([n_cells]; the entry of a cell without events is never read) into ONE point plane `pts` (all zero
+// before), G2 on it (win, img_out as above), then per event its score into scores_out (may be null) and its share of the
+// objective into cell_sums[its cell] ([n_cells], zero before).  Only cells' xy / t / cell_start / run_* fields are read;
+// the per-event state, block, best_sum and best_k are not touched.  < 0 as launch_global_batch.
+int launch_global_piecewise(const GlobalCells& cells, const GlobalGeom& g, const GlobalCand* cell_cands, uint32_t* pts,
+                            uint32_t* win, uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
 // counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
 // events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);

@@ -89,6 +89,7 @@ private:
     size_t size;   // number of events staged
     bool staged;
     std::vector<uint8_t> noise_staged;   // Event::noise as uploaded (empty: none) -- the host composition of the flow field reads it
+    size_t global_n_cells = 0;           // n_cell_x * n_cell_y of the last global_set_cells (0: none)
 
     void check(int rc, const char *what) const {
         if (rc < 0)
@@ -288,6 +289,7 @@ public:
 
     // OptimizerGlobal on the device (optimizer_global.h:27-41; optimizer_global.cpp:4-150)
     void global_set_window(int scale, int metric_wsize, bf_global_window *w) {
+        this->global_n_cells = 0;   // (a new window clears the cells)
         check(bf_global_set_window(ctx, scale, metric_wsize, w), "global_set_window");
     }
     long long global_project_all(double nx, double ny, double nz, uint8_t *img_out, float *scores_out) {
@@ -303,7 +305,9 @@ public:
     }
     // the objective per cell of a grid over the sensor (include/bf_accel.h: bf_global_set_cells, bf_global_search_cells)
     void global_set_cells(int res_x, int res_y, int cell_rows, int cell_cols, bf_global_cells *g) {
+        this->global_n_cells = 0;
         check(bf_global_set_cells(ctx, res_x, res_y, cell_rows, cell_cols, g), "global_set_cells");
+        this->global_n_cells = (size_t)g->n_cell_x * (size_t)g->n_cell_y;
     }
     void global_search_cells(const bf_global_search_opts &o, bf_global_result *r, std::vector<bf_global_cell_result> *cells,
                              std::vector<int64_t> *cell_surface) {
@@ -327,6 +331,22 @@ public:
                                              nullptr, 0, info),
               "global_search_cells_pyramid");
         if (evaluated) evaluated->resize((size_t)info->evaluated);
+    }
+    // the piecewise projection (bf_global_project_cells): one (nx, ny) per cell of the last global_set_cells' grid,
+    // row-major; grids of any other length are refused (BF_ERR_ARG) before the library is called.  cell_sums (may be null)
+    // is resized to that grid.  Returns S_pw.
+    long long global_project_cells(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz,
+                                   uint8_t *img_out, float *scores_out, std::vector<int64_t> *cell_sums) {
+        if (global_n_cells && (cell_nx.size() != global_n_cells || cell_ny.size() != global_n_cells))
+            throw bf::AccelError(BF_ERR_ARG, "AccelLib::global_project_cells: grids of " + std::to_string(cell_nx.size()) +
+                                                 " and " + std::to_string(cell_ny.size()) + " entries for " +
+                                                 std::to_string(global_n_cells) + " cells");
+        int64_t sum = 0;   // (without cells the library refuses, BF_ERR_ARG, before it reads a buffer)
+        if (cell_sums) cell_sums->assign(global_n_cells, 0);
+        check(bf_global_project_cells(ctx, cell_nx.data(), cell_ny.data(), (int64_t)global_n_cells, nz, img_out, scores_out, &sum,
+                                      cell_sums ? cell_sums->data() : nullptr, (int64_t)global_n_cells),
+              "global_project_cells");
+        return (long long)sum;
     }
     void global_get_events(double *max_score, double *best_nx, double *best_ny, double *best_pr_x, double *best_pr_y,
                            double *best_u, double *best_v) {

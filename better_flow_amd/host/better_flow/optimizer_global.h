@@ -20,6 +20,10 @@
 // get_seeds / set_seeds, and only over the same search range and cell grid: the grid is anchored at sensor pixel (0, 0), so
 // a cell means the same pixels in every slice.
 //
+// A fifth: the piecewise projection (project_cells; include/bf_accel.h, bf_global_project_cells): the slice rendered and
+// scored with every event under its own cell's (nx, ny) -- the compensated image and the objective S_pw of a per-cell
+// answer.  It folds nothing into the per-event state.
+//
 // Each object stages its slice on a device context of its OWN (not the thread's shared one that OptimizerLocal and
 // OptimizerRolling use): the window and the per-event best state live there and accumulate over project_all /
 // compute_flow_bruteforce calls, so no other optimiser on the thread may replace them.  Objects are not copyable.
@@ -63,13 +67,17 @@ protected:
     std::vector<bf_global_cell_result> cell_results;                      // [n_cell_x][n_cell_y]
     std::vector<int64_t> seeds;                                           // per cell: a lattice index or -1 (empty: none)
     bf_global_pyramid_info pyramid_info;
+    std::vector<int64_t> cell_sums;                                       // S_pw(cell) of the last project_cells
 
-    void stage_cells() {
+    void ensure_cells() {   // the slice, the window and the cell grid are on the device
         this->stage();
         if (!this->cells_staged) {
             accel.global_set_cells(cells_res_x, cells_res_y, cell_rows, cell_cols, &this->cell_grid);   // (throws before set_cells)
             this->cells_staged = true;
         }
+    }
+    void stage_cells() {    // ... for a search: its results start empty
+        this->ensure_cells();
         this->cell_results.assign((size_t)cell_grid.n_cell_x * (size_t)cell_grid.n_cell_y, bf_global_cell_result());
         this->surface.clear();
     }
@@ -186,6 +194,30 @@ public:
             for (size_t i = 0; i < seeds.size(); ++i) any = any || seeds[i] >= 0;
         this->search_pyramid(pyramid, any ? this->seeds : std::vector<int64_t>());
     }
+
+    // The piecewise projection under one (nx, ny) per cell, row-major [n_cell_x][n_cell_y] (the entry of a cell without
+    // events is not read): project_img and current_scores are refreshed like project_all, the per-event state is not
+    // touched.  Returns S_pw and keeps the per-cell sums (get_cell_sums).
+    long long project_cells(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz_ = NZ) {
+        this->ensure_cells();
+        this->project_img = bf::Image2D<uint8_t>(scale_bordered_img_x, scale_bordered_img_y);
+        this->current_scores.assign((size_t)scale_img_x * (size_t)scale_img_y, 0.0f);
+        this->last_sum = accel.global_project_cells(cell_nx, cell_ny, nz_, this->project_img.ptr(0),
+                                                    this->current_scores.empty() ? nullptr : this->current_scores.data(),
+                                                    &this->cell_sums);
+        return this->last_sum;
+    }
+
+    // ... under the answers of the last compute_flow_cells / _pyramid / _seeded call (cell_results' best_nx, best_ny, with
+    // the search range's nz).  Throws when there are none.
+    long long project_cells() {
+        if (this->cell_results.empty())
+            throw bf::AccelError(BF_ERR_STATE, "OptimizerGlobal::project_cells: no per-cell results (call compute_flow_cells first)");
+        std::vector<double> cx(cell_results.size()), cy(cell_results.size());
+        for (size_t i = 0; i < cell_results.size(); ++i) { cx[i] = cell_results[i].best_nx; cy[i] = cell_results[i].best_ny; }
+        return this->project_cells(cx, cy, this->range.nz);
+    }
+    const std::vector<int64_t> &get_cell_sums() const { return cell_sums; }   // [n_cell_x][n_cell_y]
 
     void clear_seeds() { this->seeds.clear(); }
     const std::vector<int64_t> &get_seeds() const { return seeds; }

@@ -663,6 +663,35 @@ int bf_global_search_cells_pyramid(bf_ctx *ctx, const bf_global_search_opts *opt
                                    int64_t cells_cap, int64_t *evaluated_out, int64_t evaluated_cap, int64_t *cell_surface_out,
                                    int64_t cell_surface_cap, bf_global_pyramid_info *info);
 
+/* The piecewise projection: the slice rendered and scored with every event under the flow of its own cell.  A fifth
+ * definition of this build ("OptimizerGlobal"), over the window of bf_global_set_window and the grid of
+ * bf_global_set_cells, given one candidate (nx_c, ny_c) per cell and a common nz:
+ *   - Projection.  Every event is projected by Event::project in its float form under the candidate of the cell of its
+ *     recorded address (the membership of bf_global_set_cells); kx = float(nx_c) / nz and ky are computed once per cell,
+ *     on the host, by the expressions of every other candidate of this family.
+ *   - Image.  Every later step is bf_global_project_all's, with all events in ONE image: the pixel truncation and the
+ *     acceptance test, the saturating scale x scale splat into the bordered image, this build's 8-bit Gaussian, and per
+ *     accepted event the mean of the non-zero blurred pixels in its metric_wsize^2 window.
+ *   - Objective.  S_pw(cell) = sum of floor(score * 2^32) over the accepted events of the cell, each (sum << 32) / count;
+ *     S_pw = sum over the cells of S_pw(cell).  Exact int64, order free.  (Not S(k, cell): that is measured with EVERY
+ *     event moved by k, the neighbours from other cells included.)
+ *   - State.  The per-event best state is not touched -- a piecewise field is no candidate of the sweep, apply_score has
+ *     nothing to record for it -- nor are the cells' running bests or the scratch of the pyramid; the uploaded events are
+ *     not moved.  The call may be mixed freely with bf_global_project_all and the searches on one window.
+ *   - The entry of a cell without events is never read: it may hold anything, NaN included.
+ *   - Identity.  With the same (nx, ny) in every cell, img_out, scores_out and S_pw are bf_global_project_all(nx, ny, nz)'s
+ *     outputs bit for bit.
+ *   - Interpolating between cell centres (a smooth field) is not part of this definition.
+ * cell_nx / cell_ny: cells_cap entries each, row-major [n_cell_x][n_cell_y] like cells_out.  img_out, scores_out, sum_out
+ * (S_pw) as in bf_global_project_all, each may be NULL; cell_sums_out (may be NULL; cell_sums_cap entries) S_pw(cell), row-major.
+ * An empty cloud: every sum 0, the images zero, BF_OK.  BF_ERR_ARG without a window or cells, for a buffer shorter than the
+ * grid, nz <= 0, or a value in a cell that has events that is not finite in the projection's float form (inf, NaN, or a
+ * double past float range such as 1e39: kx or ky would not be finite); nothing ran then and every state is as before.
+ * BF_ERR_STATE when an upload happened since bf_global_set_window. */
+int bf_global_project_cells(bf_ctx *ctx, const double *cell_nx, const double *cell_ny, int64_t cells_cap, double nz,
+                            uint8_t *img_out, float *scores_out, int64_t *sum_out, int64_t *cell_sums_out,
+                            int64_t cell_sums_cap);
+
 /* ---- per-event flow table on the device: DVS_flow::get_accumulated (dvs_flow.h:351-389) -----------------------------
  * The -o table (every event once, with the flow of the first slice that solved it) built slice by slice on the device,
  * with the marking rule of bf::StreamEngine::get_accumulated (stream_flow.h), for slices cut from one event ring whose
