@@ -172,6 +172,7 @@ EXPORTS = [
     "bf_color_time_img", "bf_eval_sincos", "bf_device_numa_node", "bf_bind_thread_to_numa_node", "bf_bind_thread_to_device_numa",
     "bf_global_search_opts_default", "bf_global_set_window", "bf_global_project_all", "bf_global_search", "bf_global_get_events",
     "bf_global_set_cells", "bf_global_search_cells", "bf_global_search_cells_pyramid", "bf_global_project_cells",
+    "bf_global_project_field",
     "bf_emit_create", "bf_emit_destroy", "bf_emit_reset", "bf_emit_output", "bf_emit_slice", "bf_emit_wait", "bf_emit_release",
     "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
     "bf_flow_field", "bf_color_flow_img", "bf_flow_frame_create", "bf_flow_frame_destroy", "bf_flow_frame_render",
@@ -292,6 +293,7 @@ def load(path=None):
                                                      C.c_int64, C.c_void_p, C.c_int64, C.POINTER(GlobalPyramidInfo)]
         L.bf_global_project_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_int64), C.c_void_p, C.c_int64]
+        L.bf_global_project_field.argtypes = L.bf_global_project_cells.argtypes + [C.c_void_p] * 4
         L.bf_projection_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_color_time_img.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         L.bf_upload_ring_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
@@ -637,6 +639,32 @@ class Accel:
         if sums is not None:
             sums = sums[:nc].reshape(g.n_cell_x, g.n_cell_y)
         return img, sc, S.value, sums
+
+    def global_project_field(self, cell_nx, cell_ny, nz=127.0, want_img=True, want_scores=True, want_events=False,
+                             want_cell_sums=True):
+        """The interpolated field (bf_global_project_field): global_project_cells with the (nx, ny) of every event
+        interpolated between the centres of the cells around its recorded address.  cell_nx / cell_ny as there, but EVERY
+        entry is read and must be finite.  The per-event state is not touched.  Returns (blurred bordered image or None,
+        current_scores or None, S_f, S_f(cell) as int64 [n_cell_x, n_cell_y] or None) and, with want_events, a fifth item:
+        the dict of nx, ny (the interpolated values) and u, v (compute_uv of them), n doubles each in upload order."""
+        w, g = self._gwin, self._gcells   # None before global_set_window / global_set_cells: the library reports BF_ERR_ARG
+        nc = g.n_cell_x * g.n_cell_y if g else 0
+        cx = np.ascontiguousarray(np.asarray(cell_nx, dtype=np.float64).reshape(-1))
+        cy = np.ascontiguousarray(np.asarray(cell_ny, dtype=np.float64).reshape(-1))
+        if len(cx) != len(cy):
+            raise ValueError("cell_nx has %d entries, cell_ny %d" % (len(cx), len(cy)))
+        img = np.empty((w.scale_bordered_img_x, w.scale_bordered_img_y), dtype=np.uint8) if want_img and w else None
+        sc = np.empty((w.scale_img_x, w.scale_img_y), dtype=np.float32) if want_scores and w else None
+        sums = np.zeros(nc, dtype=np.int64) if want_cell_sums else None
+        keys = ("nx", "ny", "u", "v")
+        ev = {k: np.zeros(self.n, dtype=np.float64) for k in keys} if want_events else None
+        S = C.c_int64()
+        self._chk(self.L.bf_global_project_field(self.h, _ptr(cx), _ptr(cy), len(cx), nz, _ptr(img), _ptr(sc), C.byref(S),
+                                                 _ptr(sums), 0 if sums is None else len(sums),
+                                                 *[_ptr(ev[k]) if ev else None for k in keys]))
+        if sums is not None:
+            sums = sums[:nc].reshape(g.n_cell_x, g.n_cell_y)
+        return (img, sc, S.value, sums, ev) if want_events else (img, sc, S.value, sums)
 
     def global_get_events(self):
         """Per-event state in upload order: dict of max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v."""

@@ -22,6 +22,8 @@
 //   PW  bf_global_project_cells: one image of the slice with every event under its own cell's candidate:
 //       k_global_project_cells (G1 over the cell-ordered runs, all into plane 0), the unchanged G2 on that one plane, and
 //       k_global_score_cells (the score part of G3 per event, summed per cell); no per-event state is touched.
+//   PF  bf_global_project_field: PW with the candidate of every event interpolated between the cell centres around its
+//       address (include/bf_global_field.h): k_global_project_field, the unchanged G2, k_global_score_field.
 //
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
 // order in which work-groups run.
@@ -35,6 +37,7 @@
 #include "bf_device.h"
 #include "bf_device_fns.h"
 #include "bf_kernels.h"
+#include "../../include/bf_global_field.h"
 
 namespace bf {
 
@@ -371,6 +374,127 @@ __global__ __launch_bounds__(T) void k_global_score_cells(GlobalCells cl, Global
     }
 }
 
+// ---- the interpolated field (include/bf_accel.h, bf_global_project_field): every event under the flow interpolated
+// between the cell centres around its recorded address (include/bf_global_field.h) ----
+// The run's cell (ca, cb) is the same for every lane, and every event of it has its upper-left corner a0 in {ca - 1, ca},
+// b0 in {cb - 1, cb}: the four corners lie in the 3 x 3 neighbourhood of the cell, clamped at the borders of the grid
+// (where bf_field_axis_in_cell clamps too).  Those 18 doubles are read through wave-uniform addresses into scalar
+// registers; a lane picks its corners from them with selects -- no per-event gather from the tables.
+struct GlobalFieldNbhd {
+    double nx[3][3], ny[3][3];
+    uint32_t ca, cb;
+    __device__ __forceinline__ void load(const GlobalCellGrid& cg, uint32_t n_cell_x, uint32_t cell,
+                                         const double* __restrict__ cell_nx, const double* __restrict__ cell_ny) {
+        const uint32_t n_cell_y = (uint32_t)cg.n_cell_y;
+        ca = cell / n_cell_y; cb = cell - ca * n_cell_y;
+        const uint32_t ra[3] = {ca > 0u ? ca - 1u : 0u, ca, ca + 1u < n_cell_x ? ca + 1u : n_cell_x - 1u};
+        const uint32_t rb[3] = {cb > 0u ? cb - 1u : 0u, cb, cb + 1u < n_cell_y ? cb + 1u : n_cell_y - 1u};
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                nx[i][j] = cell_nx[ra[i] * n_cell_y + rb[j]];
+                ny[i][j] = cell_ny[ra[i] * n_cell_y + rb[j]];
+            }
+    }
+    // (nx_e, ny_e) of the event at address v, and the projection's (kx, ky) of it: make_cand's expressions
+    __device__ __forceinline__ GlobalCand at(const GlobalCellGrid& cg, uint32_t n_cell_x, uint32_t v, double nz) const {
+        uint32_t a0, a1, wx, b0, b1, wy;
+        bf_field_axis_in_cell(ca, (v & 0xffffu) - ca * (uint32_t)cg.cell_rows, (uint32_t)cg.cell_rows, n_cell_x, &a0, &a1, &wx);
+        bf_field_axis_in_cell(cb, (v >> 16) - cb * (uint32_t)cg.cell_cols, (uint32_t)cg.cell_cols, (uint32_t)cg.n_cell_y, &b0, &b1,
+                              &wy);
+        const double tx = bf_field_weight(wx, (uint32_t)cg.cell_rows), ty = bf_field_weight(wy, (uint32_t)cg.cell_cols);
+        // a0 == ca: rows (1, 2) of the neighbourhood, else a0 == ca - 1 >= 0: rows (0, 1); a1 is the second of the pair
+        // either way (row 2 is min(ca + 1, n_cell_x - 1)).  Likewise the columns.
+        const bool ha = a0 == ca, hb = b0 == cb;
+        double cx[2][2], cy[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            double rx[3], ry[3];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                rx[j] = ha ? nx[i + 1][j] : nx[i][j];
+                ry[j] = ha ? ny[i + 1][j] : ny[i][j];
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                cx[i][j] = hb ? rx[j + 1] : rx[j];
+                cy[i][j] = hb ? ry[j + 1] : ry[j];
+            }
+        }
+        GlobalCand c;
+        c.nx = bf_field_interp(cx[0][0], cx[0][1], cx[1][0], cx[1][1], tx, ty);
+        c.ny = bf_field_interp(cy[0][0], cy[0][1], cy[1][0], cy[1][1], tx, ty);
+        c.nz = nz;
+        c.kx = (float)((double)(float)c.nx / nz);
+        c.ky = (float)((double)(float)c.ny / nz);
+        return c;
+    }
+};
+
+// k_global_project_cells with the candidate interpolated per event.  ev_nx / ev_ny (null: not asked for): (nx_e, ny_e) of
+// EVERY event of the slice, accepted or not, at its upload index.
+template <int T>
+__global__ __launch_bounds__(T) void k_global_project_field(GlobalCells cl, GlobalGeom g, GlobalCellGrid cg, uint32_t n_cell_x,
+                                                            const double* __restrict__ cell_nx,
+                                                            const double* __restrict__ cell_ny, double nz,
+                                                            uint32_t* __restrict__ pts, double* __restrict__ ev_nx,
+                                                            double* __restrict__ ev_ny) {
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    GlobalFieldNbhd nb;
+    nb.load(cg, n_cell_x, cell, cell_nx, cell_ny);
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    if (j >= cl.cell_start[cell + 1]) return;
+    const uint32_t v = cl.xy[j];
+    const GlobalCand c = nb.at(cg, n_cell_x, v, nz);
+    if (ev_nx) {
+        const uint32_t e = cl.idx[j];   // the event's upload index
+        ev_nx[e] = c.nx; ev_ny[e] = c.ny;
+    }
+    double pr_x, pr_y;
+    int X, Y;
+    if (!global_pixel(g, c, v, cl.t[j], pr_x, pr_y, X, Y)) return;
+    const int off = g.scale / 2 + g.mw / 2;   // the splat's centre, as in k_global_project
+    atomicAdd(&pts[(size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)], 1u);
+}
+
+// k_global_score_cells with the same per-event candidate, recomputed.
+template <int T>
+__global__ __launch_bounds__(T) void k_global_score_field(GlobalCells cl, GlobalGeom g, GlobalCellGrid cg, uint32_t n_cell_x,
+                                                          const double* __restrict__ cell_nx,
+                                                          const double* __restrict__ cell_ny, double nz,
+                                                          const uint32_t* __restrict__ win, float* __restrict__ scores_out,
+                                                          unsigned long long* __restrict__ cell_sums) {
+    constexpr int kWaves = T / 64;
+    __shared__ unsigned long long s_part[kWaves];
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    GlobalFieldNbhd nb;
+    nb.load(cg, n_cell_x, cell, cell_nx, cell_ny);
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    unsigned long long contrib = 0;
+    if (j < cl.cell_start[cell + 1]) {
+        const uint32_t v = cl.xy[j];
+        double pr_x, pr_y;
+        int X, Y;
+        float f;
+        if (global_pixel(g, nb.at(cg, n_cell_x, v, nz), v, cl.t[j], pr_x, pr_y, X, Y))
+            contrib = global_score_pixel(g, 0, X, Y, win, scores_out, f);
+    }
+    const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
+    if (kWaves == 1) {
+        if (threadIdx.x == 63 && tot) atomicAdd(&cell_sums[cell], tot);
+    } else {
+        if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = tot;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            unsigned long long all = 0;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) all += s_part[w];
+            if (all) atomicAdd(&cell_sums[cell], all);
+        }
+    }
+}
+
 // One batch's block [cell][b], kGlobalCellStride threads per cell (8 cells per work-group).  Slot b is lattice point
 // k = ks[b], or k0 + b without a list.  The cell's best of the batch is its largest sum, lowest k among equals, and it
 // replaces the running best when it is larger, or as large with a lower k: the exhaustive rule (largest S, then lowest k)
@@ -580,6 +704,30 @@ int launch_global_piecewise(const GlobalCells& cells, const GlobalGeom& g, const
         hipLaunchKernelGGL(k_global_score_cells<64>, runs, dim3(64), 0, s, cells, g, cell_cands, win, scores_out, cell_sums);
     else
         hipLaunchKernelGGL(k_global_score_cells<kGT>, runs, dim3(kGT), 0, s, cells, g, cell_cands, win, scores_out, cell_sums);
+    return 0;
+}
+
+int launch_global_field(const GlobalCells& cells, const GlobalGeom& g, const GlobalCellGrid& cg, const double* cell_nx,
+                        const double* cell_ny, double nz, uint32_t* pts, uint32_t* win, uint8_t* img_out, float* scores_out,
+                        unsigned long long* cell_sums, double* ev_nx, double* ev_ny, hipStream_t s) {
+    if (cells.n_runs <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
+    if (g.scale / 2 > 3) return -1;
+    const dim3 runs((unsigned)cells.n_runs);
+    const uint32_t n_cell_x = (uint32_t)(cg.n_cells / cg.n_cell_y);
+    if (cells.run_len == 64)
+        hipLaunchKernelGGL(k_global_project_field<64>, runs, dim3(64), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, pts, ev_nx,
+                           ev_ny);
+    else
+        hipLaunchKernelGGL(k_global_project_field<kGT>, runs, dim3(kGT), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, pts, ev_nx,
+                           ev_ny);
+    const int tr = launch_global_tile(g, 1, pts, win, img_out, s);
+    if (tr != 0) return tr;
+    if (cells.run_len == 64)
+        hipLaunchKernelGGL(k_global_score_field<64>, runs, dim3(64), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, win,
+                           scores_out, cell_sums);
+    else
+        hipLaunchKernelGGL(k_global_score_field<kGT>, runs, dim3(kGT), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, win,
+                           scores_out, cell_sums);
     return 0;
 }
 

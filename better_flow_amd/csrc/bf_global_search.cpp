@@ -1,8 +1,8 @@
 // bf_global_search.cpp -- C-ABI of the exhaustive search, OptimizerGlobal (optimizer_global.h / optimizer_global.cpp): the window
 // (update_fields), one project_all, compute_flow_bruteforce over a candidate grid (per slice, and per cell of a grid over the
 // sensor), and the per-event state.  The kernels are in bf_global.hip; the definitions this build adds (the per-event best
-// candidate, the objective S, the objective per cell, the candidate set of a pyramid level, the piecewise projection) are
-// stated in include/bf_accel.h and DESIGN.md.
+// candidate, the objective S, the objective per cell, the candidate set of a pyramid level, the piecewise projection, the
+// interpolated field) are stated in include/bf_accel.h and DESIGN.md.
 #include "bf_ctx.h"
 
 struct GlobalSearch {
@@ -36,6 +36,9 @@ struct GlobalSearch {
         std::vector<GlobalCand> h_pw_cands;
         DevArray<GlobalCand> d_pw_cands;
         DevArray<unsigned long long> d_pw_sums;
+        // bf_global_project_field: the grid as two tables of n_cells doubles (nx, then ny) and, when asked for, the
+        // per-event (nx_e, ny_e) as two arrays of n doubles; its per-cell sums go through d_pw_sums
+        DevArray<double> d_field_grid, d_field_ev;
     } cells;
 
     // scratch of one bf_global_search_cells_pyramid call: the lattice bitmaps (one bit per k), the compaction's scratch,
@@ -711,6 +714,88 @@ int bf_global_project_cells(bf_ctx* c, const double* cell_nx, const double* cell
         if (cell_sums_out) cell_sums_out[i] = (int64_t)sums[(size_t)i];
     }
     if (sum_out) *sum_out = (int64_t)S;
+    return BF_OK;
+}
+
+int bf_global_project_field(bf_ctx* c, const double* cell_nx, const double* cell_ny, int64_t cells_cap, double nz,
+                            uint8_t* img_out, float* scores_out, int64_t* sum_out, int64_t* cell_sums_out,
+                            int64_t cell_sums_cap, double* event_nx_out, double* event_ny_out, double* event_u_out,
+                            double* event_v_out) {
+    if (!c) return BF_ERR_ARG;
+    int rc = global_ready(c);
+    if (rc != BF_OK) return rc;
+    GlobalSearch* gs = c->glob.get();
+    GlobalSearch::Cells& cs = gs->cells;
+    if (!cs.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    const long long nc = cs.cg.n_cells;
+    if (!cell_nx || !cell_ny) return fail(c, BF_ERR_ARG, "bf_global_project_field: no candidate grid");
+    if (cells_cap < nc) return fail(c, BF_ERR_ARG, "candidate grid holds %lld of %lld cells", (long long)cells_cap, nc);
+    if (cell_sums_out && cell_sums_cap < nc)
+        return fail(c, BF_ERR_ARG, "cell sum buffer holds %lld of %lld", (long long)cell_sums_cap, nc);
+    if (!(nz > 0)) return fail(c, BF_ERR_ARG, "bad nz");
+    // every cell is a corner for its neighbours, with events or without: all of the grid is read, and all of it must be
+    // finite in the float form the projection uses (make_cand's kx, ky; 1e39 is as infinite there as inf and NaN are)
+    for (long long i = 0; i < nc; ++i) {
+        const GlobalCand k = make_cand(cell_nx[i], cell_ny[i], nz);
+        if (!std::isfinite(k.kx) || !std::isfinite(k.ky))
+            return fail(c, BF_ERR_ARG, "the candidate of cell %lld is not finite as a float", i);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bf_global_window& w = gs->w;
+    const size_t img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
+    const size_t sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
+    const size_t n = (size_t)gs->n;
+    const bool want_ev = event_nx_out || event_ny_out || event_u_out || event_v_out;
+    if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
+    if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
+    if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
+    if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
+    std::vector<unsigned long long> sums((size_t)nc, 0ull);
+    std::vector<double> ev;   // (nx_e, then ny_e) of every event
+    if (n > 0) {   // (no event: nothing is launched, every sum is 0, the images are zero, no per-event value is written)
+        HIP_TRY(c, cs.d_field_grid.grow((size_t)nc * 2));
+        HIP_TRY(c, cs.d_pw_sums.grow((size_t)nc));
+        if (want_ev) {
+            HIP_TRY(c, cs.d_field_ev.grow(n * 2));
+            ev.resize(n * 2);
+        }
+        if ((rc = ensure_batch(c, gs, 1)) != BF_OK) return rc;
+        double* d_nx = cs.d_field_grid;
+        double* d_ny = d_nx + nc;
+        HIP_TRY(c, hipMemcpyAsync(d_nx, cell_nx, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_ny, cell_ny, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(cs.d_pw_sums, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
+        double* d_ev = want_ev ? cs.d_field_ev.get() : nullptr;
+        const int lr = launch_global_field(cells_view(gs, nullptr, 0), gs->g, cs.cg, d_nx, d_ny, nz, gs->d_pts, gs->d_win,
+                                           img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr,
+                                           cs.d_pw_sums, d_ev, d_ev ? d_ev + n : nullptr, c->stream);
+        if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
+        if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
+        if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(sums.data(), cs.d_pw_sums, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                  c->stream));
+        if (want_ev) HIP_TRY(c, hipMemcpyAsync(ev.data(), d_ev, n * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    if (img_out && img_px) HIP_TRY(c, hipMemcpyAsync(img_out, gs->d_img, img_px, hipMemcpyDeviceToHost, c->stream));
+    if (scores_out && sc_px)
+        HIP_TRY(c, hipMemcpyAsync(scores_out, gs->d_scores, sc_px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the caller's grids are read until here)
+    unsigned long long S = 0;
+    for (long long i = 0; i < nc; ++i) {
+        S += sums[(size_t)i];
+        if (cell_sums_out) cell_sums_out[i] = (int64_t)sums[(size_t)i];
+    }
+    if (sum_out) *sum_out = (int64_t)S;
+    for (size_t i = 0; want_ev && i < n; ++i) {   // u / v: compute_uv of the event's own (nx_e, ny_e), as bf_global_get_events
+        if (event_nx_out) event_nx_out[i] = ev[i];
+        if (event_ny_out) event_ny_out[i] = ev[n + i];
+        double u, v;
+        cand_uv(ev[i], ev[n + i], nz, &u, &v);
+        if (event_u_out) event_u_out[i] = u;
+        if (event_v_out) event_v_out[i] = v;
+    }
     return BF_OK;
 }
 

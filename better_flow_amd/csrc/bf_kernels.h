@@ -313,6 +313,13 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
 // the per-event state, block, best_sum and best_k are not touched.  < 0 as launch_global_batch.
 int launch_global_piecewise(const GlobalCells& cells, const GlobalGeom& g, const GlobalCand* cell_cands, uint32_t* pts,
                             uint32_t* win, uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
+// The interpolated field (include/bf_accel.h, bf_global_project_field): launch_global_piecewise with the candidate of every
+// event interpolated between the centres of the cells around its address (include/bf_global_field.h).  cell_nx / cell_ny:
+// [n_cells] on the device, ALL read (an empty cell is a corner for its neighbours).  ev_nx / ev_ny (null, or n doubles each):
+// the interpolated (nx, ny) of every event at its upload index (cells.idx).  < 0 as launch_global_batch.
+int launch_global_field(const GlobalCells& cells, const GlobalGeom& g, const GlobalCellGrid& cg, const double* cell_nx,
+                        const double* cell_ny, double nz, uint32_t* pts, uint32_t* win, uint8_t* img_out, float* scores_out,
+                        unsigned long long* cell_sums, double* ev_nx, double* ev_ny, hipStream_t s);
 // counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
 // events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);

@@ -348,6 +348,29 @@ public:
               "global_project_cells");
         return (long long)sum;
     }
+    // the interpolated field (bf_global_project_field): global_project_cells with every event's (nx, ny) interpolated
+    // between the cell centres; the whole grid is read.  events (may be null): four vectors, resized to the slice --
+    // the per-event nx, ny (interpolated) and u, v (compute_uv of them).  Returns S_f.
+    long long global_project_field(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz,
+                                   uint8_t *img_out, float *scores_out, std::vector<int64_t> *cell_sums,
+                                   std::vector<double> *events) {
+        if (global_n_cells && (cell_nx.size() != global_n_cells || cell_ny.size() != global_n_cells))
+            throw bf::AccelError(BF_ERR_ARG, "AccelLib::global_project_field: grids of " + std::to_string(cell_nx.size()) +
+                                                 " and " + std::to_string(cell_ny.size()) + " entries for " +
+                                                 std::to_string(global_n_cells) + " cells");
+        int64_t sum = 0;   // (without cells the library refuses, BF_ERR_ARG, before it reads a buffer)
+        std::vector<int64_t> sums(cell_sums ? global_n_cells : 0, 0);
+        std::vector<double> ev[4];
+        for (int k = 0; events && k < 4; ++k) ev[k].assign((size_t)size, 0.0);
+        double *ep[4];
+        for (int k = 0; k < 4; ++k) ep[k] = events && size ? ev[k].data() : nullptr;
+        check(bf_global_project_field(ctx, cell_nx.data(), cell_ny.data(), (int64_t)global_n_cells, nz, img_out, scores_out, &sum,
+                                      cell_sums ? sums.data() : nullptr, (int64_t)global_n_cells, ep[0], ep[1], ep[2], ep[3]),
+              "global_project_field");
+        if (cell_sums) cell_sums->swap(sums);   // (a refused call leaves the caller's vectors as they were)
+        for (int k = 0; events && k < 4; ++k) events[k].swap(ev[k]);
+        return (long long)sum;
+    }
     void global_get_events(double *max_score, double *best_nx, double *best_ny, double *best_pr_x, double *best_pr_y,
                            double *best_u, double *best_v) {
         check(bf_global_get_events(ctx, max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v), "global_get_events");

@@ -24,6 +24,13 @@
 // scored with every event under its own cell's (nx, ny) -- the compensated image and the objective S_pw of a per-cell
 // answer.  It folds nothing into the per-event state.
 //
+// A sixth: the interpolated field (project_field; include/bf_accel.h, bf_global_project_field; the arithmetic is
+// include/bf_global_field.h): project_cells with every event's (nx, ny) interpolated between the centres of the cells around
+// its recorded address -- a smooth field instead of steps at the cell borders --, which also gives a flow per event
+// (get_event_field).  project_field() takes the cell results after bf_field_fill: a cell with events == 0 or best_sum == 0
+// carries no answer and takes the (nx, ny) of the nearest cell that does.  write_field_flo writes the field sampled at every
+// sensor pixel as a .flo with write_cell_flo's conventions: width = res_y, height = res_x, horizontal = v, vertical = u.
+//
 // Each object stages its slice on a device context of its OWN (not the thread's shared one that OptimizerLocal and
 // OptimizerRolling use): the window and the per-event best state live there and accumulate over project_all /
 // compute_flow_bruteforce calls, so no other optimiser on the thread may replace them.  Objects are not copyable.
@@ -35,6 +42,7 @@
 #include <better_flow/datastructures.h>
 #include <better_flow/event.h>
 #include <better_flow/flow_field.h>
+#include <bf_global_field.h>
 
 #include <string>
 #include <vector>
@@ -67,7 +75,10 @@ protected:
     std::vector<bf_global_cell_result> cell_results;                      // [n_cell_x][n_cell_y]
     std::vector<int64_t> seeds;                                           // per cell: a lattice index or -1 (empty: none)
     bf_global_pyramid_info pyramid_info;
-    std::vector<int64_t> cell_sums;                                       // S_pw(cell) of the last project_cells
+    std::vector<int64_t> cell_sums;                                       // S_pw(cell) / S_f(cell) of the last project_cells / _field
+    std::vector<double> field_nx, field_ny;                               // the grid of the last project_field, and its nz
+    double field_nz = NZ;
+    std::vector<double> event_field[4];                                   // per event: nx, ny, u, v of the last project_field
 
     void ensure_cells() {   // the slice, the window and the cell grid are on the device
         this->stage();
@@ -218,6 +229,69 @@ public:
         return this->project_cells(cx, cy, this->range.nz);
     }
     const std::vector<int64_t> &get_cell_sums() const { return cell_sums; }   // [n_cell_x][n_cell_y]
+
+    // The interpolated field under one (nx, ny) per cell, row-major [n_cell_x][n_cell_y]; every entry is read and must be
+    // finite.  Refreshes project_img, current_scores, the per-cell sums (get_cell_sums) and the per-event field
+    // (get_event_field); the per-event best state is not touched.  Returns S_f.  A refused grid leaves the previous
+    // results in place.
+    long long project_field(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz_ = NZ) {
+        this->ensure_cells();
+        bf::Image2D<uint8_t> img(scale_bordered_img_x, scale_bordered_img_y);
+        std::vector<float> scores((size_t)scale_img_x * (size_t)scale_img_y, 0.0f);
+        const long long S = accel.global_project_field(cell_nx, cell_ny, nz_, img.ptr(0), scores.empty() ? nullptr : scores.data(),
+                                                       &this->cell_sums, this->event_field);
+        this->project_img = img;
+        this->current_scores.swap(scores);
+        this->field_nx = cell_nx; this->field_ny = cell_ny; this->field_nz = nz_;
+        this->last_sum = S;
+        return S;
+    }
+
+    // ... under the answers of the last compute_flow_cells / _pyramid / _seeded call after the fill (bf_field_fill: a cell
+    // is valid when events > 0 and best_sum > 0), with the search range's nz.  Throws when there are none.
+    long long project_field() {
+        if (this->cell_results.empty())
+            throw bf::AccelError(BF_ERR_STATE, "OptimizerGlobal::project_field: no per-cell results (call compute_flow_cells first)");
+        std::vector<double> cx, cy;
+        this->filled_cell_grid(&cx, &cy);
+        return this->project_field(cx, cy, this->range.nz);
+    }
+
+    // The cell results' (best_nx, best_ny) with the cells that carry no answer filled from their nearest valid neighbour
+    void filled_cell_grid(std::vector<double> *cx, std::vector<double> *cy) const {
+        const size_t nc = cell_results.size();
+        std::vector<uint8_t> valid(nc);
+        cx->assign(nc, 0.0); cy->assign(nc, 0.0);
+        for (size_t i = 0; i < nc; ++i) {
+            valid[i] = cell_results[i].events > 0 && cell_results[i].best_sum > 0 ? 1 : 0;
+            (*cx)[i] = cell_results[i].best_nx; (*cy)[i] = cell_results[i].best_ny;
+        }
+        if (nc) bf_field_fill(cell_grid.n_cell_x, cell_grid.n_cell_y, valid.data(), cx->data(), cy->data());
+    }
+
+    // Per event, in the cloud's order: the interpolated nx (k = 0), ny (1) and compute_uv of them, u (2), v (3), of the
+    // last project_field.
+    const std::vector<double> &get_event_field(int k) const { return event_field[k]; }
+    const std::vector<double> &get_field_nx() const { return field_nx; }   // the grid of the last project_field
+    const std::vector<double> &get_field_ny() const { return field_ny; }
+
+    // The field of the last project_field sampled at every pixel of the res_x x res_y sensor of set_cells, as a .flo (the
+    // conventions are at the top of this file): per pixel Event::compute_uv of the interpolated (nx, ny).
+    bool write_field_flo(const std::string &path) const {
+        if (field_nx.empty() || field_nx.size() != (size_t)cell_grid.n_cell_x * (size_t)cell_grid.n_cell_y) return false;
+        bf::FlowField f(cells_res_x, cells_res_y);
+        for (int x = 0; x < cells_res_x; ++x)
+            for (int y = 0; y < cells_res_y; ++y) {
+                double nx, ny;
+                bf_field_at((uint32_t)x, (uint32_t)y, (uint32_t)cell_rows, (uint32_t)cell_cols, (uint32_t)cell_grid.n_cell_x,
+                            (uint32_t)cell_grid.n_cell_y, field_nx.data(), field_ny.data(), &nx, &ny);
+                const size_t at = (size_t)x * cells_res_y + y;
+                f.owner[at] = 0;
+                bf_field_uv(nx, ny, field_nz, &f.u[at], &f.v[at]);
+            }
+        const std::vector<float> payload = bf::flo_payload(f);
+        return bf::write_flo(path, f.rows, f.cols, payload.data());
+    }
 
     void clear_seeds() { this->seeds.clear(); }
     const std::vector<int64_t> &get_seeds() const { return seeds; }

@@ -681,7 +681,7 @@ int bf_global_search_cells_pyramid(bf_ctx *ctx, const bf_global_search_opts *opt
  *   - The entry of a cell without events is never read: it may hold anything, NaN included.
  *   - Identity.  With the same (nx, ny) in every cell, img_out, scores_out and S_pw are bf_global_project_all(nx, ny, nz)'s
  *     outputs bit for bit.
- *   - Interpolating between cell centres (a smooth field) is not part of this definition.
+ *   - Interpolating between cell centres (a smooth field) is not part of this definition: bf_global_project_field below.
  * cell_nx / cell_ny: cells_cap entries each, row-major [n_cell_x][n_cell_y] like cells_out.  img_out, scores_out, sum_out
  * (S_pw) as in bf_global_project_all, each may be NULL; cell_sums_out (may be NULL; cell_sums_cap entries) S_pw(cell), row-major.
  * An empty cloud: every sum 0, the images zero, BF_OK.  BF_ERR_ARG without a window or cells, for a buffer shorter than the
@@ -691,6 +691,48 @@ int bf_global_search_cells_pyramid(bf_ctx *ctx, const bf_global_search_opts *opt
 int bf_global_project_cells(bf_ctx *ctx, const double *cell_nx, const double *cell_ny, int64_t cells_cap, double nz,
                             uint8_t *img_out, float *scores_out, int64_t *sum_out, int64_t *cell_sums_out,
                             int64_t cell_sums_cap);
+
+/* The interpolated field: the slice rendered and scored with every event under the flow interpolated between the cell
+ * centres around its recorded address.  A sixth definition of this build ("OptimizerGlobal"), beside
+ * bf_global_project_cells, over the same window and grid, given one candidate (nx_c, ny_c) per cell and a common nz.  The
+ * arithmetic is stated once, for device and host, in include/bf_global_field.h; every operation is an integer one or a
+ * single IEEE double operation (no contraction).
+ *   - Cell centres.  Cell a along the rows has its nominal centre at (a + 0.5) * cell_rows - 0.5 sensor pixels, likewise
+ *     along the columns; a ragged last cell keeps its nominal centre.
+ *   - Corners and weights, per axis, as integers.  For the recorded address x on an axis of n_cell cells of `size` pixels:
+ *     p = 2x + 1 - size, D = 2 * size, a0 = floor(p / D), w = p - a0 * D in [0, D); then a0 < 0 -> a0 = 0, w = 0, and
+ *     a0 >= n_cell - 1 -> a0 = n_cell - 1, w = 0; a1 = min(a0 + 1, n_cell - 1).  Beyond the outermost centres the field is
+ *     constant; an axis with one cell has no interpolation.
+ *   - Value per event, for nx and identically for ny, all double: tx = (double)wx / (double)Dx, ty = (double)wy / (double)Dy;
+ *     top = n00 + ty * (n01 - n00); bot = n10 + ty * (n11 - n10); nx_e = top + tx * (bot - top), with n_ab the grid value at
+ *     (row a_a, column b_b).  This order is part of the definition, for three identities: a uniform grid gives nx_e == n;
+ *     an event at a cell centre (w == 0 on both axes) gets its cell's value; cell_rows == cell_cols == 1 gives w == 0
+ *     everywhere.  (As values: a grid entry -0.0 comes back as +0.0.)
+ *   - Projection.  kx = (float)((double)(float)nx_e / nz), ky likewise: the expressions of every other candidate of this
+ *     family, evaluated per event on the device.  Every later step is bf_global_project_cells': the pixel truncation and
+ *     the acceptance test, the splat into ONE image, the 8-bit Gaussian, the window score.
+ *   - Objective.  S_f(cell) = sum of floor(score * 2^32) over the accepted events of the cell of the event's recorded
+ *     address; S_f = sum over the cells.  Exact int64, order free.
+ *   - The WHOLE grid is read -- a cell without events is still a corner for its neighbours -- and every one of its entries
+ *     must be finite in the projection's float form (as in bf_global_project_cells, but for every cell).
+ *     The check is on the entries, and is taken to bound the interpolated values: those lie between their corners up to
+ *     rounding.  An event whose own kx or ky still came out infinite or NaN (corners at opposite ends of the float range, a
+ *     tiny nz) fails the acceptance test like under any such candidate: it is not drawn and not scored.
+ *   - State.  As bf_global_project_cells: the per-event best state, the cells' running bests, the scratch of the pyramid
+ *     and the uploaded events are left alone; the call mixes freely with every other call of the family.
+ *   - Identities.  With the same (nx, ny) in every cell the outputs are bf_global_project_all(nx, ny, nz)'s bit for bit; with
+ *     cell_rows == cell_cols == 1 they are bf_global_project_cells' over the same grid.
+ * cell_nx / cell_ny, img_out, scores_out, sum_out (S_f), cell_sums_out (S_f(cell)) as in bf_global_project_cells.  Per-event
+ * outputs, n doubles each in upload order, each may be NULL: event_nx_out / event_ny_out the interpolated (nx_e, ny_e) of
+ * every event, accepted or not (written on the device, only when one of the four is asked for); event_u_out / event_v_out
+ * Event::compute_uv of them with nz, the expression of bf_global_get_events, on the host.  An empty cloud: every sum 0, the
+ * images zero, nothing written to the per-event outputs, BF_OK.  BF_ERR_ARG without a window or cells, for a buffer
+ * shorter than the grid, nz <= 0, or an entry of ANY cell that is not finite in the projection's float form; nothing ran
+ * then and every state and output is as before.  BF_ERR_STATE when an upload happened since bf_global_set_window. */
+int bf_global_project_field(bf_ctx *ctx, const double *cell_nx, const double *cell_ny, int64_t cells_cap, double nz,
+                            uint8_t *img_out, float *scores_out, int64_t *sum_out, int64_t *cell_sums_out,
+                            int64_t cell_sums_cap, double *event_nx_out, double *event_ny_out, double *event_u_out,
+                            double *event_v_out);
 
 /* ---- per-event flow table on the device: DVS_flow::get_accumulated (dvs_flow.h:351-389) -----------------------------
  * The -o table (every event once, with the flow of the first slice that solved it) built slice by slice on the device,
