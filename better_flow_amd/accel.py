@@ -617,6 +617,20 @@ class Accel:
             surf = surf[:nc * ne].reshape(g.n_cell_x, g.n_cell_y, ne)
         return r, cells[:nc].reshape(g.n_cell_x, g.n_cell_y), ev[:ne].copy(), surf, info
 
+    def _project_runs_args(self, cell_nx, cell_ny, want_img, want_scores, want_cell_sums):
+        """What global_project_cells and global_project_field pass alike: the grids as flat float64 arrays (ValueError when
+        their lengths differ) and the output buffers asked for, the per-cell sums as [n_cell_x, n_cell_y].  Returns
+        (cx, cy, img, sc, sums)."""
+        w, g = self._gwin, self._gcells   # None before global_set_window / global_set_cells: the library reports BF_ERR_ARG
+        cx = np.ascontiguousarray(np.asarray(cell_nx, dtype=np.float64).reshape(-1))
+        cy = np.ascontiguousarray(np.asarray(cell_ny, dtype=np.float64).reshape(-1))
+        if len(cx) != len(cy):
+            raise ValueError("cell_nx has %d entries, cell_ny %d" % (len(cx), len(cy)))
+        img = np.empty((w.scale_bordered_img_x, w.scale_bordered_img_y), dtype=np.uint8) if want_img and w else None
+        sc = np.empty((w.scale_img_x, w.scale_img_y), dtype=np.float32) if want_scores and w else None
+        sums = np.zeros((g.n_cell_x, g.n_cell_y) if g else 0, dtype=np.int64) if want_cell_sums else None
+        return cx, cy, img, sc, sums
+
     def global_project_cells(self, cell_nx, cell_ny, nz=127.0, want_img=True, want_scores=True, want_cell_sums=True):
         """The piecewise projection (bf_global_project_cells): the slice rendered and scored with every event under its own
         cell's (nx, ny).  cell_nx / cell_ny: n_cell_x * n_cell_y values in any shape, row-major [n_cell_x, n_cell_y] (for
@@ -624,20 +638,10 @@ class Accel:
         The per-event state is not touched.  want_cell_sums False passes no per-cell buffer, like want_img and want_scores
         for theirs.  Returns (blurred bordered image or None, current_scores or None, S_pw,
         S_pw(cell) as int64 [n_cell_x, n_cell_y] or None)."""
-        w, g = self._gwin, self._gcells   # None before global_set_window / global_set_cells: the library reports BF_ERR_ARG
-        nc = g.n_cell_x * g.n_cell_y if g else 0
-        cx = np.ascontiguousarray(np.asarray(cell_nx, dtype=np.float64).reshape(-1))
-        cy = np.ascontiguousarray(np.asarray(cell_ny, dtype=np.float64).reshape(-1))
-        if len(cx) != len(cy):
-            raise ValueError("cell_nx has %d entries, cell_ny %d" % (len(cx), len(cy)))
-        img = np.empty((w.scale_bordered_img_x, w.scale_bordered_img_y), dtype=np.uint8) if want_img and w else None
-        sc = np.empty((w.scale_img_x, w.scale_img_y), dtype=np.float32) if want_scores and w else None
-        sums = np.zeros(nc, dtype=np.int64) if want_cell_sums else None
+        cx, cy, img, sc, sums = self._project_runs_args(cell_nx, cell_ny, want_img, want_scores, want_cell_sums)
         S = C.c_int64()
         self._chk(self.L.bf_global_project_cells(self.h, _ptr(cx), _ptr(cy), len(cx), nz, _ptr(img), _ptr(sc), C.byref(S),
-                                                 _ptr(sums), 0 if sums is None else len(sums)))
-        if sums is not None:
-            sums = sums[:nc].reshape(g.n_cell_x, g.n_cell_y)
+                                                 _ptr(sums), 0 if sums is None else sums.size))
         return img, sc, S.value, sums
 
     def global_project_field(self, cell_nx, cell_ny, nz=127.0, want_img=True, want_scores=True, want_events=False,
@@ -647,23 +651,13 @@ class Accel:
         entry is read and must be finite.  The per-event state is not touched.  Returns (blurred bordered image or None,
         current_scores or None, S_f, S_f(cell) as int64 [n_cell_x, n_cell_y] or None) and, with want_events, a fifth item:
         the dict of nx, ny (the interpolated values) and u, v (compute_uv of them), n doubles each in upload order."""
-        w, g = self._gwin, self._gcells   # None before global_set_window / global_set_cells: the library reports BF_ERR_ARG
-        nc = g.n_cell_x * g.n_cell_y if g else 0
-        cx = np.ascontiguousarray(np.asarray(cell_nx, dtype=np.float64).reshape(-1))
-        cy = np.ascontiguousarray(np.asarray(cell_ny, dtype=np.float64).reshape(-1))
-        if len(cx) != len(cy):
-            raise ValueError("cell_nx has %d entries, cell_ny %d" % (len(cx), len(cy)))
-        img = np.empty((w.scale_bordered_img_x, w.scale_bordered_img_y), dtype=np.uint8) if want_img and w else None
-        sc = np.empty((w.scale_img_x, w.scale_img_y), dtype=np.float32) if want_scores and w else None
-        sums = np.zeros(nc, dtype=np.int64) if want_cell_sums else None
+        cx, cy, img, sc, sums = self._project_runs_args(cell_nx, cell_ny, want_img, want_scores, want_cell_sums)
         keys = ("nx", "ny", "u", "v")
         ev = {k: np.zeros(self.n, dtype=np.float64) for k in keys} if want_events else None
         S = C.c_int64()
         self._chk(self.L.bf_global_project_field(self.h, _ptr(cx), _ptr(cy), len(cx), nz, _ptr(img), _ptr(sc), C.byref(S),
-                                                 _ptr(sums), 0 if sums is None else len(sums),
+                                                 _ptr(sums), 0 if sums is None else sums.size,
                                                  *[_ptr(ev[k]) if ev else None for k in keys]))
-        if sums is not None:
-            sums = sums[:nc].reshape(g.n_cell_x, g.n_cell_y)
         return (img, sc, S.value, sums, ev) if want_events else (img, sc, S.value, sums)
 
     def global_get_events(self):

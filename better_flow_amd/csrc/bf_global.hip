@@ -20,10 +20,11 @@
 //       ascending list of k, k_global_cands_from_lattice), scored by the unchanged G1, G2 and G3c; the batch carries the
 //       lattice k of each slot (GlobalCells::ks), by which k_global_cells_best breaks ties.
 //   PW  bf_global_project_cells: one image of the slice with every event under its own cell's candidate:
-//       k_global_project_cells (G1 over the cell-ordered runs, all into plane 0), the unchanged G2 on that one plane, and
-//       k_global_score_cells (the score part of G3 per event, summed per cell); no per-event state is touched.
-//   PF  bf_global_project_field: PW with the candidate of every event interpolated between the cell centres around its
-//       address (include/bf_global_field.h): k_global_project_field, the unchanged G2, k_global_score_field.
+//       k_global_project_runs (G1 over the cell-ordered runs, all into plane 0), the unchanged G2 on that one plane, and
+//       k_global_score_runs (the score part of G3 per event, summed per cell); no per-event state is touched.  Both take the
+//       event's candidate from a source, here the per-cell table (GlobalTableSource).
+//   PF  bf_global_project_field: PW, the same two kernels, with the source that interpolates the candidate of every event
+//       between the cell centres around its address (GlobalFieldSource; include/bf_global_field.h).
 //
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
 // order in which work-groups run.
@@ -321,59 +322,6 @@ __global__ __launch_bounds__(T) void k_global_fold_cells(GlobalCells cl, GlobalG
     }
 }
 
-// ---- the piecewise projection (include/bf_accel.h, bf_global_project_cells): every event under its own cell's candidate ----
-// G1 over the runs of k_global_fold_cells: one work-group per run, so the cell -- and with it the candidate, read from the
-// [n_cells] table through a wave-uniform address -- is the same for every lane.  All cells splat into plane 0.
-template <int T>
-__global__ __launch_bounds__(T) void k_global_project_cells(GlobalCells cl, GlobalGeom g,
-                                                            const GlobalCand* __restrict__ cell_cands,
-                                                            uint32_t* __restrict__ pts) {
-    const uint32_t cell = cl.run_cell[blockIdx.x];
-    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
-    if (j >= cl.cell_start[cell + 1]) return;
-    const GlobalCand c = cell_cands[cell];
-    double pr_x, pr_y;
-    int X, Y;
-    if (!global_pixel(g, c, cl.xy[j], cl.t[j], pr_x, pr_y, X, Y)) return;
-    const int off = g.scale / 2 + g.mw / 2;   // the splat's centre, as in k_global_project
-    atomicAdd(&pts[(size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)], 1u);
-}
-
-// G3 of the piecewise projection over the same runs: per event global_score_pixel at its pixel under its cell's candidate
-// (window plane 0), then the work-group's total into cell_sums[cell] with one 64-bit atomic (none when it is 0), summed as
-// in k_global_fold_cells.  The per-event state is neither read nor written.
-template <int T>
-__global__ __launch_bounds__(T) void k_global_score_cells(GlobalCells cl, GlobalGeom g,
-                                                          const GlobalCand* __restrict__ cell_cands,
-                                                          const uint32_t* __restrict__ win, float* __restrict__ scores_out,
-                                                          unsigned long long* __restrict__ cell_sums) {
-    constexpr int kWaves = T / 64;
-    __shared__ unsigned long long s_part[kWaves];
-    const uint32_t cell = cl.run_cell[blockIdx.x];
-    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
-    unsigned long long contrib = 0;
-    if (j < cl.cell_start[cell + 1]) {
-        double pr_x, pr_y;
-        int X, Y;
-        float f;
-        if (global_pixel(g, cell_cands[cell], cl.xy[j], cl.t[j], pr_x, pr_y, X, Y))
-            contrib = global_score_pixel(g, 0, X, Y, win, scores_out, f);
-    }
-    const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
-    if (kWaves == 1) {
-        if (threadIdx.x == 63 && tot) atomicAdd(&cell_sums[cell], tot);
-    } else {
-        if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = tot;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            unsigned long long all = 0;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) all += s_part[w];
-            if (all) atomicAdd(&cell_sums[cell], all);
-        }
-    }
-}
-
 // ---- the interpolated field (include/bf_accel.h, bf_global_project_field): every event under the flow interpolated
 // between the cell centres around its recorded address (include/bf_global_field.h) ----
 // The run's cell (ca, cb) is the same for every lane, and every event of it has its upper-left corner a0 in {ca - 1, ca},
@@ -432,57 +380,46 @@ struct GlobalFieldNbhd {
     }
 };
 
-// k_global_project_cells with the candidate interpolated per event.  ev_nx / ev_ny (null: not asked for): (nx_e, ny_e) of
-// EVERY event of the slice, accepted or not, at its upload index.
-template <int T>
-__global__ __launch_bounds__(T) void k_global_project_field(GlobalCells cl, GlobalGeom g, GlobalCellGrid cg, uint32_t n_cell_x,
-                                                            const double* __restrict__ cell_nx,
-                                                            const double* __restrict__ cell_ny, double nz,
-                                                            uint32_t* __restrict__ pts, double* __restrict__ ev_nx,
-                                                            double* __restrict__ ev_ny) {
-    const uint32_t cell = cl.run_cell[blockIdx.x];
-    GlobalFieldNbhd nb;
-    nb.load(cg, n_cell_x, cell, cell_nx, cell_ny);
-    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
-    if (j >= cl.cell_start[cell + 1]) return;
-    const uint32_t v = cl.xy[j];
-    const GlobalCand c = nb.at(cg, n_cell_x, v, nz);
-    if (ev_nx) {
-        const uint32_t e = cl.idx[j];   // the event's upload index
+// ---- the projections over cell runs (include/bf_accel.h): bf_global_project_cells and bf_global_project_field ----
+// Where the candidate of an event comes from is a source: a plain struct passed to the kernel by value, with
+//   Run               what it keeps per run, in registers;
+//   load(run, cell)   once per work-group: the run's cell is the same for every lane, so its reads go through wave-uniform
+//                     addresses;
+//   at(run, v)        the candidate of the event at address v;
+//   store_event(...)  whatever it writes per event of the slice, accepted or not (the projecting kernel only).
+// The kernels below are instantiated per (run length, source): nothing about the source is decided while they run.
+
+// The per-cell table (bf_global_project_cells): every event under its own cell's candidate.
+struct GlobalTableSource : GlobalCandTable {
+    using Run = GlobalCand;
+    __device__ __forceinline__ void load(Run& run, uint32_t cell) const { run = cell_cands[cell]; }
+    __device__ __forceinline__ GlobalCand at(const Run& run, uint32_t) const { return run; }
+    __device__ __forceinline__ void store_event(const GlobalCand&, const uint32_t*, uint32_t) const {}
+};
+
+// The interpolated field (bf_global_project_field): the neighbourhood of the run's cell, then the candidate per event.
+// ev_nx / ev_ny (null: not asked for): (nx_e, ny_e) of the event at its upload index.
+struct GlobalFieldSource : GlobalCandField {
+    using Run = GlobalFieldNbhd;
+    __device__ __forceinline__ void load(Run& run, uint32_t cell) const { run.load(cg, n_cell_x, cell, cell_nx, cell_ny); }
+    __device__ __forceinline__ GlobalCand at(const Run& run, uint32_t v) const { return run.at(cg, n_cell_x, v, nz); }
+    __device__ __forceinline__ void store_event(const GlobalCand& c, const uint32_t* __restrict__ idx, uint32_t j) const {
+        if (!ev_nx) return;
+        const uint32_t e = idx[j];   // the event's upload index
         ev_nx[e] = c.nx; ev_ny[e] = c.ny;
     }
-    double pr_x, pr_y;
-    int X, Y;
-    if (!global_pixel(g, c, v, cl.t[j], pr_x, pr_y, X, Y)) return;
-    const int off = g.scale / 2 + g.mw / 2;   // the splat's centre, as in k_global_project
-    atomicAdd(&pts[(size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)], 1u);
-}
+};
 
-// k_global_score_cells with the same per-event candidate, recomputed.
+// The total of `contrib` over the work-group of T threads, all of which call this, into *out with one 64-bit atomic (none
+// when it is 0).  T == 64: the wave's total is the work-group's.  T == 256: lane 63 of each wave parks its total in LDS,
+// and after one barrier thread 0 adds the four.
 template <int T>
-__global__ __launch_bounds__(T) void k_global_score_field(GlobalCells cl, GlobalGeom g, GlobalCellGrid cg, uint32_t n_cell_x,
-                                                          const double* __restrict__ cell_nx,
-                                                          const double* __restrict__ cell_ny, double nz,
-                                                          const uint32_t* __restrict__ win, float* __restrict__ scores_out,
-                                                          unsigned long long* __restrict__ cell_sums) {
+__device__ __forceinline__ void global_group_total(unsigned long long contrib, unsigned long long* __restrict__ out) {
     constexpr int kWaves = T / 64;
     __shared__ unsigned long long s_part[kWaves];
-    const uint32_t cell = cl.run_cell[blockIdx.x];
-    GlobalFieldNbhd nb;
-    nb.load(cg, n_cell_x, cell, cell_nx, cell_ny);
-    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
-    unsigned long long contrib = 0;
-    if (j < cl.cell_start[cell + 1]) {
-        const uint32_t v = cl.xy[j];
-        double pr_x, pr_y;
-        int X, Y;
-        float f;
-        if (global_pixel(g, nb.at(cg, n_cell_x, v, nz), v, cl.t[j], pr_x, pr_y, X, Y))
-            contrib = global_score_pixel(g, 0, X, Y, win, scores_out, f);
-    }
     const unsigned long long tot = (unsigned long long)wave_total_dpp((long long)contrib);
     if (kWaves == 1) {
-        if (threadIdx.x == 63 && tot) atomicAdd(&cell_sums[cell], tot);
+        if (threadIdx.x == 63 && tot) atomicAdd(out, tot);
     } else {
         if ((threadIdx.x & 63) == 63) s_part[threadIdx.x >> 6] = tot;
         __syncthreads();
@@ -490,9 +427,49 @@ __global__ __launch_bounds__(T) void k_global_score_field(GlobalCells cl, Global
             unsigned long long all = 0;
 #pragma unroll
             for (int w = 0; w < kWaves; ++w) all += s_part[w];
-            if (all) atomicAdd(&cell_sums[cell], all);
+            if (all) atomicAdd(out, all);
         }
     }
+}
+
+// G1 over the runs of k_global_fold_cells, one work-group per run; all cells splat into plane 0.
+template <int T, class Src>
+__global__ __launch_bounds__(T) void k_global_project_runs(GlobalCells cl, GlobalGeom g, Src src, uint32_t* __restrict__ pts) {
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    typename Src::Run run;
+    src.load(run, cell);
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    if (j >= cl.cell_start[cell + 1]) return;
+    const uint32_t v = cl.xy[j];
+    const GlobalCand c = src.at(run, v);
+    src.store_event(c, cl.idx, j);
+    double pr_x, pr_y;
+    int X, Y;
+    if (!global_pixel(g, c, v, cl.t[j], pr_x, pr_y, X, Y)) return;
+    const int off = g.scale / 2 + g.mw / 2;   // the splat's centre, as in k_global_project
+    atomicAdd(&pts[(size_t)(X + off) * (size_t)g.Cb + (size_t)(Y + off)], 1u);
+}
+
+// G3 over the same runs: per event global_score_pixel at its pixel under its candidate, recomputed (window plane 0), then
+// the work-group's total into cell_sums[cell].  The per-event state is neither read nor written.
+template <int T, class Src>
+__global__ __launch_bounds__(T) void k_global_score_runs(GlobalCells cl, GlobalGeom g, Src src, const uint32_t* __restrict__ win,
+                                                         float* __restrict__ scores_out,
+                                                         unsigned long long* __restrict__ cell_sums) {
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    typename Src::Run run;
+    src.load(run, cell);
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    unsigned long long contrib = 0;
+    if (j < cl.cell_start[cell + 1]) {
+        const uint32_t v = cl.xy[j];
+        double pr_x, pr_y;
+        int X, Y;
+        float f;
+        if (global_pixel(g, src.at(run, v), v, cl.t[j], pr_x, pr_y, X, Y))
+            contrib = global_score_pixel(g, 0, X, Y, win, scores_out, f);
+    }
+    global_group_total<T>(contrib, &cell_sums[cell]);
 }
 
 // One batch's block [cell][b], kGlobalCellStride threads per cell (8 cells per work-group).  Slot b is lattice point
@@ -662,6 +639,25 @@ int launch_global_tile(const GlobalGeom& g, int nb, const uint32_t* pts, uint32_
     hipLaunchKernelGGL(k, grid, dim3(kGT), lds, s, pts, g, win, img_out);
     return 0;
 }
+// A kernel over the cell runs, compiled for both run lengths: one work-group of cells.run_len (64 or kGT) threads per run.
+template <class T> struct AsIs { using type = T; };   // (the argument types come from the kernel, not from the call)
+template <class... A>
+void launch_over_runs(const GlobalCells& cells, hipStream_t s, void (*k64)(A...), void (*k256)(A...), typename AsIs<A>::type... args) {
+    const bool one_wave = cells.run_len == 64;
+    hipLaunchKernelGGL(one_wave ? k64 : k256, dim3((unsigned)cells.n_runs), dim3(one_wave ? 64 : kGT), 0, s, args...);
+}
+
+template <class Src>
+int launch_runs(const GlobalCells& cells, const GlobalGeom& g, const Src& src, uint32_t* pts, uint32_t* win, uint8_t* img_out,
+                float* scores_out, unsigned long long* cell_sums, hipStream_t s) {
+    if (cells.n_runs <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
+    if (g.scale / 2 > 3) return -1;
+    launch_over_runs(cells, s, k_global_project_runs<64, Src>, k_global_project_runs<kGT, Src>, cells, g, src, pts);
+    const int tr = launch_global_tile(g, 1, pts, win, img_out, s);
+    if (tr != 0) return tr;
+    launch_over_runs(cells, s, k_global_score_runs<64, Src>, k_global_score_runs<kGT, Src>, cells, g, src, win, scores_out, cell_sums);
+    return 0;
+}
 }  // namespace
 
 int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalGeom& g,
@@ -679,56 +675,21 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
         hipLaunchKernelGGL(k_global_fold, dim3(eg), dim3(kGT), 0, s, xy, t, perm, n, g, cands, nb, win, st, S, scores_out);
         return 0;
     }
-    if (cells->run_len == 64)
-        hipLaunchKernelGGL(k_global_fold_cells<64>, dim3((unsigned)cells->n_runs), dim3(64), 0, s, *cells, g, cands, nb, win, st);
-    else
-        hipLaunchKernelGGL(k_global_fold_cells<kGT>, dim3((unsigned)cells->n_runs), dim3(kGT), 0, s, *cells, g, cands, nb, win, st);
+    launch_over_runs(*cells, s, k_global_fold_cells<64>, k_global_fold_cells<kGT>, *cells, g, cands, nb, win, st);
     constexpr int per = kGT / kGlobalCellStride;
     const dim3 cgrid((unsigned)((cells->n_cells + per - 1) / per));
     hipLaunchKernelGGL(k_global_cells_best, cgrid, dim3(kGT), 0, s, *cells, nb, S);
     return 0;
 }
 
-int launch_global_piecewise(const GlobalCells& cells, const GlobalGeom& g, const GlobalCand* cell_cands, uint32_t* pts,
-                            uint32_t* win, uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s) {
-    if (cells.n_runs <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
-    if (g.scale / 2 > 3) return -1;
-    const dim3 runs((unsigned)cells.n_runs);
-    if (cells.run_len == 64)
-        hipLaunchKernelGGL(k_global_project_cells<64>, runs, dim3(64), 0, s, cells, g, cell_cands, pts);
-    else
-        hipLaunchKernelGGL(k_global_project_cells<kGT>, runs, dim3(kGT), 0, s, cells, g, cell_cands, pts);
-    const int tr = launch_global_tile(g, 1, pts, win, img_out, s);
-    if (tr != 0) return tr;
-    if (cells.run_len == 64)
-        hipLaunchKernelGGL(k_global_score_cells<64>, runs, dim3(64), 0, s, cells, g, cell_cands, win, scores_out, cell_sums);
-    else
-        hipLaunchKernelGGL(k_global_score_cells<kGT>, runs, dim3(kGT), 0, s, cells, g, cell_cands, win, scores_out, cell_sums);
-    return 0;
+int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const GlobalCandTable& src, uint32_t* pts, uint32_t* win,
+                       uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s) {
+    return launch_runs(cells, g, GlobalTableSource{src}, pts, win, img_out, scores_out, cell_sums, s);
 }
 
-int launch_global_field(const GlobalCells& cells, const GlobalGeom& g, const GlobalCellGrid& cg, const double* cell_nx,
-                        const double* cell_ny, double nz, uint32_t* pts, uint32_t* win, uint8_t* img_out, float* scores_out,
-                        unsigned long long* cell_sums, double* ev_nx, double* ev_ny, hipStream_t s) {
-    if (cells.n_runs <= 0 || g.Rb <= 0 || g.Cb <= 0) return 0;
-    if (g.scale / 2 > 3) return -1;
-    const dim3 runs((unsigned)cells.n_runs);
-    const uint32_t n_cell_x = (uint32_t)(cg.n_cells / cg.n_cell_y);
-    if (cells.run_len == 64)
-        hipLaunchKernelGGL(k_global_project_field<64>, runs, dim3(64), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, pts, ev_nx,
-                           ev_ny);
-    else
-        hipLaunchKernelGGL(k_global_project_field<kGT>, runs, dim3(kGT), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, pts, ev_nx,
-                           ev_ny);
-    const int tr = launch_global_tile(g, 1, pts, win, img_out, s);
-    if (tr != 0) return tr;
-    if (cells.run_len == 64)
-        hipLaunchKernelGGL(k_global_score_field<64>, runs, dim3(64), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, win,
-                           scores_out, cell_sums);
-    else
-        hipLaunchKernelGGL(k_global_score_field<kGT>, runs, dim3(kGT), 0, s, cells, g, cg, n_cell_x, cell_nx, cell_ny, nz, win,
-                           scores_out, cell_sums);
-    return 0;
+int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const GlobalCandField& src, uint32_t* pts, uint32_t* win,
+                       uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s) {
+    return launch_runs(cells, g, GlobalFieldSource{src}, pts, win, img_out, scores_out, cell_sums, s);
 }
 
 void launch_global_stride_mark(const GlobalLattice& lt, long long stride, uint32_t* level, hipStream_t s) {

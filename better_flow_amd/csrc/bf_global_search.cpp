@@ -63,8 +63,6 @@ struct GlobalSearch {
 
 void GlobalSearchFree::operator()(GlobalSearch* g) const { delete g; }
 
-extern "C" {
-
 namespace {
 
 constexpr long long kGlobalBatchBytes = 512ll << 20;   // point + window planes of one batch
@@ -102,6 +100,15 @@ int global_ready(bf_ctx* c) {
     return BF_OK;
 }
 
+// what a launcher of bf_global.hip returned, and the launches' own errors, as the call's result
+int launch_rc(bf_ctx* c, const GlobalSearch* gs, int lr) {
+    if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
+    if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
+    if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
+    HIP_TRY(c, hipGetLastError());
+    return BF_OK;
+}
+
 // the k candidates at d_cands: S into d_S, folded into the per-event state.
 // cells (may be null): the per-cell form of the fold, batch after batch; its k0 and ks advance with the batches
 int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k, uint8_t* d_img, float* d_scores, GlobalCells* cells = nullptr) {
@@ -115,12 +122,9 @@ int run_candidates(bf_ctx* c, GlobalSearch* gs, long long k, uint8_t* d_img, flo
     for (long long b0 = 0; b0 < k; b0 += B) {
         const int nb = (int)std::min((long long)B, k - b0);
         HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)nb * (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
-        const int lr = launch_global_batch(e.xy, e.t, perm, gs->n, gs->g, gs->d_cands + b0, nb, gs->d_pts, gs->d_win, d_img,
-                                           gs->state(), gs->d_S + b0, d_scores, cells, c->stream);
-        if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
-        if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
-        if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
-        HIP_TRY(c, hipGetLastError());
+        rc = launch_rc(c, gs, launch_global_batch(e.xy, e.t, perm, gs->n, gs->g, gs->d_cands + b0, nb, gs->d_pts, gs->d_win, d_img,
+                                                  gs->state(), gs->d_S + b0, d_scores, cells, c->stream));
+        if (rc != BF_OK) return rc;
         if (cells) {
             cells->k0 += nb;
             if (cells->ks) cells->ks += nb;
@@ -246,7 +250,100 @@ void write_cells(bf_global_cell_result* out, const GlobalSearch* gs, const std::
     }
 }
 
+// The blurred image and current_scores of one projection, for the outputs the caller asked for (a null one is neither
+// rendered nor copied): begin() leaves their device buffers zeroed for the launches (d_img / d_scores: null when not asked
+// for), copy_back() queues the copies to the caller.
+struct ProjectionOut {
+    uint8_t* img_out; float* scores_out;
+    size_t img_px = 0, sc_px = 0;
+    uint8_t* d_img = nullptr; float* d_scores = nullptr;
+    ProjectionOut(uint8_t* img, float* scores) : img_out(img), scores_out(scores) {}
+    int begin(bf_ctx* c, GlobalSearch* gs) {
+        const bf_global_window& w = gs->w;
+        img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
+        sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
+        if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
+        if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
+        if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
+        if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
+        d_img = img_out ? gs->d_img.get() : nullptr;
+        d_scores = scores_out ? gs->d_scores.get() : nullptr;
+        return BF_OK;
+    }
+    int copy_back(bf_ctx* c, GlobalSearch* gs) const {
+        if (img_out && img_px) HIP_TRY(c, hipMemcpyAsync(img_out, gs->d_img, img_px, hipMemcpyDeviceToHost, c->stream));
+        if (scores_out && sc_px)
+            HIP_TRY(c, hipMemcpyAsync(scores_out, gs->d_scores, sc_px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        return BF_OK;
+    }
+};
+
+// The checks bf_global_project_cells and bf_global_project_field share, in their order; `who`: the entry point's name
+int check_project_runs(bf_ctx* c, const char* who, const double* cell_nx, const double* cell_ny, int64_t cells_cap, double nz,
+                       const int64_t* cell_sums_out, int64_t cell_sums_cap) {
+    int rc = global_ready(c);
+    if (rc != BF_OK) return rc;
+    if (!c->glob->cells.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
+    const long long nc = c->glob->cells.cg.n_cells;
+    if (!cell_nx || !cell_ny) return fail(c, BF_ERR_ARG, "%s: no candidate grid", who);
+    if (cells_cap < nc) return fail(c, BF_ERR_ARG, "candidate grid holds %lld of %lld cells", (long long)cells_cap, nc);
+    if (cell_sums_out && cell_sums_cap < nc)
+        return fail(c, BF_ERR_ARG, "cell sum buffer holds %lld of %lld", (long long)cell_sums_cap, nc);
+    if (!(nz > 0)) return fail(c, BF_ERR_ARG, "bad nz");
+    return BF_OK;
+}
+
+// The per-cell sums at d_pw_sums (have false: nothing was launched, all zero) to the host, the stream waited for, and
+// their total: at most 65 536 values, added on the host after the one copy that brought them back
+int fetch_cell_sums(bf_ctx* c, GlobalSearch* gs, bool have, int64_t* sum_out, int64_t* cell_sums_out) {
+    const size_t nc = (size_t)gs->cells.cg.n_cells;
+    std::vector<unsigned long long> sums(nc, 0ull);
+    if (have)
+        HIP_TRY(c, hipMemcpyAsync(sums.data(), gs->cells.d_pw_sums, nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                  c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    unsigned long long S = 0;
+    for (size_t i = 0; i < nc; ++i) {
+        S += sums[i];
+        if (cell_sums_out) cell_sums_out[i] = (int64_t)sums[i];
+    }
+    if (sum_out) *sum_out = (int64_t)S;
+    return BF_OK;
+}
+
+// What bf_global_project_cells and bf_global_project_field do once their own checks have passed: the slice rendered and
+// scored with every event's candidate taken from `src` (a GlobalCandTable or a GlobalCandField whose device arrays the
+// caller has queued the uploads of; not used when the slice has no event: then nothing is launched, every sum is 0 and the
+// images are zero).  `also` (bytes 0: nothing): one more array the launches wrote, brought back with the rest.  Ends with
+// the call's one synchronise: whatever host memory the caller's uploads read is free after it.
+struct AlsoBack {
+    void* dst = nullptr; const void* d_src = nullptr; size_t bytes = 0;
+};
+template <class Src>
+int project_runs(bf_ctx* c, GlobalSearch* gs, const Src& src, uint8_t* img_out, float* scores_out, int64_t* sum_out,
+                 int64_t* cell_sums_out, const AlsoBack& also = AlsoBack()) {
+    GlobalSearch::Cells& cs = gs->cells;
+    const size_t nc = (size_t)cs.cg.n_cells;
+    ProjectionOut po(img_out, scores_out);
+    int rc = po.begin(c, gs);
+    if (rc != BF_OK) return rc;
+    if (gs->n > 0) {
+        HIP_TRY(c, cs.d_pw_sums.grow(nc));
+        if ((rc = ensure_batch(c, gs, 1)) != BF_OK) return rc;
+        HIP_TRY(c, hipMemsetAsync(cs.d_pw_sums, 0, nc * sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
+        rc = launch_rc(c, gs, launch_global_runs(cells_view(gs, nullptr, 0), gs->g, src, gs->d_pts, gs->d_win, po.d_img, po.d_scores,
+                                                 cs.d_pw_sums, c->stream));
+        if (rc != BF_OK) return rc;
+        if (also.bytes) HIP_TRY(c, hipMemcpyAsync(also.dst, also.d_src, also.bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    if ((rc = po.copy_back(c, gs)) != BF_OK) return rc;
+    return fetch_cell_sums(c, gs, gs->n > 0, sum_out, cell_sums_out);
+}
+
 }  // namespace
+
+extern "C" {
 
 void bf_global_search_opts_default(bf_global_search_opts* o) {
     if (!o) return;
@@ -314,24 +411,16 @@ int bf_global_project_all(bf_ctx* c, double nx, double ny, double nz, uint8_t* i
     if (rc != BF_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     GlobalSearch* gs = c->glob.get();
-    const bf_global_window& w = gs->w;
-    const size_t img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
-    const size_t sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
     if ((rc = ensure_cands(c, gs, 1)) != BF_OK) return rc;
-    if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
-    if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
+    ProjectionOut po(img_out, scores_out);
     gs->h_cands.assign(1, make_cand(nx, ny, nz));
     HIP_TRY(c, hipMemcpyAsync(gs->d_cands, gs->h_cands.data(), sizeof(GlobalCand), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(gs->d_S, 0, sizeof(unsigned long long), c->stream));
-    if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
-    if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
-    if ((rc = run_candidates(c, gs, 1, img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr)) != BF_OK)
-        return rc;
+    if ((rc = po.begin(c, gs)) != BF_OK) return rc;
+    if ((rc = run_candidates(c, gs, 1, po.d_img, po.d_scores)) != BF_OK) return rc;
     unsigned long long S = 0;
     HIP_TRY(c, hipMemcpyAsync(&S, gs->d_S, sizeof(S), hipMemcpyDeviceToHost, c->stream));
-    if (img_out && img_px) HIP_TRY(c, hipMemcpyAsync(img_out, gs->d_img, img_px, hipMemcpyDeviceToHost, c->stream));
-    if (scores_out && sc_px)
-        HIP_TRY(c, hipMemcpyAsync(scores_out, gs->d_scores, sc_px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if ((rc = po.copy_back(c, gs)) != BF_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (sum_out) *sum_out = (int64_t)S;
     return BF_OK;
@@ -656,17 +745,11 @@ int bf_global_project_cells(bf_ctx* c, const double* cell_nx, const double* cell
                             uint8_t* img_out, float* scores_out, int64_t* sum_out, int64_t* cell_sums_out,
                             int64_t cell_sums_cap) {
     if (!c) return BF_ERR_ARG;
-    int rc = global_ready(c);
+    int rc = check_project_runs(c, "bf_global_project_cells", cell_nx, cell_ny, cells_cap, nz, cell_sums_out, cell_sums_cap);
     if (rc != BF_OK) return rc;
     GlobalSearch* gs = c->glob.get();
     GlobalSearch::Cells& cs = gs->cells;
-    if (!cs.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
     const long long nc = cs.cg.n_cells;
-    if (!cell_nx || !cell_ny) return fail(c, BF_ERR_ARG, "bf_global_project_cells: no candidate grid");
-    if (cells_cap < nc) return fail(c, BF_ERR_ARG, "candidate grid holds %lld of %lld cells", (long long)cells_cap, nc);
-    if (cell_sums_out && cell_sums_cap < nc)
-        return fail(c, BF_ERR_ARG, "cell sum buffer holds %lld of %lld", (long long)cell_sums_cap, nc);
-    if (!(nz > 0)) return fail(c, BF_ERR_ARG, "bad nz");
     // one candidate per cell that has events (kx, ky once per cell, here); the entry of any other cell is not read
     // (finite means finite in the float form the projection uses, kx and ky: 1e39 is as infinite there as inf and NaN are)
     std::vector<GlobalCand> cands((size_t)nc, make_cand(0.0, 0.0, nz));
@@ -678,43 +761,12 @@ int bf_global_project_cells(bf_ctx* c, const double* cell_nx, const double* cell
     }
     cs.h_pw_cands.swap(cands);   // (nothing of this object is written before every check has passed)
     HIP_TRY(c, hipSetDevice(c->device));
-    const bf_global_window& w = gs->w;
-    const size_t img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
-    const size_t sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
-    if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
-    if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
-    if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
-    if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
-    std::vector<unsigned long long> sums((size_t)nc, 0ull);
-    if (gs->n > 0) {   // (no event: nothing is launched, every sum is 0 and the images are zero)
+    if (gs->n > 0) {
         HIP_TRY(c, cs.d_pw_cands.grow((size_t)nc));
-        HIP_TRY(c, cs.d_pw_sums.grow((size_t)nc));
-        if ((rc = ensure_batch(c, gs, 1)) != BF_OK) return rc;
         HIP_TRY(c, hipMemcpyAsync(cs.d_pw_cands, cs.h_pw_cands.data(), (size_t)nc * sizeof(GlobalCand), hipMemcpyHostToDevice,
-                                  c->stream));
-        HIP_TRY(c, hipMemsetAsync(cs.d_pw_sums, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
-        const int lr = launch_global_piecewise(cells_view(gs, nullptr, 0), gs->g, cs.d_pw_cands, gs->d_pts, gs->d_win,
-                                               img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr,
-                                               cs.d_pw_sums, c->stream);
-        if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
-        if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
-        if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(sums.data(), cs.d_pw_sums, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                  c->stream));
+                                  c->stream));   // (h_pw_cands is read until project_runs has synchronised)
     }
-    if (img_out && img_px) HIP_TRY(c, hipMemcpyAsync(img_out, gs->d_img, img_px, hipMemcpyDeviceToHost, c->stream));
-    if (scores_out && sc_px)
-        HIP_TRY(c, hipMemcpyAsync(scores_out, gs->d_scores, sc_px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (h_pw_cands is read until here)
-    unsigned long long S = 0;   // at most 65 536 cell sums: on the host, after the one copy that brought them back
-    for (long long i = 0; i < nc; ++i) {
-        S += sums[(size_t)i];
-        if (cell_sums_out) cell_sums_out[i] = (int64_t)sums[(size_t)i];
-    }
-    if (sum_out) *sum_out = (int64_t)S;
-    return BF_OK;
+    return project_runs(c, gs, GlobalCandTable{cs.d_pw_cands}, img_out, scores_out, sum_out, cell_sums_out);
 }
 
 int bf_global_project_field(bf_ctx* c, const double* cell_nx, const double* cell_ny, int64_t cells_cap, double nz,
@@ -722,17 +774,11 @@ int bf_global_project_field(bf_ctx* c, const double* cell_nx, const double* cell
                             int64_t cell_sums_cap, double* event_nx_out, double* event_ny_out, double* event_u_out,
                             double* event_v_out) {
     if (!c) return BF_ERR_ARG;
-    int rc = global_ready(c);
+    int rc = check_project_runs(c, "bf_global_project_field", cell_nx, cell_ny, cells_cap, nz, cell_sums_out, cell_sums_cap);
     if (rc != BF_OK) return rc;
     GlobalSearch* gs = c->glob.get();
     GlobalSearch::Cells& cs = gs->cells;
-    if (!cs.have) return fail(c, BF_ERR_ARG, "no cells: call bf_global_set_cells first");
     const long long nc = cs.cg.n_cells;
-    if (!cell_nx || !cell_ny) return fail(c, BF_ERR_ARG, "bf_global_project_field: no candidate grid");
-    if (cells_cap < nc) return fail(c, BF_ERR_ARG, "candidate grid holds %lld of %lld cells", (long long)cells_cap, nc);
-    if (cell_sums_out && cell_sums_cap < nc)
-        return fail(c, BF_ERR_ARG, "cell sum buffer holds %lld of %lld", (long long)cell_sums_cap, nc);
-    if (!(nz > 0)) return fail(c, BF_ERR_ARG, "bad nz");
     // every cell is a corner for its neighbours, with events or without: all of the grid is read, and all of it must be
     // finite in the float form the projection uses (make_cand's kx, ky; 1e39 is as infinite there as inf and NaN are)
     for (long long i = 0; i < nc; ++i) {
@@ -741,54 +787,27 @@ int bf_global_project_field(bf_ctx* c, const double* cell_nx, const double* cell
             return fail(c, BF_ERR_ARG, "the candidate of cell %lld is not finite as a float", i);
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    const bf_global_window& w = gs->w;
-    const size_t img_px = (size_t)w.scale_bordered_img_x * (size_t)w.scale_bordered_img_y;
-    const size_t sc_px = (size_t)w.scale_img_x * (size_t)w.scale_img_y;
     const size_t n = (size_t)gs->n;
     const bool want_ev = event_nx_out || event_ny_out || event_u_out || event_v_out;
-    if (img_out) HIP_TRY(c, gs->d_img.grow(img_px));
-    if (scores_out) HIP_TRY(c, gs->d_scores.grow(sc_px));
-    if (img_out && img_px) HIP_TRY(c, hipMemsetAsync(gs->d_img, 0, img_px, c->stream));
-    if (scores_out && sc_px) HIP_TRY(c, hipMemsetAsync(gs->d_scores, 0, sc_px * sizeof(float), c->stream));
-    std::vector<unsigned long long> sums((size_t)nc, 0ull);
     std::vector<double> ev;   // (nx_e, then ny_e) of every event
-    if (n > 0) {   // (no event: nothing is launched, every sum is 0, the images are zero, no per-event value is written)
+    GlobalCandField src{cs.cg, (uint32_t)(nc / cs.cg.n_cell_y), nullptr, nullptr, nz, nullptr, nullptr};
+    AlsoBack ev_back;
+    if (n > 0) {   // (no event: no per-event value is written)
         HIP_TRY(c, cs.d_field_grid.grow((size_t)nc * 2));
-        HIP_TRY(c, cs.d_pw_sums.grow((size_t)nc));
-        if (want_ev) {
+        src.cell_nx = cs.d_field_grid;
+        src.cell_ny = src.cell_nx + nc;
+        HIP_TRY(c, hipMemcpyAsync(cs.d_field_grid, cell_nx, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(cs.d_field_grid + nc, cell_ny, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (want_ev) {   // (the caller's grids are read until project_runs has synchronised)
             HIP_TRY(c, cs.d_field_ev.grow(n * 2));
             ev.resize(n * 2);
+            src.ev_nx = cs.d_field_ev;
+            src.ev_ny = src.ev_nx + n;
+            ev_back = AlsoBack{ev.data(), src.ev_nx, n * 2 * sizeof(double)};
         }
-        if ((rc = ensure_batch(c, gs, 1)) != BF_OK) return rc;
-        double* d_nx = cs.d_field_grid;
-        double* d_ny = d_nx + nc;
-        HIP_TRY(c, hipMemcpyAsync(d_nx, cell_nx, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_ny, cell_ny, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemsetAsync(cs.d_pw_sums, 0, (size_t)nc * sizeof(unsigned long long), c->stream));
-        HIP_TRY(c, hipMemsetAsync(gs->d_pts, 0, (size_t)gs->g.plane * sizeof(uint32_t), c->stream));
-        double* d_ev = want_ev ? cs.d_field_ev.get() : nullptr;
-        const int lr = launch_global_field(cells_view(gs, nullptr, 0), gs->g, cs.cg, d_nx, d_ny, nz, gs->d_pts, gs->d_win,
-                                           img_out ? gs->d_img.get() : nullptr, scores_out ? gs->d_scores.get() : nullptr,
-                                           cs.d_pw_sums, d_ev, d_ev ? d_ev + n : nullptr, c->stream);
-        if (lr == -1) return fail(c, BF_ERR_ARG, "the 8-bit Gaussian is defined for scale <= 7");
-        if (lr == -3) return fail(c, BF_ERR_ARG, "metric_wsize %d: the tile does not fit the LDS", gs->w.metric_wsize);
-        if (lr != 0) return fail(c, BF_ERR_HIP, "bf_global: kernel attributes");
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(sums.data(), cs.d_pw_sums, (size_t)nc * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                                  c->stream));
-        if (want_ev) HIP_TRY(c, hipMemcpyAsync(ev.data(), d_ev, n * 2 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
-    if (img_out && img_px) HIP_TRY(c, hipMemcpyAsync(img_out, gs->d_img, img_px, hipMemcpyDeviceToHost, c->stream));
-    if (scores_out && sc_px)
-        HIP_TRY(c, hipMemcpyAsync(scores_out, gs->d_scores, sc_px * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the caller's grids are read until here)
-    unsigned long long S = 0;
-    for (long long i = 0; i < nc; ++i) {
-        S += sums[(size_t)i];
-        if (cell_sums_out) cell_sums_out[i] = (int64_t)sums[(size_t)i];
-    }
-    if (sum_out) *sum_out = (int64_t)S;
-    for (size_t i = 0; want_ev && i < n; ++i) {   // u / v: compute_uv of the event's own (nx_e, ny_e), as bf_global_get_events
+    if ((rc = project_runs(c, gs, src, img_out, scores_out, sum_out, cell_sums_out, ev_back)) != BF_OK) return rc;
+    for (size_t i = 0; i < ev.size() / 2; ++i) {   // u / v: compute_uv of the event's own (nx_e, ny_e), as bf_global_get_events
         if (event_nx_out) event_nx_out[i] = ev[i];
         if (event_ny_out) event_ny_out[i] = ev[n + i];
         double u, v;

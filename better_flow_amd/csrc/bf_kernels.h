@@ -306,20 +306,25 @@ int launch_global_batch(const uint32_t* xy, const int32_t* t, const uint32_t* pe
                         const GlobalCand* cands, int nb, uint32_t* pts, uint32_t* win, uint8_t* img_out,
                         const GlobalEventState& st, unsigned long long* S, float* scores_out, const GlobalCells* cells,
                         hipStream_t s);
-// The piecewise projection (include/bf_accel.h, bf_global_project_cells): every event of the cell-ordered slice under
-// cell_cands[its cell] ([n_cells]; the entry of a cell without events is never read) into ONE point plane `pts` (all zero
-// before), G2 on it (win, img_out as above), then per event its score into scores_out (may be null) and its share of the
-// objective into cell_sums[its cell] ([n_cells], zero before).  Only cells' xy / t / cell_start / run_* fields are read;
-// the per-event state, block, best_sum and best_k are not touched.  < 0 as launch_global_batch.
-int launch_global_piecewise(const GlobalCells& cells, const GlobalGeom& g, const GlobalCand* cell_cands, uint32_t* pts,
-                            uint32_t* win, uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
-// The interpolated field (include/bf_accel.h, bf_global_project_field): launch_global_piecewise with the candidate of every
-// event interpolated between the centres of the cells around its address (include/bf_global_field.h).  cell_nx / cell_ny:
-// [n_cells] on the device, ALL read (an empty cell is a corner for its neighbours).  ev_nx / ev_ny (null, or n doubles each):
-// the interpolated (nx, ny) of every event at its upload index (cells.idx).  < 0 as launch_global_batch.
-int launch_global_field(const GlobalCells& cells, const GlobalGeom& g, const GlobalCellGrid& cg, const double* cell_nx,
-                        const double* cell_ny, double nz, uint32_t* pts, uint32_t* win, uint8_t* img_out, float* scores_out,
-                        unsigned long long* cell_sums, double* ev_nx, double* ev_ny, hipStream_t s);
+// The projections over the cell runs (include/bf_accel.h): every event of the cell-ordered slice under a candidate of its own
+// into ONE point plane `pts` (all zero before), G2 on it (win, img_out as above), then per event its score into scores_out (may
+// be null) and its share of the objective into cell_sums[its cell] ([n_cells], zero before).  Only cells' xy / t / idx /
+// cell_start / run_* fields are read; the per-event state, block, best_sum and best_k are not touched.  < 0 as
+// launch_global_batch.  Where the candidate comes from:
+struct GlobalCandTable {      // bf_global_project_cells: cell_cands[the event's cell]
+    const GlobalCand* cell_cands;   // [n_cells] on the device; the entry of a cell without events is never read
+};
+struct GlobalCandField {      // bf_global_project_field: interpolated between the centres of the cells around the event's
+    GlobalCellGrid cg;              // address (include/bf_global_field.h)
+    uint32_t n_cell_x;
+    const double *cell_nx, *cell_ny;   // [n_cells] on the device, ALL read (an empty cell is a corner for its neighbours)
+    double nz;
+    double *ev_nx, *ev_ny;          // null, or n doubles each: the interpolated (nx, ny) of every event at its upload index
+};
+int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const GlobalCandTable& src, uint32_t* pts, uint32_t* win,
+                       uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
+int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const GlobalCandField& src, uint32_t* pts, uint32_t* win,
+                       uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
 // counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
 // events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);

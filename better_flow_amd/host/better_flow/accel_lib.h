@@ -96,6 +96,14 @@ private:
             throw bf::AccelError(rc, std::string("AccelLib::") + what + " failed (" + std::to_string(rc) + "): " +
                                          (ctx ? bf_last_error(ctx) : "no ctx"));
     }
+    // the candidate grids of global_project_cells / global_project_field: one entry per cell of the last global_set_cells
+    // (without cells the library refuses, BF_ERR_ARG, before it reads a buffer)
+    void check_cell_grids(const char *who, const std::vector<double> &cell_nx, const std::vector<double> &cell_ny) const {
+        if (global_n_cells && (cell_nx.size() != global_n_cells || cell_ny.size() != global_n_cells))
+            throw bf::AccelError(BF_ERR_ARG, std::string("AccelLib::") + who + ": grids of " + std::to_string(cell_nx.size()) +
+                                                 " and " + std::to_string(cell_ny.size()) + " entries for " +
+                                                 std::to_string(global_n_cells) + " cells");
+    }
 
 public:
     bool gpu_enabled;   // accel_lib.h:41 -- here: always true
@@ -337,11 +345,8 @@ public:
     // is resized to that grid.  Returns S_pw.
     long long global_project_cells(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz,
                                    uint8_t *img_out, float *scores_out, std::vector<int64_t> *cell_sums) {
-        if (global_n_cells && (cell_nx.size() != global_n_cells || cell_ny.size() != global_n_cells))
-            throw bf::AccelError(BF_ERR_ARG, "AccelLib::global_project_cells: grids of " + std::to_string(cell_nx.size()) +
-                                                 " and " + std::to_string(cell_ny.size()) + " entries for " +
-                                                 std::to_string(global_n_cells) + " cells");
-        int64_t sum = 0;   // (without cells the library refuses, BF_ERR_ARG, before it reads a buffer)
+        check_cell_grids("global_project_cells", cell_nx, cell_ny);
+        int64_t sum = 0;
         if (cell_sums) cell_sums->assign(global_n_cells, 0);
         check(bf_global_project_cells(ctx, cell_nx.data(), cell_ny.data(), (int64_t)global_n_cells, nz, img_out, scores_out, &sum,
                                       cell_sums ? cell_sums->data() : nullptr, (int64_t)global_n_cells),
@@ -354,11 +359,8 @@ public:
     long long global_project_field(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz,
                                    uint8_t *img_out, float *scores_out, std::vector<int64_t> *cell_sums,
                                    std::vector<double> *events) {
-        if (global_n_cells && (cell_nx.size() != global_n_cells || cell_ny.size() != global_n_cells))
-            throw bf::AccelError(BF_ERR_ARG, "AccelLib::global_project_field: grids of " + std::to_string(cell_nx.size()) +
-                                                 " and " + std::to_string(cell_ny.size()) + " entries for " +
-                                                 std::to_string(global_n_cells) + " cells");
-        int64_t sum = 0;   // (without cells the library refuses, BF_ERR_ARG, before it reads a buffer)
+        check_cell_grids("global_project_field", cell_nx, cell_ny);
+        int64_t sum = 0;
         std::vector<int64_t> sums(cell_sums ? global_n_cells : 0, 0);
         std::vector<double> ev[4];
         for (int k = 0; events && k < 4; ++k) ev[k].assign((size_t)size, 0.0);

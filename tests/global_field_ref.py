@@ -72,26 +72,8 @@ def event_uv(nx_e, ny_e, nz=G.NZ):
 def project_field(gc, cell_rows, cell_cols, cell_nx, cell_ny, nz=G.NZ):
     """Returns (blurred bordered image uint8, current_scores float32, S_f int, S_f(cell) int64 [n_cell_x, n_cell_y],
     nx_e, ny_e float64 [n])."""
-    w = gc.w
     nx_e, ny_e = field_at_events(gc, cell_rows, cell_cols, cell_nx, cell_ny)
-    pr_x, pr_y = PW.project_per_event(gc.fr_x, gc.fr_y, gc.t, nx_e, ny_e, nz)
-    X, Y, ok = G.pixels(pr_x, pr_y, w)
-    s, mw = w["scale"], w["metric_wsize"]
-    off = s // 2 + mw // 2
-    pts = np.zeros((w["scale_bordered_img_x"], w["scale_bordered_img_y"]), dtype=np.int64)
-    np.add.at(pts, (X[ok] + off, Y[ok] + off), 1)
-    h = s // 2
-    cnt = np.minimum(G._box(pts, -h, h), 255)
-    img = G.blur8(cnt, s) if s > 1 else cnt.astype(np.uint8)
-    ssum, scnt = G.window_sums(img, w)
-    es = ssum[X + off, Y + off]
-    ec = scnt[X + off, Y + off]
-    f32 = np.where(ec > 0, es / np.maximum(ec, 1), 0.0).astype(np.float32)
-    cur = np.zeros((w["scale_img_x"], w["scale_img_y"]), dtype=np.float32)
-    cur[X[ok], Y[ok]] = f32[ok]
-    sums = np.zeros(gc.n_cells, dtype=np.int64)
-    np.add.at(sums, gc.cell[ok], G.score_fixed(es[ok], ec[ok]))      # exact: int64 into int64
-    return img, cur, int(sums.sum()), sums.reshape(gc.n_cell_x, gc.n_cell_y), nx_e, ny_e
+    return PW.render_and_score(gc, nx_e, ny_e, nz) + (nx_e, ny_e)
 
 
 def fill_cells(valid, cell_nx, cell_ny):

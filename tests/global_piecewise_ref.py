@@ -26,17 +26,12 @@ def project_per_event(fr_x, fr_y, t, nx_e, ny_e, nz=G.NZ):
     return pr_x, pr_y
 
 
-def project_cells(gc, cell_nx, cell_ny, nz=G.NZ):
-    """gc: a global_cells_ref.GlobalCells (its window, membership and event counts; its per-event state is left alone).
-    cell_nx / cell_ny: n_cells values in any shape, row-major [n_cell_x, n_cell_y].
-    Returns (blurred bordered image uint8, current_scores float32, S_pw int, S_pw(cell) int64 [n_cell_x, n_cell_y])."""
+def render_and_score(gc, nx_e, ny_e, nz=G.NZ):
+    """The slice of gc (a global_cells_ref.GlobalCells: its window and membership; its per-event state is left alone) with
+    every event under its own (nx_e, ny_e): one image, the 8-bit Gaussian, the window score, the sums by the event's cell.
+    Returns (blurred bordered image uint8, current_scores float32, S int, S(cell) int64 [n_cell_x, n_cell_y])."""
     w = gc.w
-    cx = np.asarray(cell_nx, dtype=np.float64).reshape(-1)
-    cy = np.asarray(cell_ny, dtype=np.float64).reshape(-1)
-    assert len(cx) == len(cy) == gc.n_cells
-    occupied = gc.events > 0
-    assert np.isfinite(cx[occupied]).all() and np.isfinite(cy[occupied]).all()
-    pr_x, pr_y = project_per_event(gc.fr_x, gc.fr_y, gc.t, cx[gc.cell], cy[gc.cell], nz)
+    pr_x, pr_y = project_per_event(gc.fr_x, gc.fr_y, gc.t, nx_e, ny_e, nz)
     X, Y, ok = G.pixels(pr_x, pr_y, w)
     s, mw = w["scale"], w["metric_wsize"]
     off = s // 2 + mw // 2
@@ -54,6 +49,18 @@ def project_cells(gc, cell_nx, cell_ny, nz=G.NZ):
     sums = np.zeros(gc.n_cells, dtype=np.int64)
     np.add.at(sums, gc.cell[ok], G.score_fixed(es[ok], ec[ok]))      # exact: int64 into int64
     return img, cur, int(sums.sum()), sums.reshape(gc.n_cell_x, gc.n_cell_y)
+
+
+def project_cells(gc, cell_nx, cell_ny, nz=G.NZ):
+    """gc: a global_cells_ref.GlobalCells (its window, membership and event counts; its per-event state is left alone).
+    cell_nx / cell_ny: n_cells values in any shape, row-major [n_cell_x, n_cell_y].
+    Returns (blurred bordered image uint8, current_scores float32, S_pw int, S_pw(cell) int64 [n_cell_x, n_cell_y])."""
+    cx = np.asarray(cell_nx, dtype=np.float64).reshape(-1)
+    cy = np.asarray(cell_ny, dtype=np.float64).reshape(-1)
+    assert len(cx) == len(cy) == gc.n_cells
+    occupied = gc.events > 0
+    assert np.isfinite(cx[occupied]).all() and np.isfinite(cy[occupied]).all()
+    return render_and_score(gc, cx[gc.cell], cy[gc.cell], nz)
 
 
 def accepted_per_cell(gc, cell_nx, cell_ny, nz=G.NZ):

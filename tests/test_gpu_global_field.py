@@ -10,6 +10,8 @@ import pytest
 
 import global_cells_ref as GC
 import global_field_ref as F
+import global_piecewise_ref as PW
+import global_ref as G
 
 pytestmark = pytest.mark.gpu
 
@@ -216,6 +218,50 @@ def test_shear_slice_recovery(accel_mod):
     assert (got[3] >= pw[3]).all()
     assert S_f >= (1 + F.SHEAR_GAIN / 2) * S_pw
     assert mirrored < S_pw
+
+
+def test_calls_share_their_scratch_without_leftovers(accel_mod):
+    """bf_global_project_cells, bf_global_project_field and bf_global_project_all run through the same device buffers (point
+    and window planes, image, scores, per-cell sums): each call of a mixed sequence, with grids of its own, is bit for bit its
+    restatement, whatever the call before left there.  Once with runs of 64 (3 x 3 cells) and once with runs of 256 (one
+    cell), on one context."""
+    ev = GC.tie_slice(False)
+    rng = np.random.default_rng(53)
+    acc = _accel(accel_mod, ev)
+    try:
+        for grid, shape in ((GC.TIE_GRID, (3, 3)), ((24, 24, 24, 24), (1, 1))):
+            gc = GC.GlobalCells(*ev, *grid, scale=3, metric_wsize=15)
+            ax, ay, bx, by, cx, cy = rng.uniform(-0.2, 0.2, (6,) + shape)
+            nx, ny = rng.uniform(-0.2, 0.2, 2)
+
+            def window_and_cells():
+                acc.global_set_window(3, 15)
+                g = acc.global_set_cells(*grid)
+                assert (g.n_cell_x, g.n_cell_y) == shape
+
+            window_and_cells()
+            want_pw = PW.project_cells(gc, ax, ay)
+            first = acc.global_project_cells(ax, ay)
+            _same_bits(first, want_pw)
+            assert first[2] > 0
+            _same(acc.global_project_field(bx, by, want_events=True), F.project_field(gc, grid[2], grid[3], bx, by))
+            S, img, cur = acc.global_project_all(nx, ny)
+            img0, cur0, S0 = G.Global(*ev, scale=3, metric_wsize=15).project_all(nx, ny)
+            assert S == S0 > 0 and np.array_equal(img, img0) and np.array_equal(_bits(cur), _bits(cur0))
+            none, sc, S_f, sums = acc.global_project_field(cx, cy, want_img=False)
+            want_f = F.project_field(gc, grid[2], grid[3], cx, cy)
+            assert none is None and np.array_equal(_bits(sc), _bits(want_f[1])) and S_f == want_f[2] > 0
+            assert np.array_equal(sums, want_f[3])
+            last = acc.global_project_cells(ax, ay)
+            _same_bits(last, want_pw)
+            _same_bits(last, first)
+            after = acc.global_get_events()
+            window_and_cells()                                      # (resets the per-event state)
+            assert acc.global_project_all(nx, ny)[0] == S
+            _same_state(after, acc.global_get_events())             # what project_all alone leaves
+            assert after["max_score"].any()
+    finally:
+        acc.close()
 
 
 def test_empty_cloud(accel_mod):
