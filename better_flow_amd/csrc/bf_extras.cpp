@@ -47,8 +47,9 @@ int tiles_prepare(bf_ctx* c, const bf_tile_opts* o, hipStream_t s, TileArgs& a, 
     const bf_ctx::EvSet& dst = c->set[c->cs ^ 1];
     {
         ProfScope ps(c, 3);
-        launch_tile_sort(src.xy, src.t, c->has_perm ? src.perm : nullptr, c->n, g, c->d_tile_hist, c->d_tile_start,
-                         c->d_tile_cursor, dst.xy, dst.t, dst.p, dst.perm, s);
+        if (launch_tile_sort(src.xy, src.t, c->has_perm ? src.perm : nullptr, c->n, g, c->d_tile_hist, c->d_tile_start,
+                             c->d_tile_cursor, dst.xy, dst.t, dst.p, dst.perm, s) != 0)
+            return fail(c, BF_ERR_HIP, "cannot configure the tile sort for %d tiles", nt);
     }
     c->cs ^= 1;
     c->has_perm = true;

@@ -143,9 +143,9 @@ struct TileArgs {
     DevState* states;                  // one per tile: in = zero-model template, out = final state
     int32_t scale, seed_res_x, seed_res_y, guard_res_x, guard_res_y, min_events, max_px;
 };
-void launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const TileGrid& g,
-                      uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
-                      uint32_t* operm, hipStream_t s);
+int launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const TileGrid& g,
+                     uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
+                     uint32_t* operm, hipStream_t s);   // -1: the histograms' LDS cannot be configured
 int launch_tile_optimizer(const TileArgs& a, int ntiles, hipStream_t s);
 int launch_tile_optimizer_many(const TileArgs* slices, int nslices, int ntiles, int scale, int max_px, uint32_t* counter, int n_cus,
                                hipStream_t s);

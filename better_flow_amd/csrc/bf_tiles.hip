@@ -170,7 +170,9 @@ __device__ __forceinline__ void tile_optimizer_body(const TileArgs& a, const int
         st.hot.done = done;
     }
     __syncthreads();
-    const int R = s_st.hot.R, C = s_st.hot.C, P = R * C;
+    // (a tile that is done before its first iteration has no planes: an empty tile's R and C are both NEGATIVE -- x_min is the
+    // sensor size, x_max 0 -- and their product a large positive pixel count, far beyond the max_px-sized layout)
+    const int R = s_st.hot.R, C = s_st.hot.C, P = s_st.hot.done ? 0 : R * C;
     const int s = a.scale, hsc = s / 2;
     // A tile's events live in registers for the whole loop (up to kTileUR per thread; a fuller tile streams the rest
     // from global memory as before): the loop body then touches global memory only to stream that rest.
@@ -384,13 +386,23 @@ void launch_fill_states(DevState* states, const DevState& tmpl, int nt, hipStrea
     hipLaunchKernelGGL(k_fill_states, dim3((nt + 63) / 64), dim3(64), 0, s, states, tmpl, nt);
 }
 
-void launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const TileGrid& g,
-                      uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
-                      uint32_t* operm, hipStream_t s) {
+// The sort's LDS histograms grow with the grid: 4 bytes per tile in k_tile_count, 8 in k_tile_scatter -- 64 and 128 KiB at the
+// 16384 tiles the C-ABI accepts.  Above the 48 KiB every HIP runtime launches unasked, the kernel's dynamic-LDS limit is raised
+// first, like every other large-LDS launcher here (the common grids stay below and pay nothing).
+template <class K>
+static int tile_sort_lds(K k, size_t bytes) {
+    if (bytes <= 48 * 1024) return 0;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
+}
+
+int launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const TileGrid& g,
+                     uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
+                     uint32_t* operm, hipStream_t s) {
     const int nt = g.rows * g.cols;
     long long blocks = (n + kThreads * 8 - 1) / (kThreads * 8);
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
+    if (tile_sort_lds(k_tile_count, (size_t)nt * 4) != 0 || tile_sort_lds(k_tile_scatter, (size_t)nt * 8) != 0) return -1;
     hipLaunchKernelGGL(k_tile_count, dim3((unsigned)blocks), dim3(kThreads), (size_t)nt * 4, s, xy, n, g, hist);
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, s, hist, nt, start, cursor);
     if (n > 0) {
@@ -398,6 +410,7 @@ void launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm
         hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)((n + per - 1) / per)), dim3(kThreads), (size_t)nt * 8, s, xy, t,
                            perm_in, n, g, start, cursor, oxy, ot, op, operm);
     }
+    return 0;
 }
 
 // (256 threads per tile optimizer; 512 / 1024: measured, no gain -- experiments/rounds_1_to_3.md)
