@@ -5,9 +5,7 @@
 #include <limits.h>
 #include <cstdlib>
 
-#include "bf_device.h"
-#include "bf_device_fns.h"
-#include "bf_kernels.h"
+#include "bf_fused_tile.h"
 
 namespace bf {
 
@@ -34,17 +32,8 @@ namespace bf {
 template <int HS, int NSUB, int U>
 __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __restrict__ pre_ftab, const DevState* pre_st_in, MomentAcc* pre_acc_in,
                                                            const uint32_t* pre_lost, int pre_j, FusedArgs a) {
-    constexpr int THREADS = 256 * NSUB;
-    constexpr int TR = kTileR, TC = kTileC;
-    constexpr int H = HS + 1;
-    constexpr int TSR = TR * NSUB;
-    constexpr int AR = TSR + 2 * H, AC = TC + 2 * H;   // the LDS tile
-    constexpr int PC = AC;
-    constexpr int TH = TR + 2, TW = TC + 2;
-    extern __shared__ unsigned long long s_dyn[];       // (above 64 KiB for the 64-row tile: dynamic, see launch_fused_pass)
-    unsigned long long* const s_acc = s_dyn;                                         // [AR * AC]
-    float (*const s_time)[TH * TW] = reinterpret_cast<float (*)[TH * TW]>(s_dyn + AR * AC);   // [NSUB][TH * TW]
-    uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(&s_time[NSUB][0]);           // [AR * AC]   (bin_ok == 0 only)
+    using T = FusedTile<HS, NSUB>;   // the tile pass itself: bf_fused_tile.h
+    constexpr int THREADS = T::THREADS, TR = T::TR, TC = T::TC, H = T::H, TSR = T::TSR;
     __shared__ unsigned long long s_rpart[NSUB][kSumFields * 4];
     __shared__ DevState s_state;
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -55,12 +44,7 @@ __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __res
     // successor's.  One shared word was read by late work-groups of a pass AFTER early ones of the same pass had raised it.)
     const uint32_t lost_prev = sload(pre_lost + (pre_j + 2) % 3);
     const FusedTab ft = sload(reinterpret_cast<const FusedTab*>(pre_ftab) + b);
-    // running index -> global index: off[0] plus the offset STEPS of the ranges the index has passed.  (A chain of
-    // selects among the offsets themselves was turned into a select among ADDRESSES of a scratch copy of the table: a
-    // scratch load in front of every event load.)
-    uint32_t off_step[kFusedRanges];
-#pragma unroll
-    for (int r = 1; r < kFusedRanges; ++r) off_step[r] = ft.off[r] - ft.off[r - 1];
+    const FusedIndex index_of(ft);
     unsigned long long accv[kAccPerLane];
     if (tid < 64) acc_load_wave<false, false>(pre_acc_in, tid, accv);
     unsigned long long state_word = 0;
@@ -115,10 +99,7 @@ __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __res
         for (int k = 0; k < U; ++k) {
             uint32_t v = base + k * THREADS + tid;
             v = v < M ? v : 0u;
-            uint32_t off = ft.off[0];
-#pragma unroll
-            for (int r = 1; r < kFusedRanges; ++r) off += v >= ft.pre[r] ? off_step[r] : 0u;
-            const uint32_t i = v + off;
+            const uint32_t i = index_of(ft, v);
             vi[k] = i;
             vxy[k] = xy[i];
             vt[k] = t[i];
@@ -127,12 +108,7 @@ __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __res
     };
     if (M) load_pass();
     asm volatile("" ::: "memory");
-    {
-        ulonglong2* z = reinterpret_cast<ulonglong2*>(s_acc);
-        for (int i = tid; i < AR * AC / 2; i += THREADS) z[i] = make_ulonglong2(0ull, 0ull);
-        if (!h0.bin_ok)
-            for (int i = tid; i < AR * AC; i += THREADS) s_cnt[i] = 0u;
-    }
+    T::clear(tid, THREADS, !h0.bin_ok);
     if (tid < kStateWords) reinterpret_cast<unsigned long long*>(&s_state)[tid] = state_word;
     double ppx[U], ppy[U];
     auto previous_positions = [&]() {
@@ -171,8 +147,6 @@ __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __res
         return;
     }
     if (pending && tid < 64) previous_positions();
-    const int hsc = hs.scale / 2;
-    const bool packed = hs.bin_ok != 0;
     bool lost_here = false;
     for (;;) {
 #pragma unroll
@@ -192,33 +166,7 @@ __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __res
                 px = pr_from_p(vxy[k] & 0xffffu, q.x);
                 py = pr_from_p(vxy[k] >> 16, q.y);
             }
-            const int X = trunc_scatter(px * (double)hs.scale + (double)hs.x_sh);   // accel_lib.h:154-158
-            const int Y = trunc_scatter(py * (double)hs.scale + (double)hs.y_sh);
-            if ((X >= hs.wsx + hsc) || (X < hsc) || (Y >= hs.wsy + hsc) || (Y < hsc)) continue;
-            const int lx = X - X0, ly = Y - Y0;
-            if (lx >= 0 && lx < AR && ly >= 0 && ly < AC) {
-                const unsigned long long dt = (unsigned long long)((long long)vt[k] - hs.tmin);
-                if (packed) {
-                    atomicAdd(&s_acc[lx * AC + ly], (1ull << hs.bin_tbits) + dt);
-                } else {
-                    atomicAdd(&s_acc[lx * AC + ly], dt);
-                    atomicAdd(&s_cnt[lx * AC + ly], 1u);
-                }
-            }
-            if (mine) {
-                // Does every tile whose halo window holds (X, Y) read this event?  The tile of its sort key does; the
-                // neighbours read the key's edge strips.  dx, dy: the landing pixel relative to the key's tile.
-                const int dx = lx - H, dy = ly - H;
-                if (dx < H || dx >= TSR - H || dy < H || dy >= TC - H) {
-                    int z = 0;
-#pragma unroll
-                    for (int q = 0; q < kFusedZones - 1; ++q) z += v >= ft.zone[q] ? 1 : 0;
-                    const bool top = (0x00eu >> z) & 1u, right = (0x038u >> z) & 1u, bottom = (0x0e0u >> z) & 1u, left = (0x182u >> z) & 1u;
-                    const bool ok = (dx >= H || top) && (dx < TSR - H || bottom) && dx >= H - TSR && dx < 2 * TSR - H &&
-                                    (dy >= H || left) && (dy < TC - H || right) && dy >= H - TC && dy < 2 * TC - H;
-                    lost_here |= !ok;
-                }
-            }
+            lost_here |= T::scatter(px, py, vt[k], v, mine, ft, X0, Y0, hs);
         }
         base += THREADS * U;
         if (base >= M) break;
@@ -232,95 +180,43 @@ __global__ __launch_bounds__(256 * NSUB) void k_fused_pass(const uint32_t* __res
     store_state();
     // ---- the stencil of k_stencil_binned, one 16 x 64 sub-tile per 256-thread sub-group, on the LDS tile ----
     const int g = tid >> 8, lt = tid & 255;
-    const int R = a.R, C = a.C;
+    const int R = a.R, C = a.C, hR = R / 2, hC = C / 2;
     const int r0 = br * TSR + g * TR, c0 = bc * TC;
-    const int bt = hs.bin_tbits;
-    const unsigned long long bm = (1ull << bt) - 1ull;
-    const unsigned long long* win = s_acc + (g * TR) * AC;   // rows r0 - H .. of this sub-tile
-    const uint32_t* cwin = s_cnt + (g * TR) * AC;
-    for (int idx = lt; idx < TH * TW; idx += 256) {
-        const int tr = idx / TW, tc = idx - tr * TW;
-        const int gr = r0 - 1 + tr, gc = c0 - 1 + tc;
-        float tv = 0.f;
-        if (gr >= 0 && gr < R && gc >= 0 && gc < C) {
-            // s x s box sum == the s x s splat of accel_lib.h:160-165 on integer planes
-            unsigned long long pk = 0;
-            uint32_t cacc = 0;
-#pragma unroll
-            for (int da = 0; da <= 2 * HS; ++da)
-#pragma unroll
-                for (int db = 0; db <= 2 * HS; ++db) {
-                    pk += win[(tr + da) * PC + (tc + db)];
-                    if (!packed) cacc += cwin[(tr + da) * PC + (tc + db)];
-                }
-            unsigned long long acc = pk;
-            if (packed) { acc = pk & bm; cacc = (uint32_t)(pk >> bt); }
-            tv = time_from_sums(cacc, (long long)acc, hs.tmin);
-        }
-        s_time[g][idx] = tv;
-    }
+    T::time_image(g, lt, r0, c0, R, C, hs);
     tl_stamp(a.tl, a.j, 7);
     __syncthreads();
     tl_stamp(a.tl, a.j, 8);
-    SumsT smt;   // (a thread's own pixels: 32-bit integer sums, see bf_device_fns.h)
-    sums_zero(smt);
-    const int hR = R / 2, hC = C / 2;
-#pragma unroll
-    for (int k = 0; k < (TR * TC) / 256; ++k) {
-        const int pidx = lt + k * 256;
-        const int lr = pidx / TC, lc = pidx - lr * TC;
-        const int gr = r0 + lr, gc = c0 + lc;
-        if (gr < R && gc < C) {
-            float gx, gy;
-            stencil_px<TW>(&s_time[g][(lr + 1) * TW + (lc + 1)], gr, gc, R, C, hR, hC, smt, gx, gy);
-        }
-    }
-    const Sums sm = sums_widen(smt);
-    constexpr bool kPack = TR * TC <= 1024 && TR <= 64 && TC <= 64;
+    const Sums sm = T::moments(g, lt, r0, c0, R, C);
     tl_stamp(a.tl, a.j, 9);
-    block_reduce_publish<256, kPack>(sm, s_rpart[g], lt, r0 - hR, c0 - hC);
+    block_reduce_publish<256, T::kPack>(sm, s_rpart[g], lt, r0 - hR, c0 - hC);
     tl_stamp(a.tl, a.j, 10);
     if (tid < 64) clear_next_acc();
     if (lt >= 64 || r0 >= R) return;   // (a sub-tile below the image has nothing to add)
-    const Sums blk = block_reduce_total<256, kPack>(s_rpart[g], r0 - hR, c0 - hC);
+    const Sums blk = block_reduce_total<256, T::kPack>(s_rpart[g], r0 - hR, c0 - hC);
     acc_add(a.acc_out, (b * NSUB + g) % kAccGroups, blk, lt);
     tl_stamp(a.tl, a.j, 11);
 }
 
-// One pass of the one-kernel iteration (k_fused_pass).  rows_per_tile: 32 or 64.
+// One pass of the one-kernel iteration (k_fused_pass).
 template <int HS, int NSUB>
 static hipError_t launch_fused2(const FusedArgs& a, hipStream_t s) {
     constexpr int U = 4;
-    constexpr int H = HS + 1, AR = 16 * NSUB + 2 * H, AC = kTileC + 2 * H;
-    constexpr size_t lds = (size_t)AR * AC * 12 + (size_t)NSUB * (kTileR + 2) * (kTileC + 2) * 4;
-    static_assert(lds + 4096 <= (size_t)kBinTileLdsMax, "the tile fits a CU");
-    static std::atomic<unsigned long long> raised{0ull};   // (per device: see launch_bws2)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    const unsigned long long dev_bit = 1ull << (dev & 63);
-    if (lds > 48 * 1024 && !(raised.load(std::memory_order_acquire) & dev_bit)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fused_pass<HS, NSUB, U>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, kBinTileLdsMax);
+    using T = FusedTile<HS, NSUB>;
+    if constexpr (T::kLds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised{0ull};
+        const void* fns[1] = {reinterpret_cast<const void*>(&k_fused_pass<HS, NSUB, U>)};
+        const hipError_t e = raise_dynamic_lds(raised, fns);
         if (e != hipSuccess) return e;
-        raised.fetch_or(dev_bit, std::memory_order_release);
     }
-    launch_timed(k_fused_pass<HS, NSUB, U>, dim3(a.nbr * a.nbc), dim3(256 * NSUB), lds, s, a.ftab, a.st_in, a.acc_in, a.lost, a.j, a);
+    launch_timed(k_fused_pass<HS, NSUB, U>, dim3(a.nbr * a.nbc), dim3(T::THREADS), T::kLds, s, a.ftab, a.st_in, a.acc_in, a.lost, a.j, a);
     return hipSuccess;
 }
-template <int HS>
-static hipError_t launch_fused1(const FusedArgs& a, int rows_per_tile, hipStream_t s) {
-    return rows_per_tile == 64 ? launch_fused2<HS, 4>(a, s) : launch_fused2<HS, 2>(a, s);
-}
+// rows_per_tile: 32 or 64.
 hipError_t launch_fused_pass(const FusedArgs& a, int half_scale, int rows_per_tile, hipStream_t s) {
-    switch (half_scale) {
-        case 0: return launch_fused1<0>(a, rows_per_tile, s);
-        case 1: return launch_fused1<1>(a, rows_per_tile, s);
-        case 2: return launch_fused1<2>(a, rows_per_tile, s);
-        case 3: return launch_fused1<3>(a, rows_per_tile, s);
-        case 4: return launch_fused1<4>(a, rows_per_tile, s);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_half_scale(half_scale, hipErrorInvalidValue, [&](auto hs) {
+        constexpr int HS = decltype(hs)::value;
+        return rows_per_tile == 64 ? launch_fused2<HS, 4>(a, s) : launch_fused2<HS, 2>(a, s);
+    });
 }
-
 
 }  // namespace bf

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <atomic>
 
 #include "bf_device.h"
 #include "bf_plan_rules.h"
@@ -101,6 +102,24 @@ static inline void launch_timed(K kernel, dim3 grid, dim3 block, size_t lds, hip
     } else {
         hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
     }
+}
+
+// LDS tiles above 64 KiB need the dynamic-LDS attribute raised (160 KiB per CU on gfx950).  The attribute belongs to the
+// (function, device) pair, so it is raised once per device the functions of one launcher are launched on: `raised`, that
+// launcher's own static word, holds a bit per device ordinal, set after the calls succeeded (two threads racing here both
+// make the calls, which is harmless).  The launchers whose limit depends on the call's sizes set it per call instead.
+template <size_t N>
+static inline hipError_t raise_dynamic_lds(std::atomic<unsigned long long>& raised, const void* const (&fns)[N]) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
+    const unsigned long long dev_bit = 1ull << (dev & 63);
+    if (raised.load(std::memory_order_acquire) & dev_bit) return hipSuccess;
+    for (const void* f : fns) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kBinTileLdsMax);
+        if (e != hipSuccess) return e;
+    }
+    raised.fetch_or(dev_bit, std::memory_order_release);
+    return hipSuccess;
 }
 
 void launch_set_state(DevState* st, const DevState& v, hipStream_t s);

@@ -8,8 +8,9 @@
 // (one per image tile, all co-resident: the grid is checked against the occupancy query), keep their events in REGISTERS, and
 // replace the launch boundary by an all-to-all exchange of the moment sums through memory:
 //
-//   pass     as k_fused_pass: the tile's own events and the neighbouring tiles' edge strips are warped and added to an LDS
-//            tile; each 256-thread sub-group runs K3's box sum / time image / Scharr / moments on one 16 x 64 sub-tile
+//   pass     as k_fused_pass (the same FusedTile, bf_fused_tile.h): the tile's own events and the neighbouring tiles' edge
+//            strips are warped and added to an LDS tile; each 256-thread sub-group runs K3's box sum / time image /
+//            Scharr / moments on one 16 x 64 sub-tile
 //            -- same thread -> pixel mapping and reduction tree, so every f64 sub-tile partial carries the bits of the
 //            other loops;
 //   publish  the sub-tile's sums as the fifteen exact integer words of MomentAcc (sums_lane_word) -- not added to shared
@@ -45,9 +46,7 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 
-#include "bf_device.h"
-#include "bf_device_fns.h"
-#include "bf_kernels.h"
+#include "bf_fused_tile.h"
 
 namespace bf {
 
@@ -121,17 +120,8 @@ __device__ __forceinline__ bool xchg_poll_sum(const unsigned long long* base, co
 
 template <int HS, int NSUB, int U>
 __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(FusedLoopArgs a) {
-    constexpr int THREADS = 256 * NSUB;
-    constexpr int TR = kTileR, TC = kTileC;
-    constexpr int H = HS + 1;
-    constexpr int TSR = TR * NSUB;
-    constexpr int AR = TSR + 2 * H, AC = TC + 2 * H;   // the LDS tile
-    constexpr int PC = AC;
-    constexpr int TH = TR + 2, TW = TC + 2;
-    extern __shared__ unsigned long long s_dyn[];
-    unsigned long long* const s_acc = s_dyn;                                                    // [AR * AC]
-    float (*const s_time)[TH * TW] = reinterpret_cast<float (*)[TH * TW]>(s_dyn + AR * AC);    // [NSUB][TH * TW]
-    uint32_t* const s_cnt = reinterpret_cast<uint32_t*>(&s_time[NSUB][0]);                      // [AR * AC]   (bin_ok == 0 only)
+    using T = FusedTile<HS, NSUB>;   // the tile pass itself: bf_fused_tile.h
+    constexpr int THREADS = T::THREADS, TR = T::TR, TC = T::TC, H = T::H, TSR = T::TSR;
     __shared__ unsigned long long s_rpart[NSUB][kSumFields * 4];
     __shared__ DevState s_state;
     __shared__ int s_lost, s_exit, s_abort, s_rest;
@@ -142,9 +132,7 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
 
     // ---- entry: state -> LDS (written by the previous kernel: plain loads), range table, events -> registers ----
     const FusedTab ft = sload(reinterpret_cast<const FusedTab*>(a.ftab) + b);
-    uint32_t off_step[kFusedRanges];
-#pragma unroll
-    for (int r = 1; r < kFusedRanges; ++r) off_step[r] = ft.off[r] - ft.off[r - 1];
+    const FusedIndex index_of(ft);
     if (tid < kStateWords) reinterpret_cast<unsigned long long*>(&s_state)[tid] = reinterpret_cast<const unsigned long long*>(a.st)[tid];
     if (tid == 0) { s_lost = 0; s_exit = 0; s_abort = 0; s_rest = 0; sincos_table_fill(s_sctab); }
     __syncthreads();
@@ -188,10 +176,7 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
     // event's in the array of the reader's direction (N / S -> 0, W / E -> 1, diagonal -> 2: no two readers of an event
     // share a direction class)
     auto entry_of = [&](uint32_t v, uint32_t& i, float2*& parr) {
-        uint32_t off = ft.off[0];
-#pragma unroll
-        for (int r = 1; r < kFusedRanges; ++r) off += v >= ft.pre[r] ? off_step[r] : 0u;
-        i = v + off;
+        i = index_of(ft, v);
         const int slot = (v >= ft.pre[1] ? 1 : 0) + (v >= ft.pre[3] ? 1 : 0) + (v >= ft.pre[6] ? 1 : 0);
         parr = slot == 0 ? a.scratch[3] : (slot == 1 ? a.scratch[0] : (slot == 2 ? a.scratch[1] : a.scratch[2]));
     };
@@ -229,12 +214,8 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
     int j = s_state.last_j + 1;
     bool first_of_run = s_state.last_j < 0;
     int passes = 0;
-    {   // the LDS tile, zeroed once here and then under every pass's exchange
-        ulonglong2* z = reinterpret_cast<ulonglong2*>(s_acc);
-        for (int i = tid; i < AR * AC / 2; i += THREADS) z[i] = make_ulonglong2(0ull, 0ull);
-        for (int i = tid; i < AR * AC; i += THREADS) s_cnt[i] = 0u;
-        __syncthreads();
-    }
+    T::clear(tid, THREADS, true);   // the LDS tile, zeroed once here and then under every pass's exchange
+    __syncthreads();
     for (;;) {
         // (opaque copies of the thread's indices: everything derived from them inside a pass would otherwise be hoisted out
         // of the pass loop as loop-invariant -- ~100 registers of addresses and pixel coordinates, twice the budget of two
@@ -246,8 +227,6 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
         const ScatterHot hs = scatter_hot(&s_state);
         const bool redo = lds_sreg(&s_state.hot.redo) != 0;
         const bool do_warp = (first_of_run ? a.first_warp != 0 : true) && !redo;
-        const int hsc = hs.scale / 2;
-        const bool packed = hs.bin_ok != 0;
         // (the LDS tile is zero: cleared before the loop, and by the idle waves under the previous pass's exchange)
         if (tid_ == THREADS - 1 && s_rest) {   // bookkeeping of the last update, off the critical path: a thread of the last wave
             model_update_rest(&s_state, b == 0 ? a.trace : nullptr, 0, 0u);
@@ -277,31 +256,7 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
                     px = pr_from_p(vxy[k] & 0xffffu, q.x);
                     py = pr_from_p(vxy[k] >> 16, q.y);
                 }
-                const int X = trunc_scatter(px * (double)hs.scale + (double)hs.x_sh);   // accel_lib.h:154-158
-                const int Y = trunc_scatter(py * (double)hs.scale + (double)hs.y_sh);
-                if ((X >= hs.wsx + hsc) || (X < hsc) || (Y >= hs.wsy + hsc) || (Y < hsc)) continue;
-                const int lx = X - X0, ly = Y - Y0;
-                if (lx >= 0 && lx < AR && ly >= 0 && ly < AC) {
-                    const unsigned long long dt = (unsigned long long)((long long)vt[k] - hs.tmin);
-                    if (packed) {
-                        atomicAdd(&s_acc[lx * AC + ly], (1ull << hs.bin_tbits) + dt);
-                    } else {
-                        atomicAdd(&s_acc[lx * AC + ly], dt);
-                        atomicAdd(&s_cnt[lx * AC + ly], 1u);
-                    }
-                }
-                if (mine) {   // does every tile whose halo window holds (X, Y) read this event?  (see k_fused_pass)
-                    const int dx = lx - H, dy = ly - H;
-                    if (dx < H || dx >= TSR - H || dy < H || dy >= TC - H) {
-                        int z = 0;
-#pragma unroll
-                        for (int q = 0; q < kFusedZones - 1; ++q) z += v >= ft.zone[q] ? 1 : 0;
-                        const bool top = (0x00eu >> z) & 1u, right = (0x038u >> z) & 1u, bottom = (0x0e0u >> z) & 1u, left = (0x182u >> z) & 1u;
-                        const bool ok = (dx >= H || top) && (dx < TSR - H || bottom) && dx >= H - TSR && dx < 2 * TSR - H &&
-                                        (dy >= H || left) && (dy < TC - H || right) && dy >= H - TC && dy < 2 * TC - H;
-                        lost_here |= !ok;
-                    }
-                }
+                lost_here |= T::scatter(px, py, vt[k], v, mine, ft, X0, Y0, hs);
             }
         }
         if (lost_here) s_lost = 1;
@@ -309,56 +264,20 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
         __syncthreads();
         tl_stamp(a.tl, j, 3);
         // ---- the stencil of k_stencil_binned, one 16 x 64 sub-tile per 256-thread sub-group, on the LDS tile ----
-        const int bt = hs.bin_tbits;
-        const unsigned long long bm = (1ull << bt) - 1ull;
-        const unsigned long long* win = s_acc + (g * TR) * AC;
-        const uint32_t* cwin = s_cnt + (g * TR) * AC;
-        for (int idx = lt_; idx < TH * TW; idx += 256) {
-            const int tr = idx / TW, tc = idx - tr * TW;
-            const int gr = r0 - 1 + tr, gc = c0 - 1 + tc;
-            float tv = 0.f;
-            if (gr >= 0 && gr < R && gc >= 0 && gc < C) {
-                unsigned long long pk = 0;
-                uint32_t cacc = 0;
-#pragma unroll
-                for (int da = 0; da <= 2 * HS; ++da)
-#pragma unroll
-                    for (int db = 0; db <= 2 * HS; ++db) {
-                        pk += win[(tr + da) * PC + (tc + db)];
-                        if (!packed) cacc += cwin[(tr + da) * PC + (tc + db)];
-                    }
-                unsigned long long acc = pk;
-                if (packed) { acc = pk & bm; cacc = (uint32_t)(pk >> bt); }
-                tv = time_from_sums(cacc, (long long)acc, hs.tmin);
-            }
-            s_time[g][idx] = tv;
-        }
+        T::time_image(g, lt_, r0, c0, R, C, hs);
         tl_stamp(a.tl, j, 4);
         __syncthreads();
         tl_stamp(a.tl, j, 5);
-        SumsT smt;   // (a thread's own pixels: 32-bit integer sums, see bf_device_fns.h)
-        sums_zero(smt);
-#pragma unroll
-        for (int k = 0; k < (TR * TC) / 256; ++k) {
-            const int pidx = lt_ + k * 256;
-            const int lr = pidx / TC, lc = pidx - lr * TC;
-            const int gr = r0 + lr, gc = c0 + lc;
-            if (gr < R && gc < C) {
-                float gx, gy;
-                stencil_px<TW>(&s_time[g][(lr + 1) * TW + (lc + 1)], gr, gc, R, C, hR, hC, smt, gx, gy);
-            }
-        }
-        const Sums sm = sums_widen(smt);
-        constexpr bool kPack = TR * TC <= 1024 && TR <= 64 && TC <= 64;
+        const Sums sm = T::moments(g, lt_, r0, c0, R, C);
         tl_stamp(a.tl, j, 6);
-        block_reduce_publish<256, kPack>(sm, s_rpart[g], lt_, r0 - hR, c0 - hC);   // (work-group barrier inside)
+        block_reduce_publish<256, T::kPack>(sm, s_rpart[g], lt_, r0 - hR, c0 - hC);   // (work-group barrier inside)
         tl_stamp(a.tl, j, 7);
         // ---- publish: this sub-tile's record of pass j ----
         const unsigned long long tag = run_hi | (unsigned long long)(unsigned int)(j + 1);
         unsigned long long* const rec = a.rec + (size_t)(j & 1) * (size_t)nrec * kRecWords;
         unsigned long long* const red = a.red + (size_t)(j & 1) * (size_t)kLoopReducers * kRecWords;
         if (lt_ < 64) {
-            const Sums blk = block_reduce_total<256, kPack>(s_rpart[g], r0 - hR, c0 - hC);
+            const Sums blk = block_reduce_total<256, T::kPack>(s_rpart[g], r0 - hR, c0 - hC);
             if (lt_ < 16) {
                 unsigned long long w = (r0 < R) ? sums_lane_word(blk, lt_) : 0ull;   // (a sub-tile below the image adds nothing)
                 if (lt_ == 15) w = (g == 0 && s_lost) ? 1ull : 0ull;                  // lane 15: events outran their bins
@@ -367,12 +286,8 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
             }
         }
         tl_stamp(a.tl, j, 8);
-        if (tid_ >= 128) {   // waves that take no part in the exchange clear the tile for the next pass meanwhile
-            ulonglong2* z = reinterpret_cast<ulonglong2*>(s_acc);
-            for (int i = tid_ - 128; i < AR * AC / 2; i += THREADS - 128) z[i] = make_ulonglong2(0ull, 0ull);
-            if (!packed)
-                for (int i = tid_ - 128; i < AR * AC; i += THREADS - 128) s_cnt[i] = 0u;
-        }
+        // waves that take no part in the exchange clear the tile for the next pass meanwhile
+        if (tid_ >= 128) T::clear(tid_ - 128, THREADS - 128, !hs.bin_ok);
         // ---- reduce: wave 1 of the first work-groups adds up its share of the records ----
         if (tid_ >= 64 && tid_ < 128 && b < nred) {
             const int lane = tid_ - 64, f = lane & 15, sub = lane >> 4;
@@ -512,81 +427,52 @@ __global__ __launch_bounds__(256 * NSUB, NSUB == 2 ? 4 : 2) void k_fused_loop(Fu
 }
 
 // Raises the dynamic-LDS limit of one instantiation (once per device) and returns how many of its work-groups fit a CU.
-template <int HS, int NSUB>
-static hipError_t loop_setup(int* per_cu, size_t* lds_out) {
-    constexpr int U = BF_LOOP_U;
-    constexpr int H = HS + 1, AR = 16 * NSUB + 2 * H, AC = kTileC + 2 * H;
-    constexpr size_t lds = (size_t)AR * AC * 12 + (size_t)NSUB * (kTileR + 2) * (kTileC + 2) * 4;
-    const void* fn = reinterpret_cast<const void*>(&k_fused_loop<HS, NSUB, U>);
-    static std::atomic<unsigned long long> raised{0ull};   // (per device: see launch_bws2)
-    static std::atomic<int> cached_per_cu{-1};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    const unsigned long long dev_bit = 1ull << (dev & 63);
-    if (lds > 48 * 1024 && !(raised.load(std::memory_order_acquire) & dev_bit)) {
-        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kBinTileLdsMax);
-        if (e != hipSuccess) return e;
-        raised.fetch_or(dev_bit, std::memory_order_release);
-    }
-    int n = cached_per_cu.load(std::memory_order_acquire);   // (the devices of one node are alike)
-    if (n < 0) {
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, 256 * NSUB, lds);
-        if (e != hipSuccess) return e;
-        cached_per_cu.store(n, std::memory_order_release);
-    }
-    *per_cu = n;
-    *lds_out = lds;
-    return hipSuccess;
-}
-template <int HS, int NSUB>
-static hipError_t launch_loop2(const FusedLoopArgs& a, int n_cus, hipStream_t s) {
-    int per_cu = 0;
-    size_t lds = 0;
-    const hipError_t e = loop_setup<HS, NSUB>(&per_cu, &lds);
-    if (e != hipSuccess) return e;
-    const int ntiles = a.nbr * a.nbc;
-    if ((long long)per_cu * n_cus < ntiles) return hipErrorCooperativeLaunchTooLarge;
-    // A plain launch: the grid was checked against the occupancy query above, which is all hipLaunchCooperativeKernel adds
-    // (at 15-19 us of host time per launch on this stack); residency is the same either way, and should the hardware admit
-    // fewer work-groups than the query says, the kernel's waiters time out and the launch undoes itself.
-    hipLaunchKernelGGL((k_fused_loop<HS, NSUB, BF_LOOP_U>), dim3(ntiles), dim3(256 * NSUB), lds, s, a);
-    return hipGetLastError();
-}
 // Only the 32-row tiles (NSUB = 2) are instantiated: bf_set_cloud takes 64-row tiles when the nine sort keys per 32-row tile
 // would not fit the counting sort (> 910 tiles), and that many tiles are never all resident -- the persistent form of the
 // 64-row tile could only run when forced by an option, which went in round 5.
 template <int HS>
-static hipError_t launch_loop1(const FusedLoopArgs& a, int rows_per_tile, int n_cus, hipStream_t s) {
-    return rows_per_tile == 32 ? launch_loop2<HS, 2>(a, n_cus, s) : hipErrorInvalidValue;
+static hipError_t loop_setup(int* per_cu) {
+    using T = FusedTile<HS, 2>;
+    const void* fns[1] = {reinterpret_cast<const void*>(&k_fused_loop<HS, 2, BF_LOOP_U>)};
+    static std::atomic<int> cached_per_cu{-1};
+    if constexpr (T::kLds > 48 * 1024) {
+        static std::atomic<unsigned long long> raised{0ull};
+        const hipError_t e = raise_dynamic_lds(raised, fns);
+        if (e != hipSuccess) return e;
+    }
+    int n = cached_per_cu.load(std::memory_order_acquire);   // (the devices of one node are alike)
+    if (n < 0) {
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fns[0], T::THREADS, T::kLds);
+        if (e != hipSuccess) return e;
+        cached_per_cu.store(n, std::memory_order_release);
+    }
+    *per_cu = n;
+    return hipSuccess;
 }
 hipError_t launch_fused_loop(const FusedLoopArgs& a, int half_scale, int rows_per_tile, int n_cus, hipStream_t s) {
-    switch (half_scale) {
-        case 0: return launch_loop1<0>(a, rows_per_tile, n_cus, s);
-        case 1: return launch_loop1<1>(a, rows_per_tile, n_cus, s);
-        case 2: return launch_loop1<2>(a, rows_per_tile, n_cus, s);
-        case 3: return launch_loop1<3>(a, rows_per_tile, n_cus, s);
-        case 4: return launch_loop1<4>(a, rows_per_tile, n_cus, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-template <int HS>
-static bool loop_resident1(int rows_per_tile, int n_cus, int ntiles) {
-    if (rows_per_tile != 32) return false;
-    int per_cu = 0;
-    size_t lds = 0;
-    const hipError_t e = loop_setup<HS, 2>(&per_cu, &lds);
-    if (e != hipSuccess) { (void)hipGetLastError(); return false; }
-    return (long long)per_cu * n_cus >= ntiles;
+    if (rows_per_tile != 32) return hipErrorInvalidValue;
+    return dispatch_half_scale(half_scale, hipErrorInvalidValue, [&](auto hs) {
+        constexpr int HS = decltype(hs)::value;
+        using T = FusedTile<HS, 2>;
+        int per_cu = 0;
+        const hipError_t e = loop_setup<HS>(&per_cu);
+        if (e != hipSuccess) return e;
+        const int ntiles = a.nbr * a.nbc;
+        if ((long long)per_cu * n_cus < ntiles) return hipErrorCooperativeLaunchTooLarge;
+        // A plain launch: the grid was checked against the occupancy query above, which is all hipLaunchCooperativeKernel adds
+        // (at 15-19 us of host time per launch on this stack); residency is the same either way, and should the hardware admit
+        // fewer work-groups than the query says, the kernel's waiters time out and the launch undoes itself.
+        hipLaunchKernelGGL((k_fused_loop<HS, 2, BF_LOOP_U>), dim3(ntiles), dim3(T::THREADS), T::kLds, s, a);
+        return hipGetLastError();
+    });
 }
 bool fused_loop_resident(int half_scale, int rows_per_tile, int n_cus, int ntiles) {
-    switch (half_scale) {
-        case 0: return loop_resident1<0>(rows_per_tile, n_cus, ntiles);
-        case 1: return loop_resident1<1>(rows_per_tile, n_cus, ntiles);
-        case 2: return loop_resident1<2>(rows_per_tile, n_cus, ntiles);
-        case 3: return loop_resident1<3>(rows_per_tile, n_cus, ntiles);
-        case 4: return loop_resident1<4>(rows_per_tile, n_cus, ntiles);
-        default: return false;
-    }
+    if (rows_per_tile != 32) return false;
+    return dispatch_half_scale(half_scale, false, [&](auto hs) {
+        int per_cu = 0;
+        if (loop_setup<decltype(hs)::value>(&per_cu) != hipSuccess) { (void)hipGetLastError(); return false; }
+        return (long long)per_cu * n_cus >= ntiles;
+    });
 }
 
 }  // namespace bf

@@ -690,24 +690,13 @@ template <bool HEAD, int THREADS, int U, int FMT>
 static hipError_t launch_bws2(const BinScatterArgs& a, bool warp, hipStream_t s) {
     // dynamic LDS: the bin's tile; event lists: none
     const size_t lds = FMT == 2 ? 0 : (size_t)a.g.LR * a.g.L * sizeof(unsigned long long) + 16;
-    // LDS tiles above 64 KiB need the dynamic-LDS attribute raised (160 KiB per CU on gfx950).  The attribute belongs to
-    // the (function, device) pair, so it is raised once per device the instantiation is launched on: a bit per device
-    // ordinal, set after the calls succeeded (two threads racing here both make the calls, which is harmless).
     static std::atomic<unsigned long long> raised{0ull};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
-    const unsigned long long dev_bit = 1ull << (dev & 63);
     const void* fns[2] = {HEAD ? reinterpret_cast<const void*>(&k_bin_warp_scatter<true, THREADS, U, FMT>)
                                : reinterpret_cast<const void*>(&k_bin_warp_scatter_lean<true, THREADS, U, FMT>),
                           HEAD ? reinterpret_cast<const void*>(&k_bin_warp_scatter<false, THREADS, U, FMT>)
                                : reinterpret_cast<const void*>(&k_bin_warp_scatter_lean<false, THREADS, U, FMT>)};
-    if (!(raised.load(std::memory_order_acquire) & dev_bit)) {
-        for (const void* f : fns) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kBinTileLdsMax);
-            if (e != hipSuccess) return e;
-        }
-        raised.fetch_or(dev_bit, std::memory_order_release);
-    }
+    const hipError_t e = raise_dynamic_lds(raised, fns);
+    if (e != hipSuccess) return e;
     if constexpr (HEAD) {
         if (warp) launch_timed(k_bin_warp_scatter<true, THREADS, U, FMT>, dim3(a.g.nbins), dim3(THREADS), lds, s, a.bin_start, a.st_in, a.acc, a);
         else launch_timed(k_bin_warp_scatter<false, THREADS, U, FMT>, dim3(a.g.nbins), dim3(THREADS), lds, s, a.bin_start, a.st_in, a.acc, a);

@@ -4,7 +4,7 @@ work-group, events of a tile's edge strips read by the neighbouring tiles' work-
 It must return the bits of the two-kernel tile-binned loop (same integer accumulators, same per-sub-tile f64 partials) --
 model, iteration count, every trace record, per-event flow, and the warm start that follows -- with the default margin,
 with margins so small that events outrun their bins (the `lost` flag, a re-bin, the pass repeated before its update),
-with 64-row tiles (the 640x480 case: too many 32-row tiles for the counting sort), with the unpacked LDS planes, without the predictive re-bin -- and so must its persistent form
+with 64-row tiles (the 640x480 case: too many 32-row tiles for the counting sort), with the unpacked LDS planes, without the predictive re-bin, at the scales 7 and 9 whose instantiations spill registers -- and so must its persistent form
 (k_fused_loop, bf_loop.hip: many iterations per launch, sums exchanged through tagged records), forced for the cold run
 as well ("persist" = 2; by default only the warm start takes it).  And `auto` must take the one-kernel loop exactly for
 the slices it was measured to be faster on (bf_set_cloud).
@@ -65,6 +65,28 @@ def test_same_bits_as_the_two_kernel_loop(accel_mod, case):
             assert got[key] == ref[key], (name, key)
         if name == "margin 1":
             assert got["rebins"] > ref["rebins"], "margin 1 must exercise the lost -> re-bin -> repeat path"
+
+
+# Scales 7 and 9 (HS = 3, 4: the instantiations that spill registers), at the smallest shapes that reach each kernel by the plan's
+# own rule -- 32-row tiles (k_fused_pass<HS,2>, k_fused_loop<HS,2>: 126 and 216 tiles, all resident) while nine sort keys per tile fit
+# the counting sort, else 64-row tiles (k_fused_pass<HS,4>).  (No launch counts here: at these scales an iteration moves events
+# by many scaled pixels and re-bins are frequent, so the two loops' launch counts -- 134 against 166 at 240x180, scale 9 -- come too
+# close for the 0.75 above to tell which one ran.)
+@pytest.mark.parametrize("case", [(20000, 60, 80, 7, 5), (20000, 60, 80, 9, 5), (50000, 180, 240, 7, 3), (50000, 180, 240, 9, 3)],
+                         ids=lambda c: "%dev_%dx%d_s%d" % (c[0], c[2], c[1], c[3]))
+def test_same_bits_at_the_large_scales(accel_mod, case):
+    n, H, W, s, seed = case
+    sl = synth.make_slice(n, H, W, 0.03, seed=seed)
+    ref = run(accel_mod, sl, H, W, s, {"binned": 2, "fused": 0}, 60)
+    assert ref["rc"][0] == 0 and ref["it"][0] > 20
+    for name, o in VARIANTS:
+        if name not in ("default margin", "persistent kernel", "unpacked planes", "margin 1"):
+            continue
+        got = run(accel_mod, sl, H, W, s, dict({"binned": 2, "fused": 2, "persist": 0}, **o), 60)
+        if name == "persistent kernel" and (s * H + s + 31) // 32 * ((s * W + s + 63) // 64) <= 256:
+            assert got["persistent"] == 1
+        for key in ("rc", "it", "model", "trace", "flow"):
+            assert got[key] == ref[key], (name, key)
 
 
 def test_auto_takes_it_where_it_was_measured_faster(accel_mod):
