@@ -177,11 +177,14 @@ EXPORTS = [
     "bf_frame_create", "bf_frame_destroy", "bf_frame_render", "bf_frame_wait", "bf_frame_release", "bf_render_frame",
     "bf_flow_field", "bf_color_flow_img", "bf_flow_frame_create", "bf_flow_frame_destroy", "bf_flow_frame_render",
     "bf_flow_frame_wait", "bf_flow_frame_release", "bf_render_flow_frame",
+    "bf_global_hold_field", "bf_global_hold_best", "bf_global_get_flow", "bf_global_flow_field", "bf_global_color_flow_img",
+    "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
 BF_FLOW_FRAME_FLO = 4               # ... and bf_flow_frame_create's third
 BF_FLOW_LAST_UPLOADED, BF_FLOW_FIRST_UPLOADED = 0, 1   # owner_rule of the per-pixel flow
+BF_GLOBAL_HOLD_CELLS, BF_GLOBAL_HOLD_FIELD = 1, 2      # mode of bf_global_hold_field
 
 _lib = None
 
@@ -363,6 +366,15 @@ def load(path=None):
                                          C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.POINTER(C.c_float))]
         L.bf_flow_frame_release.argtypes = [C.c_void_p, C.c_int64]
         L.bf_render_flow_frame.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        # the held flow of the exhaustive search (include/bf_accel.h: bf_global_hold_*, bf_global_get_flow and its outputs)
+        L.bf_global_hold_field.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32]
+        L.bf_global_hold_best.argtypes = [C.c_void_p]
+        L.bf_global_get_flow.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+        L.bf_global_flow_field.argtypes = L.bf_flow_field.argtypes
+        L.bf_global_color_flow_img.argtypes = L.bf_color_flow_img.argtypes
+        L.bf_global_flow_frame_render.argtypes = L.bf_flow_frame_render.argtypes
+        L.bf_global_render_flow_frame.argtypes = L.bf_render_flow_frame.argtypes
+        L.bf_global_emit_slice.argtypes = L.bf_emit_slice.argtypes
         _libs[path] = L
         if path == LIB_PATH:
             _lib = L
@@ -690,23 +702,23 @@ class Accel:
         self._chk(self.L.bf_render_frame(self.h, res_x, res_y, _ptr(p), _ptr(a)))
         return p, a
 
-    def flow_field(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED):
+    def flow_field(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, _call=None):
         """The per-pixel flow field of the live slice (bf_flow_field): (owner, u, v), each (res_x, res_y) -- the upload index
         of the event that owns the pixel (-1: none) and its (best_u, best_v) as bf_compute_uv returns them (0: none)."""
         owner = np.empty((res_x, res_y), dtype=np.int32)
         u, v = np.empty((res_x, res_y)), np.empty((res_x, res_y))
-        self._chk(self.L.bf_flow_field(self.h, res_x, res_y, owner_rule, _ptr(owner), _ptr(u), _ptr(v)))
+        self._chk((_call or self.L.bf_flow_field)(self.h, res_x, res_y, owner_rule, _ptr(owner), _ptr(u), _ptr(v)))
         return owner, u, v
 
-    def color_flow_img(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, want_hs=False):
+    def color_flow_img(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, want_hs=False, _call=None):
         """EventFile::color_flow_img (event_file.h:318-350): the (res_x, res_y, 3) B, G, R colour-coded flow of the live
         slice; with want_hs also the (res_x, res_y, 2) H and S bytes before the conversion."""
         bgr = np.empty((res_x, res_y, 3), dtype=np.uint8)
         hs = np.empty((res_x, res_y, 2), dtype=np.uint8) if want_hs else None
-        self._chk(self.L.bf_color_flow_img(self.h, res_x, res_y, owner_rule, _ptr(bgr), _ptr(hs)))
+        self._chk((_call or self.L.bf_color_flow_img)(self.h, res_x, res_y, owner_rule, _ptr(bgr), _ptr(hs)))
         return (bgr, hs) if want_hs else bgr
 
-    def render_flow_frame(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, ppm=True, avi=True, flo=True):
+    def render_flow_frame(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, ppm=True, avi=True, flo=True, _call=None):
         """The flow frame of the live slice, composed on the device (bf_render_flow_frame): compensated events | colour-coded
         flow | raw events.  Returns (ppm, avi, flo): the PPM payload as a (res_x, 3 res_y, 3) RGB array, the AVI payload as a
         (res_x, stride) byte array of bottom-up BGR rows, the .flo payload as (res_x, res_y, 2) float32 (horizontal = v,
@@ -714,8 +726,38 @@ class Accel:
         p = np.empty((res_x, 3 * res_y, 3), dtype=np.uint8) if ppm else None
         a = np.empty((res_x, (9 * res_y + 3) & ~3), dtype=np.uint8) if avi else None
         f = np.empty((res_x, res_y, 2), dtype=np.float32) if flo else None
-        self._chk(self.L.bf_render_flow_frame(self.h, res_x, res_y, owner_rule, _ptr(p), _ptr(a), _ptr(f)))
+        self._chk((_call or self.L.bf_render_flow_frame)(self.h, res_x, res_y, owner_rule, _ptr(p), _ptr(a), _ptr(f)))
         return p, a, f
+
+    # ---- the held flow of the exhaustive search (include/bf_accel.h: "the held flow") ----
+    def global_hold_field(self, cell_nx, cell_ny, nz=127.0, mode=BF_GLOBAL_HOLD_FIELD):
+        """Keeps on the device the flow global_project_field (mode BF_GLOBAL_HOLD_FIELD) or global_project_cells
+        (BF_GLOBAL_HOLD_CELLS) would project every event under; grids and refusals as there.  Nothing is rendered or scored."""
+        cx, cy, _, _, _ = self._project_runs_args(cell_nx, cell_ny, False, False, False)
+        self._chk(self.L.bf_global_hold_field(self.h, _ptr(cx), _ptr(cy), len(cx), nz, mode))
+
+    def global_hold_best(self):
+        """Keeps on the device a snapshot of the searches' per-event best flow (bf_global_hold_best)."""
+        self._chk(self.L.bf_global_hold_best(self.h))
+
+    def global_get_flow(self, keys=("nx", "ny", "u", "v", "pr_x", "pr_y")):
+        """The held flow (bf_global_get_flow): dict of the arrays asked for, n doubles each in upload order."""
+        every = ("nx", "ny", "u", "v", "pr_x", "pr_y")
+        out = {k: np.zeros(self.n, dtype=np.float64) for k in keys}
+        self._chk(self.L.bf_global_get_flow(self.h, *[_ptr(out.get(k)) for k in every]))
+        return out
+
+    def global_flow_field(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED):
+        """flow_field of the held flow (bf_global_flow_field): every event, the held (u, v) of the owner as bits."""
+        return self.flow_field(res_x, res_y, owner_rule, _call=self.L.bf_global_flow_field)
+
+    def global_color_flow_img(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, want_hs=False):
+        """color_flow_img of the held flow (bf_global_color_flow_img)."""
+        return self.color_flow_img(res_x, res_y, owner_rule, want_hs, _call=self.L.bf_global_color_flow_img)
+
+    def global_render_flow_frame(self, res_x, res_y, owner_rule=BF_FLOW_LAST_UPLOADED, ppm=True, avi=True, flo=True):
+        """render_flow_frame of the held flow (bf_global_render_flow_frame): held positions | colour-coded flow | raw events."""
+        return self.render_flow_frame(res_x, res_y, owner_rule, ppm, avi, flo, _call=self.L.bf_global_render_flow_frame)
 
     def local_run(self, res_x=180, res_y=240, max_evaluations=100000):
         st = LocalState()
@@ -864,3 +906,39 @@ class Accel:
         g = C.c_double(0)
         self._chk(self.L.bf_copy_bandwidth(self.h, nbytes, reps, C.byref(g)))
         return g.value
+
+
+class Emit:
+    """One bf_emit: the -o table accumulated on the device (include/bf_accel.h, bf_emit_*), minimal.  slice() enqueues one
+    slice of `accel`'s context -- with the rolling optimiser's flow, or with held=True the held flow of the exhaustive
+    search (bf_global_emit_slice) -- waits for it, copies its rows out of the pinned ring and releases them."""
+
+    def __init__(self, accel, ring_cap, rows, cols, out_rows):
+        self.acc, self.L = accel, accel.L
+        self.h = C.c_void_p()
+        accel._chk(self.L.bf_emit_create(accel.h, ring_cap, rows, cols, out_rows, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            self.L.bf_emit_destroy(self.h)
+            self.h = None
+
+    def slice(self, n, first, start_time, lead=None, held=False):
+        """lead: None or (t, row, col) of the ring's oldest element.  Returns (ticket, rows): ticket -1 and rows None when
+        there was nothing to enqueue, else rows = dict of t (uint64), row, col (uint16), u, v (float64)."""
+        call = self.L.bf_global_emit_slice if held else self.L.bf_emit_slice
+        lt, lr, lc = lead if lead is not None else (0, 0, 0)
+        ticket = C.c_int64(-2)
+        self.acc._chk(call(self.acc.h, self.h, n, first, start_time, 0 if lead is None else 1, lt, lr, lc, C.byref(ticket)))
+        if ticket.value < 0:
+            return ticket.value, None
+        first_row, rows = C.c_uint64(), C.c_int64()
+        self.acc._chk(self.L.bf_emit_wait(self.acc.h, self.h, ticket.value, C.byref(first_row), C.byref(rows)))
+        cols = [C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint16)(), C.POINTER(C.c_uint16)(), C.POINTER(C.c_double)(),
+                C.POINTER(C.c_double)()]
+        R = C.c_int64()
+        self.acc._chk(self.L.bf_emit_output(self.h, *[C.byref(x) for x in cols], C.byref(R)))
+        idx = (first_row.value + np.arange(rows.value, dtype=np.uint64)) % np.uint64(R.value)
+        out = {k: np.ctypeslib.as_array(x, shape=(R.value,))[idx].copy() for k, x in zip(("t", "row", "col", "u", "v"), cols)}
+        self.acc._chk(self.L.bf_emit_release(self.h, first_row.value + rows.value))
+        return ticket.value, out

@@ -263,11 +263,25 @@ extern "C" int ctx_device_uv(bf_ctx* c, const double2** uv);
 // warp has run (Event::reset: n = 0) or the window is degenerate (bf_operators.cpp)
 extern "C" int ctx_device_nxny(bf_ctx* c, const double2** nxny);
 
+// The held flow of the exhaustive search (bf_global_search.cpp; include/bf_accel.h, bf_global_hold_field / bf_global_hold_best)
+// as the renderers and the -o table read it: address words and f32 products in the order the hold computed them in, `idx` the
+// upload index of a position, (nx, ny) and (u, v) in upload order; every pointer null when n == 0.  BF_ERR_STATE (message
+// set, `who` the entry point's name) when there is none for the slice uploaded now.
+struct GlobalHeldFlow {
+    const uint32_t* xy; const float2* p; const uint32_t* idx; const double2 *nxny, *uv;
+    long long n;
+};
+int global_held_flow(bf_ctx* c, const char* who, GlobalHeldFlow* out);
+
 // The two frame tiles of the live slice (bf_extras.cpp), ENQUEUED on the context stream into device memory: the 8-bit projection
 // image, (scale res_x) x (scale res_y), and the colour-coded time image, (scale res_x + scale) x (scale res_y + scale) BGR.  A
 // pending bf_set_model warp is applied first.  bf_projection_img / bf_color_time_img are these, a copy and a sync; bf_frame_render
 // runs them into its own tiles.
 extern "C" int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img);
+// render_projection_img of n events given as arrays (address words, f32 products, noise flags or null, all in one order)
+// instead of the live slice: no pending warp is applied, nothing of the live slice is read.
+extern "C" int render_projection_img_of(bf_ctx* c, const uint32_t* xy, const float2* p, const uint8_t* noise, long long n,
+                                        int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img);
 extern "C" int render_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_bgr);
 
 // Which loop a slice runs (bf_plan.cpp): plan_slice once per slice, plan_run once per run; nothing else decides it.

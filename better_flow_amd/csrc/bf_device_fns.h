@@ -70,6 +70,18 @@ __device__ __forceinline__ double2 uv_from_n(double2 v) {
     return o;
 }
 
+// Event::compute_uv for an nz of the event's own (the exhaustive search's candidates carry theirs): cand_uv's expression
+// (bf_global_search.cpp) on the device -- uv_from_n with nz in place of the constant 127.  The ONE place the held flow of
+// bf_global_hold_field / bf_global_hold_best takes its (u, v) from.  With nz == 127 the bits are uv_from_n's.
+__device__ __forceinline__ double2 uv_from_n_nz(double2 v, double nz) {
+    const double len = hypot(v.x, v.y);
+    const double speed = len / (nz / (double)(1000000000 / (1 * 10000)));
+    double2 o;
+    o.x = (len == 0) ? 0 : speed * v.x / len;
+    o.y = (len == 0) ? 0 : speed * v.y / len;
+    return o;
+}
+
 // Previous / new projected position from the stored f32 product (event.h:167-168):
 //   pr = float(fr) - (kx * float(t)) / 10000.0      (f32 product, f64 divide and subtract)
 // (float(fr) is exact for a 16-bit coordinate, so the u32 -> f64 conversion gives the same double in one step)

@@ -88,6 +88,81 @@ int create_failed(bf_ctx* c, hipError_t err, const char* what) {
     return fail(c, err == hipErrorOutOfMemory ? BF_ERR_CAPACITY : BF_ERR_HIP, "bf_emit_create: %s: %s", what, hipGetErrorString(err));
 }
 
+// bf_emit_slice (held false: the rows' flow is the live slice's, bf_compute_uv's) and bf_global_emit_slice (held true: the held
+// flow of the exhaustive search, which must be of these n events); `name`: the entry point's.
+int emit_slice(bf_ctx* c, bf_emit* e, const char* name, bool held, int64_t n, uint64_t first, uint64_t start_time, int32_t lead,
+               uint64_t lead_t, int32_t lead_row, int32_t lead_col, int64_t* ticket_out) {
+    if (!c || !e || !ticket_out) return BF_ERR_ARG;
+    *ticket_out = -1;
+    GlobalHeldFlow hf;
+    if (held) {
+        const int hrc = global_held_flow(c, name, &hf);
+        if (hrc != BF_OK) return hrc;
+        if (hf.n != n) return fail(c, BF_ERR_STATE, "%s: the held flow has %lld events, not %lld", name, hf.n, (long long)n);
+    }
+    if (c->device != e->device) return fail(c, BF_ERR_ARG, "%s: state on device %d, context on device %d", name, e->device, c->device);
+    if (n < 0 || (lead && first == 0)) return fail(c, BF_ERR_ARG, "%s: bad slice (n %lld, first %llu, lead %d)", name, (long long)n,
+                                                   (unsigned long long)first, lead);
+    const long long m = n + (lead ? 1 : 0);
+    std::lock_guard<std::mutex> g(e->mu);
+    if ((unsigned long long)m > e->cap)
+        return fail(c, BF_ERR_ARG, "%s: %lld elements exceed the ring capacity %llu", name, m, e->cap);
+    if (first < e->prev_first)
+        return fail(c, BF_ERR_ARG, "%s: slice starts at %llu, before the previous one (%llu)", name, (unsigned long long)first, e->prev_first);
+    if (n > 0 && (!c->uploaded || c->n != n))
+        return fail(c, BF_ERR_STATE, "%s: the context's slice has %lld events, not %lld", name, c->uploaded ? c->n : 0ll, (long long)n);
+    if (lead && (lead_row < 0 || lead_col < 0)) return fail(c, BF_ERR_ARG, "%s: negative lead address", name);
+    if (m == 0) return BF_OK;
+    // (checked before anything runs: the state is untouched)
+    if (e->known_end + e->pending_bound + (unsigned long long)m - e->released > e->out_rows || e->issued - e->waited >= kRecs)
+        return fail(c, BF_ERR_CAPACITY, "%s: the output ring (%llu rows) may overflow: release consumed rows first", name, e->out_rows);
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = emit_reserve(c, e, m);
+    if (rc != BF_OK) return rc;
+    EmitSlice a;
+    std::memset(&a, 0, sizeof(a));
+    const double2* uv = nullptr;
+    if (n > 0) {
+        if (held) uv = hf.uv;
+        else if ((rc = ctx_device_uv(c, &uv)) != BF_OK) return rc;
+        const bf_ctx::EvSet& s = c->set[c->cs];
+        a.xy = s.xy; a.tloc = s.t; a.perm = c->has_perm ? s.perm : nullptr;
+    }
+    const long long ticket = e->issued;
+    const int slot = (int)(ticket % kRecs);
+    a.uv = uv;
+    a.n = n; a.lead = lead ? 1 : 0;
+    a.first = first; a.cap = e->cap; a.start_time = start_time; a.prev_end = e->prev_end;
+    a.last = first + (unsigned long long)n - 1;   // (n == 0: the lead)
+    a.lead_t = lead_t; a.lead_row = (uint32_t)lead_row; a.lead_col = (uint32_t)lead_col;
+    a.rows = e->rows; a.cols = e->cols;
+    a.plane = e->plane; a.tail_t = e->tail_t; a.tail_g = e->tail_g;
+    a.t = e->t; a.rc = e->rc; a.flag = e->flag; a.keys = e->keys; a.pos = e->pos;
+    a.jbits = bits_for((unsigned long long)m - 1);
+    a.kbits = a.jbits + bits_for((unsigned long long)e->rows * (unsigned long long)e->cols - 1);
+    a.err = e->d_err;
+    a.out_t = (unsigned long long*)e->out_t.get(); a.out_row = e->out_row; a.out_col = e->out_col; a.out_u = e->out_u; a.out_v = e->out_v;
+    a.out_rows = e->out_rows;
+    a.off_in = e->d_off + (ticket & 1);
+    a.off_out = e->d_off + ((ticket + 1) & 1);
+    a.rec = e->recs + 4 * slot;
+    // after the previous slice, whichever context enqueued it: it wrote the plane, the tail and the offset this one reads
+    if (e->have_last) HIP_TRY(c, hipStreamWaitEvent(c->stream, e->last, 0));
+    HIP_TRY(c, hipMemsetAsync(e->d_err, 0, 4, c->stream));
+    HIP_TRY(c, launch_emit(a, e->keys2, e->temp, e->temp.size(), c->stream));
+    HIP_TRY(c, hipEventRecord(e->done[slot], c->stream));
+    e->last = e->done[slot];
+    e->have_last = true;
+    e->rec_m[slot] = m;
+    e->pending_bound += (unsigned long long)m;
+    e->issued = ticket + 1;
+    const unsigned long long end = first + (unsigned long long)n;
+    if (end > e->prev_end) e->prev_end = end;
+    e->prev_first = first;
+    *ticket_out = ticket;
+    return BF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -157,69 +232,12 @@ int bf_emit_output(bf_emit* e, uint64_t** t, uint16_t** row, uint16_t** col, dou
 
 int bf_emit_slice(bf_ctx* c, bf_emit* e, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
                   int32_t lead_row, int32_t lead_col, int64_t* ticket_out) {
-    if (!c || !e || !ticket_out) return BF_ERR_ARG;
-    *ticket_out = -1;
-    if (c->device != e->device) return fail(c, BF_ERR_ARG, "bf_emit_slice: state on device %d, context on device %d", e->device, c->device);
-    if (n < 0 || (lead && first == 0)) return fail(c, BF_ERR_ARG, "bf_emit_slice: bad slice (n %lld, first %llu, lead %d)", (long long)n,
-                                                   (unsigned long long)first, lead);
-    const long long m = n + (lead ? 1 : 0);
-    std::lock_guard<std::mutex> g(e->mu);
-    if ((unsigned long long)m > e->cap)
-        return fail(c, BF_ERR_ARG, "bf_emit_slice: %lld elements exceed the ring capacity %llu", m, e->cap);
-    if (first < e->prev_first)
-        return fail(c, BF_ERR_ARG, "bf_emit_slice: slice starts at %llu, before the previous one (%llu)", (unsigned long long)first, e->prev_first);
-    if (n > 0 && (!c->uploaded || c->n != n))
-        return fail(c, BF_ERR_STATE, "bf_emit_slice: the context's slice has %lld events, not %lld", c->uploaded ? c->n : 0ll, (long long)n);
-    if (lead && (lead_row < 0 || lead_col < 0)) return fail(c, BF_ERR_ARG, "bf_emit_slice: negative lead address");
-    if (m == 0) return BF_OK;
-    // (checked before anything runs: the state is untouched)
-    if (e->known_end + e->pending_bound + (unsigned long long)m - e->released > e->out_rows || e->issued - e->waited >= kRecs)
-        return fail(c, BF_ERR_CAPACITY, "bf_emit_slice: the output ring (%llu rows) may overflow: release consumed rows first", e->out_rows);
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc = emit_reserve(c, e, m);
-    if (rc != BF_OK) return rc;
-    EmitSlice a;
-    std::memset(&a, 0, sizeof(a));
-    const double2* uv = nullptr;
-    if (n > 0) {
-        rc = ctx_device_uv(c, &uv);
-        if (rc != BF_OK) return rc;
-        const bf_ctx::EvSet& s = c->set[c->cs];
-        a.xy = s.xy; a.tloc = s.t; a.perm = c->has_perm ? s.perm : nullptr;
-    }
-    const long long ticket = e->issued;
-    const int slot = (int)(ticket % kRecs);
-    a.uv = uv;
-    a.n = n; a.lead = lead ? 1 : 0;
-    a.first = first; a.cap = e->cap; a.start_time = start_time; a.prev_end = e->prev_end;
-    a.last = first + (unsigned long long)n - 1;   // (n == 0: the lead)
-    a.lead_t = lead_t; a.lead_row = (uint32_t)lead_row; a.lead_col = (uint32_t)lead_col;
-    a.rows = e->rows; a.cols = e->cols;
-    a.plane = e->plane; a.tail_t = e->tail_t; a.tail_g = e->tail_g;
-    a.t = e->t; a.rc = e->rc; a.flag = e->flag; a.keys = e->keys; a.pos = e->pos;
-    a.jbits = bits_for((unsigned long long)m - 1);
-    a.kbits = a.jbits + bits_for((unsigned long long)e->rows * (unsigned long long)e->cols - 1);
-    a.err = e->d_err;
-    a.out_t = (unsigned long long*)e->out_t.get(); a.out_row = e->out_row; a.out_col = e->out_col; a.out_u = e->out_u; a.out_v = e->out_v;
-    a.out_rows = e->out_rows;
-    a.off_in = e->d_off + (ticket & 1);
-    a.off_out = e->d_off + ((ticket + 1) & 1);
-    a.rec = e->recs + 4 * slot;
-    // after the previous slice, whichever context enqueued it: it wrote the plane, the tail and the offset this one reads
-    if (e->have_last) HIP_TRY(c, hipStreamWaitEvent(c->stream, e->last, 0));
-    HIP_TRY(c, hipMemsetAsync(e->d_err, 0, 4, c->stream));
-    HIP_TRY(c, launch_emit(a, e->keys2, e->temp, e->temp.size(), c->stream));
-    HIP_TRY(c, hipEventRecord(e->done[slot], c->stream));
-    e->last = e->done[slot];
-    e->have_last = true;
-    e->rec_m[slot] = m;
-    e->pending_bound += (unsigned long long)m;
-    e->issued = ticket + 1;
-    const unsigned long long end = first + (unsigned long long)n;
-    if (end > e->prev_end) e->prev_end = end;
-    e->prev_first = first;
-    *ticket_out = ticket;
-    return BF_OK;
+    return emit_slice(c, e, "bf_emit_slice", false, n, first, start_time, lead, lead_t, lead_row, lead_col, ticket_out);
+}
+
+int bf_global_emit_slice(bf_ctx* c, bf_emit* e, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
+                         int32_t lead_row, int32_t lead_col, int64_t* ticket_out) {
+    return emit_slice(c, e, "bf_global_emit_slice", true, n, first, start_time, lead, lead_t, lead_row, lead_col, ticket_out);
 }
 
 int bf_emit_wait(bf_ctx* c, bf_emit* e, int64_t ticket, uint64_t* first_row, int64_t* rows) {

@@ -269,21 +269,20 @@ int local_step(bf_ctx* c, double nx, double ny, double* score, bool want_img) {
 
 }  // namespace
 
-// EventFile::projection_img (event_file.h:460-515) of the live slice into d_img (at least (scale res_x) x (scale res_y) bytes):
-// enqueued on the context stream, nothing copied, nothing waited for.  Arguments checked by the callers.
-int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img) {
+// EventFile::projection_img (event_file.h:460-515) of n events (address words, f32 products, noise flags or null) into d_img (at
+// least (scale res_x) x (scale res_y) bytes): enqueued on the context stream, nothing copied, nothing waited for.  Arguments
+// checked by the callers.
+int render_projection_img_of(bf_ctx* c, const uint32_t* xy, const float2* p, const uint8_t* noise, long long n, int32_t scale,
+                             int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img) {
     const size_t px = (size_t)res_x * scale * (size_t)res_y * scale;
-    int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
+    int rc = ensure_lplanes(c);
     if (rc != BF_OK) return rc;
-    if ((rc = ensure_lplanes(c)) != BF_OK) return rc;
     // the point planes are shared with the contrast-score path: lay them out afresh for this geometry
     for (int i = 0; i < 2; ++i) HIP_TRY(c, hipMemsetAsync(c->d_lplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
     c->have_lwin = false;
     c->lcur = 0;
     HIP_TRY(c, hipMemsetAsync(c->d_lscore, 0, 2 * sizeof(unsigned long long), c->stream));
-    const bf_ctx::EvSet& e = c->set[c->cs];
-    launch_proj_count(e.xy, e.p, c->has_noise ? c->d_noise : nullptr, c->n, scale, res_x, res_y, show_final ? 1 : 0,
-                      c->d_lplane[0], c->stream);
+    launch_proj_count(xy, p, noise, n, scale, res_x, res_y, show_final ? 1 : 0, c->d_lplane[0], c->stream);
     LocalGeom g;
     memset(&g, 0, sizeof(g));
     g.scale = scale; g.R = res_x * scale; g.C = res_y * scale;
@@ -292,6 +291,14 @@ int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y
     launch_proj_scale(d_img, (long long)px, c->d_lscore, c->stream);
     HIP_TRY(c, hipGetLastError());
     return BF_OK;
+}
+
+// The same of the live slice.
+int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img) {
+    const int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
+    if (rc != BF_OK) return rc;
+    const bf_ctx::EvSet& e = c->set[c->cs];
+    return render_projection_img_of(c, e.xy, e.p, c->has_noise ? c->d_noise.get() : nullptr, c->n, scale, res_x, res_y, show_final, d_img);
 }
 
 // EventFile::color_time_img (event_file.h:649-747) of the live slice into d_bgr ((scale res_x + scale) x (scale res_y + scale)

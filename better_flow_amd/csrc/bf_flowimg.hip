@@ -12,6 +12,8 @@
 //                     -- the expression of k_compute_uv, so the field is bf_compute_uv's value at the owner as bits --, then
 //                     whichever of the outputs were asked for: owner index, f64 (u, v), the .flo pair, the H / S bytes
 //                     (bf_flow_hs) and the B, G, R bytes (bf_hsv_to_bgr_u8, the conversion of the colour-coded time image).
+//   F2' k_flow_field_uv  F2 with the owner's (u, v) read from an upload-ordered array instead of derived from (nx, ny): the
+//                     bf_global_* renders of a held flow (bf_global_hold_field / bf_global_hold_best).
 //   k_flow_frame_compose  the flow frame: compensated projection image | colour-coded flow | raw projection image, written in
 //                     the byte layouts of the files, one thread per output dword (like k_frame_compose, without a resize: every
 //                     tile already has the frame's resolution).
@@ -66,6 +68,28 @@ __global__ __launch_bounds__(kThreads) void k_flow_field(const uint32_t* __restr
     }
 }
 
+// k_flow_field for a flow that is (u, v) already (the held flow of the exhaustive search, whose nz is the candidate's own):
+// the owner's pair is copied, not derived; every output as there.
+__global__ __launch_bounds__(kThreads) void k_flow_field_uv(const uint32_t* __restrict__ owner, const double2* __restrict__ uvs,
+                                                            long long px, FlowFieldOut o) {
+    const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (i >= px) return;
+    const uint32_t w = owner[i];
+    const bool has = w != kNoOwner;
+    double2 uv = make_double2(0.0, 0.0);
+    if (has && uvs) uv = uvs[w];
+    if (o.owner) o.owner[i] = has ? (int32_t)w : -1;
+    if (o.u) o.u[i] = uv.x;
+    if (o.v) o.v[i] = uv.y;
+    if (o.flo) o.flo[i] = has ? make_float2((float)uv.y, (float)uv.x) : make_float2(1e9f, 1e9f);
+    if (o.hs || o.bgr) {
+        int H = 0, S = 0;
+        if (has) bf_flow_hs(uv.x, uv.y, &H, &S);
+        if (o.hs) { o.hs[2 * i] = (uint8_t)H; o.hs[2 * i + 1] = (uint8_t)S; }
+        if (o.bgr) bf_hsv_to_bgr_u8(H, S, 255, o.bgr + 3 * i);
+    }
+}
+
 // one channel (0 B, 1 G, 2 R) of frame pixel (r, c); c in [0, 3 C)
 __device__ __forceinline__ uint32_t flow_frame_byte(const FlowFrameCompose& a, int r, int c, int ch) {
     const int tile = c / a.C, cc = c - tile * a.C;
@@ -113,6 +137,11 @@ void launch_flow_owner(const FlowSources& e, int res_x, int res_y, int first, ui
 void launch_flow_field(const uint32_t* owner, const double2* nxny, long long px, const FlowFieldOut& o, hipStream_t s) {
     if (px <= 0) return;
     hipLaunchKernelGGL(k_flow_field, dim3((unsigned)((px + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, owner, nxny, px, o);
+}
+
+void launch_flow_field_uv(const uint32_t* owner, const double2* uv, long long px, const FlowFieldOut& o, hipStream_t s) {
+    if (px <= 0) return;
+    hipLaunchKernelGGL(k_flow_field_uv, dim3((unsigned)((px + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, owner, uv, px, o);
 }
 
 void launch_flow_frame_compose(const FlowFrameCompose& a, hipStream_t s) {

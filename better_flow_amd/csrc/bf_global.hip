@@ -26,8 +26,11 @@
 //   PF  bf_global_project_field: PW, the same two kernels, with the source that interpolates the candidate of every event
 //       between the cell centres around its address (GlobalFieldSource; include/bf_global_field.h).
 //
+//   H   bf_global_hold_field / bf_global_hold_best: the per-event flow kept on the device for the renderers and the -o table
+//       (k_global_hold_runs over the runs of PW / PF with their sources; k_global_hold_best from the per-event best state).
+//
 // Everything is an integer or one IEEE operation of the reference's own expression: results do not depend on the
-// order in which work-groups run.
+// order in which work-groups run.  (The one exception is the held flow's (u, v): the device's hypot, see uv_from_n_nz.)
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
@@ -472,6 +475,45 @@ __global__ __launch_bounds__(T) void k_global_score_runs(GlobalCells cl, GlobalG
     global_group_total<T>(contrib, &cell_sums[cell]);
 }
 
+// ---- the held flow (include/bf_accel.h): bf_global_hold_field and bf_global_hold_best ----
+// What one event keeps under candidate c: the products of Event::apply_project at position j of the source order, and
+// (nx, ny) and compute_uv of them (uv_from_n_nz, with the candidate's own nz) at its upload index e.
+__device__ __forceinline__ void global_hold_event(const GlobalHeld& h, const GlobalCand& c, int32_t t, long long j, long long e) {
+    const float ft = (float)t;
+    h.p[j] = make_float2(c.kx * ft, c.ky * ft);   // (global_pixel's products: pr_from_p of them is its pr)
+    const double2 n = make_double2(c.nx, c.ny);
+    h.nxny[e] = n;
+    h.uv[e] = uv_from_n_nz(n, c.nz);
+}
+
+// k_global_project_runs without the pixel: over the same runs, the candidate of every event from the same source, kept
+// instead of splatted.
+template <int T, class Src>
+__global__ __launch_bounds__(T) void k_global_hold_runs(GlobalCells cl, Src src, GlobalHeld h) {
+    const uint32_t cell = cl.run_cell[blockIdx.x];
+    typename Src::Run run;
+    src.load(run, cell);
+    const uint32_t j = cl.run_start[blockIdx.x] + threadIdx.x;
+    if (j >= cl.cell_start[cell + 1]) return;
+    global_hold_event(h, src.at(run, cl.xy[j]), cl.t[j], (long long)j, (long long)cl.idx[j]);
+}
+
+// The per-event best state, one thread per slot: the candidate is the event's (best_nx, best_ny, best_nz), kx / ky by
+// make_cand's expression.  An event no candidate was accepted for holds k_global_reset's (0, 0, 127): zero products, pr = fr.
+__global__ __launch_bounds__(kGT) void k_global_hold_best(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
+                                                          const uint32_t* __restrict__ perm, long long n, GlobalEventState st,
+                                                          GlobalHeld h) {
+    const long long i = (long long)blockIdx.x * kGT + threadIdx.x;
+    if (i >= n) return;
+    const long long e = perm ? (long long)perm[i] : i;
+    GlobalCand c;
+    c.nx = st.best_nx[e]; c.ny = st.best_ny[e]; c.nz = st.best_nz[e];
+    c.kx = (float)((double)(float)c.nx / c.nz);
+    c.ky = (float)((double)(float)c.ny / c.nz);
+    h.xy[i] = xy[i]; h.idx[i] = (uint32_t)e;
+    global_hold_event(h, c, t[i], i, e);
+}
+
 // One batch's block [cell][b], kGlobalCellStride threads per cell (8 cells per work-group).  Slot b is lattice point
 // k = ks[b], or k0 + b without a list.  The cell's best of the batch is its largest sum, lowest k among equals, and it
 // replaces the running best when it is larger, or as large with a lower k: the exhaustive rule (largest S, then lowest k)
@@ -690,6 +732,24 @@ int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const Glob
 int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const GlobalCandField& src, uint32_t* pts, uint32_t* win,
                        uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s) {
     return launch_runs(cells, g, GlobalFieldSource{src}, pts, win, img_out, scores_out, cell_sums, s);
+}
+
+void launch_global_hold(const GlobalCells& cells, const GlobalCandTable& src, const GlobalHeld& h, hipStream_t s) {
+    if (cells.n_runs <= 0) return;
+    launch_over_runs(cells, s, k_global_hold_runs<64, GlobalTableSource>, k_global_hold_runs<kGT, GlobalTableSource>, cells,
+                     GlobalTableSource{src}, h);
+}
+
+void launch_global_hold(const GlobalCells& cells, const GlobalCandField& src, const GlobalHeld& h, hipStream_t s) {
+    if (cells.n_runs <= 0) return;
+    launch_over_runs(cells, s, k_global_hold_runs<64, GlobalFieldSource>, k_global_hold_runs<kGT, GlobalFieldSource>, cells,
+                     GlobalFieldSource{src}, h);
+}
+
+void launch_global_hold_best(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalEventState& st,
+                             const GlobalHeld& h, hipStream_t s) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_global_hold_best, dim3((unsigned)((n + kGT - 1) / kGT)), dim3(kGT), 0, s, xy, t, perm, n, st, h);
 }
 
 void launch_global_stride_mark(const GlobalLattice& lt, long long stride, uint32_t* level, hipStream_t s) {

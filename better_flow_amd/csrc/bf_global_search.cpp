@@ -2,8 +2,10 @@
 // (update_fields), one project_all, compute_flow_bruteforce over a candidate grid (per slice, and per cell of a grid over the
 // sensor), and the per-event state.  The kernels are in bf_global.hip; the definitions this build adds (the per-event best
 // candidate, the objective S, the objective per cell, the candidate set of a pyramid level, the piecewise projection, the
-// interpolated field) are stated in include/bf_accel.h and DESIGN.md.
+// interpolated field, the held flow) are stated in include/bf_accel.h and DESIGN.md.
 #include "bf_ctx.h"
+
+constexpr int kGlobalHoldBest = 3;   // GlobalSearch::Held::mode after bf_global_hold_best (1, 2: BF_GLOBAL_HOLD_CELLS / _FIELD)
 
 struct GlobalSearch {
     // the window of bf_global_set_window, the per-event state and the buffers of one batch of candidates
@@ -51,6 +53,21 @@ struct GlobalSearch {
         DevArray<int32_t> d_seed;
         DevArray<double> d_state_save;
     } pyr;
+
+    // The held flow (bf_global_hold_field / bf_global_hold_best), of the slice the window was set on: valid while `have` and
+    // mode != 0.  bf_global_set_window drops it, bf_global_set_cells drops one of the grid modes (whose address words and
+    // upload indices are the cells' own d_cxy / d_cidx); an upload invalidates it with the window (bf_ctx::glob_valid).
+    // The nz it was formed with (one for a grid mode, best_nz per event for the snapshot) is spent at the hold: d_p and
+    // d_uv carry it.
+    struct Held {
+        int mode = 0;                      // 0: none, BF_GLOBAL_HOLD_CELLS, BF_GLOBAL_HOLD_FIELD or kGlobalHoldBest
+        DevArray<double2> d_nxny, d_uv;    // upload order
+        DevArray<float2> d_p;              // the hold's source order: the cells', or (kGlobalHoldBest) that of d_xy / d_idx
+        DevArray<uint32_t> d_xy, d_idx;    // kGlobalHoldBest: the context's slot order at the hold
+        DevArray<double2> d_pr;            // bf_global_get_flow: the positions, upload order
+        HostArray<double2> h_stage;        // ... and its pinned staging, 3 n pairs
+        Event landed[3];                   // ... one per array: its copy has landed in h_stage
+    } held;
 
     GlobalEventState state() const {
         GlobalEventState s;
@@ -293,6 +310,67 @@ int check_project_runs(bf_ctx* c, const char* who, const double* cell_nx, const 
     return BF_OK;
 }
 
+// The grid of the piecewise projection as one candidate per cell (kx, ky once per cell, here): a cell that has events must
+// be finite in the float form the projection uses, kx and ky (1e39 is as infinite there as inf and NaN are); the entry of
+// any other cell is not read.
+int table_cands(bf_ctx* c, const GlobalSearch::Cells& cs, const double* cell_nx, const double* cell_ny, double nz,
+                std::vector<GlobalCand>& cands) {
+    const long long nc = cs.cg.n_cells;
+    cands.assign((size_t)nc, make_cand(0.0, 0.0, nz));
+    for (long long i = 0; i < nc; ++i) {
+        if (cs.h_count[(size_t)i] == 0u) continue;
+        cands[(size_t)i] = make_cand(cell_nx[i], cell_ny[i], nz);
+        if (!std::isfinite(cands[(size_t)i].kx) || !std::isfinite(cands[(size_t)i].ky))
+            return fail(c, BF_ERR_ARG, "the candidate of cell %lld, which has events, is not finite as a float", i);
+    }
+    return BF_OK;
+}
+
+// The grid of the interpolated field: every cell is a corner for its neighbours, with events or without, so all of the
+// grid is read, and all of it must be finite in that float form.
+int check_field_grid(bf_ctx* c, long long nc, const double* cell_nx, const double* cell_ny, double nz) {
+    for (long long i = 0; i < nc; ++i) {
+        const GlobalCand k = make_cand(cell_nx[i], cell_ny[i], nz);
+        if (!std::isfinite(k.kx) || !std::isfinite(k.ky))
+            return fail(c, BF_ERR_ARG, "the candidate of cell %lld is not finite as a float", i);
+    }
+    return BF_OK;
+}
+
+// The checked grid onto the device (n > 0: the slice has events), for the launches of the piecewise / the interpolated form.
+// h_pw_cands / the caller's grids are read until the stream has been waited for.
+int upload_table(bf_ctx* c, GlobalSearch::Cells& cs) {
+    const size_t nc = (size_t)cs.cg.n_cells;
+    HIP_TRY(c, cs.d_pw_cands.grow(nc));
+    HIP_TRY(c, hipMemcpyAsync(cs.d_pw_cands, cs.h_pw_cands.data(), nc * sizeof(GlobalCand), hipMemcpyHostToDevice, c->stream));
+    return BF_OK;
+}
+int upload_field_grid(bf_ctx* c, GlobalSearch::Cells& cs, const double* cell_nx, const double* cell_ny, GlobalCandField& src) {
+    const size_t nc = (size_t)cs.cg.n_cells;
+    HIP_TRY(c, cs.d_field_grid.grow(nc * 2));
+    src.cell_nx = cs.d_field_grid;
+    src.cell_ny = src.cell_nx + nc;
+    HIP_TRY(c, hipMemcpyAsync(cs.d_field_grid, cell_nx, nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(cs.d_field_grid + nc, cell_ny, nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return BF_OK;
+}
+
+// room for a held flow of the window's slice; best: with the hold's own copy of the slot order
+int ensure_held(bf_ctx* c, GlobalSearch* gs, bool best, GlobalHeld& h) {
+    GlobalSearch::Held& hd = gs->held;
+    const size_t n = (size_t)gs->n;
+    HIP_TRY(c, hd.d_nxny.grow(n));
+    HIP_TRY(c, hd.d_uv.grow(n));
+    HIP_TRY(c, hd.d_p.grow(n));
+    if (best) {
+        HIP_TRY(c, hd.d_xy.grow(n));
+        HIP_TRY(c, hd.d_idx.grow(n));
+    }
+    h.nxny = hd.d_nxny; h.uv = hd.d_uv; h.p = hd.d_p;
+    h.xy = best ? hd.d_xy.get() : nullptr; h.idx = best ? hd.d_idx.get() : nullptr;
+    return BF_OK;
+}
+
 // The per-cell sums at d_pw_sums (have false: nothing was launched, all zero) to the host, the stream waited for, and
 // their total: at most 65 536 values, added on the host after the one copy that brought them back
 int fetch_cell_sums(bf_ctx* c, GlobalSearch* gs, bool have, int64_t* sum_out, int64_t* cell_sums_out) {
@@ -385,6 +463,7 @@ int bf_global_set_window(bf_ctx* c, int32_t scale, int32_t metric_wsize, bf_glob
     GlobalSearch* gs = c->glob.get();
     gs->have = false;
     gs->cells.have = false;
+    gs->held.mode = 0;
     c->glob_valid = false;
     HIP_TRY(c, gs->d_state.grow((size_t)c->cap_events * 6));   // (n <= cap_events: one allocation for every slice)
     GlobalGeom& g = gs->g;
@@ -456,6 +535,7 @@ int bf_global_set_cells(bf_ctx* c, int32_t res_x, int32_t res_y, int32_t cell_ro
     GlobalSearch* gs = c->glob.get();
     GlobalSearch::Cells& cs = gs->cells;
     cs.have = false;
+    if (gs->held.mode != kGlobalHoldBest) gs->held.mode = 0;   // (a grid hold lives in the cells' order)
     if (res_x <= 0 || res_y <= 0 || cell_rows <= 0 || cell_cols <= 0)
         return fail(c, BF_ERR_ARG, "sensor %d x %d, cells %d x %d: every size must be positive", res_x, res_y, cell_rows, cell_cols);
     if (gs->n > 0 && (gs->w.x_max >= res_x || gs->w.y_max >= res_y))   // (addresses are unsigned: x_min, y_min >= 0)
@@ -749,23 +829,11 @@ int bf_global_project_cells(bf_ctx* c, const double* cell_nx, const double* cell
     if (rc != BF_OK) return rc;
     GlobalSearch* gs = c->glob.get();
     GlobalSearch::Cells& cs = gs->cells;
-    const long long nc = cs.cg.n_cells;
-    // one candidate per cell that has events (kx, ky once per cell, here); the entry of any other cell is not read
-    // (finite means finite in the float form the projection uses, kx and ky: 1e39 is as infinite there as inf and NaN are)
-    std::vector<GlobalCand> cands((size_t)nc, make_cand(0.0, 0.0, nz));
-    for (long long i = 0; i < nc; ++i) {
-        if (cs.h_count[(size_t)i] == 0u) continue;
-        cands[(size_t)i] = make_cand(cell_nx[i], cell_ny[i], nz);
-        if (!std::isfinite(cands[(size_t)i].kx) || !std::isfinite(cands[(size_t)i].ky))
-            return fail(c, BF_ERR_ARG, "the candidate of cell %lld, which has events, is not finite as a float", i);
-    }
+    std::vector<GlobalCand> cands;
+    if ((rc = table_cands(c, cs, cell_nx, cell_ny, nz, cands)) != BF_OK) return rc;
     cs.h_pw_cands.swap(cands);   // (nothing of this object is written before every check has passed)
     HIP_TRY(c, hipSetDevice(c->device));
-    if (gs->n > 0) {
-        HIP_TRY(c, cs.d_pw_cands.grow((size_t)nc));
-        HIP_TRY(c, hipMemcpyAsync(cs.d_pw_cands, cs.h_pw_cands.data(), (size_t)nc * sizeof(GlobalCand), hipMemcpyHostToDevice,
-                                  c->stream));   // (h_pw_cands is read until project_runs has synchronised)
-    }
+    if (gs->n > 0 && (rc = upload_table(c, cs)) != BF_OK) return rc;   // (h_pw_cands is read until project_runs has synchronised)
     return project_runs(c, gs, GlobalCandTable{cs.d_pw_cands}, img_out, scores_out, sum_out, cell_sums_out);
 }
 
@@ -779,13 +847,7 @@ int bf_global_project_field(bf_ctx* c, const double* cell_nx, const double* cell
     GlobalSearch* gs = c->glob.get();
     GlobalSearch::Cells& cs = gs->cells;
     const long long nc = cs.cg.n_cells;
-    // every cell is a corner for its neighbours, with events or without: all of the grid is read, and all of it must be
-    // finite in the float form the projection uses (make_cand's kx, ky; 1e39 is as infinite there as inf and NaN are)
-    for (long long i = 0; i < nc; ++i) {
-        const GlobalCand k = make_cand(cell_nx[i], cell_ny[i], nz);
-        if (!std::isfinite(k.kx) || !std::isfinite(k.ky))
-            return fail(c, BF_ERR_ARG, "the candidate of cell %lld is not finite as a float", i);
-    }
+    if ((rc = check_field_grid(c, nc, cell_nx, cell_ny, nz)) != BF_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t n = (size_t)gs->n;
     const bool want_ev = event_nx_out || event_ny_out || event_u_out || event_v_out;
@@ -793,11 +855,7 @@ int bf_global_project_field(bf_ctx* c, const double* cell_nx, const double* cell
     GlobalCandField src{cs.cg, (uint32_t)(nc / cs.cg.n_cell_y), nullptr, nullptr, nz, nullptr, nullptr};
     AlsoBack ev_back;
     if (n > 0) {   // (no event: no per-event value is written)
-        HIP_TRY(c, cs.d_field_grid.grow((size_t)nc * 2));
-        src.cell_nx = cs.d_field_grid;
-        src.cell_ny = src.cell_nx + nc;
-        HIP_TRY(c, hipMemcpyAsync(cs.d_field_grid, cell_nx, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(cs.d_field_grid + nc, cell_ny, (size_t)nc * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if ((rc = upload_field_grid(c, cs, cell_nx, cell_ny, src)) != BF_OK) return rc;
         if (want_ev) {   // (the caller's grids are read until project_runs has synchronised)
             HIP_TRY(c, cs.d_field_ev.grow(n * 2));
             ev.resize(n * 2);
@@ -847,4 +905,114 @@ int bf_global_get_events(bf_ctx* c, double* max_score, double* best_nx, double* 
     return BF_OK;
 }
 
+int bf_global_hold_field(bf_ctx* c, const double* cell_nx, const double* cell_ny, int64_t cells_cap, double nz, int32_t mode) {
+    if (!c) return BF_ERR_ARG;
+    if (mode != BF_GLOBAL_HOLD_CELLS && mode != BF_GLOBAL_HOLD_FIELD)
+        return fail(c, BF_ERR_ARG, "bf_global_hold_field: unknown mode %d", mode);
+    int rc = check_project_runs(c, "bf_global_hold_field", cell_nx, cell_ny, cells_cap, nz, nullptr, 0);
+    if (rc != BF_OK) return rc;
+    GlobalSearch* gs = c->glob.get();
+    GlobalSearch::Cells& cs = gs->cells;
+    const long long nc = cs.cg.n_cells;
+    const bool table = mode == BF_GLOBAL_HOLD_CELLS;
+    std::vector<GlobalCand> cands;
+    rc = table ? table_cands(c, cs, cell_nx, cell_ny, nz, cands) : check_field_grid(c, nc, cell_nx, cell_ny, nz);
+    if (rc != BF_OK) return rc;
+    if (table) cs.h_pw_cands.swap(cands);
+    HIP_TRY(c, hipSetDevice(c->device));
+    gs->held.mode = 0;   // (a failure below leaves no held flow)
+    if (gs->n > 0) {
+        GlobalHeld h;
+        if ((rc = ensure_held(c, gs, false, h)) != BF_OK) return rc;
+        const GlobalCells cl = cells_view(gs, nullptr, 0);
+        if (table) {
+            if ((rc = upload_table(c, cs)) != BF_OK) return rc;
+            launch_global_hold(cl, GlobalCandTable{cs.d_pw_cands}, h, c->stream);
+        } else {
+            GlobalCandField src{cs.cg, (uint32_t)(nc / cs.cg.n_cell_y), nullptr, nullptr, nz, nullptr, nullptr};
+            if ((rc = upload_field_grid(c, cs, cell_nx, cell_ny, src)) != BF_OK) return rc;
+            launch_global_hold(cl, src, h, c->stream);
+        }
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the grids are the caller's, or h_pw_cands: read until here)
+    }
+    gs->held.mode = mode;
+    return BF_OK;
+}
+
+int bf_global_hold_best(bf_ctx* c) {
+    if (!c) return BF_ERR_ARG;
+    int rc = global_ready(c);
+    if (rc != BF_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    GlobalSearch* gs = c->glob.get();
+    gs->held.mode = 0;
+    if (gs->n > 0) {
+        GlobalHeld h;
+        if ((rc = ensure_held(c, gs, true, h)) != BF_OK) return rc;
+        const bf_ctx::EvSet& e = c->set[c->cs];
+        launch_global_hold_best(e.xy, e.t, c->has_perm ? e.perm.get() : nullptr, gs->n, gs->state(), h, c->stream);
+        HIP_TRY(c, hipGetLastError());
+    }
+    gs->held.mode = kGlobalHoldBest;
+    return BF_OK;
+}
+
+int bf_global_get_flow(bf_ctx* c, double* nx, double* ny, double* u, double* v, double* pr_x, double* pr_y) {
+    if (!c) return BF_ERR_ARG;
+    GlobalHeldFlow f;
+    int rc = global_held_flow(c, "bf_global_get_flow", &f);
+    if (rc != BF_OK) return rc;
+    const size_t n = (size_t)f.n;
+    if (n == 0) return BF_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    GlobalSearch::Held& hd = c->glob->held;
+    // up to three arrays of n pairs through pinned memory, every copy followed by an event of its own: the host takes an
+    // array apart as soon as ITS copy has landed, while the copies behind it are still on their way
+    struct Part { double *a, *b; const double2* d_src; } part[3] = {{nx, ny, f.nxny}, {u, v, f.uv}, {pr_x, pr_y, nullptr}};
+    if (pr_x || pr_y) {
+        HIP_TRY(c, hd.d_pr.grow(n));
+        launch_expand_pr(f.xy, f.p, f.idx, hd.d_pr, f.n, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        part[2].d_src = hd.d_pr;
+    }
+    HIP_TRY(c, hd.h_stage.grow(3 * n));
+    for (int i = 0; i < 3; ++i) {
+        if (!part[i].a && !part[i].b) continue;
+        HIP_TRY(c, hd.landed[i].create(hipEventDisableTiming));
+        HIP_TRY(c, hipMemcpyAsync(hd.h_stage + (size_t)i * n, part[i].d_src, n * sizeof(double2), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipEventRecord(hd.landed[i], c->stream));
+    }
+    for (int i = 0; i < 3; ++i) {
+        if (!part[i].a && !part[i].b) continue;
+        HIP_TRY(c, hipEventSynchronize(hd.landed[i]));
+        const double2* src = hd.h_stage + (size_t)i * n;
+        double *a = part[i].a, *b = part[i].b;
+        for (size_t j = 0; j < n; ++j) {
+            if (a) a[j] = src[j].x;
+            if (b) b[j] = src[j].y;
+        }
+    }
+    return BF_OK;
+}
+
 }  // extern "C"
+
+int global_held_flow(bf_ctx* c, const char* who, GlobalHeldFlow* out) {
+    GlobalSearch* gs = c->glob.get();
+    if (!gs || !gs->have || !gs->held.mode)
+        return fail(c, BF_ERR_STATE, "%s: no held flow: call bf_global_hold_field or bf_global_hold_best first", who);
+    if (!c->uploaded || !c->glob_valid || c->n != gs->n)
+        return fail(c, BF_ERR_STATE, "%s: events were uploaded since the flow was held", who);
+    const GlobalSearch::Held& hd = gs->held;
+    std::memset(out, 0, sizeof(*out));
+    out->n = gs->n;
+    if (gs->n <= 0) return BF_OK;
+    const bool best = hd.mode == kGlobalHoldBest;
+    out->xy = best ? hd.d_xy.get() : gs->cells.d_cxy.get();
+    out->idx = best ? hd.d_idx.get() : gs->cells.d_cidx.get();
+    out->p = hd.d_p;
+    out->nxny = hd.d_nxny;
+    out->uv = hd.d_uv;
+    return BF_OK;
+}

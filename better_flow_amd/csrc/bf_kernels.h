@@ -344,6 +344,22 @@ int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const Glob
                        uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
 int launch_global_runs(const GlobalCells& cells, const GlobalGeom& g, const GlobalCandField& src, uint32_t* pts, uint32_t* win,
                        uint8_t* img_out, float* scores_out, unsigned long long* cell_sums, hipStream_t s);
+// The held flow (include/bf_accel.h, bf_global_hold_field / bf_global_hold_best): per event of the slice its (nx, ny) and
+// (u, v) at its UPLOAD index, and the two f32 products (kx * float(t), ky * float(t)) of Event::apply_project at its position
+// in the order of the arrays it was computed from (the cell order of GlobalCells::xy / idx, or the context's slot order).
+struct GlobalHeld {
+    double2 *nxny, *uv;   // n each, upload order
+    float2* p;            // n, source order
+    uint32_t *xy, *idx;   // launch_global_hold_best only: its own copy of the source order's address words and upload indices
+};
+// One launch over the cell runs (k_global_hold_runs): every event under the candidate launch_global_runs would project it
+// under.  Nothing is rendered or scored; only cells' xy / t / idx / cell_start / run_* fields are read.
+void launch_global_hold(const GlobalCells& cells, const GlobalCandTable& src, const GlobalHeld& h, hipStream_t s);
+void launch_global_hold(const GlobalCells& cells, const GlobalCandField& src, const GlobalHeld& h, hipStream_t s);
+// The per-event best state as a held flow: slot i (upload index perm[i]; null: i) under (best_nx, best_ny, best_nz) of its event.
+// The slot order is copied into h.xy / h.idx: a later bf_run may re-bin the context's slots, the held flow stays what it was.
+void launch_global_hold_best(const uint32_t* xy, const int32_t* t, const uint32_t* perm, long long n, const GlobalEventState& st,
+                             const GlobalHeld& h, hipStream_t s);
 // counting sort of the slice by cell, in two launches around the host's scan of `count`: the events per cell, then the
 // events into cell order (`cursor`: n_cells zeros; cells.xy / t / idx as mutable arrays of n)
 void launch_global_cell_count(const uint32_t* xy, long long n, const GlobalCellGrid& cg, uint32_t* count, hipStream_t s);
@@ -453,6 +469,9 @@ struct FlowFieldOut {
     int32_t* owner; double *u, *v; float2* flo; uint8_t *hs, *bgr;
 };
 void launch_flow_field(const uint32_t* owner, const double2* nxny, long long px, const FlowFieldOut& o, hipStream_t s);
+// the same per pixel from a flow that is (u, v) already, in upload order (the held flow of the exhaustive search: its nz is
+// the candidate's own, not the constant of uv_from_n); null: zero flow
+void launch_flow_field_uv(const uint32_t* owner, const double2* uv, long long px, const FlowFieldOut& o, hipStream_t s);
 // The flow frame: three R x C tiles side by side -- grey | B, G, R | grey -- as PPM payload (top-down RGB, ppm_dwords dwords
 // cover its 9 R C bytes) and / or AVI payload (bottom-up BGR rows of `stride` bytes, zero padding); a null destination is skipped.
 struct FlowFrameCompose {

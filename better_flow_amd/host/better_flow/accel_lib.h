@@ -377,6 +377,37 @@ public:
                            double *best_u, double *best_v) {
         check(bf_global_get_events(ctx, max_score, best_nx, best_ny, best_pr_x, best_pr_y, best_u, best_v), "global_get_events");
     }
+    // The held flow (include/bf_accel.h, "the held flow"): the search's per-event flow kept on the device -- under one
+    // (nx, ny) per cell (mode BF_GLOBAL_HOLD_CELLS: the event's cell's; BF_GLOBAL_HOLD_FIELD: interpolated at its address; grids
+    // as in global_project_cells) or as a snapshot of the per-event best state -- and what reads it.
+    void global_hold_field(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, double nz, int mode) {
+        check_cell_grids("global_hold_field", cell_nx, cell_ny);
+        check(bf_global_hold_field(ctx, cell_nx.data(), cell_ny.data(), (int64_t)global_n_cells, nz, mode), "global_hold_field");
+    }
+    void global_hold_best() { check(bf_global_hold_best(ctx), "global_hold_best"); }
+    // n doubles each, in the cloud's order; each may be null
+    void global_get_flow(double *nx, double *ny, double *u, double *v, double *pr_x, double *pr_y) {
+        check(bf_global_get_flow(ctx, nx, ny, u, v, pr_x, pr_y), "global_get_flow");
+    }
+    // flow_field() of the held flow: every event takes part, a pixel's (u, v) is its owner's held flow
+    bf::FlowField global_flow_field() {
+        bf::FlowField f(RES_X, RES_Y);
+        check(bf_global_flow_field(ctx, RES_X, RES_Y, BF_FLOW_LAST_UPLOADED, f.owner.data(), f.u.data(), f.v.data()), "global_flow_field");
+        return f;
+    }
+    // the flow frame of the held flow (held positions | colour-coded flow | raw events), composed on the device: the PPM
+    // payload (RES_X x 3 RES_Y x 3 bytes, top-down RGB), the AVI payload and the .flo payload; each may be null, not all
+    void global_render_flow_frame(uint8_t *ppm_out, uint8_t *avi_out, float *flo_out) {
+        check(bf_global_render_flow_frame(ctx, RES_X, RES_Y, BF_FLOW_LAST_UPLOADED, ppm_out, avi_out, flo_out), "global_render_flow_frame");
+    }
+    // bf_emit_slice with the rows' (u, v) from the held flow; returns the ticket (-1: nothing to enqueue)
+    int64_t global_emit_slice(bf_emit *emit, uint64_t first, uint64_t start_time, bool lead, uint64_t lead_t, int lead_row,
+                              int lead_col) {
+        int64_t ticket = -1;
+        check(bf_global_emit_slice(ctx, emit, (int64_t)size, first, start_time, lead ? 1 : 0, lead_t, lead_row, lead_col, &ticket),
+              "global_emit_slice");
+        return ticket;
+    }
 
     // The fused OptimizerRolling::run (optimizer_rolling.h:48-125) on the device.
     int run(int max_itercount, ObjectModel &model, bf_run_info *info) {

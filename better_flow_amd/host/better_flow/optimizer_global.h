@@ -31,6 +31,11 @@
 // carries no answer and takes the (nx, ny) of the nearest cell that does.  write_field_flo writes the field sampled at every
 // sensor pixel as a .flo with write_cell_flo's conventions: width = res_y, height = res_x, horizontal = v, vertical = u.
 //
+// A seventh: the held flow (hold_field, hold_best; include/bf_accel.h, "the held flow"): the per-event flow of the piecewise
+// projection, of the interpolated field or of the searches' best state kept on the device, where the renderers of the rolling
+// optimiser and the -o table read it -- get_flow, flow_field, write_flow_flo, write_flow_ppm on the RES_X x RES_Y sensor, and
+// emit_slice.  An upload, a new window and (for the two grid forms) set_cells end it; its readers throw (BF_ERR_STATE) then.
+//
 // Each object stages its slice on a device context of its OWN (not the thread's shared one that OptimizerLocal and
 // OptimizerRolling use): the window and the per-event best state live there and accumulate over project_all /
 // compute_flow_bruteforce calls, so no other optimiser on the thread may replace them.  Objects are not copyable.
@@ -42,7 +47,10 @@
 #include <better_flow/datastructures.h>
 #include <better_flow/event.h>
 #include <better_flow/flow_field.h>
+#include <better_flow/frame_writer.h>
 #include <bf_global_field.h>
+
+#include <algorithm>
 
 #include <string>
 #include <vector>
@@ -107,7 +115,9 @@ protected:
         if (accel.is_staged()) return;
         if (!own.ctx) {
             const long long n = (long long)this->events->size();
-            int rc = bf_create(bf::DeviceContext::device(), n > 1024 ? n : 1024, 64, 64, nullptr, &own.ctx);
+            // (images of the sensor's size at least: the held flow's renders are RES_X x RES_Y)
+            int rc = bf_create(bf::DeviceContext::device(), n > 1024 ? n : 1024, std::max(64, RES_X), std::max(64, RES_Y), nullptr,
+                               &own.ctx);
             if (rc != BF_OK) {
                 own.ctx = nullptr;
                 throw bf::AccelError(rc, "OptimizerGlobal: bf_create failed (" + std::to_string(rc) + "): the search needs a "
@@ -291,6 +301,77 @@ public:
             }
         const std::vector<float> payload = bf::flo_payload(f);
         return bf::write_flo(path, f.rows, f.cols, payload.data());
+    }
+
+    // Keeps the per-event flow of project_cells (mode BF_GLOBAL_HOLD_CELLS) or project_field (BF_GLOBAL_HOLD_FIELD) under the
+    // given grids on the device, without rendering or scoring anything; grids and refusals as there.
+    void hold_field(const std::vector<double> &cell_nx, const std::vector<double> &cell_ny, int mode = BF_GLOBAL_HOLD_FIELD,
+                    double nz_ = NZ) {
+        this->ensure_cells();
+        accel.global_hold_field(cell_nx, cell_ny, nz_, mode);
+    }
+
+    // ... the smooth form under the answers of the last compute_flow_cells / _pyramid / _seeded call after the fill, with the
+    // search range's nz: the flow project_field() renders.  Throws when there are none.
+    void hold_field() {
+        if (this->cell_results.empty())
+            throw bf::AccelError(BF_ERR_STATE, "OptimizerGlobal::hold_field: no per-cell results (call compute_flow_cells first)");
+        std::vector<double> cx, cy;
+        this->filled_cell_grid(&cx, &cy);
+        this->hold_field(cx, cy, BF_GLOBAL_HOLD_FIELD, this->range.nz);
+    }
+
+    // Keeps a snapshot of every event's best candidate so far (what read_back returns); later searches do not change it.
+    void hold_best() {
+        this->stage();
+        accel.global_hold_best();
+    }
+
+    // The held flow per event, in the cloud's order; each vector may be null.  (This and every reader below throw
+    // BF_ERR_STATE without a held flow.)
+    void get_flow(std::vector<double> *nx, std::vector<double> *ny, std::vector<double> *u, std::vector<double> *v,
+                  std::vector<double> *pr_x = nullptr, std::vector<double> *pr_y = nullptr) {
+        std::vector<double> *out[6] = {nx, ny, u, v, pr_x, pr_y};
+        double *p[6];
+        for (int k = 0; k < 6; ++k) {
+            if (out[k]) out[k]->assign(this->events->size(), 0.0);
+            p[k] = out[k] && !out[k]->empty() ? out[k]->data() : nullptr;
+        }
+        this->stage();
+        accel.global_get_flow(p[0], p[1], p[2], p[3], p[4], p[5]);
+    }
+
+    // The per-pixel field of the held flow on the RES_X x RES_Y sensor: the last event of the cloud that lands on a pixel
+    // owns it (AccelLib::flow_field's rule, every event taking part).
+    bf::FlowField flow_field() {
+        this->stage();
+        return accel.global_flow_field();
+    }
+
+    // ... as a Middlebury .flo (flow_field.h's writer and conventions), and the flow frame of the held flow -- held positions |
+    // colour-coded flow | raw events -- as a PPM (frame_writer.h), composed on the device.
+    bool write_flow_flo(const std::string &path) {
+        const bf::FlowField f = this->flow_field();
+        const std::vector<float> payload = bf::flo_payload(f);
+        return bf::write_flo(path, f.rows, f.cols, payload.data());
+    }
+    bool write_flow_ppm(const std::string &path) {
+        std::vector<uint8_t> ppm((size_t)RES_X * (size_t)(3 * RES_Y) * 3);
+        this->stage();
+        accel.global_render_flow_frame(ppm.data(), nullptr, nullptr);
+        return bf::write_ppm_raw(path, RES_X, 3 * RES_Y, ppm.data());
+    }
+
+    // The slice's rows of the -o table into `emit` (bf_emit_create on own_context()) with the held flow as their (u, v):
+    // bf_emit_slice's arguments, rule and ticket (wait and release with bf_emit_wait / bf_emit_release).
+    int64_t emit_slice(bf_emit *emit, uint64_t first, uint64_t start_time, bool lead = false, uint64_t lead_t = 0, int lead_row = 0,
+                       int lead_col = 0) {
+        this->stage();
+        return accel.global_emit_slice(emit, first, start_time, lead, lead_t, lead_row, lead_col);
+    }
+    bf_ctx *own_context() {   // (staged: the context exists)
+        this->stage();
+        return own.ctx;
     }
 
     void clear_seeds() { this->seeds.clear(); }

@@ -865,6 +865,52 @@ int bf_flow_frame_release(bf_flow_frame *frame, int64_t ticket);
 int bf_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, uint8_t *ppm_out, uint8_t *avi_out,
                          float *flo_out);
 
+/* ---- the held flow of the exhaustive search: a per-event flow kept on the device, and its outputs -------------------------
+ * A seventh definition of this build ("OptimizerGlobal").  A HELD FLOW is, for the n events of the slice
+ * bf_global_set_window ran on: (nx, ny) and (u, v) per event in upload order, the two f32 products
+ * p = (kx * float(t), ky * float(t)) of Event::apply_project, from which the event's position is pr = float(fr) -
+ * (double)p / 10000.0 (the device's pr_from_p, exactly the division).  The nz a flow was formed with -- one for a grid mode,
+ * best_nz per event for the snapshot -- is spent when it is formed: p and (u, v) carry it, and it is not kept.  kx =
+ * (float)((double)(float)nx / nz), ky likewise, as for every candidate of the family; (u, v) is Event::compute_uv --
+ * len = hypot(nx, ny), speed = len / (nz / 100000.0), u = len == 0 ? 0 : speed * nx / len, v likewise -- evaluated on the
+ * device with the device's hypot: each of u, v is within 4 * 2^-52 (relative) of the host's value whatever either hypot
+ * returns (len cancels: both are three correctly rounded operations away from n / (nz / 100000)), and exactly 0 for a zero flow.
+ * There is at most one held flow per context.  It becomes invalid at an upload, at bf_global_set_window and, when it came
+ * from bf_global_hold_field, at bf_global_set_cells; every consumer below then returns BF_ERR_STATE, as it does before any hold.
+ *
+ *   bf_global_hold_field  every event under the candidate bf_global_project_cells (mode BF_GLOBAL_HOLD_CELLS: its cell's) or
+ *       bf_global_project_field (BF_GLOBAL_HOLD_FIELD: interpolated at its address) would project it under, with the
+ *       arguments, grid checks and error codes of those calls (the piecewise form reads no empty cell, the smooth form reads
+ *       and checks the whole grid, nz <= 0 is refused; BF_ERR_ARG also for an unknown mode).  One launch; nothing is rendered
+ *       or scored, and the per-event best state, the cells' running bests, the pyramid's scratch and the rolling optimiser's
+ *       state are left alone.  A refused call leaves the held flow as it was.
+ *   bf_global_hold_best   a snapshot of the searches' per-event state: (nx, ny) = (best_nx, best_ny) with nz = best_nz PER
+ *       EVENT; pr comes out as best_pr bit for bit.  An event no candidate was accepted for gets zero flow and pr = fr.  Needs a
+ *       window (BF_ERR_ARG without), no cells; searches that run afterwards do not change it.
+ *   bf_global_get_flow    the held flow to the host through pinned staging: n doubles each, upload order, each may be NULL.
+ *       An empty cloud: BF_OK, nothing written.
+ *   bf_global_flow_field, bf_global_color_flow_img, bf_global_render_flow_frame, bf_global_flow_frame_render
+ *       bf_flow_field, bf_color_flow_img, bf_render_flow_frame and bf_flow_frame_render (same arguments, layouts, frame
+ *       objects, tickets, wait and release) read from the held flow: EVERY event takes part (the family has no noise flags,
+ *       and the scaled window's acceptance test plays no role), it lands on pixel ((int)pr_x, (int)pr_y) and is dropped
+ *       outside the sensor, ownership is by upload index under owner_rule, and a pixel's field is the held (u, v) of its
+ *       owner as bits.  The frame's left tile is the scale-1 projection image of the held positions, its right tile that of
+ *       the raw ones.  An empty cloud gives the images of no event (white flow).
+ *   bf_global_emit_slice  bf_emit_slice (same arguments, rule, ticket, wait and release) with the rows' (u, v) taken from
+ *       the held flow.  BF_ERR_STATE without a held flow or when n is not the number of events it holds. */
+#define BF_GLOBAL_HOLD_CELLS 1
+#define BF_GLOBAL_HOLD_FIELD 2
+int bf_global_hold_field(bf_ctx *ctx, const double *cell_nx, const double *cell_ny, int64_t cells_cap, double nz, int32_t mode);
+int bf_global_hold_best(bf_ctx *ctx);
+int bf_global_get_flow(bf_ctx *ctx, double *nx, double *ny, double *u, double *v, double *pr_x, double *pr_y);
+int bf_global_flow_field(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, int32_t *owner_out, double *u_out, double *v_out);
+int bf_global_color_flow_img(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, uint8_t *bgr_out, uint8_t *hs_out);
+int bf_global_flow_frame_render(bf_ctx *ctx, bf_flow_frame *frame, int32_t owner_rule, int64_t *ticket_out);
+int bf_global_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, uint8_t *ppm_out, uint8_t *avi_out,
+                                float *flo_out);
+int bf_global_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
+                         int32_t lead_row, int32_t lead_col, int64_t *ticket_out);
+
 /* NUMA placement of a feeder thread (no reference counterpart: the reference is single-threaded, SURVEY 8(b) "Threading"; the
  * 8-GPU farm of SURVEY 8(e) wants one feeder thread per GPU with NUMA-local pinned buffers).
  *   bf_device_numa_node          host NUMA node of HIP device `device` (sysfs numa_node of its PCI function); -1: unknown.
