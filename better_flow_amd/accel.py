@@ -158,6 +158,27 @@ class GlobalPyramidInfo(C.Structure):
     ]
 
 
+class SegmentOpts(C.Structure):
+    _fields_ = [("above_s", C.c_double), ("below_s", C.c_double), ("min_count", C.c_int32), ("connectivity", C.c_int32),
+                ("min_pixels", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SegmentInfo(C.Structure):
+    _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("n1", C.c_int64), ("q_sum", C.c_int64), ("q_mean", C.c_int64),
+                ("foreground_pixels", C.c_int32), ("components_found", C.c_int32), ("components", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class Component(C.Structure):
+    _fields_ = [("id", C.c_int32), ("first_pixel", C.c_int32), ("pixels", C.c_int32), ("events", C.c_int32),
+                ("row_min", C.c_int32), ("row_max", C.c_int32), ("col_min", C.c_int32), ("col_max", C.c_int32),
+                ("row_sum", C.c_int64), ("col_sum", C.c_int64), ("q_sum", C.c_int64)]
+
+
+# the numpy view of a bf_component table
+COMPONENT_DTYPE = np.dtype([(n, np.int32) for n in ("id", "first_pixel", "pixels", "events", "row_min", "row_max", "col_min",
+                                                    "col_max")] + [(n, np.int64) for n in ("row_sum", "col_sum", "q_sum")])
+
 # every symbol include/bf_accel.h declares
 EXPORTS = [
     "bf_device_count", "bf_create", "bf_destroy", "bf_last_error", "bf_version",
@@ -179,6 +200,7 @@ EXPORTS = [
     "bf_flow_frame_wait", "bf_flow_frame_release", "bf_render_flow_frame",
     "bf_global_hold_field", "bf_global_hold_best", "bf_global_get_flow", "bf_global_flow_field", "bf_global_color_flow_img",
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
+    "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -309,6 +331,12 @@ def load(path=None):
         L.bf_project_4param_reinit.argtypes = [C.c_void_p] + [C.c_double] * 6
         L.bf_project_4param.argtypes = [C.c_void_p] + [C.c_double] * 6
         L.bf_get_time_img.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bf_segment_opts_default.argtypes = [C.POINTER(SegmentOpts)]
+        L.bf_segment_opts_default.restype = None
+        L.bf_segment.argtypes = [C.c_void_p, C.POINTER(SegmentOpts), C.POINTER(SegmentInfo)]
+        L.bf_segment_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.bf_label_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_int32, C.POINTER(C.c_int32)]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.bf_fast_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model)]
         L.bf_writeout_events.argtypes = [C.c_void_p] + [C.c_void_p] * 4
@@ -484,6 +512,39 @@ class Accel:
         gy = np.empty_like(img)
         self._chk(self.L.bf_sobel(self.h, _ptr(img), img.shape[0], img.shape[1], _ptr(gx), _ptr(gy)))
         return gx, gy
+
+    # ---- moving-object segmentation (include/bf_accel.h) ----
+    def segment(self, above_s=-1.0, below_s=-1.0, min_count=1, connectivity=8, min_pixels=1):
+        """bf_segment: the time-image pass, then the components of the thresholded time image; returns SegmentInfo.  Labels,
+        table and cl_id stay on the device (segment_get)."""
+        o = SegmentOpts(above_s, below_s, min_count, connectivity, min_pixels, 0)
+        info = SegmentInfo()
+        self._chk(self.L.bf_segment(self.h, C.byref(o), C.byref(info)))
+        self._seg_info = info
+        return info
+
+    def segment_get(self, want_labels=True, want_components=True, want_cl_id=True, comps_cap=None):
+        """bf_segment_get: (labels (R, C) int32, components (COMPONENT_DTYPE rows), cl_id (n,) int32); None where not asked."""
+        R, Cc = self.window.scale_img_x, self.window.scale_img_y
+        K = getattr(self, "_seg_info", SegmentInfo()).components if comps_cap is None else comps_cap
+        labels = np.empty((R, Cc), dtype=np.int32) if want_labels else None
+        comps = np.zeros(K, dtype=COMPONENT_DTYPE) if want_components else None
+        cl = np.empty(self.n, dtype=np.int32) if want_cl_id else None
+        self._chk(self.L.bf_segment_get(self.h, _ptr(labels), _ptr(comps), K, _ptr(cl)))
+        return labels, comps, cl
+
+    def label_image(self, mask, connectivity=8, min_pixels=1, comps_cap=None):
+        """bf_label_image: components of a host mask (non-zero = foreground); returns (labels, components, K).  comps_cap None:
+        room for every possible component."""
+        mask = np.ascontiguousarray(mask, dtype=np.uint8)
+        R, Cc = mask.shape
+        cap = (R * Cc + 1) // 2 if comps_cap is None else comps_cap
+        labels = np.empty((R, Cc), dtype=np.int32)
+        comps = np.zeros(cap, dtype=COMPONENT_DTYPE)
+        k = C.c_int32(0)
+        self._chk(self.L.bf_label_image(self.h, _ptr(mask), R, Cc, connectivity, min_pixels, _ptr(labels), _ptr(comps), cap,
+                                        C.byref(k)))
+        return labels, comps[:min(cap, k.value)], k.value
 
     def fast_model(self, img=None):
         m = Model()

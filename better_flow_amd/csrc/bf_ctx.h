@@ -1,5 +1,5 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
@@ -29,6 +29,7 @@
 #include "bf_device.h"
 #include "bf_kernels.h"
 #include "bf_mem.h"
+#include "bf_segment.h"
 
 using namespace bf;
 using bf_mem::DevArray;
@@ -210,6 +211,16 @@ struct bf_ctx {
     // exhaustive search (bf_global.hip / bf_global_search.cpp)
     std::unique_ptr<GlobalSearch, GlobalSearchFree> glob;
     bool glob_valid = false;         // bf_global_set_window ran on the slice uploaded now (every upload clears it)
+    // segmentation (bf_segment.hip / bf_segment_abi.cpp): label, size and id planes of the image, the scan's per-work-group words,
+    // the scalars, the component table (seg_K rows) and the per-event ids; grown on first use, sized from the image / the slice
+    DevArray<int32_t> d_seg_lab, d_seg_sz, d_seg_nid, d_seg_cl;
+    DevArray<unsigned long long> d_seg_scan;
+    DevArray<SegDev> d_seg_dev;
+    HostArray<SegDev> h_seg_dev;
+    DevArray<bf_component> d_seg_table;
+    DevArray<uint8_t> d_seg_mask;    // bf_label_image: the host mask
+    bool seg_valid = false;          // a segmentation of the current window is held (an upload, bf_set_cloud and every warp clear it)
+    int seg_K = 0;
     SliceStats stats;                // folded k_prepare statistics of the uploaded slice
     bool stats_valid = false;
 
@@ -283,6 +294,10 @@ extern "C" int render_projection_img(bf_ctx* c, int32_t scale, int32_t res_x, in
 extern "C" int render_projection_img_of(bf_ctx* c, const uint32_t* xy, const float2* p, const uint8_t* noise, long long n,
                                         int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_img);
 extern "C" int render_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_bgr);
+
+// The launches of bf_get_time_img without its read-back (bf_operators.cpp): a pending warp applied, the current window's time and
+// count images left in d_time / d_count.  BF_ERR_STATE (message set, `who` the entry point's name) without a usable window.
+int ctx_time_img_pass(bf_ctx* c, const char* who);
 
 // Which loop a slice runs (bf_plan.cpp): plan_slice once per slice, plan_run once per run; nothing else decides it.
 struct SlicePlan {
@@ -598,6 +613,7 @@ int flush_pending(bf_ctx* c) {
     }
     c->pending_warp = false;
     c->p_clean = false;
+    c->seg_valid = false;
     c->n_valid = true;
     c->uv_valid = false;
     c->out_sorted = false;
@@ -656,6 +672,7 @@ int after_upload(bf_ctx* c, long long n) {
     c->stats_valid = false;
     c->have_lwin = false;
     c->glob_valid = false;
+    c->seg_valid = false;
     c->n = n;
     c->uploaded = true;
     c->have_window = false;

@@ -80,6 +80,7 @@ void tiles_collect(bf_ctx* c, const std::vector<DevState>& st, int nt, bf_model*
         }
     }
     c->p_clean = false;
+    c->seg_valid = false;
     c->n_valid = true;
     c->uv_valid = false;
     c->out_sorted = false;

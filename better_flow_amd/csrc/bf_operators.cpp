@@ -13,6 +13,7 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
     int rc = fold_stats(c);
     if (rc != BF_OK) return rc;
     const SliceStats s = c->stats;
+    c->seg_valid = false;
     bf_window w;
     memset(&w, 0, sizeof(w));
     w.scale = scale;
@@ -185,6 +186,7 @@ int bf_project_4param_reinit(bf_ctx* c, double dnx_, double dny_, double cx, dou
         launch_warp_scatter(ws_args(c, c->cur, 0), true, false, true, c->stream);
     }
     c->p_clean = false;
+    c->seg_valid = false;
     c->n_valid = true;
     c->uv_valid = false;
     c->out_sorted = false;
@@ -205,6 +207,7 @@ int bf_project_4param(bf_ctx* c, double dnx_, double dny_, double cx, double cy,
         launch_project_dn(e.xy, e.t, e.p, c->d_nxny, c->has_perm ? e.perm : nullptr, c->n_valid ? 1 : 0, c->d_state, c->n, c->stream);
     }
     c->p_clean = false;
+    c->seg_valid = false;
     c->n_valid = true;
     c->uv_valid = false;
     c->out_sorted = false;
@@ -212,8 +215,10 @@ int bf_project_4param(bf_ctx* c, double dnx_, double dny_, double cx, double cy,
     return BF_OK;
 }
 
-int bf_get_time_img(bf_ctx* c, float* time_out, uint32_t* count_out) {
-    int rc = window_op_begin(c, "bf_get_time_img");
+}  // extern "C"
+
+int ctx_time_img_pass(bf_ctx* c, const char* who) {
+    int rc = window_op_begin(c, who);
     if (rc != BF_OK) return rc;
     launch_set_state(c->d_state, c->hst, c->stream);
     const int buf = c->cur;
@@ -233,6 +238,14 @@ int bf_get_time_img(bf_ctx* c, float* time_out, uint32_t* count_out) {
     c->cur = buf ^ 1;   // the stencil zeroed the other buffer; `buf` is cleared by the next pass
     c->hst.hot.ovf_cnt[buf] = 1;
     c->hst.hot.ovf_cnt[buf ^ 1] = 0;
+    return BF_OK;
+}
+
+extern "C" {
+
+int bf_get_time_img(bf_ctx* c, float* time_out, uint32_t* count_out) {
+    int rc = ctx_time_img_pass(c, "bf_get_time_img");
+    if (rc != BF_OK) return rc;
     const size_t P = (size_t)c->win.scale_img_x * (size_t)c->win.scale_img_y;
     if (time_out)
         HIP_TRY(c, hipMemcpyAsync(time_out, c->d_time, P * sizeof(float), hipMemcpyDeviceToHost, c->stream));

@@ -52,6 +52,7 @@ int run_begin(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L) {
     L.b0 = L.buf = c->cur;
     L.trace = o.trace_cap > 0 ? c->d_trace : nullptr;
     c->p_clean = false;   // the loop warps the events
+    c->seg_valid = false;
     c->pending_warp = false;
     h.x_div = h.y_div = 1.0f;            // :61
     h.rot_div = h.div_div = 10000.0f;    // :62-63

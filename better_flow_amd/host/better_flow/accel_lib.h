@@ -13,6 +13,7 @@
 #define BF_HOST_ACCEL_LIB_H
 
 #include <better_flow/event.h>
+#include <better_flow/clustering.h>
 #include <better_flow/flow_field.h>
 #include <better_flow/object_model.h>
 #include <bf_accel.h>
@@ -270,6 +271,13 @@ public:
         else check(bf::flow_field_from_readbacks(ctx, size, noise_staged.empty() ? nullptr : noise_staged.data(), RES_X, RES_Y,
                                                  BF_FLOW_LAST_UPLOADED, f), "flow_field");
         return f;
+    }
+
+    // The segmentation of the staged slice under window w (bf::Segmenter: the device entries, or the host path on read-backs)
+    bf::Segmentation segmentation(const bf::Segmenter &seg, const bf_window &w) {
+        bf::Segmentation out;
+        check(seg.run(ctx, w, size, noise_staged.empty() ? nullptr : noise_staged.data(), out), "segmentation");
+        return out;
     }
 
     // EventFile::color_flow_img (event_file.h:318-350) of the staged slice: RES_X x RES_Y pixels of B, G, R bytes

@@ -51,6 +51,10 @@ protected:
     std::string img_prefix;
     bool generate_flow_img = false, generate_flow_field = false;   // --flow-img / --flow-field: flow_N.ppm / flow_N.flo
     std::string flow_prefix;
+    bool generate_segments = false;            // --segments: segments_N.txt / segments_N.pgm
+    bf::Segmenter segmenter;
+    std::string segments_prefix;
+    ull segments_count = 0;
     bf::AviWriter flowvideo;
     ull flow_count = 0;
     bool stm_disable;
@@ -95,6 +99,10 @@ public:
     // (flow_N.flo) of every slice under `prefix`; with set_generate_video, the flow frames also go to bf::flow_video_name
     void set_generate_flow(bool img, bool field, std::string prefix = "./") {
         generate_flow_img = img; generate_flow_field = field; flow_prefix = prefix;
+    }
+    // the component table (segments_N.txt) and the label image (segments_N.pgm) of every slice under `prefix`
+    void set_generate_segments(const bf_segment_opts &opts, std::string prefix = "./") {
+        generate_segments = true; segmenter.opts = opts; segments_prefix = prefix;
     }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
@@ -208,6 +216,12 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::recompute() {
         optimizer.fetch_uv();                  // "compute the actual u and v after minimizations are done", :233-235
         if (frames) render_frame(optimizer);
         if (generate_flow_img || generate_flow_field) render_flow_frame(optimizer);
+        if (generate_segments) {   // (after every other output: it reads the slice, and changes nothing the others read)
+            const bf::Segmentation sg = optimizer.get_segmentation(segmenter);
+            const std::string base = segments_prefix + "/segments_" + std::to_string(segments_count++);
+            if ((!bf::write_segments_txt(base + ".txt", sg) || !bf::write_labels_pgm(base + ".pgm", sg)) && !quiet)
+                std::cerr << "cannot write " << base << ".txt / .pgm\n";
+        }
         info = optimizer.get_run_info();
     }
     ++slices_done;

@@ -127,6 +127,23 @@ public:
     std::vector<uint8_t> get_color_flow_img() { this->stage(); return accel.color_flow_img(); }
     bf::FlowField get_flow_field() { this->stage(); return accel.flow_field(); }
 
+    // The moving-object segmentation of the slice as it is compensated now (include/bf_accel.h, "moving-object
+    // segmentation"); a degenerate window (an empty slice) has no image: an empty segmentation.
+    bf::Segmentation get_segmentation(const bf::Segmenter &seg) {
+        this->stage();
+        if (scale_img_x <= 0 || scale_img_y <= 0) {
+            bf::Segmentation none;
+            none.cl_id.assign(this->events->size(), -1);
+            return none;
+        }
+        bf_window w = bf_window();
+        w.scale = scale; w.x_min = x_min; w.y_min = y_min; w.x_max = x_max; w.y_max = y_max;
+        w.metric_wsizex = metric_wsizex; w.metric_wsizey = metric_wsizey;
+        w.scale_img_x = scale_img_x; w.scale_img_y = scale_img_y;
+        w.x_shift = x_shift; w.y_shift = y_shift;
+        return accel.segmentation(seg, w);
+    }
+
     const bf_run_info &get_run_info() const { return last_info; }
     int get_scale_img_x() { this->stage(); return scale_img_x; }
     int get_scale_img_y() { this->stage(); return scale_img_y; }

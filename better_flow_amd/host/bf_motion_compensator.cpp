@@ -36,6 +36,9 @@ struct Options {
     bool interactive = false, quiet = false, gpu_flag = false, stm_disable = false, bufferize = false;
     bool frames = false, video = false;
     bool flow_img = false, flow_field = false;   // --flow-img / --flow-field: flow_N.ppm / flow_N.flo per slice
+    bool segments = false;                       // --segments=<seconds>: segments_N.txt / segments_N.pgm per slice
+    double seg_above = -1.0, seg_below = -1.0;
+    int seg_min_count = 1, seg_min_pixels = 1, seg_connectivity = 8;
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
     int scale = 3, max_iter = -1;
@@ -104,6 +107,12 @@ const std::vector<Flag> &flag_table() {
          "write one flow frame per slice (flow_N.ppm): compensated events | colour-coded flow | raw events; with --video, also <video-name>_flow"},
         {"--flow-field", Arg::None, [](Options &o, const char *) { o.flow_field = true; }, "",
          "write the per-pixel flow field of every slice (flow_N.flo, Middlebury layout: horizontal = column flow, 1e9 = no event)"},
+        {"--segments", Arg::Inline, [](Options &o, const char *v) { o.segments = true; o.seg_above = atof(v); }, "<seconds>",
+         "label the moving objects of every compensated slice (segments_N.txt: one component per line; segments_N.pgm: 16-bit labels, id + 1): pixels whose mean timestamp exceeds the slice's mean by more than <seconds>; ring engine"},
+        {"--segments-below", Arg::Inline, [](Options &o, const char *v) { o.seg_below = atof(v); }, "<seconds>", "... or falls short of it by more than this"},
+        {"--segments-min-count", Arg::Inline, [](Options &o, const char *v) { o.seg_min_count = atoi(v); }, "<n>", "... on pixels with at least this many events (1)"},
+        {"--segments-min-pixels", Arg::Inline, [](Options &o, const char *v) { o.seg_min_pixels = atoi(v); }, "<n>", "drop components smaller than this (1)"},
+        {"--segments-connectivity", Arg::Inline, [](Options &o, const char *v) { o.seg_connectivity = atoi(v); }, "<4|8>", "pixel connectivity (8)"},
         {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
         {"--video", Arg::None, [](Options &o, const char *) { o.video = true; }, "", "write the frames to a video (uncompressed AVI)"},
         {"--video-name", Arg::Next, [](Options &o, const char *v) { o.video_name = v; }, "<file>", "name of that video"},
@@ -203,8 +212,17 @@ int parse(int argc, char **argv, Options &o) {
     if (!o.have_input) { std::fprintf(stderr, "no input file\n"); return 1; }
     if (o.scale < 1 || o.scale % 2 == 0) { std::fprintf(stderr, "--scale must be odd\n"); return 1; }
     if (!o.engine.empty() && o.engine != "stream" && o.engine != "ring") { std::fprintf(stderr, "--engine must be stream or ring\n"); return 1; }
+    if (o.segments && (o.engine == "stream" || !o.more_inputs.empty())) {
+        std::fprintf(stderr, "--segments labels the slices of the reference ring: not with --engine=stream or several input files\n");
+        return 1;
+    }
+    if (o.segments && (o.seg_min_count < 1 || o.seg_min_pixels < 1 || (o.seg_connectivity != 4 && o.seg_connectivity != 8) ||
+                       !std::isfinite(o.seg_above) || !std::isfinite(o.seg_below))) {
+        std::fprintf(stderr, "--segments: finite thresholds, --segments-min-count and --segments-min-pixels >= 1, --segments-connectivity 4 or 8\n");
+        return 1;
+    }
     // (--img / --video / --flow-img / --flow-field run on both engines; without --engine they keep the reference ring)
-    const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive;
+    const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive || o.segments;
     if (o.engine.empty()) o.engine = needs_ring ? "ring" : "stream";
     if (o.engine == "stream" && o.interactive) { std::fprintf(stderr, "-i works on the reference ring: drop --engine=stream\n"); return 1; }
     if (o.have_output_bin && o.output_bin.empty()) { std::fprintf(stderr, "--outfile-bin needs a file name: --outfile-bin=<file>\n"); return 1; }
@@ -268,6 +286,12 @@ int run_ring(const Options &o) {
     if (o.frames) estimator.set_generate_pictures(true, o.frame_prefix);
     if (o.video) estimator.set_generate_video(true, o.video_name, o.video_fps);
     if (o.flow_img || o.flow_field) estimator.set_generate_flow(o.flow_img, o.flow_field, o.frame_prefix);
+    if (o.segments) {
+        bf_segment_opts so;
+        so.above_s = o.seg_above; so.below_s = o.seg_below; so.min_count = o.seg_min_count; so.connectivity = o.seg_connectivity;
+        so.min_pixels = o.seg_min_pixels; so.reserved = 0;
+        estimator.set_generate_segments(so, o.frame_prefix);
+    }
     if (o.stm_disable) estimator.set_stm_disable(true);
     if (!o.slice_log.empty() && !estimator.open_slice_log(o.slice_log)) {
         std::fprintf(stderr, "cannot write '%s'\n", o.slice_log.c_str());

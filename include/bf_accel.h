@@ -911,6 +911,66 @@ int bf_global_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32
 int bf_global_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
                          int32_t lead_row, int32_t lead_col, int64_t *ticket_out);
 
+/* ---- moving-object segmentation: connected components of the compensated time image ---------------------------------------
+ * An eighth definition of this build ("Segmentation"); the reference only carries the vocabulary (Event::cl,
+ * cl_id = -1, visited: event.h:23-34; Cluster: clustering.h).  Everything is defined on integers, so no result depends on
+ * the order work-groups run in.  The image is the current window's time image T (f32 seconds) and count image c (u32),
+ * R x C, exactly as bf_get_time_img produces them; a pixel index is p = row * C + col.
+ *   1. q(p) = floor((double)T(p) * 2^30) as int64 (conversion and product are exact).
+ *   2. n1 = number of pixels with c >= 1; Q = sum of q over them (int64); mu = floor_div(Q, n1) -- a floor, not C's truncation.
+ *      n1 == 0: no foreground, zero components, BF_OK.
+ *   3. A = floor(above_s * 2^30), B = floor(below_s * 2^30), in double on the host.  A negative threshold is disabled; NaN or
+ *      an infinity is BF_ERR_ARG.  p is foreground iff c(p) >= min_count (min_count >= 1) and: both thresholds are disabled,
+ *      or above_s >= 0 and q - mu > A, or below_s >= 0 and mu - q > B.
+ *   4. Components under 4- or 8-connectivity (anything else: BF_ERR_ARG); a component's provisional name is its smallest
+ *      pixel index.  Those with fewer than min_pixels pixels are dropped (their pixels become background); the kept ones are
+ *      numbered 0 .. K-1 in ascending order of that smallest index.  labels[p] is the id, or -1.
+ *   5. bf_component per kept component: id, first_pixel (the smallest index), pixels, events, the bounding box, and the
+ *      int64 sums of row, column and q over its pixels.
+ *   6. cl_id[i], upload order: the label of the event's centre pixel -- (int)(pr_x * scale + x_sh), (int)(pr_y * scale + y_sh)
+ *      of get_time_img_cpu (accel_lib.h:154-155), the scatter kernel's own pixel -- and -1 when the time image skips the event
+ *      (noise, outside the window) or the pixel is background.  A component's `events` counts the events with its cl_id.
+ * Thresholds are seconds: the paper's rho > lambda is above_s = lambda * dt, and the caller knows dt.
+ *
+ *   bf_segment      runs the time-image pass itself (the launches of bf_get_time_img without its read-back: it can never label
+ *                   a stale image), then the segmentation; labels, table and cl_id stay on the device.  BF_ERR_STATE before
+ *                   bf_set_cloud or on a degenerate window; BF_ERR_ARG for bad options (NULL: the defaults).
+ *   bf_segment_get  what the last bf_segment left: labels_out R * C, comps_out at most comps_cap rows, cl_id_out n; any pointer
+ *                   may be NULL.  BF_ERR_STATE when no segmentation of the current window is held: an upload, bf_set_cloud
+ *                   and every warp invalidate it.
+ *   bf_label_image  the labelling alone (4. and 5.; q_sum = events = 0) of a host mask, non-zero = foreground, in the manner of
+ *                   bf_sobel.  components_out: K.  BF_ERR_CAPACITY beyond the context's pixel capacity.  Leaves a held
+ *                   segmentation invalid (it uses the same planes). */
+typedef struct bf_segment_opts {
+    double above_s, below_s;   /* seconds; negative: disabled */
+    int32_t min_count;         /* >= 1 */
+    int32_t connectivity;      /* 4 or 8 */
+    int32_t min_pixels;        /* >= 1 */
+    int32_t reserved;
+} bf_segment_opts;
+
+typedef struct bf_segment_info {
+    int32_t rows, cols;
+    int64_t n1, q_sum, q_mean;
+    int32_t foreground_pixels;   /* before the size filter */
+    int32_t components_found;    /* before the size filter */
+    int32_t components;          /* kept */
+    int32_t reserved;
+} bf_segment_info;
+
+typedef struct bf_component {
+    int32_t id, first_pixel, pixels, events;
+    int32_t row_min, row_max, col_min, col_max;
+    int64_t row_sum, col_sum, q_sum;
+} bf_component;
+
+/* above_s = below_s = -1 (regions of activity), min_count 1, connectivity 8, min_pixels 1 */
+void bf_segment_opts_default(bf_segment_opts *opts);
+int bf_segment(bf_ctx *ctx, const bf_segment_opts *opts, bf_segment_info *info);
+int bf_segment_get(bf_ctx *ctx, int32_t *labels_out, bf_component *comps_out, int32_t comps_cap, int32_t *cl_id_out);
+int bf_label_image(bf_ctx *ctx, const uint8_t *mask, int32_t rows, int32_t cols, int32_t connectivity, int32_t min_pixels,
+                   int32_t *labels_out, bf_component *comps_out, int32_t comps_cap, int32_t *components_out);
+
 /* NUMA placement of a feeder thread (no reference counterpart: the reference is single-threaded, SURVEY 8(b) "Threading"; the
  * 8-GPU farm of SURVEY 8(e) wants one feeder thread per GPU with NUMA-local pinned buffers).
  *   bf_device_numa_node          host NUMA node of HIP device `device` (sysfs numa_node of its PCI function); -1: unknown.
