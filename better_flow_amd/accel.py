@@ -175,6 +175,17 @@ class Component(C.Structure):
                 ("row_sum", C.c_int64), ("col_sum", C.c_int64), ("q_sum", C.c_int64)]
 
 
+class GroupOpts(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("sensor_res_x", C.c_int32), ("sensor_res_y", C.c_int32),
+                ("guard_res_x", C.c_int32), ("guard_res_y", C.c_int32), ("min_events", C.c_int32),
+                ("max_iter", C.c_int32), ("hard_iter_cap", C.c_int32)]
+
+
+class GroupInfo(C.Structure):
+    _fields_ = [("events", C.c_int32), ("row_min", C.c_int32), ("row_max", C.c_int32), ("col_min", C.c_int32),
+                ("col_max", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32)]
+
+
 # the numpy view of a bf_component table
 COMPONENT_DTYPE = np.dtype([(n, np.int32) for n in ("id", "first_pixel", "pixels", "events", "row_min", "row_max", "col_min",
                                                     "col_max")] + [(n, np.int64) for n in ("row_sum", "col_sum", "q_sum")])
@@ -201,6 +212,7 @@ EXPORTS = [
     "bf_global_hold_field", "bf_global_hold_best", "bf_global_get_flow", "bf_global_flow_field", "bf_global_color_flow_img",
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
+    "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -337,6 +349,9 @@ def load(path=None):
         L.bf_segment_get.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
         L.bf_label_image.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_int32, C.POINTER(C.c_int32)]
+        L.bf_set_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.bf_set_groups_from_segments.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        L.bf_run_groups.argtypes = [C.c_void_p, C.POINTER(GroupOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.bf_fast_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model)]
         L.bf_writeout_events.argtypes = [C.c_void_p] + [C.c_void_p] * 4
@@ -859,6 +874,35 @@ class Accel:
         infos = (RunInfo * nt)()
         self._chk(self.L.bf_run_tiles(self.h, C.byref(o), models, infos))
         return list(models), list(infos)
+
+    def set_groups(self, group_id, groups):
+        """bf_set_groups: a group id per event (-1 .. groups - 1, upload order) for bf_run_groups; holds until the next upload."""
+        gid = np.ascontiguousarray(group_id, dtype=np.int32)
+        self._chk(self.L.bf_set_groups(self.h, _ptr(gid), int(groups)))
+
+    def set_groups_from_segments(self):
+        """bf_set_groups_from_segments: the held segmentation's cl_id becomes the grouping, on the device; returns K."""
+        k = C.c_int32(0)
+        self._chk(self.L.bf_set_groups_from_segments(self.h, C.byref(k)))
+        return k.value
+
+    def run_groups(self, groups, scale, sensor_res, guard_res, min_events, warm=None, max_iter=-1, hard_iter_cap=20000):
+        """bf_run_groups on the held grouping of `groups` groups: one optimizer per group, cold (warm None), every group from
+        one Model, or from one Model per group (a sequence of `groups`).  Returns (models, infos, GroupInfo per group)."""
+        o = GroupOpts(scale, sensor_res[0], sensor_res[1], guard_res[0], guard_res[1], min_events, max_iter, hard_iter_cap)
+        if warm is None:
+            wm, wn = None, 0
+        elif isinstance(warm, Model):
+            wm, wn = (Model * 1)(warm), 1
+        else:
+            wn = len(warm)
+            wm = (Model * max(wn, 1))(*warm)
+        K = max(int(groups), 0)
+        models = (Model * max(K, 1))()
+        infos = (RunInfo * max(K, 1))()
+        ginfo = (GroupInfo * max(K, 1))()
+        self._chk(self.L.bf_run_groups(self.h, C.byref(o), wm, wn, models, infos, ginfo))
+        return list(models)[:K], list(infos)[:K], list(ginfo)[:K]
 
     def get_trace(self, cap):
         buf = (TraceRec * max(cap, 1))()

@@ -214,7 +214,9 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         {"k3_half_scale", c->launched.k3_half_scale}, {"k3_mode", c->launched.k3_mode}, {"k3_capped", c->launched.k3_capped},
         // ... and the bin grid bf_set_cloud planned for it (0: the slice does not take that loop)
         {"bin_rows", c->use_binned ? c->grid.TSR : 0}, {"bin_cols", c->use_binned ? c->grid.TS : 0},
-        {"bin_margin", c->use_binned ? c->grid.D : 0}, {"bins", c->use_binned ? c->grid.nbins : 0}};
+        {"bin_margin", c->use_binned ? c->grid.D : 0}, {"bins", c->use_binned ? c->grid.nbins : 0},
+        // ... and what the last bf_run_groups launched: the optimizers' dynamic LDS (bytes) and their work-groups per CU
+        {"groups_lds", c->groups_lds}, {"groups_per_cu", c->groups_per_cu}};
     for (const auto& e : launched)
         if (!strcmp(key, e.name)) {
             *value = e.v;

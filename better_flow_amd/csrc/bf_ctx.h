@@ -129,6 +129,13 @@ struct bf_ctx {
     DevArray<uint8_t> d_ltile;       // bf_local_run_tiles: the windows' states, then their return codes
     DevArray<uint8_t> d_many_args;   // bf_run_tiles_many (lead context): the slices' launch arguments + the claim counter
     HostArray<TileArgs> h_many_args; // ... and their pinned staging copy
+    // event groups (bf_set_groups / bf_set_groups_from_segments / bf_run_groups): the group id per event in upload order, the
+    // groups' fr boxes (x min, x max, y min, y max), the claim order (descending event count) and the claim counter
+    DevArray<int32_t> d_group_id, d_group_box;
+    DevArray<uint32_t> d_group_order, d_group_counter;
+    int groups_K = 0;
+    bool groups_valid = false;       // a grouping of the uploaded slice is held (every upload clears it)
+    int groups_lds = 0, groups_per_cu = 0;   // what the last bf_run_groups launched: dynamic LDS bytes, work-groups per CU (bf_get_stat)
     // One staging slot of the asynchronous uploads (bf_upload.cpp).  Its state:
     //   FREE      not taken;
     //   RECORDED  taken, `src` describes what to copy, no HIP call issued yet ("defer_uploads");
@@ -673,6 +680,7 @@ int after_upload(bf_ctx* c, long long n) {
     c->have_lwin = false;
     c->glob_valid = false;
     c->seg_valid = false;
+    c->groups_valid = false;
     c->n = n;
     c->uploaded = true;
     c->have_window = false;

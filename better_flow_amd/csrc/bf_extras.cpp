@@ -218,6 +218,168 @@ int bf_local_run_tiles(bf_ctx* c, const bf_local_tile_opts* o, bf_local_state* s
     return BF_OK;
 }
 
+// ---- Event groups: the reference's queue of (events, model) tasks over one uploaded slice (bf_accel.h, "event groups") ----
+
+int bf_set_groups(bf_ctx* c, const int32_t* group_id, int32_t groups) {
+    if (!c) return BF_ERR_ARG;
+    if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_set_groups before bf_upload_events");
+    if (groups < 0 || (c->n > 0 && !group_id)) return fail(c, BF_ERR_ARG, "bf_set_groups: %d groups, ids %p", groups, (const void*)group_id);
+    if ((long long)groups + 1 > 16384) return fail(c, BF_ERR_CAPACITY, "bf_set_groups: %d groups + 1 exceed the sort's 16384 buckets", groups);
+    for (long long i = 0; i < c->n; ++i)
+        if (group_id[i] < -1 || group_id[i] >= groups)
+            return fail(c, BF_ERR_ARG, "bf_set_groups: event %lld has id %d outside -1 .. %d", i, group_id[i], groups - 1);
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->groups_valid = false;
+    HIP_TRY(c, c->d_group_id.grow((size_t)(c->n > 0 ? c->n : 1)));
+    if (c->n > 0) {
+        HIP_TRY(c, hipMemcpyAsync(c->d_group_id, group_id, (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the caller's array is free again)
+    }
+    c->groups_K = groups;
+    c->groups_valid = true;
+    return BF_OK;
+}
+
+int bf_set_groups_from_segments(bf_ctx* c, int32_t* groups_out) {
+    if (!c) return BF_ERR_ARG;
+    if (!c->seg_valid || c->pending_warp || !c->have_window)
+        return fail(c, BF_ERR_STATE, "bf_set_groups_from_segments: no segmentation of the current window is held");
+    if ((long long)c->seg_K + 1 > 16384)
+        return fail(c, BF_ERR_CAPACITY, "bf_set_groups_from_segments: %d components + 1 exceed the sort's 16384 buckets", c->seg_K);
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->groups_valid = false;
+    HIP_TRY(c, c->d_group_id.grow((size_t)(c->n > 0 ? c->n : 1)));
+    if (c->n > 0)   // (the context's own plane: the grouping outlives the segmentation)
+        HIP_TRY(c, hipMemcpyAsync(c->d_group_id, c->d_seg_cl, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    c->groups_K = c->seg_K;
+    c->groups_valid = true;
+    if (groups_out) *groups_out = c->seg_K;
+    return BF_OK;
+}
+
+int bf_run_groups(bf_ctx* c, const bf_group_opts* o, const bf_model* warm, int32_t warm_count, bf_model* models_out,
+                  bf_run_info* infos_out, bf_group_info* groups_out) {
+    if (!c || !o) return BF_ERR_ARG;
+    if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_run_groups before bf_upload_events");
+    if (!c->groups_valid) return fail(c, BF_ERR_STATE, "bf_run_groups: no grouping of the uploaded slice is held");
+    const int K = c->groups_K;
+    if (o->scale < 1 || o->scale % 2 == 0 || o->scale / 2 > kMaxHalfScale) return fail(c, BF_ERR_ARG, "scale must be odd");
+    if (o->sensor_res_x < 1 || o->sensor_res_y < 1) return fail(c, BF_ERR_ARG, "bad sensor size");
+    if (c->has_noise) return fail(c, BF_ERR_ARG, "bf_run_groups does not take a noise mask");
+    if (!(warm_count == 0 || warm_count == 1 || warm_count == K) || (warm_count > 0 && !warm))
+        return fail(c, BF_ERR_ARG, "bf_run_groups: %d warm models for %d groups (0, 1 or one per group)", warm_count, K);
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+    int rc = ensure_second_set(c);
+    if (rc != BF_OK) return rc;
+    const int nb = K + 1;   // buckets: the groups, then the events of none
+    bool fresh;
+    HIP_TRY(c, c->d_tile_hist.grow((size_t)nb + 1, &fresh));
+    if (fresh) HIP_TRY(c, hipMemsetAsync(c->d_tile_hist, 0, (size_t)(nb + 1) * 4, s));
+    HIP_TRY(c, c->d_tile_start.grow((size_t)nb + 1));
+    HIP_TRY(c, c->d_tile_cursor.grow((size_t)nb + 1));
+    HIP_TRY(c, c->d_tile_states.grow((size_t)(K > 0 ? K : 1)));
+    HIP_TRY(c, c->d_group_box.grow((size_t)(K > 0 ? K : 1) * 4));
+    HIP_TRY(c, c->d_group_order.grow((size_t)(K > 0 ? K : 1)));
+    HIP_TRY(c, c->d_group_counter.grow(1));
+
+    const bf_ctx::EvSet& src = c->set[c->cs];
+    const bf_ctx::EvSet& dst = c->set[c->cs ^ 1];
+    {
+        ProfScope ps(c, 3);
+        if (launch_group_sort(src.xy, src.t, c->has_perm ? src.perm : nullptr, c->n, c->d_group_id, K, c->d_tile_hist,
+                              c->d_tile_start, c->d_tile_cursor, dst.xy, dst.t, dst.p, dst.perm, s) != 0)
+            return fail(c, BF_ERR_HIP, "cannot configure the sort for %d groups", K);
+        launch_group_boxes(dst.xy, dst.perm, c->d_group_id, c->d_tile_start, c->n, K, c->d_group_box, s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    c->cs ^= 1;
+    c->has_perm = true;
+
+    // the groups' event counts and boxes: what the windows will be, which of them run, the LDS they need
+    std::vector<uint32_t> start((size_t)nb + 1);
+    std::vector<int32_t> box((size_t)K * 4);
+    HIP_TRY(c, hipMemcpyAsync(start.data(), c->d_tile_start, ((size_t)nb + 1) * 4, hipMemcpyDeviceToHost, s));
+    if (K > 0) HIP_TRY(c, hipMemcpyAsync(box.data(), c->d_group_box, (size_t)K * 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const int sc = o->scale;
+    long long max_px = 1;
+    std::vector<bf_group_info> gi((size_t)K);
+    for (int g = 0; g < K; ++g) {
+        const int n = (int)(start[(size_t)g + 1] - start[(size_t)g]);
+        int x_min = o->sensor_res_x, y_min = o->sensor_res_y, x_max = 0, y_max = 0;   // optimizer_rolling.h:252-253
+        if (n > 0) {
+            x_min = std::min(x_min, box[4 * (size_t)g]); x_max = std::max(x_max, box[4 * (size_t)g + 1]);
+            y_min = std::min(y_min, box[4 * (size_t)g + 2]); y_max = std::max(y_max, box[4 * (size_t)g + 3]);
+        }
+        const int R = sc * (x_max - x_min) + sc, C = sc * (y_max - y_min) + sc;
+        bf_group_info& q = gi[(size_t)g];
+        memset(&q, 0, sizeof(q));
+        q.events = n;
+        q.row_min = x_min; q.row_max = x_max; q.col_min = y_min; q.col_max = y_max;
+        q.rows = R; q.cols = C;
+        // the guards of run() as the kernel evaluates them (tile_optimizer_body): a group they skip needs no planes
+        const bool skipped = ((R < sc * o->guard_res_x / 15) && (C < sc * o->guard_res_y / 15)) || n < o->min_events;
+        if (!skipped && R > 0 && C > 0 && (long long)R * C * 16 <= (long long)kGroupLdsBudget) max_px = std::max(max_px, (long long)R * C);
+    }
+    if (groups_out) for (int g = 0; g < K; ++g) groups_out[g] = gi[(size_t)g];
+
+    if (K > 0) {
+        DevState tmpl;
+        memset(&tmpl, 0, sizeof(tmpl));
+        tmpl.x_div = tmpl.y_div = 1.0f;           // optimizer_rolling.h:61-63
+        tmpl.rot_div = tmpl.div_div = 10000.0f;
+        tmpl.max_iter = o->max_iter;
+        tmpl.hard_cap = o->hard_iter_cap;
+        tmpl.hot.wp = identity_warp();
+        auto warm_state = [&](const bf_model& m) {   // bf_set_model (optimizer_rolling.h:289-299) on the reset state
+            DevState w = tmpl;
+            w.model = m;
+            set_warp(w.hot.wp, -m.total_dx, -m.total_dy, m.cx, m.cy, m.total_div, -m.total_rot);
+            return w;
+        };
+        // the claim order: descending event count, so that the longest loops start first
+        std::vector<uint32_t> order((size_t)K);
+        for (int g = 0; g < K; ++g) order[(size_t)g] = (uint32_t)g;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return gi[a].events > gi[b].events; });
+        HIP_TRY(c, hipMemcpyAsync(c->d_group_order, order.data(), (size_t)K * 4, hipMemcpyHostToDevice, s));
+        std::vector<DevState> warm_st;
+        if (warm_count == K && K > 1) {
+            warm_st.resize((size_t)K);
+            for (int g = 0; g < K; ++g) warm_st[(size_t)g] = warm_state(warm[g]);
+            HIP_TRY(c, hipMemcpyAsync(c->d_tile_states, warm_st.data(), (size_t)K * sizeof(DevState), hipMemcpyHostToDevice, s));
+        } else {
+            launch_fill_states(c->d_tile_states, warm_count > 0 ? warm_state(warm[0]) : tmpl, K, s);
+        }
+        HIP_TRY(c, hipStreamSynchronize(s));   // (order and warm_st are pageable and leave scope below)
+        HIP_TRY(c, hipMemsetAsync(c->d_group_counter, 0, sizeof(uint32_t), s));
+
+        TileArgs a;
+        a.xy = dst.xy; a.t = dst.t; a.p = dst.p; a.perm = dst.perm;
+        a.nxny = c->d_nxny;
+        a.tile_start = c->d_tile_start;
+        a.states = c->d_tile_states;
+        a.scale = sc;
+        a.seed_res_x = o->sensor_res_x; a.seed_res_y = o->sensor_res_y;
+        a.guard_res_x = o->guard_res_x; a.guard_res_y = o->guard_res_y;
+        a.min_events = o->min_events;
+        a.max_px = (int32_t)max_px;   // the largest window that runs: the others are skipped, or BF_ERR_CAPACITY in their own rc
+        ProfScope ps(c, 0, c->n);
+        int per_cu = 0;
+        if (launch_group_optimizer(a, c->d_group_order, K, warm_count > 0, c->d_group_counter, c->n_cus, s, &per_cu) != 0)
+            return fail(c, BF_ERR_HIP, "cannot configure the group kernel");
+        c->groups_lds = (int)(max_px * 16);
+        c->groups_per_cu = per_cu;
+    }
+    launch_group_rest(dst.perm, c->d_tile_start, K, c->d_nxny, s);
+    HIP_TRY(c, hipGetLastError());
+    std::vector<DevState> st((size_t)K);
+    if (K > 0) HIP_TRY(c, hipMemcpyAsync(st.data(), c->d_tile_states, (size_t)K * sizeof(DevState), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    tiles_collect(c, st, K, models_out, infos_out);
+    return BF_OK;
+}
+
 // ---- OptimizerLocal: the contrast-score optimiser (optimizer_sampler.h / .cpp) ------------------
 
 namespace {

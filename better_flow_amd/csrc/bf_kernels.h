@@ -169,6 +169,19 @@ int launch_tile_optimizer(const TileArgs& a, int ntiles, hipStream_t s);
 int launch_tile_optimizer_many(const TileArgs* slices, int nslices, int ntiles, int scale, int max_px, uint32_t* counter, int n_cus,
                                hipStream_t s);
 void launch_fill_states(DevState* states, const DevState& tmpl, int nt, hipStream_t s);
+// Event groups (bf_run_groups): the same counting sort keyed by gid[upload index] (-1 and anything outside 0 .. K-1: the
+// trailing bucket K; hist / start / cursor hold K + 2 words), the groups' fr boxes (box: K x {x min, x max, y min, y max} of
+// the SORTED events), the optimizers -- one work-group per group, claimed in `order` from `counter` (one zeroed word) -- and
+// the (0, 0) of the trailing bucket.  warm: every group's state holds set_model's warp and model.
+constexpr int kGroupLdsBudget = 156 * 1024;   // the planes of one group's window (16 bytes per pixel), as for a tile
+int launch_group_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const int32_t* gid, int K,
+                      uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
+                      uint32_t* operm, hipStream_t s);
+void launch_group_boxes(const uint32_t* xy, const uint32_t* perm, const int32_t* gid, const uint32_t* start, long long n, int K,
+                        int32_t* box, hipStream_t s);
+int launch_group_optimizer(const TileArgs& a, const uint32_t* order, int K, bool warm, uint32_t* counter, int n_cus,
+                           hipStream_t s, int* per_cu_out);
+void launch_group_rest(const uint32_t* perm, const uint32_t* start, int K, double2* nxny, hipStream_t s);
 
 // bf_rebin.hip / bf_scatter.hip / bf_stencil.hip / bf_fused.hip (the tile-binned loops)
 int bin_kernel_setup();

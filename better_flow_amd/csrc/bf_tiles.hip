@@ -24,14 +24,33 @@ __device__ __forceinline__ int tile_of(uint32_t xy, const TileGrid& g) {
     return tr * g.cols + tc;
 }
 
-__global__ __launch_bounds__(kThreads) void k_tile_count(const uint32_t* __restrict__ xy, long long n, TileGrid g,
+// The counting sort's key: the sensor tile of an event (bf_run_tiles), or its group (bf_run_groups: the id of its upload
+// index, with -1 -- and anything else outside 0 .. K-1 -- in the trailing bucket K).
+struct TileKey {
+    TileGrid g;
+    __device__ __forceinline__ int buckets() const { return g.rows * g.cols; }
+    __device__ __forceinline__ int operator()(const uint32_t* __restrict__ xy, long long i) const { return tile_of(xy[i], g); }
+};
+struct GroupKey {
+    const int32_t* gid;
+    const uint32_t* perm;   // slot -> upload index (null: the identity)
+    int K;
+    __device__ __forceinline__ int buckets() const { return K + 1; }
+    __device__ __forceinline__ int operator()(const uint32_t* __restrict__, long long i) const {
+        const int id = gid[perm ? perm[i] : (uint32_t)i];
+        return (id < 0 || id >= K) ? K : id;
+    }
+};
+
+template <class KEY>
+__global__ __launch_bounds__(kThreads) void k_tile_count(const uint32_t* __restrict__ xy, long long n, KEY g,
                                                          uint32_t* __restrict__ hist) {
     extern __shared__ uint32_t s_h[];
-    const int nt = g.rows * g.cols;
+    const int nt = g.buckets();
     for (int i = threadIdx.x; i < nt; i += kThreads) s_h[i] = 0;
     __syncthreads();
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads)
-        atomicAdd(&s_h[tile_of(xy[i], g)], 1u);
+        atomicAdd(&s_h[g(xy, i)], 1u);
     __syncthreads();
     for (int i = threadIdx.x; i < nt; i += kThreads)
         if (s_h[i]) atomicAdd(&hist[i], s_h[i]);
@@ -68,13 +87,14 @@ __global__ __launch_bounds__(1024) void k_tile_scan(uint32_t* __restrict__ hist,
     if (tid == 1023) start[nt] = s_sum[1023];
 }
 
+template <class KEY>
 __global__ __launch_bounds__(kThreads) void k_tile_scatter(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
-                                                           const uint32_t* __restrict__ perm_in, long long n, TileGrid g,
+                                                           const uint32_t* __restrict__ perm_in, long long n, KEY g,
                                                            const uint32_t* __restrict__ start, uint32_t* __restrict__ cursor,
                                                            uint32_t* __restrict__ oxy, int32_t* __restrict__ ot,
                                                            float2* __restrict__ op, uint32_t* __restrict__ operm) {
     extern __shared__ uint32_t s_u[];
-    const int nt = g.rows * g.cols;
+    const int nt = g.buckets();
     uint32_t* s_cnt = s_u;
     uint32_t* s_base = s_u + nt;
     for (int i = threadIdx.x; i < nt; i += kThreads) s_cnt[i] = 0;
@@ -87,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void k_tile_scatter(const uint32_t* __res
         const long long i = base + k * kThreads + threadIdx.x;
         bin[k] = -1;
         if (i < n) {
-            bin[k] = tile_of(xy[i], g);
+            bin[k] = g(xy, i);
             rank[k] = atomicAdd(&s_cnt[bin[k]], 1u);
         }
     }
@@ -115,7 +135,10 @@ __global__ __launch_bounds__(kThreads) void k_tile_scatter(const uint32_t* __res
 // the reduction across sixteen waves eats what the shorter loops give), so 256 it is.
 // HS: scale / 2 when it is 0, 1 or 2 (the box sum's eighteen LDS reads per pixel are then issued together instead of one
 // by one from a loop with run-time bounds: 4.1 -> us of a 7.8 us iteration), -1: any scale.
-template <int THREADS, int HS>
+// WARM (bf_run_groups with warm models): the state template holds set_model's model and, in hot.wp, its warp
+// (optimizer_rolling.h:289-299); every event is warped once with it before the loop, and a group that does not run keeps
+// that warp's (nx, ny).
+template <int THREADS, int HS, bool WARM = false>
 __device__ __forceinline__ void tile_optimizer_body(const TileArgs& a, const int tile, unsigned long long* s_dyn) {
     __shared__ DevState s_st;
     __shared__ int s_box[4];
@@ -189,6 +212,24 @@ __device__ __forceinline__ void tile_optimizer_body(const TileArgs& a, const int
         rp[k] = (end > beg) ? a.p[i] : make_float2(0.f, 0.f);
     }
     const uint32_t stream_beg = beg + (uint32_t)(kTileUR * THREADS);
+    if (WARM) {   // ---- set_model: one warp_reinit from the reset state, whatever the guards say next ----
+        const WarpParams wp0 = s_st.hot.wp;
+        auto warm_event = [&](uint32_t i, uint32_t v, int32_t ti, float2& q) {
+            double nx, ny;
+            warp_products(wp0, pr_from_p(v & 0xffffu, q.x), pr_from_p(v >> 16, q.y), ti, q, nx, ny);
+            a.nxny[a.perm[i]] = make_double2(nx, ny);
+        };
+#pragma unroll
+        for (int k = 0; k < kTileUR; ++k) {
+            const uint32_t i = beg + (uint32_t)(k * THREADS + tid);
+            if (i < end) warm_event(i, rxy[k], rt[k], rp[k]);
+        }
+        for (uint32_t i = stream_beg + tid; i < end; i += THREADS) {
+            float2 q = a.p[i];
+            warm_event(i, a.xy[i], a.t[i], q);
+            a.p[i] = q;
+        }
+    }
     __shared__ unsigned long long s_rpart[kSumFields * (THREADS / 64)];
     const int x_sh = s_st.hot.x_sh, y_sh = s_st.hot.y_sh, wsx = s_st.hot.wsx, wsy = s_st.hot.wsy;
     const int hR = R / 2, hC = C / 2;
@@ -328,6 +369,7 @@ __device__ __forceinline__ void tile_optimizer_body(const TileArgs& a, const int
     // ---- final state: the last project_4param_reinit of the loop, n for compute_uv ----
     const WarpParams wp = s_st.hot.wp;
     const bool ran = s_st.rc == 0 && s_st.hot.it > 0;
+    const bool keep_warm = WARM && s_st.hot.it == 0;   // (no iteration: set_model's (nx, ny) stand)
     auto final_event = [&](uint32_t i, uint32_t v, int32_t ti, float2 q) {
         double nx = 0.0, ny = 0.0;
         if (ran) {
@@ -335,7 +377,7 @@ __device__ __forceinline__ void tile_optimizer_body(const TileArgs& a, const int
             warp_products(wp, pr_x, pr_y, ti, q, nx, ny);
         }
         a.p[i] = q;
-        a.nxny[a.perm[i]] = make_double2(nx, ny);
+        if (!keep_warm) a.nxny[a.perm[i]] = make_double2(nx, ny);
     };
 #pragma unroll
     for (int k = 0; k < kTileUR; ++k) {
@@ -377,6 +419,86 @@ __global__ __launch_bounds__(THREADS) void k_tile_optimizer_many(const TileArgs*
     }
 }
 
+// bf_run_groups: one work-group per group, claimed from a device counter in the host's order (descending event count: the
+// stragglers start first) -- the claim loop of k_tile_optimizer_many over one slice's groups.
+template <int THREADS, int HS, bool WARM>
+__global__ __launch_bounds__(THREADS) void k_group_optimizer(TileArgs a, const uint32_t* __restrict__ order, int K,
+                                                             uint32_t* __restrict__ counter) {
+    extern __shared__ unsigned long long s_dyn[];
+    __shared__ uint32_t s_item;
+    for (;;) {
+        if (threadIdx.x == 0) s_item = atomicAdd(counter, 1u);
+        __syncthreads();
+        const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_item);
+        if (item >= (uint32_t)K) return;
+        const uint32_t g = order[item];
+        if (g < (uint32_t)K) tile_optimizer_body<THREADS, HS, WARM>(a, (int)g, s_dyn);
+        __syncthreads();   // (the item's LDS -- state, planes, s_item -- is free again)
+    }
+}
+
+// The fr bounding box of every group from the SORTED events (group g: slots start[g] .. start[g + 1]).  Work-groups of slab y
+// take the groups y * kBoxSlab ...: partial boxes in LDS -- a wave whose events are all of one group folds them first and
+// adds one lane's worth --, then one integer atomicMin / atomicMax per (work-group, group that it met).
+constexpr int kBoxSlab = 2048;
+__global__ __launch_bounds__(kThreads) void k_group_boxes(const uint32_t* __restrict__ xy, const uint32_t* __restrict__ perm,
+                                                          const int32_t* __restrict__ gid, const uint32_t* __restrict__ start,
+                                                          int K, int32_t* __restrict__ box) {
+    __shared__ int s_b[kBoxSlab * 4];
+    const int tid = threadIdx.x;
+    const int g0 = (int)blockIdx.y * kBoxSlab, g1 = min(K, g0 + kBoxSlab), ng = g1 - g0;
+    for (int i = tid; i < ng; i += kThreads) {
+        s_b[4 * i] = INT_MAX; s_b[4 * i + 1] = INT_MIN; s_b[4 * i + 2] = INT_MAX; s_b[4 * i + 3] = INT_MIN;
+    }
+    __syncthreads();
+    const uint32_t beg = start[g0], end = start[g1];
+    for (unsigned long long base = (unsigned long long)beg + (unsigned long long)blockIdx.x * kThreads; base < end;
+         base += (unsigned long long)gridDim.x * kThreads) {
+        const unsigned long long i = base + (unsigned)tid;
+        int g = -2, x = 0, y = 0;
+        if (i < end) {
+            const uint32_t v = xy[i];
+            x = (int)(v & 0xffffu); y = (int)(v >> 16);
+            g = gid[perm[i]] - g0;
+            if (g < 0 || g >= ng) g = -1;   // (cannot be: the slots of this slab hold its groups)
+        }
+        const int gf = __builtin_amdgcn_readfirstlane(g);
+        if (__all(g == gf)) {
+            if (gf >= 0) {
+                const int xmin = wave_min(x), xmax = wave_max(x), ymin = wave_min(y), ymax = wave_max(y);
+                if ((tid & 63) == 0) {
+                    atomicMin(&s_b[4 * gf], xmin); atomicMax(&s_b[4 * gf + 1], xmax);
+                    atomicMin(&s_b[4 * gf + 2], ymin); atomicMax(&s_b[4 * gf + 3], ymax);
+                }
+            }
+        } else if (g >= 0) {
+            atomicMin(&s_b[4 * g], x); atomicMax(&s_b[4 * g + 1], x);
+            atomicMin(&s_b[4 * g + 2], y); atomicMax(&s_b[4 * g + 3], y);
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < ng; i += kThreads)
+        if (s_b[4 * i] != INT_MAX) {
+            int32_t* b = box + 4 * (size_t)(g0 + i);
+            atomicMin(&b[0], s_b[4 * i]); atomicMax(&b[1], s_b[4 * i + 1]);
+            atomicMin(&b[2], s_b[4 * i + 2]); atomicMax(&b[3], s_b[4 * i + 3]);
+        }
+}
+
+__global__ void k_group_box_init(int32_t* box, int K) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 4 * K) box[i] = (i & 1) ? INT_MIN : INT_MAX;
+}
+
+// the events of no group (the trailing bucket): (nx, ny) = (0, 0); their products were reset by the sort
+__global__ __launch_bounds__(kThreads) void k_group_rest(const uint32_t* __restrict__ perm, const uint32_t* __restrict__ start,
+                                                         int K, double2* __restrict__ nxny) {
+    const uint32_t beg = start[K], end = start[K + 1];
+    for (unsigned long long i = (unsigned long long)beg + (unsigned long long)blockIdx.x * kThreads + threadIdx.x; i < end;
+         i += (unsigned long long)gridDim.x * kThreads)
+        nxny[perm[i]] = make_double2(0.0, 0.0);
+}
+
 __global__ void k_fill_states(DevState* states, DevState tmpl, int nt) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < nt) states[i] = tmpl;
@@ -395,22 +517,38 @@ static int tile_sort_lds(K k, size_t bytes) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? 0 : -1;
 }
 
-int launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const TileGrid& g,
-                     uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
-                     uint32_t* operm, hipStream_t s) {
-    const int nt = g.rows * g.cols;
+template <class KEY>
+static int launch_keyed_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const KEY& g, int nt,
+                             uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
+                             uint32_t* operm, hipStream_t s) {
     long long blocks = (n + kThreads * 8 - 1) / (kThreads * 8);
     if (blocks > 1024) blocks = 1024;
     if (blocks < 1) blocks = 1;
-    if (tile_sort_lds(k_tile_count, (size_t)nt * 4) != 0 || tile_sort_lds(k_tile_scatter, (size_t)nt * 8) != 0) return -1;
-    hipLaunchKernelGGL(k_tile_count, dim3((unsigned)blocks), dim3(kThreads), (size_t)nt * 4, s, xy, n, g, hist);
+    if (tile_sort_lds(k_tile_count<KEY>, (size_t)nt * 4) != 0 || tile_sort_lds(k_tile_scatter<KEY>, (size_t)nt * 8) != 0) return -1;
+    hipLaunchKernelGGL(k_tile_count<KEY>, dim3((unsigned)blocks), dim3(kThreads), (size_t)nt * 4, s, xy, n, g, hist);
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(1024), 0, s, hist, nt, start, cursor);
     if (n > 0) {
         const long long per = (long long)kThreads * 4;
-        hipLaunchKernelGGL(k_tile_scatter, dim3((unsigned)((n + per - 1) / per)), dim3(kThreads), (size_t)nt * 8, s, xy, t,
+        hipLaunchKernelGGL(k_tile_scatter<KEY>, dim3((unsigned)((n + per - 1) / per)), dim3(kThreads), (size_t)nt * 8, s, xy, t,
                            perm_in, n, g, start, cursor, oxy, ot, op, operm);
     }
     return 0;
+}
+
+int launch_tile_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const TileGrid& g,
+                     uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
+                     uint32_t* operm, hipStream_t s) {
+    TileKey key;
+    key.g = g;
+    return launch_keyed_sort(xy, t, perm_in, n, key, g.rows * g.cols, hist, start, cursor, oxy, ot, op, operm, s);
+}
+
+int launch_group_sort(const uint32_t* xy, const int32_t* t, const uint32_t* perm_in, long long n, const int32_t* gid, int K,
+                      uint32_t* hist, uint32_t* start, uint32_t* cursor, uint32_t* oxy, int32_t* ot, float2* op,
+                      uint32_t* operm, hipStream_t s) {
+    GroupKey key;
+    key.gid = gid; key.perm = perm_in; key.K = K;
+    return launch_keyed_sort(xy, t, perm_in, n, key, K + 1, hist, start, cursor, oxy, ot, op, operm, s);
 }
 
 // (256 threads per tile optimizer; 512 / 1024: measured, no gain -- experiments/rounds_1_to_3.md)
@@ -454,6 +592,48 @@ int launch_tile_optimizer_many(const TileArgs* slices, int nslices, int ntiles, 
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kTileThreads), lds, s, slices, nslices, ntiles, counter);
     return 0;
+}
+
+void launch_group_boxes(const uint32_t* xy, const uint32_t* perm, const int32_t* gid, const uint32_t* start, long long n, int K,
+                        int32_t* box, hipStream_t s) {
+    if (K < 1) return;
+    hipLaunchKernelGGL(k_group_box_init, dim3((4 * K + 255) / 256), dim3(256), 0, s, box, K);
+    long long blocks = (n + kThreads * 4 - 1) / (kThreads * 4);
+    blocks = blocks > 256 ? 256 : (blocks < 1 ? 1 : blocks);
+    hipLaunchKernelGGL(k_group_boxes, dim3((unsigned)blocks, (unsigned)((K + kBoxSlab - 1) / kBoxSlab)), dim3(kThreads), 0, s, xy,
+                       perm, gid, start, K, box);
+}
+
+void launch_group_rest(const uint32_t* perm, const uint32_t* start, int K, double2* nxny, hipStream_t s) {
+    hipLaunchKernelGGL(k_group_rest, dim3(256), dim3(kThreads), 0, s, perm, start, K, nxny);
+}
+
+template <bool WARM>
+static int launch_group_optimizer_w(const TileArgs& a, const uint32_t* order, int K, uint32_t* counter, int n_cus, hipStream_t s,
+                                    int* per_cu_out) {
+    const size_t lds = (size_t)a.max_px * (8 + 4 + 4);
+    const int hs = a.scale / 2;
+    void (*k)(TileArgs, const uint32_t*, int, uint32_t*) =
+        hs == 0 ? k_group_optimizer<kTileThreads, 0, WARM>
+                : (hs == 1 ? k_group_optimizer<kTileThreads, 1, WARM>
+                           : (hs == 2 ? k_group_optimizer<kTileThreads, 2, WARM> : k_group_optimizer<kTileThreads, -1, WARM>));
+    if (tile_kernel_lds(k) != 0) return -1;
+    // as many work-groups as the device holds at once with THIS call's LDS (more would only queue and find the counter exhausted)
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(k), kTileThreads, lds) != hipSuccess || per_cu < 1)
+        per_cu = 1;
+    if (per_cu_out) *per_cu_out = per_cu;
+    long long grid = (long long)per_cu * (n_cus > 0 ? n_cus : 256);
+    if (grid > K) grid = K;
+    if (grid < 1) grid = 1;
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kTileThreads), lds, s, a, order, K, counter);
+    return 0;
+}
+
+int launch_group_optimizer(const TileArgs& a, const uint32_t* order, int K, bool warm, uint32_t* counter, int n_cus,
+                           hipStream_t s, int* per_cu_out) {
+    return warm ? launch_group_optimizer_w<true>(a, order, K, counter, n_cus, s, per_cu_out)
+                : launch_group_optimizer_w<false>(a, order, K, counter, n_cus, s, per_cu_out);
 }
 
 }  // namespace bf

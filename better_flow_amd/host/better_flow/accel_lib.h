@@ -16,6 +16,7 @@
 #include <better_flow/clustering.h>
 #include <better_flow/flow_field.h>
 #include <better_flow/object_model.h>
+#include <better_flow/object_tasks.h>   // bf::ObjectTasks and the weak declarations of bf_set_groups / bf_run_groups
 #include <bf_accel.h>
 
 #include <stdexcept>

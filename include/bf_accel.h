@@ -376,6 +376,54 @@ int bf_run_tiles(bf_ctx *ctx, const bf_tile_opts *opts, bf_model *models_out, bf
  * read its per-event results).  Blocking; returns the first error (its text on ctxs[0]). */
 int bf_run_tiles_many(bf_ctx *const *ctxs, int32_t n, const bf_tile_opts *opts, bf_model *models_out, bf_run_info *infos_out);
 
+/* ---- event groups: the queue of (events, model) tasks over ONE uploaded slice, solved in one launch ----
+ *
+ * A grouping is a group id per event and a group count: group_id[i] in -1 .. K-1, indexed in UPLOAD order; -1: the event
+ * is in no group; K >= 0 groups.  For group g let E_g be its events in upload order.  The group's result is what the
+ * reference leaves behind after, on E_g alone and in this order,
+ *   1. OptimizerRolling::set_cloud(E_g, scale), its bounding box seeded with sensor_res_x / y as in bf_run_tiles;
+ *   2. set_time (the times are already slice-local);
+ *   3. set_model(warm_g) when a warm model is given (optimizer_rolling.h:289-299): one
+ *      warp_reinit(-total_dx, -total_dy, cx, cy, total_div, -total_rot) from the reset state; the totals carry over;
+ *   4. run() with the guards guard_res_x / y, min_events, max_iter, hard_iter_cap:
+ * the model, the bf_run_info and (nx, ny) per event.  Afterwards bf_compute_uv / bf_writeout_events read, in upload order:
+ * the group's final warp for an event of a group that ran; what set_model left -- (0, 0) cold -- for an event of a group a
+ * guard skipped (BF_SKIPPED) or whose window does not fit the LDS (BF_ERR_CAPACITY in that group's rc; the reference
+ * applies set_model before run() returns 1); (0, 0) for an event with id -1.  A group's result is a function of its event
+ * set only (integer accumulators, as in the tile path): not of K, the other groups, the numbering or the storage order.
+ *
+ *   bf_set_groups                host ids.  An id outside -1 .. K-1: BF_ERR_ARG; K + 1 beyond the sort's 16384 buckets:
+ *                                BF_ERR_CAPACITY; before an upload: BF_ERR_STATE.
+ *   bf_set_groups_from_segments  the cl_id of the held segmentation, device to device, into the context's own group plane
+ *                                (the grouping outlives the segmentation's invalidation); K = the kept components, also in
+ *                                *groups_out.  BF_ERR_STATE when no segmentation of the current window is held (the rule
+ *                                of bf_segment_get).
+ *   bf_run_groups                warm_count 0: cold (warm may be NULL); 1: every group starts from warm[0]; K: one model per
+ *                                group; anything else BF_ERR_ARG.  models_out / infos_out / groups_out: K entries each (any
+ *                                may be NULL); groups_out is what the device found per group before solving.  A noise mask
+ *                                is BF_ERR_ARG, as in bf_run_tiles.  K == 0 is BF_OK and every event reads (0, 0).  A group
+ *                                whose rows * cols * 16 bytes exceed the LDS budget (156 KiB) gets BF_ERR_CAPACITY in its
+ *                                own rc; the call still returns BF_OK and the other groups run.  The optimizers' LDS is
+ *                                sized to the largest window that runs in THIS call (bf_get_stat "groups_lds",
+ *                                "groups_per_cu").  Afterwards the context is in the state bf_run_tiles leaves it in.
+ * The grouping holds until the next upload; bf_run_groups may be called again on it, e.g. with other warm models.
+ * No membership policy is implied: which events form an object is the caller's decision. */
+typedef struct bf_group_opts {            /* 32 bytes */
+    int32_t scale;                        /* odd, scale/2 <= 4 */
+    int32_t sensor_res_x, sensor_res_y;   /* seeds of set_cloud's bounding box */
+    int32_t guard_res_x, guard_res_y;
+    int32_t min_events;
+    int32_t max_iter;                     /* <= 0: unlimited */
+    int32_t hard_iter_cap;
+} bf_group_opts;
+typedef struct bf_group_info {            /* what the device found per group before solving */
+    int32_t events, row_min, row_max, col_min, col_max, rows, cols, reserved;   /* fr bbox (set_cloud's, seeded); window R, C */
+} bf_group_info;
+int bf_set_groups(bf_ctx *ctx, const int32_t *group_id, int32_t groups);
+int bf_set_groups_from_segments(bf_ctx *ctx, int32_t *groups_out);
+int bf_run_groups(bf_ctx *ctx, const bf_group_opts *opts, const bf_model *warm, int32_t warm_count,
+                  bf_model *models_out, bf_run_info *infos_out, bf_group_info *groups_out);
+
 /* A batch of independent slices -- the reference's queue of (events, model) tasks (dvs_flow.h:200-231, executed there
  * one after the other) -- solved together: bf_run on each of the n contexts, all in flight at once (one host thread per
  * context inside the library; the contexts' streams share the GPU, set "co_schedule" on them when n > 1).  Every
