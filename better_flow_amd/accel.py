@@ -186,6 +186,16 @@ class GroupInfo(C.Structure):
                 ("col_max", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AssignOpts(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("sensor_res_x", C.c_int32), ("sensor_res_y", C.c_int32), ("margin", C.c_int32),
+                ("min_score", C.c_int32), ("use_prior", C.c_int32), ("install", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AssignInfo(C.Structure):
+    _fields_ = [("models", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("assigned", C.c_int32),
+                ("unassigned", C.c_int32), ("changed", C.c_int32), ("max_score", C.c_int32), ("reserved", C.c_int32)]
+
+
 # the numpy view of a bf_component table
 COMPONENT_DTYPE = np.dtype([(n, np.int32) for n in ("id", "first_pixel", "pixels", "events", "row_min", "row_max", "col_min",
                                                     "col_max")] + [(n, np.int64) for n in ("row_sum", "col_sum", "q_sum")])
@@ -212,7 +222,7 @@ EXPORTS = [
     "bf_global_hold_field", "bf_global_hold_best", "bf_global_get_flow", "bf_global_flow_field", "bf_global_color_flow_img",
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
-    "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups",
+    "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups", "bf_assign_groups",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -352,6 +362,8 @@ def load(path=None):
         L.bf_set_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
         L.bf_set_groups_from_segments.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.bf_run_groups.argtypes = [C.c_void_p, C.POINTER(GroupOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.bf_assign_groups.argtypes = [C.c_void_p, C.POINTER(AssignOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(AssignInfo)]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.bf_fast_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model)]
         L.bf_writeout_events.argtypes = [C.c_void_p] + [C.c_void_p] * 4
@@ -903,6 +915,22 @@ class Accel:
         ginfo = (GroupInfo * max(K, 1))()
         self._chk(self.L.bf_run_groups(self.h, C.byref(o), wm, wn, models, infos, ginfo))
         return list(models)[:K], list(infos)[:K], list(ginfo)[:K]
+
+    def assign_groups(self, models, scale, sensor_res, margin=0, min_score=1, use_prior=False, install=True):
+        """bf_assign_groups: every event to the one of the candidate `models` (a sequence of Model) under which it lands on the
+        largest pile of other events; with use_prior the held grouping restricts who votes where; with install the result
+        becomes the held grouping (len(models) groups) for run_groups.  Returns (gid int32[n], score int32[n],
+        counts int32[K + 1] (last: unassigned), AssignInfo), per-event arrays in upload order."""
+        K = len(models)
+        o = AssignOpts(scale, sensor_res[0], sensor_res[1], margin, min_score, 1 if use_prior else 0, 1 if install else 0, 0)
+        ms = (Model * max(K, 1))(*models)
+        n = int(self.n)
+        gid = np.zeros(n, dtype=np.int32)
+        score = np.zeros(n, dtype=np.int32)
+        counts = np.zeros(K + 1, dtype=np.int32)
+        info = AssignInfo()
+        self._chk(self.L.bf_assign_groups(self.h, C.byref(o), ms, K, _ptr(gid), _ptr(score), _ptr(counts), C.byref(info)))
+        return gid, score, counts, info
 
     def get_trace(self, cap):
         buf = (TraceRec * max(cap, 1))()

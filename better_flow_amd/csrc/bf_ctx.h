@@ -1,5 +1,5 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
@@ -26,6 +26,7 @@
 #include <thread>
 #include <vector>
 
+#include "bf_assign.h"
 #include "bf_device.h"
 #include "bf_kernels.h"
 #include "bf_mem.h"
@@ -136,6 +137,13 @@ struct bf_ctx {
     int groups_K = 0;
     bool groups_valid = false;       // a grouping of the uploaded slice is held (every upload clears it)
     int groups_lds = 0, groups_per_cu = 0;   // what the last bf_run_groups launched: dynamic LDS bytes, work-groups per CU (bf_get_stat)
+    // assignment (bf_assign_groups): the K vote planes and their box sums (K x R x C words each), the K warps, the ids and scores
+    // in upload order, the result block (counts, changed, max_score); grown on first use
+    DevArray<uint32_t> d_assign_votes, d_assign_box, d_assign_out;
+    DevArray<WarpParams> d_assign_wp;
+    HostArray<WarpParams> h_assign_wp;
+    DevArray<int32_t> d_assign_gid, d_assign_score;
+    HostArray<uint32_t> h_assign_out;
     // One staging slot of the asynchronous uploads (bf_upload.cpp).  Its state:
     //   FREE      not taken;
     //   RECORDED  taken, `src` describes what to copy, no HIP call issued yet ("defer_uploads");
@@ -436,6 +444,25 @@ WarpParams identity_warp() {
     w.dnx = w.dny = w.cx = w.cy = w.div = 0.0;
     w.c = 1.0;
     w.s = 0.0;
+    return w;
+}
+
+// OptimizerRolling::set_cloud's window (optimizer_rolling.h:263-282) of a bounding box in sensor pixels: the ONE place this
+// arithmetic lives on the host (bf_set_cloud on the events' seeded box, bf_assign_groups on the widened sensor box).
+bf_window window_of_box(int scale, int x_min, int x_max, int y_min, int y_max) {
+    bf_window w;
+    memset(&w, 0, sizeof(w));
+    w.scale = scale;
+    w.x_min = x_min; w.y_min = y_min; w.x_max = x_max; w.y_max = y_max;
+    w.metric_wsizex = scale * (w.x_max - w.x_min);   // :263
+    w.metric_wsizey = scale * (w.y_max - w.y_min);   // :264
+    w.scale_img_x = w.metric_wsizex + scale;         // :276
+    w.scale_img_y = w.metric_wsizey + scale;         // :277
+    // :279-282, both "/ 2" are integer divisions
+    w.x_shift = -double((w.x_max - w.x_min) / 2 + w.x_min) * double(scale) +
+                double(w.metric_wsizex) / 2.0 + scale / 2;
+    w.y_shift = -double((w.y_max - w.y_min) / 2 + w.y_min) * double(scale) +
+                double(w.metric_wsizey) / 2.0 + scale / 2;
     return w;
 }
 

@@ -14,30 +14,19 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
     if (rc != BF_OK) return rc;
     const SliceStats s = c->stats;
     c->seg_valid = false;
-    bf_window w;
-    memset(&w, 0, sizeof(w));
-    w.scale = scale;
     // optimizer_rolling.h:252-260: min seeded with RES, max with 0
-    w.x_min = res_x; w.y_min = res_y; w.x_max = 0; w.y_max = 0;
+    int x_min = res_x, y_min = res_y, x_max = 0, y_max = 0;
     if (c->n > 0) {
         if (s.tmin == INT_MIN)
             return fail(c, BF_ERR_ARG, "a slice-local event time does not fit 32 bits (slice longer than 2.1 s?)");
         if (s.xmin < 0 || s.ymin < 0 || s.xmax > 65535 || s.ymax > 65535)
             return fail(c, BF_ERR_ARG, "event coordinates outside [0, 65535]");
-        if (s.xmax > w.x_max) w.x_max = s.xmax;
-        if (s.ymax > w.y_max) w.y_max = s.ymax;
-        if (s.xmin < w.x_min) w.x_min = s.xmin;
-        if (s.ymin < w.y_min) w.y_min = s.ymin;
+        if (s.xmax > x_max) x_max = s.xmax;
+        if (s.ymax > y_max) y_max = s.ymax;
+        if (s.xmin < x_min) x_min = s.xmin;
+        if (s.ymin < y_min) y_min = s.ymin;
     }
-    w.metric_wsizex = scale * (w.x_max - w.x_min);   // :263
-    w.metric_wsizey = scale * (w.y_max - w.y_min);   // :264
-    w.scale_img_x = w.metric_wsizex + scale;         // :276
-    w.scale_img_y = w.metric_wsizey + scale;         // :277
-    // :279-282, both "/ 2" are integer divisions
-    w.x_shift = -double((w.x_max - w.x_min) / 2 + w.x_min) * double(scale) +
-                double(w.metric_wsizex) / 2.0 + scale / 2;
-    w.y_shift = -double((w.y_max - w.y_min) / 2 + w.y_min) * double(scale) +
-                double(w.metric_wsizey) / 2.0 + scale / 2;
+    const bf_window w = window_of_box(scale, x_min, x_max, y_min, y_max);
     if (w.scale_img_x <= 0 || w.scale_img_y <= 0) {
         // e.g. an empty slice: x_min = RES_X > x_max = 0.  The reference carries on and run()
         // returns 1 at the window guard (:49-55); no image operator is usable on it.

@@ -17,6 +17,7 @@
 #include <better_flow/flow_field.h>
 #include <better_flow/object_model.h>
 #include <better_flow/object_tasks.h>   // bf::ObjectTasks and the weak declarations of bf_set_groups / bf_run_groups
+#include <better_flow/motion_assign.h>  // bf::MotionAssigner and the weak declaration of bf_assign_groups
 #include <bf_accel.h>
 
 #include <stdexcept>

@@ -1,0 +1,248 @@
+// motion_assign.h -- bf::MotionAssigner: the assignment step of motion segmentation by motion compensation (every event to the
+// one of K candidate models under which it lands on the largest pile of other events; include/bf_accel.h, "event groups:
+// assignment") and its alternation with the grouped solve of bf::ObjectTasks -- the membership policy DESIGN section 14 left
+// open: assign, refit every group from its current model, assign again, until no id changes.
+//
+// assign() has two paths with the same ids, scores, counts and info (integers throughout, so equal, not close):
+//   device  bf_assign_groups: three kernels on the uploaded slice;
+//   host    against a C-ABI without that entry (the CPU stand-in the tests build): per model bf_set_cloud + bf_set_model +
+//           bf_writeout_events give the events' positions under the model's warp; the pixels in the assignment's own window,
+//           the votes, the box sums and the pick are done here.
+// The prior of a round with use_prior is the grouping of the round before it (install), or set_prior()'s.
+#ifndef BF_HOST_MOTION_ASSIGN_H
+#define BF_HOST_MOTION_ASSIGN_H
+
+#include <better_flow/object_tasks.h>
+#include <bf_accel.h>
+
+#include <algorithm>
+#include <climits>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+// (weak: the host classes also link against C-ABI implementations that lack it, as in clustering.h and object_tasks.h)
+extern "C" {
+int bf_assign_groups(bf_ctx *ctx, const bf_assign_opts *opts, const bf_model *models, int32_t n_models, int32_t *group_id_out,
+                     int32_t *score_out, int32_t *counts_out, bf_assign_info *info) __attribute__((weak));
+}
+
+namespace bf {
+
+class MotionAssigner {
+  public:
+    struct Slice {                        // borrowed for the duration of a call
+        const int32_t *fr_x, *fr_y, *t_ns;
+        size_t n;
+    };
+    struct Record {                       // one alternation
+        int32_t changed;                  // ids the first assignment of the alternation changed
+        std::vector<int32_t> counts;      // K + 1 of its last assignment (last: unassigned)
+        std::vector<int32_t> iterations;  // per group of the refit; empty: the alternation ended without one
+    };
+
+    bf_group_opts fit;                    // the refit's scale, seeds, guards and caps (bf::ObjectTasks)
+    // what assign() leaves (upload order) ...
+    std::vector<int32_t> gid, score, counts;
+    bf_assign_info info;
+    // ... and alternate(): the models, gid above, and one record per alternation
+    std::vector<bf_model> models;
+    std::vector<Record> records;
+
+    MotionAssigner() : info() { fit = ObjectTasks().opts; }
+
+    static bool device_available() { return bf_assign_groups != nullptr; }
+
+    // Uploads the slice; the held grouping is forgotten, as in the C-ABI.
+    int upload(bf_ctx *ctx, const Slice &s) {
+        n_ = s.n;
+        prior_.clear();
+        have_prior_ = false;
+        return bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
+    }
+
+    // The grouping a round with use_prior starts from (ids -1 .. groups - 1 in upload order), as bf_set_groups.
+    int set_prior(bf_ctx *ctx, const std::vector<int32_t> &ids, int32_t groups, bool force_host = false) {
+        if (ids.size() != n_) return BF_ERR_ARG;
+        prior_ = ids;
+        prior_K_ = groups;
+        have_prior_ = true;
+        if (device_available() && !force_host && bf_set_groups) return bf_set_groups(ctx, ids.data(), groups);
+        return BF_OK;
+    }
+
+    // One assignment of the uploaded slice (upload()); fills gid, score, counts, info.
+    int assign(bf_ctx *ctx, const std::vector<bf_model> &cand, const bf_assign_opts &o, bool force_host = false) {
+        const size_t K = cand.size();
+        gid.assign(n_, 0);
+        score.assign(n_, 0);
+        counts.assign(K + 1, 0);
+        std::memset(&info, 0, sizeof(info));
+        int rc;
+        if (device_available() && !force_host)
+            rc = bf_assign_groups(ctx, &o, cand.data(), (int32_t)K, gid.data(), score.data(), counts.data(), &info);
+        else
+            rc = assign_host(ctx, cand, o);
+        if (rc >= 0 && o.install) {
+            prior_ = gid;
+            prior_K_ = (int32_t)K;
+            have_prior_ = true;
+        }
+        return rc;
+    }
+
+    // Alternates assignment and refit on the slice, starting from `start`: per alternation rounds_per_fit assignments (the very
+    // first without a prior, every other with the one before it), then a refit of every group through bf::ObjectTasks, warm from
+    // its current model.  It ends when the first assignment after a refit changes no id -- the models are then the fit of exactly
+    // this membership -- or after max_alternations.  A group whose window exceeds the device path's LDS (BF_ERR_CAPACITY in its
+    // info) is refit through ObjectTasks' one-after-the-other path on `helper` (a second context with room for the slice; null:
+    // it keeps its model); a group a guard skipped keeps its model.  o.use_prior and o.install are set here.
+    int alternate(bf_ctx *ctx, const Slice &s, const std::vector<bf_model> &start, bf_assign_opts o, int rounds_per_fit,
+                  int max_alternations, bf_ctx *helper = nullptr, bool force_host = false) {
+        models = start;
+        records.clear();
+        const size_t K = models.size();
+        std::vector<int32_t> prior;
+        bool have = false;
+        o.install = 1;
+        for (int a = 0; a < max_alternations; ++a) {
+            int rc = upload(ctx, s);   // (a refit leaves a subset, or the slice sorted, behind)
+            if (rc >= 0 && have) rc = set_prior(ctx, prior, (int32_t)K, force_host);
+            if (rc < 0) return rc;
+            Record rec;
+            rec.changed = 0;
+            for (int r = 0; r < rounds_per_fit; ++r) {
+                o.use_prior = have ? 1 : 0;
+                rc = assign(ctx, models, o, force_host);
+                if (rc < 0) return rc;
+                if (r == 0) rec.changed = info.changed;
+                prior = gid;
+                have = true;
+            }
+            rec.counts = counts;
+            if (a > 0 && rec.changed == 0) {
+                records.push_back(rec);
+                break;
+            }
+            std::vector<std::vector<int32_t>> ids(K);
+            for (size_t i = 0; i < s.n; ++i)
+                if (gid[i] >= 0) ids[(size_t)gid[i]].push_back((int32_t)i);
+            ObjectTasks q;
+            q.opts = fit;
+            for (size_t k = 0; k < K; ++k) q.push(ids[k], &models[k]);
+            rc = q.run(ctx, s.fr_x, s.fr_y, s.t_ns, s.n, force_host);
+            if (rc < 0) return rc;
+            rec.iterations.assign(K, 0);
+            std::vector<size_t> large;
+            for (size_t k = 0; k < K; ++k) {
+                rec.iterations[k] = q.infos[k].iterations;
+                if (q.infos[k].rc == BF_OK) models[k] = q.models[k];
+                else if (q.infos[k].rc == BF_ERR_CAPACITY && helper) large.push_back(k);
+            }
+            if (!large.empty()) {
+                ObjectTasks one;
+                one.opts = fit;
+                for (size_t k : large) one.push(ids[k], &models[k]);
+                rc = one.run(helper, s.fr_x, s.fr_y, s.t_ns, s.n, true);
+                if (rc < 0) return rc;
+                for (size_t j = 0; j < large.size(); ++j) {
+                    rec.iterations[large[j]] = one.infos[j].iterations;
+                    if (one.infos[j].rc == BF_OK) models[large[j]] = one.models[j];
+                }
+            }
+            records.push_back(rec);
+        }
+        return BF_OK;
+    }
+
+  private:
+    // `int x = <double>` as the reference's x86-64 build does it (accel_lib.h:154-155): NaN and anything outside the int range
+    // give INT_MIN, which the window test rejects
+    static int trunc_x86(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int)v : INT_MIN; }
+
+    int assign_host(bf_ctx *ctx, const std::vector<bf_model> &cand, const bf_assign_opts &o) {
+        const int K = (int)cand.size();
+        if (o.scale < 1 || o.scale % 2 == 0 || o.scale / 2 > 4 || o.sensor_res_x < 1 || o.sensor_res_y < 1 || o.sensor_res_x > 65536 ||
+            o.sensor_res_y > 65536 || o.margin < 0 || o.margin > 65536 || o.min_score < 1 || K < 1 || K > 64)
+            return BF_ERR_ARG;
+        if (o.use_prior && !have_prior_) return BF_ERR_STATE;
+        if (o.use_prior && prior_K_ != K) return BF_ERR_ARG;
+        // the window of the sensor widened by the margin: optimizer_rolling.h:248-283
+        const int s = o.scale, hs = s / 2;
+        const int x_min = -o.margin, x_max = o.sensor_res_x - 1 + o.margin, y_min = -o.margin, y_max = o.sensor_res_y - 1 + o.margin;
+        const int wsx = s * (x_max - x_min), wsy = s * (y_max - y_min);   // :263-264
+        const int R = wsx + s, C = wsy + s;                               // :276-277
+        const double x_shift = -double((x_max - x_min) / 2 + x_min) * double(s) + double(wsx) / 2.0 + s / 2;   // :279-282
+        const double y_shift = -double((y_max - y_min) / 2 + y_min) * double(s) + double(wsy) / 2.0 + s / 2;
+        const int x_sh = (int)x_shift, y_sh = (int)y_shift;               // the parameter conversion of accel_lib.h:147
+        if ((long long)K * R * C > (1ll << 27)) return BF_ERR_CAPACITY;
+        const size_t n = n_, P = (size_t)R * (size_t)C;
+        if (n == 0) return BF_OK;
+        std::vector<int32_t> best(n, 0), arg(n, 0), pix(n);
+        std::vector<uint32_t> V(P), B(P), row(P);
+        std::vector<double> px(n), py(n);
+        for (int k = 0; k < K; ++k) {
+            // Event::reset, then set_model's warp_reinit (optimizer_rolling.h:289-299)
+            int rc = bf_set_cloud(ctx, s, o.sensor_res_x, o.sensor_res_y, nullptr);
+            if (rc >= 0) rc = bf_set_model(ctx, &cand[(size_t)k]);
+            if (rc >= 0) rc = bf_writeout_events(ctx, px.data(), py.data(), nullptr, nullptr);
+            if (rc < 0) return rc;
+            std::fill(V.begin(), V.end(), 0u);
+            for (size_t i = 0; i < n; ++i) {
+                const int X = trunc_x86(px[i] * s + x_sh), Y = trunc_x86(py[i] * s + y_sh);   // accel_lib.h:154-155
+                pix[i] = ((X >= wsx + hs) || (X < hs) || (Y >= wsy + hs) || (Y < hs)) ? -1 : X * C + Y;   // :157
+                if (pix[i] >= 0 && votes(o, i, k)) ++V[(size_t)pix[i]];
+            }
+            const std::vector<uint32_t> *S = &V;
+            if (s > 1) {   // the s x s box sum (the splat of accel_lib.h:160-165, gathered): rows, then columns
+                for (int r = 0; r < R; ++r)
+                    for (int c = 0; c < C; ++c) {
+                        uint32_t sum = 0;
+                        for (int d = -hs; d <= hs; ++d)
+                            if (c + d >= 0 && c + d < C) sum += V[(size_t)r * C + (size_t)(c + d)];
+                        row[(size_t)r * C + c] = sum;
+                    }
+                for (int r = 0; r < R; ++r)
+                    for (int c = 0; c < C; ++c) {
+                        uint32_t sum = 0;
+                        for (int d = -hs; d <= hs; ++d)
+                            if (r + d >= 0 && r + d < R) sum += row[(size_t)(r + d) * C + c];
+                        B[(size_t)r * C + c] = sum;
+                    }
+                S = &B;
+            }
+            for (size_t i = 0; i < n; ++i) {
+                if (pix[i] < 0) continue;
+                const int32_t sc = (int32_t)(*S)[(size_t)pix[i]] - (votes(o, i, k) ? 1 : 0);   // leave-one-out
+                if (sc > best[i]) { best[i] = sc; arg[i] = k; }   // (strictly larger: ties stay with the smaller k)
+            }
+        }
+        int32_t top = 0, changed = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const int32_t g = best[i] >= o.min_score ? arg[i] : -1;
+            gid[i] = g;
+            score[i] = best[i];
+            ++counts[(size_t)(g < 0 ? K : g)];
+            changed += g != (o.use_prior ? prior_[i] : -1);
+            if (best[i] > top) top = best[i];
+        }
+        info.models = K;
+        info.rows = R; info.cols = C;
+        info.unassigned = counts[(size_t)K];
+        info.assigned = (int32_t)n - counts[(size_t)K];
+        info.changed = changed;
+        info.max_score = top;
+        return BF_OK;
+    }
+
+    bool votes(const bf_assign_opts &o, size_t i, int k) const { return !o.use_prior || prior_[i] == k || prior_[i] == -1; }
+
+    size_t n_ = 0;
+    std::vector<int32_t> prior_;
+    int32_t prior_K_ = 0;
+    bool have_prior_ = false;
+};
+
+}  // namespace bf
+
+#endif  // BF_HOST_MOTION_ASSIGN_H

@@ -424,6 +424,57 @@ int bf_set_groups_from_segments(bf_ctx *ctx, int32_t *groups_out);
 int bf_run_groups(bf_ctx *ctx, const bf_group_opts *opts, const bf_model *warm, int32_t warm_count,
                   bf_model *models_out, bf_run_info *infos_out, bf_group_info *groups_out);
 
+/* ---- event groups: assignment -- every event to the one of K competing models that explains it best ----
+ *
+ * The assignment step of motion segmentation by motion compensation (Mitrokhin et al. 2018, Stoffregen et al. 2019): given
+ * K candidate models, an event goes to the model under which it lands on the largest pile of OTHER events.  It produces the
+ * membership bf_run_groups solves; alternating the two grows a seed to an object's whole event set.
+ * Everything after an event's pixel is an integer count, a maximum or a smallest index: the result does not depend on the
+ * order events are stored or work-groups run in.
+ *
+ *   window    OptimizerRolling::set_cloud's window (optimizer_rolling.h:248-283) for a bounding box that is the whole sensor
+ *             widened by `margin`: x_min = -margin, x_max = sensor_res_x - 1 + margin, columns likewise.  It does not depend
+ *             on the events.  With s = scale: wsx = s (x_max - x_min) (:263), R = wsx + s (:276), x_shift by :279-280, and
+ *             the integer x_sh = (int)x_shift (the parameter conversion of accel_lib.h:147); wsy, C, y_sh likewise.
+ *   pixel_k(i)  from the reset state (Event::reset: pr = fr) ONE warp_reinit(-total_dx, -total_dy, cx, cy, total_div,
+ *             -total_rot) of models[k] (set_model's warp, optimizer_rolling.h:289-299; cx, cy in sensor coordinates; sine
+ *             and cosine from the host's libm, as in bf_set_model); per event project_4param_reinit + apply_project
+ *             (event.h:99-110,164-168); then X = trunc(pr_x s + x_sh), Y = trunc(pr_y s + y_sh) (accel_lib.h:154-155).
+ *             The event is OUTSIDE under k when X >= wsx + s/2 || X < s/2 || Y >= wsy + s/2 || Y < s/2 (accel_lib.h:157).
+ *   votes     event i votes under k when it is inside under k and use_prior == 0, or its prior id is k, or its prior id is
+ *             -1.  V_k[X, Y] = the number of votes; B_k = the s x s box sum of V_k (the count image of the splat,
+ *             accel_lib.h:160-165, gathered).  The prior is the grouping the context holds (bf_set_groups, or an earlier call with install).
+ *   score     S_k(i) = B_k[pixel_k(i)] - (1 if i voted under k else 0): leave-one-out; 0 when i is outside under k.
+ *   result    best = max_k S_k(i); group_id_out[i] = the smallest k with S_k(i) == best, or -1 when best < min_score;
+ *             score_out[i] = best; counts_out[k] = events given k, counts_out[K] = events given -1.  info: models = K,
+ *             rows = R, cols = C, assigned, unassigned, changed = events whose id differs from the prior (use_prior == 0:
+ *             from -1), max_score = the largest best.  All per-event outputs are in UPLOAD order; any output may be NULL.
+ *   state     reads the events' addresses and times only; products, (nx, ny), the time image, a held segmentation, a held
+ *             flow and the read-back validity are untouched, and the bytes are the same whether the events are stored in
+ *             upload order or sorted (after bf_run_tiles / bf_run_groups).  install == 1: the result becomes the context's
+ *             grouping, K groups, as after bf_set_groups (it holds until the next upload); install == 0: the held grouping
+ *             is unchanged.
+ *   errors    BF_ERR_STATE before an upload, or use_prior without a held grouping; BF_ERR_ARG for an even or too large
+ *             scale, a sensor side < 1 or > 65536, a margin < 0 or > 65536, min_score < 1, n_models < 1 or > 64, a NULL
+ *             opts or models, a prior whose group count differs from n_models, a noise mask (as bf_run_groups);
+ *             BF_ERR_CAPACITY when K R C > 2^27.  Zero events: BF_OK, every output zero (info too).
+ * Blocking.  Where candidate models come from is the caller's decision. */
+typedef struct bf_assign_opts {        /* 32 bytes */
+    int32_t scale;                     /* odd, scale/2 <= 4 */
+    int32_t sensor_res_x, sensor_res_y;
+    int32_t margin;                    /* >= 0 sensor pixels added on every side of the sensor box */
+    int32_t min_score;                 /* >= 1 */
+    int32_t use_prior;                 /* 0: every event votes under every model; 1: the held grouping is the prior */
+    int32_t install;                   /* 1: the result becomes the context's grouping (K groups) for bf_run_groups */
+    int32_t reserved;
+} bf_assign_opts;
+typedef struct bf_assign_info {        /* 32 bytes */
+    int32_t models, rows, cols, assigned, unassigned, changed, max_score, reserved;
+} bf_assign_info;
+int bf_assign_groups(bf_ctx *ctx, const bf_assign_opts *opts, const bf_model *models, int32_t n_models,
+                     int32_t *group_id_out, int32_t *score_out, int32_t *counts_out /* K + 1, last = unassigned */,
+                     bf_assign_info *info);
+
 /* A batch of independent slices -- the reference's queue of (events, model) tasks (dvs_flow.h:200-231, executed there
  * one after the other) -- solved together: bf_run on each of the n contexts, all in flight at once (one host thread per
  * context inside the library; the contexts' streams share the GPU, set "co_schedule" on them when n > 1).  Every
