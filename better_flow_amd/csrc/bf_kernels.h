@@ -82,6 +82,9 @@ struct StencilArgs {
     const unsigned long long* m_cur;   // interior + margin format (compact == 3): the margin plane of buffer `cur`
     BinGrid g;
     int cur;
+    // SRC 3: which tile a work-group takes -- 0: launch order (row-major), 1: one band of tile rows per residue class mod 8 of the
+    // launch id (bf_rules::tile_of_block).  Any value gives the same bits; bf_run picks by what was measured (enqueue_iteration).
+    int tile_bands;
 };
 
 // Profiling hook: when armed (by ProfScope, bf_ctx.h), the next launch of a loop kernel goes through

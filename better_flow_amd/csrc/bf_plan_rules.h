@@ -113,6 +113,22 @@ inline long long stencil_tiles(int R, int C) {
 }
 // the build with the scalar registers capped: a launch with more work-groups than the CUs hold at once
 inline bool stencil_capped(long long tiles, int n_cus) { return n_cus > 0 && tiles >= 8ll * n_cus; }
+// Which tile a work-group of the stencil launch takes: work-groups b, b + 8, b + 16, ... (one residue class mod kTileClasses --
+// what has been observed to share an L2, never relied on for a result) take ONE contiguous run of row-major tile indices, i.e. a
+// band of tile rows, so that the halo rows and columns two neighbouring tiles both read are fetched by work-groups of one class.
+// A bijection on [0, ntiles) for every ntiles >= 1: class x holds per + (x < rem) tiles and starts at x per + min(x, rem).
+// BF_RULES_HD: the stencil kernel calls it too (uniform: scalar unit; the division by 8 is a shift).
+#if defined(__HIPCC__)
+#define BF_RULES_HD __host__ __device__
+#else
+#define BF_RULES_HD
+#endif
+constexpr int kTileClasses = 8;
+BF_RULES_HD inline int tile_of_block(int b, int ntiles) {
+    const unsigned x = (unsigned)b % kTileClasses, j = (unsigned)b / kTileClasses;   // (0 <= b < ntiles: shifts and masks)
+    const unsigned per = (unsigned)ntiles / kTileClasses, rem = (unsigned)ntiles % kTileClasses;
+    return (int)(x * per + (x < rem ? x : rem) + j);
+}
 inline int stencil_half_scale(int scale) { return scale / 2 < 4 ? scale / 2 : 4; }   // HS
 inline int stencil_mode(int fmt) { return fmt == 3 ? 2 : (fmt ? 1 : 0); }            // MODE: 0 dense slabs, 1 lists, 2 own pixels + margin plane
 

@@ -260,6 +260,14 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
             a.zero_full = j == 0 ? 1 : 0;   // (what an earlier operator left in the other buffer is not in the bitmap)
             a.st = L.state_of(j + 1);
             a.ovf_cur = L.ovf_of(j); a.ovf_prev = L.ovf_of(j - 1); a.ovf_next = L.ovf_of(j + 1);
+            // Which work-group takes which tile (same bits either way).  Bands of tile rows per residue class mod 8 of the launch
+            // id -- neighbouring tiles' shared halo then meets in one L2 -- for the slab formats of contexts that share the GPU:
+            // config 2 with four contexts in flight 206.3 -> 212.3 Mevents/s, the stencil kernel 15.7 -> 15.1 us and the lean
+            // scatter kernel 14.3 -> 14.1 us per launch.  Launch order where the bands LOST (experiments/tile_order.md): a context
+            // alone on the GPU (the scatter launch that FOLLOWS a banded stencil launch is 1.5 - 1.7 us slower there, 8.3 -> 9.8
+            // and 9.3 -> 11.0 us, against 0.4 - 0.7 us gained in the stencil kernel) and event lists (config 5, 16 slices: 3.63 ->
+            // 3.57 Mevents/s).
+            a.tile_bands = (!p.head_update && c->fmt != 2) ? 1 : 0;
         }
         if (p.head_like()) {   // accumulate only: the update runs at the head of the next warp+scatter launch (or in its own kernel)
             a.acc = L.acc_of(j); a.acc_zero = L.acc_of(j + 1);

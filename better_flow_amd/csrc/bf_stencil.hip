@@ -13,6 +13,7 @@
 namespace bf {
 
 constexpr int kStencilSgprs = 74;
+constexpr int kTileBandsBit = 0x100;   // of K3Pre::lg (log2 of the bin width, <= 6): StencilArgs::tile_bands -- the 14 preloaded dwords are taken
 
 // 64-bit load at (uniform base) + (uniform byte offset) + (per-thread byte offset): a BUFFER load -- base in a resource
 // descriptor (four scalar registers), the row part of the offset in a scalar register, the column part in one vector register
@@ -75,9 +76,25 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
     // the argument block; parked in LDS before the first barrier)
     const double rcp_v = tid < kRcpTab ? c_rcp.v[tid] : 0.0;
     const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r0 = blockIdx.y * TR, c0 = blockIdx.x * TC;
-    BinGrid g = a.g;   // (the fields the slab addresses use come from the preloaded arguments)
-    g.D = pre.D; g.lg = pre.lg; g.nbc = pre.nbc; g.nbr = pre.nbr; g.LR = pre.LR; g.L = pre.L; g.TSR = pre.TSR; g.mul_r = pre.mul_r;
+    // Which tile.  A 2-D launch of gx x gy work-groups takes them in launch order (row-major), as ever.  A 1-D launch of gx gy
+    // work-groups -- bit 8 of the preloaded `lg`: the launcher's a.tile_bands -- gives work-groups b, b + 8, ... consecutive
+    // row-major tiles (a band of tile rows, bf_rules::tile_of_block): the halo rows and columns that neighbouring tiles both
+    // read are then requested by work-groups that have been observed to share an L2 (MI355X_MICROARCH.md: round-robin over the
+    // 8 XCDs), instead of once per XCD across the fabric.  A permutation of who does which tile and nothing else -- no result
+    // depends on the order or on the placement.  From the preloaded R and C, all uniform (scalar unit, ~35 instructions with
+    // the division: only the banded launch pays them); the accumulator group and the ticket keep the launch id (the tail).
+    // (the event-list form is never launched banded -- it lost there, bf_run.cpp -- and does not carry the branch)
+    int r0, c0;
+    if (MODE != 1 && (pre.lg & kTileBandsBit)) {
+        const uint32_t gx = (uint32_t)(C + TC - 1) / (uint32_t)TC, gy = (uint32_t)(R + TR - 1) / (uint32_t)TR;
+        const uint32_t tile = (uint32_t)bf_rules::tile_of_block((int)blockIdx.x, (int)(gx * gy));
+        const uint32_t trow = tile / gx;
+        r0 = (int)trow * TR; c0 = (int)(tile - trow * gx) * TC;
+    } else {
+        r0 = blockIdx.y * TR; c0 = blockIdx.x * TC;
+    }
+    BinGrid g = a.g;  // (the fields the slab addresses use come from the preloaded arguments)
+    g.D = pre.D; g.lg = pre.lg & (kTileBandsBit - 1); g.nbc = pre.nbc; g.nbr = pre.nbr; g.LR = pre.LR; g.L = pre.L; g.TSR = pre.TSR; g.mul_r = pre.mul_r;
     const int bt = hs.bin_tbits;
     const unsigned long long bm = (1ull << bt) - 1ull;
     // (static indices only: a runtime index would push the HotState copy into scratch memory)
@@ -486,9 +503,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_num_sgpr(kStencilSgprs)))
 }
 
 
-void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n_cus) {
-    const bool full = bf_rules::stencil_capped((long long)grid.x * grid.y, n_cus);   // more work-groups than the CUs hold at once
-#define BF_K3_PRE a.slabs, a.st, a.R, a.C, a.g.D, a.g.lg, a.g.nbc, a.g.nbr, a.g.LR, a.g.L, a.g.TSR, a.g.mul_r
+void launch_stencil_binned(const StencilArgs& a, dim3 tiles, hipStream_t s, int n_cus) {
+    const bool full = bf_rules::stencil_capped((long long)tiles.x * tiles.y, n_cus);   // more work-groups than the CUs hold at once
+    // one work-group per tile: in launch order a gx x gy grid; banded a 1-D launch whose ids the kernel maps to the tiles of the
+    // (R, C) it is given (bf_rules::tile_of_block), so that grid must be exactly stencil_grid's tile count
+    const bool bands = a.tile_bands && bf_rules::stencil_mode(a.compact) != 1;   // (event lists: launch order only, as compiled)
+    const dim3 grid = bands ? dim3(tiles.x * tiles.y) : tiles;
+#define BF_K3_PRE a.slabs, a.st, a.R, a.C, a.g.D, a.g.lg | (bands ? kTileBandsBit : 0), a.g.nbc, a.g.nbr, a.g.LR, a.g.L, a.g.TSR, a.g.mul_r
 #define BF_K3(HS_)                                                                                                  \
     if (full) {                                                                                                     \
         if (a.compact == 3) launch_timed(k_stencil_binned_full<HS_, 2, kThreads>, grid, dim3(kThreads), 0, s, BF_K3_PRE, a);   \
