@@ -196,6 +196,21 @@ class AssignInfo(C.Structure):
                 ("unassigned", C.c_int32), ("changed", C.c_int32), ("max_score", C.c_int32), ("reserved", C.c_int32)]
 
 
+class AccelProposeOpts(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("suppress", C.c_int32), ("max_models", C.c_int32), ("min_votes", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class Proposal(C.Structure):
+    _fields_ = [("nx", C.c_double), ("ny", C.c_double), ("u", C.c_double), ("v", C.c_double), ("index", C.c_int64),
+                ("votes", C.c_int32), ("peak", C.c_int32)]
+
+
+class ProposeInfo(C.Structure):
+    _fields_ = [("n_x", C.c_int64), ("n_y", C.c_int64), ("voted", C.c_int32), ("unscored", C.c_int32),
+                ("off_lattice", C.c_int32), ("proposals", C.c_int32)]
+
+
 # the numpy view of a bf_component table
 COMPONENT_DTYPE = np.dtype([(n, np.int32) for n in ("id", "first_pixel", "pixels", "events", "row_min", "row_max", "col_min",
                                                     "col_max")] + [(n, np.int64) for n in ("row_sum", "col_sum", "q_sum")])
@@ -223,6 +238,7 @@ EXPORTS = [
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
     "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups", "bf_assign_groups",
+    "bf_propose_models",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -364,6 +380,8 @@ def load(path=None):
         L.bf_run_groups.argtypes = [C.c_void_p, C.POINTER(GroupOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bf_assign_groups.argtypes = [C.c_void_p, C.POINTER(AssignOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(AssignInfo)]
+        L.bf_propose_models.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(AccelProposeOpts), C.c_void_p, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ProposeInfo)]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.bf_fast_model.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(Model)]
         L.bf_writeout_events.argtypes = [C.c_void_p] + [C.c_void_p] * 4
@@ -931,6 +949,29 @@ class Accel:
         info = AssignInfo()
         self._chk(self.L.bf_assign_groups(self.h, C.byref(o), ms, K, _ptr(gid), _ptr(score), _ptr(counts), C.byref(info)))
         return gid, score, counts, info
+
+    def propose_models(self, opts=None, radius=1, suppress=2, max_models=8, min_votes=1, want_planes=False):
+        """bf_propose_models: the modes of the per-event best flow global_search left over the lattice `opts` (a
+        GlobalSearchOpts; None: the defaults) as candidate models for assign_groups.  Returns (models, proposals, ProposeInfo)
+        -- lists of Model and Proposal in pick order -- and, with want_planes, the vote plane H and its box sums B as uint32
+        [n_x, n_y]."""
+        o = opts if opts is not None else self.global_search_opts()
+        po = AccelProposeOpts(radius, suppress, max_models, min_votes)
+        cap = max(int(max_models), 1)
+        models = (Model * cap)()
+        props = (Proposal * cap)()
+        info = ProposeInfo()
+        H = B = None
+        if want_planes:
+            bins = len(_sweep(o.x_low, o.x_hi, o.x_step)) * len(_sweep(o.y_low, o.y_hi, o.y_step))
+            H = np.zeros(bins, dtype=np.uint32)
+            B = np.zeros(bins, dtype=np.uint32)
+        self._chk(self.L.bf_propose_models(self.h, C.byref(o), C.byref(po), models, props, cap, _ptr(H), _ptr(B),
+                                           0 if H is None else len(H), C.byref(info)))
+        out = (list(models)[:info.proposals], list(props)[:info.proposals], info)
+        if want_planes:
+            out += (H[:info.n_x * info.n_y].reshape(info.n_x, info.n_y), B[:info.n_x * info.n_y].reshape(info.n_x, info.n_y))
+        return out
 
     def get_trace(self, cap):
         buf = (TraceRec * max(cap, 1))()

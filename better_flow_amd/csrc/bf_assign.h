@@ -1,6 +1,7 @@
-// bf_assign.h -- launchers of the assignment kernels (bf_assign.hip) for bf_assign_abi.cpp.  The definitions they implement are in
-// include/bf_accel.h ("event groups: assignment").  Every launcher enqueues plain launches on the given stream; no kernel waits
-// for another work-group.
+// bf_assign.h -- launchers of the assignment kernels (bf_assign.hip) for bf_assign_abi.cpp, and of the kernels that propose its
+// candidate models (bf_propose.hip) for bf_propose_abi.cpp.  The definitions they implement are in include/bf_accel.h ("event
+// groups: assignment", "event groups: candidate models").  Every launcher enqueues plain launches on the given stream; no kernel
+// waits for another work-group.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,5 +33,30 @@ void launch_assign_box(const uint32_t* V, uint32_t* B, int K, int R, int C, int 
 // gid / score through perm, and the result block (zero on entry).  B: the box sums, or V itself at scale 1.
 void launch_assign_pick(const AssignArgs& a, const uint32_t* B, int min_score, int32_t* gid, int32_t* score, uint32_t* out,
                         hipStream_t s);
+
+// The proposal kernels (bf_propose.hip; include/bf_accel.h, "event groups: candidate models").
+constexpr int kProposeMaxRadius = 8, kProposeMaxSuppress = 64, kProposeMaxModels = 64;
+constexpr long long kProposeMaxBins = 1ll << 22;
+constexpr size_t kProposeLdsBytes = 63 * 1024;   // the LDS form: H and the two value tables in one work-group's LDS
+// The per-event best state (upload order), the lattice's value tables (n_x doubles, then n_y) and its planes.
+struct ProposeArgs {
+    const double *max_score, *best_nx, *best_ny;
+    const double* tab;
+    long long n;
+    int n_x, n_y;
+};
+// Words of the result block: voted, unscored, off_lattice, proposals, then (index, votes, peak) per proposal.
+constexpr int kProposeOutHead = 4;
+inline int propose_out_words(int K) { return kProposeOutHead + 3 * K; }
+inline bool propose_fits_lds(long long n_x, long long n_y) {
+    return (size_t)(n_x * n_y) * sizeof(uint32_t) + (size_t)(n_x + n_y) * sizeof(double) <= kProposeLdsBytes;
+}
+// H (n_x * n_y words, zero) += the votes; out[0 .. 3) (zero) += the three counts.  Returns the form that ran: 1 LDS, 2 global.
+int launch_propose_vote(const ProposeArgs& a, uint32_t* H, uint32_t* out, hipStream_t s);
+// B = the (2 r + 1)^2 box sum of H, every word of B written.
+void launch_propose_box(const uint32_t* H, uint32_t* B, int n_x, int n_y, int radius, hipStream_t s);
+// The greedy pick: out[3] = the proposals, out[4 + 3 p ..] = (index, B, H) of pick p.  One work-group.
+void launch_propose_pick(const uint32_t* H, const uint32_t* B, int n_x, int n_y, int suppress, int max_models, int min_votes,
+                         uint32_t* out, hipStream_t s);
 
 }  // namespace bf

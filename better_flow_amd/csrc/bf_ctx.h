@@ -1,5 +1,5 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp, bf_propose_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
@@ -144,6 +144,12 @@ struct bf_ctx {
     HostArray<WarpParams> h_assign_wp;
     DevArray<int32_t> d_assign_gid, d_assign_score;
     HostArray<uint32_t> h_assign_out;
+    // candidate models (bf_propose_models): the lattice's value tables (n_x doubles, then n_y), the vote plane H and its box
+    // sums B (n_x * n_y words each), the result block (counts, proposals); grown on first use
+    DevArray<double> d_propose_tab;
+    DevArray<uint32_t> d_propose_hist, d_propose_box, d_propose_out;
+    HostArray<uint32_t> h_propose_out;
+    int propose_form = 0;            // what the last bf_propose_models launched: 1 the LDS histogram, 2 global atomics (bf_get_stat)
     // One staging slot of the asynchronous uploads (bf_upload.cpp).  Its state:
     //   FREE      not taken;
     //   RECORDED  taken, `src` describes what to copy, no HIP call issued yet ("defer_uploads");
@@ -298,6 +304,19 @@ struct GlobalHeldFlow {
     long long n;
 };
 int global_held_flow(bf_ctx* c, const char* who, GlobalHeldFlow* out);
+
+// The per-event best state of the exhaustive search (bf_global_search.cpp) for bf_propose_models, behind the checks of a sweep
+// in their order: `lattice` validated (null: the defaults), the window ready (BF_ERR_ARG without one, BF_ERR_STATE after an
+// upload), then the sweep's own candidate values into xs / ys.  The three arrays are n doubles each in upload order on the
+// device (null when n == 0).  global_cand_uv: Event::compute_uv as bf_global_get_events evaluates it.
+struct GlobalBestState {
+    const double *max_score, *best_nx, *best_ny;
+    long long n;
+    double nz;
+};
+int global_best_state(bf_ctx* c, const bf_global_search_opts* lattice, std::vector<double>& xs, std::vector<double>& ys,
+                      GlobalBestState* out);
+void global_cand_uv(double nx, double ny, double nz, double* u, double* v);
 
 // The two frame tiles of the live slice (bf_extras.cpp), ENQUEUED on the context stream into device memory: the 8-bit projection
 // image, (scale res_x) x (scale res_y), and the colour-coded time image, (scale res_x + scale) x (scale res_y + scale) BGR.  A

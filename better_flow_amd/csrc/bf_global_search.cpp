@@ -998,6 +998,21 @@ int bf_global_get_flow(bf_ctx* c, double* nx, double* ny, double* u, double* v, 
 
 }  // extern "C"
 
+int global_best_state(bf_ctx* c, const bf_global_search_opts* lattice, std::vector<double>& xs, std::vector<double>& ys,
+                      GlobalBestState* out) {
+    std::memset(out, 0, sizeof(*out));
+    int rc = sweep_grid(c, lattice, xs, ys, out->nz);
+    if (rc != BF_OK) return rc;
+    const GlobalSearch* gs = c->glob.get();
+    out->n = gs->n;
+    if (gs->n <= 0) return BF_OK;
+    const GlobalEventState st = gs->state();
+    out->max_score = st.max_score; out->best_nx = st.best_nx; out->best_ny = st.best_ny;
+    return BF_OK;
+}
+
+void global_cand_uv(double nx, double ny, double nz, double* u, double* v) { cand_uv(nx, ny, nz, u, v); }
+
 int global_held_flow(bf_ctx* c, const char* who, GlobalHeldFlow* out) {
     GlobalSearch* gs = c->glob.get();
     if (!gs || !gs->have || !gs->held.mode)

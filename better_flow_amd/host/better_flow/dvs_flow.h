@@ -15,6 +15,7 @@
 #include <better_flow/event.h>
 #include <better_flow/event_file.h>
 #include <better_flow/frame_writer.h>
+#include <better_flow/object_finder.h>
 #include <better_flow/optimizer_rolling.h>
 
 #include <chrono>
@@ -55,6 +56,11 @@ protected:
     bf::Segmenter segmenter;
     std::string segments_prefix;
     ull segments_count = 0;
+    bool generate_objects = false;             // --objects: objects_N.txt
+    bf::ObjectFinder finder;
+    std::string objects_prefix;
+    ull objects_count = 0;
+    bf_ctx *objects_helper = nullptr;          // the refit of a group too large for the grouped solve runs here
     bf::AviWriter flowvideo;
     ull flow_count = 0;
     bool stm_disable;
@@ -66,6 +72,7 @@ protected:
     ull slice_origin();
     void render_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
     void render_flow_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
+    void write_objects(LinearEventPtrs &slice);
 
 public:
     DVS_flow(ull on_ev_change_, ull on_time_change_, ull start_time = 0)
@@ -82,7 +89,10 @@ public:
         if (slice_log) std::fprintf(slice_log, "slice,events,new_events,rc,iterations,ms,mevents_per_s\n");
         return slice_log != nullptr;
     }
-    ~DVS_flow() { if (slice_log) std::fclose(slice_log); }
+    ~DVS_flow() {
+        if (slice_log) std::fclose(slice_log);
+        if (objects_helper) bf_destroy(objects_helper);
+    }
 
     void set_accumulate(bool on = true) { accumulate = on; }
     LinearEventCloudTemplate<Event> get_accumulated();
@@ -103,6 +113,11 @@ public:
     // the component table (segments_N.txt) and the label image (segments_N.pgm) of every slice under `prefix`
     void set_generate_segments(const bf_segment_opts &opts, std::string prefix = "./") {
         generate_segments = true; segmenter.opts = opts; segments_prefix = prefix;
+    }
+    // the moving objects of every slice (objects_N.txt under `prefix`): `cfg`'s search, proposal and alternation (its result
+    // fields are not read); the number of objects is cfg.propose.max_models
+    void set_generate_objects(const bf::ObjectFinder &cfg, std::string prefix = "./") {
+        generate_objects = true; finder = cfg; objects_prefix = prefix;
     }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
@@ -189,6 +204,42 @@ void DVS_flow<MAX_SZ, SPAN>::render_flow_frame(OptimizerRolling<LinearEventPtrs>
     }
 }
 
+// The moving objects of the slice (better_flow/object_finder.h) as objects_N.txt: one line per group -- id, events, the
+// median (u, v) of its events under its model in px / s, the model's fields (cx cy dx dy rot div cnt total_dx total_dy total_rot
+// total_div), the votes of the proposal it started from --, then a last line "unassigned <events>".  Event::t holds the
+// slice-local time (set_time).
+template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(LinearEventPtrs &slice) {
+    std::vector<int32_t> fx, fy, ft;
+    fx.reserve(slice.size()); fy.reserve(slice.size()); ft.reserve(slice.size());
+    for (auto &e : slice) {
+        fx.push_back((int32_t)e.fr_x); fy.push_back((int32_t)e.fr_y); ft.push_back((int32_t)e.t);
+    }
+    const int s = finder.fit.scale;
+    bf_ctx *ctx = bf::DeviceContext::get((long long)MAX_SZ, s * RES_X + s, s * RES_Y + s);
+    if (!objects_helper && bf_create(bf::DeviceContext::device(), (long long)MAX_SZ, s * RES_X + s, s * RES_Y + s, nullptr, &objects_helper) != BF_OK)
+        objects_helper = nullptr;   // (a group too large for the grouped solve then keeps its model)
+    finder.assign.sensor_res_x = finder.fit.sensor_res_x = finder.fit.guard_res_x = RES_X;
+    finder.assign.sensor_res_y = finder.fit.sensor_res_y = finder.fit.guard_res_y = RES_Y;
+    bf::MotionAssigner::Slice sl;
+    sl.fr_x = fx.data(); sl.fr_y = fy.data(); sl.t_ns = ft.data(); sl.n = fx.size();
+    const int rc = finder.find(ctx, sl, objects_helper);
+    if (rc < 0) throw bf::AccelError(rc, "--objects: " + finder.error);
+    const std::string path = objects_prefix + "/objects_" + std::to_string(objects_count++) + ".txt";
+    FILE *f = std::fopen(path.c_str(), "w");
+    if (!f) {
+        if (!quiet) std::cerr << "cannot write " << path << "\n";
+        return;
+    }
+    for (size_t k = 0; k < finder.models.size(); ++k) {
+        const bf_model &m = finder.models[k];
+        std::fprintf(f, "%zu %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u %.17g %.17g %.17g %.17g %d\n", k, (int)finder.counts[k],
+                     finder.flow_u[k], finder.flow_v[k], m.cx, m.cy, m.dx, m.dy, m.rot, m.div, (unsigned)m.cnt, m.total_dx, m.total_dy,
+                     m.total_rot, m.total_div, k < finder.proposals.size() ? (int)finder.proposals[k].votes : 0);
+    }
+    std::fprintf(f, "unassigned %d\n", finder.counts.empty() ? 0 : (int)finder.counts.back());
+    std::fclose(f);
+}
+
 // One slice: the events now in the ring, their times made relative to the slice origin, one OptimizerRolling run --
 // warm-started from the previous slice's model unless --stm-disable (the "short-term memory", dvs_flow.h:218-224) --,
 // per-event flow fetched from the device, optional frame, bookkeeping (dvs_flow.h:185-347).
@@ -198,6 +249,8 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::recompute() {
     const bool frames = generate_video || generate_pictures;
     if (frames)   // the frames are rendered at scale 3 whatever `scale` is: make room once
         (void)bf::DeviceContext::get((long long)MAX_SZ, 3 * RES_X + 3, 3 * RES_Y + 3);
+    if (generate_objects)   // ... and the objects' refit at its own scale
+        (void)bf::DeviceContext::get((long long)MAX_SZ, finder.fit.scale * RES_X + finder.fit.scale, finder.fit.scale * RES_Y + finder.fit.scale);
 
     LinearEventPtrs slice;                     // newest -> oldest, the ring's iteration order
     slice.reserve(ev_buffer.size());
@@ -224,6 +277,8 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::recompute() {
         }
         info = optimizer.get_run_info();
     }
+    // (after every other output, and after the optimizer: it uploads the slice again, and the next slice uploads its own)
+    if (generate_objects) write_objects(slice);
     ++slices_done;
     if (rc != 0) ++slices_skipped;
     iterations_total += (ull)info.iterations;

@@ -1,0 +1,131 @@
+// object_finder.h -- bf::ObjectFinder: the moving objects of one slice without a hint from the caller:
+//   1. bf_global_set_window + bf_global_search over a lattice: every event's sharpest candidate;
+//   2. bf::ModelProposer::propose: the modes of that per-event best flow as K candidate models;
+//   3. bf::MotionAssigner::alternate from them: assignment and grouped refit until no id changes.
+// It needs the device library: the CPU stand-in the tests build has no bf_global_*.  Against a C-ABI that lacks an entry find()
+// returns BF_ERR_STATE and `error` names the entry.
+#ifndef BF_HOST_OBJECT_FINDER_H
+#define BF_HOST_OBJECT_FINDER_H
+
+#include <better_flow/model_proposer.h>
+#include <better_flow/motion_assign.h>
+
+#include <string>
+
+// (weak, as in model_proposer.h)
+extern "C" {
+int bf_global_set_window(bf_ctx *ctx, int32_t scale, int32_t metric_wsize, bf_global_window *out) __attribute__((weak));
+int bf_global_search(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_result *out, int64_t *surface_out,
+                     int64_t surface_cap) __attribute__((weak));
+}
+
+namespace bf {
+
+class ObjectFinder {
+  public:
+    // the search (its window and lattice), the proposal, the alternation (the assignment's window; the refit is `fit`)
+    int search_scale = 1, search_wsize = 5;
+    bf_global_search_opts lattice;
+    bf_propose_opts propose;
+    bf_assign_opts assign;
+    bf_group_opts fit;
+    int rounds_per_fit = 2, max_alternations = 5;
+
+    // what find() leaves: K models, the ids in upload order (-1: unassigned), K + 1 counts (last: unassigned), the proposals
+    // the models started from and one record per alternation
+    std::vector<bf_model> models;
+    std::vector<int32_t> gid, counts;
+    std::vector<bf_proposal> proposals;
+    std::vector<MotionAssigner::Record> records;
+    std::vector<double> flow_u, flow_v;   // per group: the median (u, v) in px / s of its events under its model's warp
+    std::string error;
+
+    ObjectFinder() : lattice(ModelProposer::default_lattice()), propose(ModelProposer::default_opts()), assign() {
+        assign.scale = 3;
+        assign.sensor_res_x = 180; assign.sensor_res_y = 240;
+        assign.margin = 0; assign.min_score = 1;
+        fit = ObjectTasks().opts;
+    }
+
+    // The entry the linked C-ABI lacks, or null.
+    static const char *missing_entry() {
+        if (!bf_propose_models) return "bf_propose_models";
+        if (!bf_global_search || !bf_global_set_window) return "bf_global_search";
+        if (!MotionAssigner::device_available()) return "bf_assign_groups";
+        return nullptr;
+    }
+
+    // helper: a second context with room for the slice, for the refit of a group too large for the grouped solve (may be null)
+    int find(bf_ctx *ctx, const MotionAssigner::Slice &s, bf_ctx *helper = nullptr) {
+        models.clear(); gid.clear(); counts.clear(); proposals.clear(); records.clear(); error.clear();
+        flow_u.clear(); flow_v.clear();
+        if (const char *m = missing_entry()) {
+            error = std::string("bf::ObjectFinder: the linked library has no ") + m;
+            return BF_ERR_STATE;
+        }
+        int rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
+        if (rc >= 0) rc = bf_global_set_window(ctx, search_scale, search_wsize, nullptr);
+        if (rc >= 0) rc = bf_global_search(ctx, &lattice, nullptr, nullptr, 0);
+        ModelProposer mp;
+        if (rc >= 0) rc = mp.propose(ctx, lattice, propose);
+        if (rc < 0) return fail(ctx, rc);
+        proposals = mp.result.proposals;
+        models = mp.result.models;
+        gid.assign(s.n, -1);
+        counts.assign(models.size() + 1, 0);
+        counts.back() = (int32_t)s.n;
+        flow_u.assign(models.size(), 0.0);
+        flow_v.assign(models.size(), 0.0);
+        if (models.empty()) return BF_OK;   // nothing scored: no object
+        MotionAssigner ma;
+        ma.fit = fit;
+        rc = ma.alternate(ctx, s, models, assign, rounds_per_fit, max_alternations, helper);
+        if (rc < 0) return fail(ctx, rc);
+        models = ma.models;
+        gid = ma.gid;
+        counts = ma.counts;
+        records = ma.records;
+        rc = group_flows(ctx, s);
+        return rc < 0 ? fail(ctx, rc) : BF_OK;
+    }
+
+  private:
+    // Per group its events alone under set_model's warp of its model (optimizer_rolling.h:289-299), Event::compute_uv of
+    // what that leaves, and the median per axis (the mean of the two middle values of an even count).
+    int group_flows(bf_ctx *ctx, const MotionAssigner::Slice &s) {
+        std::vector<int32_t> x, y, t;
+        std::vector<double> nx, ny, u, v;
+        for (size_t k = 0; k < models.size(); ++k) {
+            x.clear(); y.clear(); t.clear();
+            for (size_t i = 0; i < s.n; ++i)
+                if (gid[i] == (int32_t)k) { x.push_back(s.fr_x[i]); y.push_back(s.fr_y[i]); t.push_back(s.t_ns[i]); }
+            if (x.empty()) continue;
+            bf_window w;
+            int rc = bf_upload_events(ctx, x.data(), y.data(), t.data(), nullptr, (int64_t)x.size());
+            if (rc >= 0) rc = bf_set_cloud(ctx, fit.scale, fit.sensor_res_x, fit.sensor_res_y, &w);
+            if (rc >= 0) rc = bf_set_model(ctx, &models[k]);
+            nx.assign(x.size(), 0.0); ny.assign(x.size(), 0.0);
+            if (rc >= 0) rc = bf_writeout_events(ctx, nullptr, nullptr, nx.data(), ny.data());
+            if (rc < 0) return rc;
+            u.resize(x.size()); v.resize(x.size());
+            for (size_t i = 0; i < x.size(); ++i) ModelProposer::compute_uv(nx[i], ny[i], 127.0, &u[i], &v[i]);
+            flow_u[k] = median(u);
+            flow_v[k] = median(v);
+        }
+        return BF_OK;
+    }
+    static double median(std::vector<double> &a) {
+        std::sort(a.begin(), a.end());
+        const size_t m = a.size() / 2;
+        return a.size() % 2 ? a[m] : 0.5 * (a[m - 1] + a[m]);
+    }
+    int fail(bf_ctx *ctx, int rc) {
+        const char *m = bf_last_error(ctx);
+        error = m ? m : "";
+        return rc;
+    }
+};
+
+}  // namespace bf
+
+#endif  // BF_HOST_OBJECT_FINDER_H

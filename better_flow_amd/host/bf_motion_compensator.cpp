@@ -39,6 +39,10 @@ struct Options {
     bool segments = false;                       // --segments=<seconds>: segments_N.txt / segments_N.pgm per slice
     double seg_above = -1.0, seg_below = -1.0;
     int seg_min_count = 1, seg_min_pixels = 1, seg_connectivity = 8;
+    bool objects_flag = false;
+    int objects = 0;                             // --objects=<K>: objects_N.txt per slice, K candidate motions
+    double objects_range = 600.0, objects_step = 30.0;   // the search lattice in px / s
+    int objects_radius = 1, objects_suppress = 2, objects_min_votes = 1, objects_scale = 3;
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
     int scale = 3, max_iter = -1;
@@ -113,6 +117,16 @@ const std::vector<Flag> &flag_table() {
         {"--segments-min-count", Arg::Inline, [](Options &o, const char *v) { o.seg_min_count = atoi(v); }, "<n>", "... on pixels with at least this many events (1)"},
         {"--segments-min-pixels", Arg::Inline, [](Options &o, const char *v) { o.seg_min_pixels = atoi(v); }, "<n>", "drop components smaller than this (1)"},
         {"--segments-connectivity", Arg::Inline, [](Options &o, const char *v) { o.seg_connectivity = atoi(v); }, "<4|8>", "pixel connectivity (8)"},
+        {"--objects", Arg::Inline, [](Options &o, const char *v) { o.objects_flag = true; o.objects = atoi(v); }, "<K>",
+         "find up to K moving objects in every slice (objects_N.txt: per group its id, events, median flow (u, v) in px/s, model fields, "
+         "proposal votes; last line: unassigned events): exhaustive search, candidate models from the modes of the per-event best flow, "
+         "then assignment and refit in alternation; ring engine"},
+        {"--objects-range", Arg::Inline, [](Options &o, const char *v) { o.objects_range = atof(v); }, "<px/s>", "... searching flows up to this speed per axis (600)"},
+        {"--objects-step", Arg::Inline, [](Options &o, const char *v) { o.objects_step = atof(v); }, "<px/s>", "... on a lattice of this step (30)"},
+        {"--objects-radius", Arg::Inline, [](Options &o, const char *v) { o.objects_radius = atoi(v); }, "<n>", "box half-width, in lattice steps, that smooths the votes (1)"},
+        {"--objects-suppress", Arg::Inline, [](Options &o, const char *v) { o.objects_suppress = atoi(v); }, "<n>", "half-width of the square suppressed around a picked mode (2)"},
+        {"--objects-min-votes", Arg::Inline, [](Options &o, const char *v) { o.objects_min_votes = atoi(v); }, "<n>", "smallest smoothed vote count of a mode (1)"},
+        {"--objects-scale", Arg::Inline, [](Options &o, const char *v) { o.objects_scale = atoi(v); }, "<odd>", "image scale of the assignment and the refit (3)"},
         {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
         {"--video", Arg::None, [](Options &o, const char *) { o.video = true; }, "", "write the frames to a video (uncompressed AVI)"},
         {"--video-name", Arg::Next, [](Options &o, const char *v) { o.video_name = v; }, "<file>", "name of that video"},
@@ -221,8 +235,19 @@ int parse(int argc, char **argv, Options &o) {
         std::fprintf(stderr, "--segments: finite thresholds, --segments-min-count and --segments-min-pixels >= 1, --segments-connectivity 4 or 8\n");
         return 1;
     }
+    if (o.objects_flag && (o.engine == "stream" || !o.more_inputs.empty())) {
+        std::fprintf(stderr, "--objects works on the slices of the reference ring: not with --engine=stream or several input files\n");
+        return 1;
+    }
+    if (o.objects_flag && (o.objects < 1 || o.objects > 64 || !(o.objects_range > 0) || !(o.objects_step > 0) || !std::isfinite(o.objects_range) ||
+                      o.objects_radius < 0 || o.objects_radius > 8 || o.objects_suppress < 0 || o.objects_suppress > 64 ||
+                      o.objects_min_votes < 1 || o.objects_scale < 1 || o.objects_scale % 2 == 0 || o.objects_scale > 9)) {
+        std::fprintf(stderr, "--objects: 1..64 objects, a positive --objects-range and --objects-step, --objects-radius 0..8, "
+                             "--objects-suppress 0..64, --objects-min-votes >= 1, an odd --objects-scale up to 9\n");
+        return 1;
+    }
     // (--img / --video / --flow-img / --flow-field run on both engines; without --engine they keep the reference ring)
-    const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive || o.segments;
+    const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive || o.segments || o.objects_flag;
     if (o.engine.empty()) o.engine = needs_ring ? "ring" : "stream";
     if (o.engine == "stream" && o.interactive) { std::fprintf(stderr, "-i works on the reference ring: drop --engine=stream\n"); return 1; }
     if (o.have_output_bin && o.output_bin.empty()) { std::fprintf(stderr, "--outfile-bin needs a file name: --outfile-bin=<file>\n"); return 1; }
@@ -291,6 +316,21 @@ int run_ring(const Options &o) {
         so.above_s = o.seg_above; so.below_s = o.seg_below; so.min_count = o.seg_min_count; so.connectivity = o.seg_connectivity;
         so.min_pixels = o.seg_min_pixels; so.reserved = 0;
         estimator.set_generate_segments(so, o.frame_prefix);
+    }
+    if (o.objects_flag) {
+        if (const char *missing = bf::ObjectFinder::missing_entry()) {   // (before any slice: no file is written)
+            std::fprintf(stderr, "--objects needs %s, which this build of the library does not have\n", missing);
+            return 2;
+        }
+        bf::ObjectFinder cfg;
+        const double k = 127.0 / 1e5;   // px / s -> the candidate's nx (Event::compute_uv, event.h:135-142)
+        cfg.lattice.x_low = cfg.lattice.y_low = -o.objects_range * k;
+        cfg.lattice.x_hi = cfg.lattice.y_hi = o.objects_range * k;
+        cfg.lattice.x_step = cfg.lattice.y_step = o.objects_step * k;
+        cfg.propose.radius = o.objects_radius; cfg.propose.suppress = o.objects_suppress;
+        cfg.propose.max_models = o.objects; cfg.propose.min_votes = o.objects_min_votes;
+        cfg.assign.scale = cfg.fit.scale = o.objects_scale;
+        estimator.set_generate_objects(cfg, o.frame_prefix);
     }
     if (o.stm_disable) estimator.set_stm_disable(true);
     if (!o.slice_log.empty() && !estimator.open_slice_log(o.slice_log)) {

@@ -234,6 +234,8 @@ int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
  *   "k3_half_scale", "k3_mode", "k3_capped"   ... and its stencil kernel: scale / 2 (at most 4), what it read (0 dense slabs,
  *                     1 event lists, 2 own pixels + margin plane), and 1 for the build with capped scalar registers that a
  *                     launch of >= 8 tiles per CU takes; -1 as above.
+ *   "propose_form"    the vote kernel the last bf_propose_models launched: 1 a histogram per work-group in LDS, 2 one global
+ *                     atomic per vote; 0 when it launched none (no call yet, or no events).
  * BF_ERR_ARG for an unknown key. */
 int bf_get_stat(bf_ctx *ctx, const char *key, int64_t *value);
 
@@ -1009,6 +1011,59 @@ int bf_global_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32
                                 float *flo_out);
 int bf_global_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
                          int32_t lead_row, int32_t lead_col, int64_t *ticket_out);
+
+/* ---- event groups: candidate models -- the modes of the per-event best flow of the exhaustive search ----
+ *
+ * After bf_global_search every event holds the lattice candidate under which its neighbourhood was sharpest (best_nx,
+ * best_ny, max_score).  The modes of that per-event best flow are the motions present in the slice; this entry turns them
+ * into the candidate models bf_assign_groups starts from.  Everything after the index match is an
+ * integer count, a maximum or a lowest index: the result does not depend on storage order or scheduling.
+ *
+ *   lattice   x_vals (n_x values) and y_vals (n_y) of `lattice`, built as bf_global_search builds its candidates (repeated
+ *             double addition from x_low while < x_hi; y likewise); NULL: bf_global_search_opts_default.  It must be the
+ *             lattice the state was searched over.  n_x * n_y <= 2^22, else BF_ERR_CAPACITY.
+ *   votes     event e votes for (i, j) when max_score[e] > 0, best_nx[e] == x_vals[i] and best_ny[e] == y_vals[j]: exact
+ *             double equality; the values are strictly increasing, so the index is unique.  max_score == 0 counts in
+ *             `unscored`; a best that is on no lattice point (the state was continued from another range or from
+ *             bf_global_project_all) counts in `off_lattice`; neither of the two votes.  H[i][j] = the number of votes,
+ *             `voted` = its sum: voted + unscored + off_lattice = the events of the slice.
+ *   smoothing B[i][j] = the sum of H[i + a][j + b] over |a|, |b| <= radius, zero outside the lattice.
+ *   pick      up to max_models times: among the points not within Chebyshev distance `suppress` of an earlier pick the
+ *             largest B, among equals the lowest index i * n_y + j; stop when that B is below min_votes.  Proposals are in
+ *             pick order, so `votes` is non-increasing.
+ *   models    models_out[p] is all zero except total_dx = -nx and total_dy = -ny: the model whose set_model warp
+ *             (optimizer_rolling.h:289-299) compensates the flow.  lattice->nz must be 127 for models_out != NULL
+ *             (BF_ERR_ARG): the rolling path's Event has no other nz.
+ *   state     reads the per-event best state only; that state, a held flow, a held grouping, a segmentation, products, the
+ *             time image and the read-back validity are untouched.
+ *   outputs   models_out / proposals_out: `cap` entries, the first info->proposals written; hist_out / box_out: H and B,
+ *             n_x * n_y words each, row i at i * n_y (planes_cap: the words each holds).  Any output may be NULL.
+ *   errors    BF_ERR_ARG for no window, a range error of any option (opts NULL: radius 1, suppress 2, max_models 8,
+ *             min_votes 1), cap < max_models with models_out or proposals_out, planes_cap < n_x * n_y with a plane;
+ *             BF_ERR_STATE when any upload happened since bf_global_set_window (the rule of bf_global_get_events).  Zero
+ *             events: BF_OK, zero proposals, info all zero except n_x and n_y.
+ * Blocking.  bf_get_stat "propose_form": what the last call's vote kernel was, 1 a histogram per work-group in LDS (the
+ * lattice and its value tables fit 64 KiB), 2 one global atomic per vote, 0 nothing was launched. */
+typedef struct bf_propose_opts {   /* 32 bytes */
+    int32_t radius;      /* r: box half-width in lattice steps, 0..8 */
+    int32_t suppress;    /* half-width of the square suppressed around a pick, 0..64 */
+    int32_t max_models;  /* 1..64 */
+    int32_t min_votes;   /* >= 1: stop at the first peak whose smoothed count is below it */
+    int32_t reserved[4];
+} bf_propose_opts;
+typedef struct bf_proposal {       /* 48 bytes */
+    double nx, ny;       /* the lattice point's values, exactly the candidate bf_global_search used */
+    double u, v;         /* Event::compute_uv of it with lattice->nz (the expression of bf_global_get_events) */
+    int64_t index;       /* i * n_y + j */
+    int32_t votes, peak; /* B and H at the point */
+} bf_proposal;
+typedef struct bf_propose_info {   /* 32 bytes */
+    int64_t n_x, n_y;
+    int32_t voted, unscored, off_lattice, proposals;
+} bf_propose_info;
+int bf_propose_models(bf_ctx *ctx, const bf_global_search_opts *lattice, const bf_propose_opts *opts,
+                      bf_model *models_out, bf_proposal *proposals_out, int32_t cap,
+                      uint32_t *hist_out, uint32_t *box_out, int64_t planes_cap, bf_propose_info *info);
 
 /* ---- moving-object segmentation: connected components of the compensated time image ---------------------------------------
  * An eighth definition of this build ("Segmentation"); the reference only carries the vocabulary (Event::cl,
