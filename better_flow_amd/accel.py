@@ -196,6 +196,27 @@ class AssignInfo(C.Structure):
                 ("unassigned", C.c_int32), ("changed", C.c_int32), ("max_score", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ProjectOpts(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("sensor_res_x", C.c_int32), ("sensor_res_y", C.c_int32), ("margin", C.c_int32),
+                ("gain", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GroupScore(C.Structure):
+    _fields_ = [("events", C.c_int32), ("inside", C.c_int32), ("pixels_hit", C.c_int32), ("pixels_owned", C.c_int32),
+                ("max", C.c_int32), ("reserved", C.c_int32), ("sum_sq", C.c_uint64)]
+
+
+class ProjectInfo(C.Structure):
+    _fields_ = [("models", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("unassigned", C.c_int32),
+                ("outside", C.c_int32), ("pixels", C.c_int32), ("sum", C.c_uint64), ("sum_sq", C.c_uint64),
+                ("reserved", C.c_int32 * 2)]
+
+
+# BF_PROJECT_PALETTE of include/bf_accel.h: the (B, G, R) of group k is PROJECT_PALETTE[k % 12]
+PROJECT_PALETTE = ((255, 255, 255), (0, 0, 255), (0, 255, 0), (255, 0, 0), (0, 255, 255), (255, 0, 255), (255, 255, 0),
+                   (0, 128, 255), (255, 128, 0), (128, 0, 255), (0, 255, 128), (128, 128, 255))
+
+
 class AccelProposeOpts(C.Structure):
     _fields_ = [("radius", C.c_int32), ("suppress", C.c_int32), ("max_models", C.c_int32), ("min_votes", C.c_int32),
                 ("reserved", C.c_int32 * 4)]
@@ -238,7 +259,7 @@ EXPORTS = [
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
     "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups", "bf_assign_groups",
-    "bf_propose_models",
+    "bf_propose_models", "bf_project_groups",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -380,6 +401,8 @@ def load(path=None):
         L.bf_run_groups.argtypes = [C.c_void_p, C.POINTER(GroupOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bf_assign_groups.argtypes = [C.c_void_p, C.POINTER(AssignOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(AssignInfo)]
+        L.bf_project_groups.argtypes = [C.c_void_p, C.POINTER(ProjectOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.POINTER(ProjectInfo)]
         L.bf_propose_models.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(AccelProposeOpts), C.c_void_p, C.c_void_p,
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ProposeInfo)]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -949,6 +972,27 @@ class Accel:
         info = AssignInfo()
         self._chk(self.L.bf_assign_groups(self.h, C.byref(o), ms, K, _ptr(gid), _ptr(score), _ptr(counts), C.byref(info)))
         return gid, score, counts, info
+
+    def project_groups(self, models, scale, sensor_res, margin=0, gain=8, want=("count", "label", "bgr")):
+        """bf_project_groups: the slice with every event of the held grouping warped by its own group's model (`models`, one
+        Model per group).  Returns (images, scores, ProjectInfo): images a dict with those of "count" (uint32 [R, C]), "label"
+        (int32 [R, C], -1: no event) and "bgr" (uint8 [R, C, 3]) that `want` names, scores a list of GroupScore per group."""
+        K = len(models)
+        o = ProjectOpts(scale, sensor_res[0], sensor_res[1], margin, gain)
+        ms = (Model * max(K, 1))(*models)
+        R, C_ = max(scale * (sensor_res[0] + 2 * margin), 0), max(scale * (sensor_res[1] + 2 * margin), 0)   # the header's window
+        if R * C_ > (1 << 27):   # (the entry refuses it: BF_ERR_ARG or BF_ERR_CAPACITY)
+            R = C_ = 0
+        shapes = {"count": ((R, C_), np.uint32), "label": ((R, C_), np.int32), "bgr": ((R, C_, 3), np.uint8)}
+        unknown = [k for k in want if k not in shapes]
+        if unknown:
+            raise ValueError("project_groups: unknown outputs %s" % unknown)
+        img = {k: np.zeros(shapes[k][0], dtype=shapes[k][1]) for k in want}
+        scores = (GroupScore * max(K, 1))()
+        info = ProjectInfo()
+        self._chk(self.L.bf_project_groups(self.h, C.byref(o), ms, K, _ptr(img.get("count")), _ptr(img.get("label")),
+                                           _ptr(img.get("bgr")), scores, C.byref(info)))
+        return img, list(scores)[:K], info
 
     def propose_models(self, opts=None, radius=1, suppress=2, max_models=8, min_votes=1, want_planes=False):
         """bf_propose_models: the modes of the per-event best flow global_search left over the lattice `opts` (a

@@ -1,6 +1,7 @@
 // bf_assign.h -- launchers of the assignment kernels (bf_assign.hip) for bf_assign_abi.cpp, and of the kernels that propose its
-// candidate models (bf_propose.hip) for bf_propose_abi.cpp.  The definitions they implement are in include/bf_accel.h ("event
-// groups: assignment", "event groups: candidate models").  Every launcher enqueues plain launches on the given stream; no kernel
+// candidate models (bf_propose.hip) for bf_propose_abi.cpp, and of the kernels that project a grouping (bf_project.hip) for
+// bf_project_abi.cpp.  The definitions they implement are in include/bf_accel.h ("event groups: assignment", "event groups:
+// candidate models", "event groups: projection").  Every launcher enqueues plain launches on the given stream; no kernel
 // waits for another work-group.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,5 +59,19 @@ void launch_propose_box(const uint32_t* H, uint32_t* B, int n_x, int n_y, int ra
 // The greedy pick: out[3] = the proposals, out[4 + 3 p ..] = (index, B, H) of pick p.  One work-group.
 void launch_propose_pick(const uint32_t* H, const uint32_t* B, int n_x, int n_y, int suppress, int max_models, int min_votes,
                          uint32_t* out, hipStream_t s);
+
+// The projection kernels (bf_project.hip; include/bf_accel.h, "event groups: projection").  They share the assignment's window,
+// warps (AssignArgs, its prior the held grouping: here an event's ONE model) and vote planes.
+// The result block, 64-bit words: per group events, inside, pixels_hit, pixels_owned, max, sum_sq (six tables of K), then
+// unassigned, pixels, sum, sum_sq.  Every word sits on a 128-byte line of its own (word w at index w * kProjectStride): the
+// work-groups' atomics on words of one line queue behind each other.
+constexpr int kProjectTables = 6, kProjectTail = 4;
+constexpr int kProjectStride = 16;
+inline int project_out_words(int K) { return (kProjectTables * K + kProjectTail) * kProjectStride; }
+// V (K x R x C words, zero) += one vote per event on its own group's plane; out (zero) += events, inside, unassigned.
+void launch_project_vote(const AssignArgs& a, uint32_t* V, unsigned long long* out, hipStream_t s);
+// Per pixel N, the owner and its colour from the K planes B (the box sums, or V itself at scale 1); out += the rest.
+void launch_project_compose(const uint32_t* B, int K, int R, int C, int gain, uint32_t* count, int32_t* label, uint8_t* bgr,
+                            unsigned long long* out, hipStream_t s);
 
 }  // namespace bf

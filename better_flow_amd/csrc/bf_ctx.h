@@ -1,5 +1,5 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp, bf_propose_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp, bf_propose_abi.cpp, bf_project_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
@@ -144,6 +144,13 @@ struct bf_ctx {
     HostArray<WarpParams> h_assign_wp;
     DevArray<int32_t> d_assign_gid, d_assign_score;
     HostArray<uint32_t> h_assign_out;
+    // projection (bf_project_groups): the planes and warps are the assignment's; per pixel N, the owner and the colour, and the
+    // result block of 64-bit words (bf_assign.h: project_out_words); grown on first use
+    DevArray<uint32_t> d_project_count;
+    DevArray<int32_t> d_project_label;
+    DevArray<uint8_t> d_project_bgr;
+    DevArray<unsigned long long> d_project_out;
+    HostArray<unsigned long long> h_project_out;
     // candidate models (bf_propose_models): the lattice's value tables (n_x doubles, then n_y), the vote plane H and its box
     // sums B (n_x * n_y words each), the result block (counts, proposals); grown on first use
     DevArray<double> d_propose_tab;

@@ -110,6 +110,23 @@ __device__ __forceinline__ void warp_products(const WarpParams& wp, double pr_x,
     q.y = ky * ft;
 }
 
+// The event's pixel index in the R x C window under one warp from the reset state, or -1 when it is outside (accel_lib.h:157):
+// pixel_k(i) of bf_assign_groups and bf_project_groups (include/bf_accel.h, "event groups: assignment").
+__device__ __forceinline__ int assign_pixel(const WarpParams& wp, uint32_t v, int32_t t, int scale, int x_sh, int y_sh, int wsx,
+                                            int wsy, int C) {
+    const uint32_t fx = v & 0xffffu, fy = v >> 16;
+    float2 q;
+    double nx, ny;
+    // Event::reset (pr = fr), then set_model's warp_reinit (optimizer_rolling.h:289-299): event.h:99-110,164-168
+    warp_products(wp, (double)fx, (double)fy, t, q, nx, ny);
+    // accel_lib.h:154-158, as the scatter kernel forms it (bf_kernels.hip: event_body; bf_segment.hip: k_seg_events)
+    const int X = trunc_scatter(pr_from_p(fx, q.x) * (double)scale + (double)x_sh);
+    const int Y = trunc_scatter(pr_from_p(fy, q.y) * (double)scale + (double)y_sh);
+    const int hs = scale / 2;
+    if ((X >= wsx + hs) || (X < hs) || (Y >= wsy + hs) || (Y < hs)) return -1;
+    return X * C + Y;
+}
+
 // A load the compiler must issue on the SCALAR unit: through the constant address space.  For data that no work-group
 // of the running kernel writes (kernel arguments passed inside a struct lose their __restrict__, and the compiler
 // then falls back to vector loads for uniform addresses: they complete in order with every other vector load of the

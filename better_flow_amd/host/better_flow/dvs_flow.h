@@ -16,6 +16,7 @@
 #include <better_flow/event_file.h>
 #include <better_flow/frame_writer.h>
 #include <better_flow/object_finder.h>
+#include <better_flow/object_render.h>
 #include <better_flow/optimizer_rolling.h>
 
 #include <chrono>
@@ -61,6 +62,8 @@ protected:
     std::string objects_prefix;
     ull objects_count = 0;
     bf_ctx *objects_helper = nullptr;          // the refit of a group too large for the grouped solve runs here
+    bool generate_objects_img = false;         // --objects-img: objects_N.ppm / objects_N.pgm / objects_N.score.txt
+    bf::ObjectRenderer renderer;
     bf::AviWriter flowvideo;
     ull flow_count = 0;
     bool stm_disable;
@@ -119,6 +122,9 @@ public:
     void set_generate_objects(const bf::ObjectFinder &cfg, std::string prefix = "./") {
         generate_objects = true; finder = cfg; objects_prefix = prefix;
     }
+    // ... and their picture and score (objects_N.ppm, objects_N.pgm, objects_N.score.txt): the slice with every event under
+    // its own object's model, in the assignment's window; a box sum of 255 / gain saturates an object's colour
+    void set_generate_objects_img(int gain) { generate_objects_img = true; renderer.opts.gain = gain; }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
 
@@ -207,7 +213,7 @@ void DVS_flow<MAX_SZ, SPAN>::render_flow_frame(OptimizerRolling<LinearEventPtrs>
 // The moving objects of the slice (better_flow/object_finder.h) as objects_N.txt: one line per group -- id, events, the
 // median (u, v) of its events under its model in px / s, the model's fields (cx cy dx dy rot div cnt total_dx total_dy total_rot
 // total_div), the votes of the proposal it started from --, then a last line "unassigned <events>".  Event::t holds the
-// slice-local time (set_time).
+// slice-local time (set_time).  With --objects-img also the slice under its objects' models (better_flow/object_render.h).
 template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(LinearEventPtrs &slice) {
     std::vector<int32_t> fx, fy, ft;
     fx.reserve(slice.size()); fy.reserve(slice.size()); ft.reserve(slice.size());
@@ -224,7 +230,8 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
     sl.fr_x = fx.data(); sl.fr_y = fy.data(); sl.t_ns = ft.data(); sl.n = fx.size();
     const int rc = finder.find(ctx, sl, objects_helper);
     if (rc < 0) throw bf::AccelError(rc, "--objects: " + finder.error);
-    const std::string path = objects_prefix + "/objects_" + std::to_string(objects_count++) + ".txt";
+    const std::string base = objects_prefix + "/objects_" + std::to_string(objects_count++);
+    const std::string path = base + ".txt";
     FILE *f = std::fopen(path.c_str(), "w");
     if (!f) {
         if (!quiet) std::cerr << "cannot write " << path << "\n";
@@ -238,6 +245,16 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
     }
     std::fprintf(f, "unassigned %d\n", finder.counts.empty() ? 0 : (int)finder.counts.back());
     std::fclose(f);
+    if (!generate_objects_img || finder.models.empty()) return;   // (no object: nothing to project)
+    // find() leaves the context holding one group's events (its flows re-upload): the renderer uploads the slice again and
+    // holds the final ids as its grouping
+    renderer.opts.scale = finder.assign.scale;
+    renderer.opts.sensor_res_x = RES_X; renderer.opts.sensor_res_y = RES_Y;
+    renderer.opts.margin = finder.assign.margin;
+    const int prc = renderer.render(ctx, sl, finder.gid, finder.models);
+    if (prc < 0) throw bf::AccelError(prc, std::string("--objects-img: ") + bf_last_error(ctx));
+    if ((!renderer.write_ppm(base + ".ppm") || !renderer.write_label_pgm(base + ".pgm") || !renderer.write_scores(base + ".score.txt")) && !quiet)
+        std::cerr << "cannot write " << base << ".ppm / .pgm / .score.txt\n";
 }
 
 // One slice: the events now in the ring, their times made relative to the slice origin, one OptimizerRolling run --

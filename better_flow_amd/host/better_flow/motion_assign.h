@@ -155,6 +155,56 @@ class MotionAssigner {
         return BF_OK;
     }
 
+    // The host paths' pixel code, shared with bf::ObjectRenderer (object_render.h).
+    struct HostWindow {   // the window of the sensor widened by the margin: optimizer_rolling.h:248-283
+        int s, hs, wsx, wsy, R, C, x_sh, y_sh;
+    };
+    static HostWindow host_window(int scale, int res_x, int res_y, int margin) {
+        HostWindow w;
+        w.s = scale; w.hs = scale / 2;
+        const int s = scale;
+        const int x_min = -margin, x_max = res_x - 1 + margin, y_min = -margin, y_max = res_y - 1 + margin;
+        w.wsx = s * (x_max - x_min); w.wsy = s * (y_max - y_min);   // :263-264
+        w.R = w.wsx + s; w.C = w.wsy + s;                            // :276-277
+        const double x_shift = -double((x_max - x_min) / 2 + x_min) * double(s) + double(w.wsx) / 2.0 + s / 2;   // :279-282
+        const double y_shift = -double((y_max - y_min) / 2 + y_min) * double(s) + double(w.wsy) / 2.0 + s / 2;
+        w.x_sh = (int)x_shift; w.y_sh = (int)y_shift;                // the parameter conversion of accel_lib.h:147
+        return w;
+    }
+    // pix[i] = the pixel index X * C + Y of uploaded event i under set_model's warp of `m` from the reset state, -1: outside.
+    // px, py: room for the events' positions.
+    static int host_pixels(bf_ctx *ctx, const bf_model &m, const HostWindow &w, int res_x, int res_y, std::vector<double> &px,
+                           std::vector<double> &py, std::vector<int32_t> &pix) {
+        // Event::reset, then set_model's warp_reinit (optimizer_rolling.h:289-299)
+        int rc = bf_set_cloud(ctx, w.s, res_x, res_y, nullptr);
+        if (rc >= 0) rc = bf_set_model(ctx, &m);
+        if (rc >= 0) rc = bf_writeout_events(ctx, px.data(), py.data(), nullptr, nullptr);
+        if (rc < 0) return rc;
+        for (size_t i = 0; i < pix.size(); ++i) {
+            const int X = trunc_x86(px[i] * w.s + w.x_sh), Y = trunc_x86(py[i] * w.s + w.y_sh);   // accel_lib.h:154-155
+            pix[i] = ((X >= w.wsx + w.hs) || (X < w.hs) || (Y >= w.wsy + w.hs) || (Y < w.hs)) ? -1 : X * w.C + Y;   // :157
+        }
+        return BF_OK;
+    }
+    // B = the s x s box sum of V (the splat of accel_lib.h:160-165, gathered): rows, then columns.  row: scratch of R x C.
+    static void host_box_sum(const std::vector<uint32_t> &V, const HostWindow &w, std::vector<uint32_t> &row, std::vector<uint32_t> &B) {
+        const int R = w.R, C = w.C, hs = w.hs;
+        for (int r = 0; r < R; ++r)
+            for (int c = 0; c < C; ++c) {
+                uint32_t sum = 0;
+                for (int d = -hs; d <= hs; ++d)
+                    if (c + d >= 0 && c + d < C) sum += V[(size_t)r * C + (size_t)(c + d)];
+                row[(size_t)r * C + c] = sum;
+            }
+        for (int r = 0; r < R; ++r)
+            for (int c = 0; c < C; ++c) {
+                uint32_t sum = 0;
+                for (int d = -hs; d <= hs; ++d)
+                    if (r + d >= 0 && r + d < R) sum += row[(size_t)(r + d) * C + c];
+                B[(size_t)r * C + c] = sum;
+            }
+    }
+
   private:
     // `int x = <double>` as the reference's x86-64 build does it (accel_lib.h:154-155): NaN and anything outside the int range
     // give INT_MIN, which the window test rejects
@@ -167,14 +217,8 @@ class MotionAssigner {
             return BF_ERR_ARG;
         if (o.use_prior && !have_prior_) return BF_ERR_STATE;
         if (o.use_prior && prior_K_ != K) return BF_ERR_ARG;
-        // the window of the sensor widened by the margin: optimizer_rolling.h:248-283
-        const int s = o.scale, hs = s / 2;
-        const int x_min = -o.margin, x_max = o.sensor_res_x - 1 + o.margin, y_min = -o.margin, y_max = o.sensor_res_y - 1 + o.margin;
-        const int wsx = s * (x_max - x_min), wsy = s * (y_max - y_min);   // :263-264
-        const int R = wsx + s, C = wsy + s;                               // :276-277
-        const double x_shift = -double((x_max - x_min) / 2 + x_min) * double(s) + double(wsx) / 2.0 + s / 2;   // :279-282
-        const double y_shift = -double((y_max - y_min) / 2 + y_min) * double(s) + double(wsy) / 2.0 + s / 2;
-        const int x_sh = (int)x_shift, y_sh = (int)y_shift;               // the parameter conversion of accel_lib.h:147
+        const HostWindow w = host_window(o.scale, o.sensor_res_x, o.sensor_res_y, o.margin);
+        const int s = w.s, R = w.R, C = w.C;
         if ((long long)K * R * C > (1ll << 27)) return BF_ERR_CAPACITY;
         const size_t n = n_, P = (size_t)R * (size_t)C;
         if (n == 0) return BF_OK;
@@ -182,33 +226,14 @@ class MotionAssigner {
         std::vector<uint32_t> V(P), B(P), row(P);
         std::vector<double> px(n), py(n);
         for (int k = 0; k < K; ++k) {
-            // Event::reset, then set_model's warp_reinit (optimizer_rolling.h:289-299)
-            int rc = bf_set_cloud(ctx, s, o.sensor_res_x, o.sensor_res_y, nullptr);
-            if (rc >= 0) rc = bf_set_model(ctx, &cand[(size_t)k]);
-            if (rc >= 0) rc = bf_writeout_events(ctx, px.data(), py.data(), nullptr, nullptr);
+            const int rc = host_pixels(ctx, cand[(size_t)k], w, o.sensor_res_x, o.sensor_res_y, px, py, pix);
             if (rc < 0) return rc;
             std::fill(V.begin(), V.end(), 0u);
-            for (size_t i = 0; i < n; ++i) {
-                const int X = trunc_x86(px[i] * s + x_sh), Y = trunc_x86(py[i] * s + y_sh);   // accel_lib.h:154-155
-                pix[i] = ((X >= wsx + hs) || (X < hs) || (Y >= wsy + hs) || (Y < hs)) ? -1 : X * C + Y;   // :157
+            for (size_t i = 0; i < n; ++i)
                 if (pix[i] >= 0 && votes(o, i, k)) ++V[(size_t)pix[i]];
-            }
             const std::vector<uint32_t> *S = &V;
-            if (s > 1) {   // the s x s box sum (the splat of accel_lib.h:160-165, gathered): rows, then columns
-                for (int r = 0; r < R; ++r)
-                    for (int c = 0; c < C; ++c) {
-                        uint32_t sum = 0;
-                        for (int d = -hs; d <= hs; ++d)
-                            if (c + d >= 0 && c + d < C) sum += V[(size_t)r * C + (size_t)(c + d)];
-                        row[(size_t)r * C + c] = sum;
-                    }
-                for (int r = 0; r < R; ++r)
-                    for (int c = 0; c < C; ++c) {
-                        uint32_t sum = 0;
-                        for (int d = -hs; d <= hs; ++d)
-                            if (r + d >= 0 && r + d < R) sum += row[(size_t)(r + d) * C + c];
-                        B[(size_t)r * C + c] = sum;
-                    }
+            if (s > 1) {
+                host_box_sum(V, w, row, B);
                 S = &B;
             }
             for (size_t i = 0; i < n; ++i) {

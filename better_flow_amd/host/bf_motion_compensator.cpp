@@ -42,6 +42,8 @@ struct Options {
     bool objects_flag = false;
     int objects = 0;                             // --objects=<K>: objects_N.txt per slice, K candidate motions
     double objects_range = 600.0, objects_step = 30.0;   // the search lattice in px / s
+    bool objects_img = false;                    // --objects-img: objects_N.ppm / .pgm / .score.txt per slice
+    int objects_img_gain = 8;
     int objects_radius = 1, objects_suppress = 2, objects_min_votes = 1, objects_scale = 3;
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
@@ -127,6 +129,11 @@ const std::vector<Flag> &flag_table() {
         {"--objects-suppress", Arg::Inline, [](Options &o, const char *v) { o.objects_suppress = atoi(v); }, "<n>", "half-width of the square suppressed around a picked mode (2)"},
         {"--objects-min-votes", Arg::Inline, [](Options &o, const char *v) { o.objects_min_votes = atoi(v); }, "<n>", "smallest smoothed vote count of a mode (1)"},
         {"--objects-scale", Arg::Inline, [](Options &o, const char *v) { o.objects_scale = atoi(v); }, "<odd>", "image scale of the assignment and the refit (3)"},
+        {"--objects-img", Arg::None, [](Options &o, const char *) { o.objects_img = true; }, "",
+         "with --objects: render and score every slice under its objects' models (objects_N.ppm: every event warped by its own object's "
+         "model, coloured by object; objects_N.pgm: 16-bit owner per pixel, id + 1; objects_N.score.txt: per object id events inside "
+         "pixels_hit pixels_owned max sum_sq, then the info line with the slice's contrast sum N^2)"},
+        {"--objects-img-gain", Arg::Inline, [](Options &o, const char *v) { o.objects_img_gain = atoi(v); }, "<n>", "... 255 / n events on a pixel saturate an object's colour (8)"},
         {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
         {"--video", Arg::None, [](Options &o, const char *) { o.video = true; }, "", "write the frames to a video (uncompressed AVI)"},
         {"--video-name", Arg::Next, [](Options &o, const char *v) { o.video_name = v; }, "<file>", "name of that video"},
@@ -246,6 +253,8 @@ int parse(int argc, char **argv, Options &o) {
                              "--objects-suppress 0..64, --objects-min-votes >= 1, an odd --objects-scale up to 9\n");
         return 1;
     }
+    if (o.objects_img && !o.objects_flag) { std::fprintf(stderr, "--objects-img renders the objects --objects=<K> finds: give both\n"); return 1; }
+    if (o.objects_img && o.objects_img_gain < 1) { std::fprintf(stderr, "--objects-img-gain must be at least 1\n"); return 1; }
     // (--img / --video / --flow-img / --flow-field run on both engines; without --engine they keep the reference ring)
     const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive || o.segments || o.objects_flag;
     if (o.engine.empty()) o.engine = needs_ring ? "ring" : "stream";
@@ -331,6 +340,13 @@ int run_ring(const Options &o) {
         cfg.propose.max_models = o.objects; cfg.propose.min_votes = o.objects_min_votes;
         cfg.assign.scale = cfg.fit.scale = o.objects_scale;
         estimator.set_generate_objects(cfg, o.frame_prefix);
+        if (o.objects_img) {
+            if (!bf::ObjectRenderer::device_available()) {
+                std::fprintf(stderr, "--objects-img needs bf_project_groups, which this build of the library does not have\n");
+                return 2;
+            }
+            estimator.set_generate_objects_img(o.objects_img_gain);
+        }
     }
     if (o.stm_disable) estimator.set_stm_disable(true);
     if (!o.slice_log.empty() && !estimator.open_slice_log(o.slice_log)) {

@@ -477,6 +477,63 @@ int bf_assign_groups(bf_ctx *ctx, const bf_assign_opts *opts, const bf_model *mo
                      int32_t *group_id_out, int32_t *score_out, int32_t *counts_out /* K + 1, last = unassigned */,
                      bf_assign_info *info);
 
+/* ---- event groups: projection -- the slice with every event warped by its own group's model, as an image and a score ----
+ *
+ * The picture and the objective of motion segmentation by motion compensation: the image in which every object is sharpened
+ * by its own model, coloured by object, and its contrast sum N^2 -- the number that says whether one grouping under K models
+ * explains the slice better than another.  Everything after an event's pixel is an integer count, a sum,
+ * a maximum or a smallest index: the bytes do not depend on the order events are stored or work-groups run in.
+ *
+ *   grouping  the one the context holds (bf_set_groups, bf_set_groups_from_segments, or bf_assign_groups with install): ids
+ *             -1 .. K-1 in upload order.  n_models must equal K; event i of group k is projected under models[k].
+ *   window    exactly bf_assign_groups': the whole sensor widened by `margin`; R, C, wsx, wsy, x_sh, y_sh as there.
+ *   pixel_k(i)  exactly bf_assign_groups': ONE set_model warp of models[k] from the reset state, sine and cosine from the
+ *             host's libm, the scatter kernel's truncation and window test.
+ *   planes    V_k[p] = the number of events with id k that are inside under model k at p; B_k = the s x s box sum of V_k,
+ *             zero beyond the plane; at scale 1 B_k = V_k.
+ *   counts    an event with id -1 is in no plane and counts in info.unassigned; an event of group k that is outside under
+ *             model k counts in info.outside (and is scores[k].events - scores[k].inside).
+ *   pixel     count_out[p] = N[p] = sum_k B_k[p];  label_out[p] = the smallest k with the largest B_k[p], -1 where N[p] == 0;
+ *             bgr_out[3 p + c] = BF_PROJECT_PALETTE[label % 12][c] * min(255, B_label[p] * gain) / 255 (integer division; the
+ *             product B * gain in 64 bits), 0 where the label is -1.  p = X * C + Y, planes of R x C.
+ *   group     scores_out[k]: events (with id k), inside, pixels_hit = #{p: B_k[p] > 0}, pixels_owned = #{p: label[p] == k},
+ *             max = max_p B_k[p], sum_sq = sum_p B_k[p]^2.
+ *   info      models = K, rows = R, cols = C, unassigned, outside, pixels = #{p: N[p] > 0}, sum = sum_p N[p] (= s^2 times
+ *             the inside events less what the box sums lose beyond the plane's edge), sum_sq = sum_p N[p]^2.
+ *   overflow  the uint64 sums wrap by definition.  sum_sq <= sum^2 <= (s^2 n)^2 with s <= 9: none can wrap, and no 32-bit
+ *             count or box sum either, while the slice has fewer than 2^32 / 81 = 53 024 287 events.
+ *   state     reads the events' addresses and times, the permutation and the held grouping only; products, (nx, ny), the
+ *             time image, a held segmentation, a held flow, the per-event best state, the held grouping and the read-back
+ *             validity are untouched.  The vote planes are bf_assign_groups' (each call of either clears them first).
+ *   errors    BF_ERR_STATE before an upload, or with no held grouping; BF_ERR_ARG for an even or too large scale, a sensor
+ *             side < 1 or > 65536, a margin < 0 or > 65536, gain < 1, n_models < 1 or > 64 or different from the held K,
+ *             a NULL opts or models, a noise mask; BF_ERR_CAPACITY when K R C > 2^27.  Zero events: BF_OK, scores and info
+ *             zero (rows and cols too), count and bgr zero over the R x C window and every label -1 (N == 0 everywhere).
+ * Any output may be NULL.  Blocking. */
+#define BF_PROJECT_PALETTE_SIZE 12
+#define BF_PROJECT_PALETTE /* B, G, R */ \
+    {{255, 255, 255}, {0, 0, 255}, {0, 255, 0}, {255, 0, 0}, {0, 255, 255}, {255, 0, 255}, {255, 255, 0}, {0, 128, 255}, \
+     {255, 128, 0}, {128, 0, 255}, {0, 255, 128}, {128, 128, 255}}
+typedef struct bf_project_opts {       /* 32 bytes */
+    int32_t scale;                     /* odd, scale/2 <= 4 */
+    int32_t sensor_res_x, sensor_res_y;
+    int32_t margin;                    /* >= 0 sensor pixels added on every side of the sensor box */
+    int32_t gain;                      /* >= 1: a box sum of 255 / gain or more saturates the colour */
+    int32_t reserved[3];
+} bf_project_opts;
+typedef struct bf_group_score {        /* 32 bytes */
+    int32_t events, inside, pixels_hit, pixels_owned, max, reserved;
+    uint64_t sum_sq;
+} bf_group_score;
+typedef struct bf_project_info {       /* 48 bytes */
+    int32_t models, rows, cols, unassigned, outside, pixels;
+    uint64_t sum, sum_sq;
+    int32_t reserved[2];
+} bf_project_info;
+int bf_project_groups(bf_ctx *ctx, const bf_project_opts *opts, const bf_model *models, int32_t n_models,
+                      uint32_t *count_out /* R x C */, int32_t *label_out /* R x C */, uint8_t *bgr_out /* R x C x 3 */,
+                      bf_group_score *scores_out /* K */, bf_project_info *info);
+
 /* A batch of independent slices -- the reference's queue of (events, model) tasks (dvs_flow.h:200-231, executed there
  * one after the other) -- solved together: bf_run on each of the n contexts, all in flight at once (one host thread per
  * context inside the library; the contexts' streams share the GPU, set "co_schedule" on them when n > 1).  Every
