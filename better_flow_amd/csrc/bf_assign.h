@@ -1,8 +1,10 @@
-// bf_assign.h -- launchers of the assignment kernels (bf_assign.hip) for bf_assign_abi.cpp, and of the kernels that propose its
-// candidate models (bf_propose.hip) for bf_propose_abi.cpp, and of the kernels that project a grouping (bf_project.hip) for
-// bf_project_abi.cpp.  The definitions they implement are in include/bf_accel.h ("event groups: assignment", "event groups:
-// candidate models", "event groups: projection").  Every launcher enqueues plain launches on the given stream; no kernel
-// waits for another work-group.
+// bf_assign.h -- launchers of the assignment kernels (bf_assign.hip) and of the kernels that project a grouping (bf_project.hip),
+// both for bf_assign_abi.cpp, which sets up the K vote planes they share once; and of the kernels that propose the candidate
+// models (bf_propose.hip) for bf_propose_abi.cpp.  The definitions they implement are in include/bf_accel.h ("event groups:
+// assignment", "event groups: candidate models", "event groups: projection").  Every launcher enqueues plain launches on the
+// given stream; no kernel waits for another work-group.  What the kernel files share on the device is in bf_device_fns.h: the box
+// sum of a tile (box_sum_tile: k_assign_box, k_propose_box), the tally per distinct key of a wave (for_each_wave_key) and the
+// wave reductions.
 #pragma once
 #include <hip/hip_runtime.h>
 

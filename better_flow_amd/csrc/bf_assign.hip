@@ -7,12 +7,12 @@
 //                      state, the scatter kernel's own pixel and window test, the vote test, one atomic add without a return
 //                      value on the model's vote plane.  (Folding equal keys of neighbouring lanes into one add was measured and
 //                      did not pay: DESIGN section 15.)
-//   A2 k_assign_box    (scale > 1) B_k = the s x s box sum of V_k: a 32 x 64 tile plus a halo of s / 2 in LDS, row sums, then
-//                      column sums; planes x tiles as the grid.  Every word of B is written.
+//   A2 k_assign_box    (scale > 1) B_k = the s x s box sum of V_k: box_sum_tile (bf_device_fns.h) with a halo of at most
+//                      kMaxHalfScale, planes x tiles as the grid.  Every word of B is written.
 //   A3 k_assign_pick   four events per thread: the K pixels again (recomputed, not stored), the gathers, leave-one-out, the
 //                      smallest model with the largest score; id and score through perm; the counts per distinct id of the
-//                      wave with ballots into LDS, `changed` and `max_score` likewise, then one global atomic per work-group
-//                      and non-zero word.
+//                      wave (for_each_wave_key, bf_device_fns.h) into LDS, `changed` and `max_score` likewise, then one global
+//                      atomic per work-group and non-zero word.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
@@ -26,7 +26,6 @@ namespace bf {
 namespace {
 
 constexpr int kAssignEv = 4;                      // events per thread (a work-group's are consecutive per round)
-constexpr int kBoxTR = 32, kBoxTC = 64;           // tile of k_assign_box
 
 // What a thread keeps of its events: address word, time, prior id (-1: votes under every model; -2: no event in this slot).
 struct AssignEv {
@@ -65,33 +64,10 @@ __global__ __launch_bounds__(kThreads) void k_assign_vote(AssignArgs a, uint32_t
     }
 }
 
+// (planes x tiles as the grid: blockIdx.z the plane, .y and .x the tile's row and column)
 __global__ __launch_bounds__(kThreads) void k_assign_box(const uint32_t* __restrict__ V, uint32_t* __restrict__ B, int R, int C, int hs) {
-    __shared__ uint32_t s_in[(kBoxTR + 2 * kMaxHalfScale) * (kBoxTC + 2 * kMaxHalfScale)];
-    __shared__ uint32_t s_row[(kBoxTR + 2 * kMaxHalfScale) * kBoxTC];
     const size_t base = (size_t)blockIdx.z * (size_t)R * (size_t)C;
-    const int tr0 = blockIdx.y * kBoxTR, tc0 = blockIdx.x * kBoxTC;
-    const int IR = kBoxTR + 2 * hs, IC = kBoxTC + 2 * hs;
-    for (int idx = threadIdx.x; idx < IR * IC; idx += kThreads) {
-        const int lr = idx / IC, lc = idx - lr * IC;
-        const int gr = tr0 - hs + lr, gc = tc0 - hs + lc;
-        s_in[idx] = (gr >= 0 && gr < R && gc >= 0 && gc < C) ? V[base + (size_t)gr * C + gc] : 0u;   // (zero beyond the plane)
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < IR * kBoxTC; idx += kThreads) {
-        const int lr = idx / kBoxTC, lc = idx % kBoxTC;
-        uint32_t sum = 0;
-        for (int d = 0; d <= 2 * hs; ++d) sum += s_in[lr * IC + lc + d];
-        s_row[idx] = sum;
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < kBoxTR * kBoxTC; idx += kThreads) {
-        const int lr = idx / kBoxTC, lc = idx % kBoxTC;
-        const int gr = tr0 + lr, gc = tc0 + lc;
-        if (gr >= R || gc >= C) continue;
-        uint32_t sum = 0;
-        for (int d = 0; d <= 2 * hs; ++d) sum += s_row[(lr + d) * kBoxTC + lc];
-        B[base + (size_t)gr * C + gc] = sum;
-    }
+    box_sum_tile<kMaxHalfScale>(V + base, B + base, R, C, hs, blockIdx.y * kBoxTR, blockIdx.x * kBoxTC);
 }
 
 __global__ __launch_bounds__(kThreads) void k_assign_pick(AssignArgs a, const uint32_t* __restrict__ B, int min_score,
@@ -135,15 +111,10 @@ __global__ __launch_bounds__(kThreads) void k_assign_pick(AssignArgs a, const ui
             changed += g != e.pri[j];
             top = max(top, best[j]);
         }
-        // one LDS add per distinct id of the wave.  `pending` is the same in all 64 lanes: the loop is wave-uniform and ends after
-        // at most 64 rounds (every round clears at least the leader's bit)
-        unsigned long long pending = __ballot(slot >= 0);
-        while (pending) {
-            const int k0 = __shfl(slot, __ffsll((long long)pending) - 1, 64);
-            const unsigned long long same = __ballot(slot == k0);
+        // one LDS add per distinct id of the wave
+        for_each_wave_key(slot, [&](int k0, unsigned long long same) {
             if ((threadIdx.x & 63) == 0) atomicAdd(&s_out[k0], (uint32_t)__popcll(same));
-            pending &= ~same;
-        }
+        });
     }
     changed = (int)wave_sum((long long)changed);
     top = wave_max(top);

@@ -1,7 +1,85 @@
-// bf_assign_abi.cpp -- C-ABI of the assignment step (include/bf_accel.h, "event groups: assignment"; kernels in bf_assign.hip):
-// bf_assign_groups gives every event of the uploaded slice to one of K candidate models, and may install the result as the
-// context's grouping for bf_run_groups.
+// bf_assign_abi.cpp -- C-ABI of the two entries that work on the K models' vote planes (include/bf_accel.h, "event groups:
+// assignment" and "event groups: projection"; kernels in bf_assign.hip and bf_project.hip):
+//   bf_assign_groups   gives every event of the uploaded slice to one of K candidate models, and may install the result as the
+//                      context's grouping for bf_run_groups;
+//   bf_project_groups  renders the slice with every event warped by its own group's model -- per pixel the event count, the
+//                      owning group and its colour -- and scores it: per group and overall the integer moments of that image.
+// What they share is here once: the option checks, the window of the widened sensor and its capacity check (vote_planes_check),
+// and the planes, the staged warps and the kernels' AssignArgs (vote_planes_stage).  Between the two each entry zeroes its own
+// outputs and applies its own rule for a slice without events.
 #include "bf_ctx.h"
+
+namespace {
+
+// The K-model vote planes of one call: the kernels' arguments, and the R x C window with its words per plane.
+struct VotePlanes {
+    AssignArgs a;
+    int R, C;
+    size_t plane;
+};
+
+// The checks both entries make after those of their own pointers, in their order; `who`: the entry point's name; `knob`: the
+// entry's own option, which must be >= 1, and its name; `prior`: null when the held grouping is not read, else what the message
+// says before "no grouping ... is held".  Then the window and the capacity check.  Fills everything of vp but a's pointers.
+int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_y, int margin, const char* knob_name, int knob,
+                      int n_models, const char* prior, VotePlanes& vp) {
+    if (scale < 1 || scale % 2 == 0 || scale / 2 > kMaxHalfScale)
+        return fail(c, BF_ERR_ARG, "scale must be odd and <= %d (got %d)", 2 * kMaxHalfScale + 1, scale);
+    if (res_x < 1 || res_y < 1 || res_x > 65536 || res_y > 65536) return fail(c, BF_ERR_ARG, "bad sensor size");
+    if (margin < 0 || margin > 65536 || knob < 1)
+        return fail(c, BF_ERR_ARG, "%s: margin %d (0 .. 65536), %s %d (>= 1)", who, margin, knob_name, knob);
+    if (n_models < 1 || n_models > kAssignMaxModels) return fail(c, BF_ERR_ARG, "%s: %d models (1 .. %d)", who, n_models, kAssignMaxModels);
+    if (c->has_noise) return fail(c, BF_ERR_ARG, "%s does not take a noise mask", who);
+    const int K = n_models;
+    if (prior) {
+        if (!c->groups_valid) return fail(c, BF_ERR_STATE, "%s: %sno grouping of the uploaded slice is held", who, prior);
+        if (c->groups_K != K) return fail(c, BF_ERR_ARG, "%s: the held grouping has %d groups, %d models given", who, c->groups_K, K);
+    }
+    // the window of the whole sensor widened by the margin (optimizer_rolling.h:248-283): the same for every call on a sensor
+    const bf_window w = window_of_box(scale, -margin, res_x - 1 + margin, -margin, res_y - 1 + margin);
+    vp.R = w.scale_img_x;
+    vp.C = w.scale_img_y;
+    vp.plane = (size_t)vp.R * (size_t)vp.C;
+    if ((long long)K * (long long)vp.plane > kAssignMaxWords)
+        return fail(c, BF_ERR_CAPACITY, "%s: %d planes of %d x %d exceed 2^27 words", who, K, vp.R, vp.C);
+    AssignArgs& a = vp.a;
+    a.xy = nullptr; a.t = nullptr; a.perm = nullptr; a.wp = nullptr;
+    a.prior = nullptr;
+    a.n = c->n;
+    a.K = K; a.scale = scale;
+    a.x_sh = (int)w.x_shift;   // double -> int parameter conversion of accel_lib.h:147
+    a.y_sh = (int)w.y_shift;
+    a.wsx = w.metric_wsizex; a.wsy = w.metric_wsizey;
+    a.R = vp.R; a.C = vp.C;
+    return BF_OK;
+}
+
+// (n > 0, the device set) The vote planes grown and V cleared, the box planes grown when they are used, the K warps staged, and
+// a's pointers; `prior`: the held grouping is the kernels' prior.
+int vote_planes_stage(bf_ctx* c, const bf_model* models, bool prior, VotePlanes& vp) {
+    AssignArgs& a = vp.a;
+    const size_t words = (size_t)a.K * vp.plane;
+    HIP_TRY(c, c->d_assign_votes.grow(words));
+    if (a.scale > 1) HIP_TRY(c, c->d_assign_box.grow(words));
+    HIP_TRY(c, c->d_assign_wp.grow((size_t)kAssignMaxModels));
+    HIP_TRY(c, c->h_assign_wp.grow((size_t)kAssignMaxModels));
+    for (int k = 0; k < a.K; ++k) set_model_warp(c->h_assign_wp[k], models[k]);   // (sine and cosine from the host's libm)
+    HIP_TRY(c, hipMemcpyAsync(c->d_assign_wp, c->h_assign_wp, (size_t)a.K * sizeof(WarpParams), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_assign_votes, 0, words * sizeof(uint32_t), c->stream));
+    const bf_ctx::EvSet& e = c->set[c->cs];
+    a.xy = e.xy; a.t = e.t;
+    a.perm = c->has_perm ? e.perm.get() : nullptr;
+    a.wp = c->d_assign_wp;
+    a.prior = prior ? c->d_group_id.get() : nullptr;
+    return BF_OK;
+}
+
+// The planes the second kernel of either entry reads: the box sums, or V itself at scale 1.
+const uint32_t* vote_planes_summed(bf_ctx* c, const VotePlanes& vp) {
+    return vp.a.scale > 1 ? c->d_assign_box.get() : c->d_assign_votes.get();
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -10,26 +88,12 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
     if (!c) return BF_ERR_ARG;
     if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_assign_groups before bf_upload_events");
     if (!o || !models) return fail(c, BF_ERR_ARG, "bf_assign_groups: opts %p, models %p", (const void*)o, (const void*)models);
-    if (o->scale < 1 || o->scale % 2 == 0 || o->scale / 2 > kMaxHalfScale)
-        return fail(c, BF_ERR_ARG, "scale must be odd and <= %d (got %d)", 2 * kMaxHalfScale + 1, o->scale);
-    if (o->sensor_res_x < 1 || o->sensor_res_y < 1 || o->sensor_res_x > 65536 || o->sensor_res_y > 65536)
-        return fail(c, BF_ERR_ARG, "bad sensor size");
-    if (o->margin < 0 || o->margin > 65536 || o->min_score < 1)
-        return fail(c, BF_ERR_ARG, "bf_assign_groups: margin %d (0 .. 65536), min_score %d (>= 1)", o->margin, o->min_score);
-    if (n_models < 1 || n_models > kAssignMaxModels)
-        return fail(c, BF_ERR_ARG, "bf_assign_groups: %d models (1 .. %d)", n_models, kAssignMaxModels);
-    if (c->has_noise) return fail(c, BF_ERR_ARG, "bf_assign_groups does not take a noise mask");
-    const int K = n_models;
-    if (o->use_prior) {
-        if (!c->groups_valid) return fail(c, BF_ERR_STATE, "bf_assign_groups: use_prior, but no grouping of the uploaded slice is held");
-        if (c->groups_K != K) return fail(c, BF_ERR_ARG, "bf_assign_groups: the held grouping has %d groups, %d models given", c->groups_K, K);
-    }
-    // the window of the whole sensor widened by the margin (optimizer_rolling.h:248-283): the same for every call on a sensor
-    const bf_window w = window_of_box(o->scale, -o->margin, o->sensor_res_x - 1 + o->margin, -o->margin, o->sensor_res_y - 1 + o->margin);
-    const int R = w.scale_img_x, C = w.scale_img_y;
-    const long long plane = (long long)R * C;
-    if ((long long)K * plane > kAssignMaxWords)
-        return fail(c, BF_ERR_CAPACITY, "bf_assign_groups: %d planes of %d x %d exceed 2^27 words", K, R, C);
+    VotePlanes vp;
+    int rc = vote_planes_check(c, "bf_assign_groups", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "min_score",
+                               o->min_score, n_models, o->use_prior ? "use_prior, but " : nullptr, vp);
+    if (rc != BF_OK) return rc;
+    const AssignArgs& a = vp.a;
+    const int K = a.K;
 
     if (counts_out) memset(counts_out, 0, ((size_t)K + 1) * sizeof(int32_t));
     if (info) memset(info, 0, sizeof(*info));
@@ -44,42 +108,19 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
         return BF_OK;
     }
 
-    const size_t words = (size_t)K * (size_t)plane;
     const int nout = assign_out_words(K);
-    HIP_TRY(c, c->d_assign_votes.grow(words));
-    if (o->scale > 1) HIP_TRY(c, c->d_assign_box.grow(words));
-    HIP_TRY(c, c->d_assign_wp.grow((size_t)kAssignMaxModels));
-    HIP_TRY(c, c->h_assign_wp.grow((size_t)kAssignMaxModels));
+    rc = vote_planes_stage(c, models, o->use_prior != 0, vp);
+    if (rc != BF_OK) return rc;
     HIP_TRY(c, c->d_assign_gid.grow((size_t)c->n));
     HIP_TRY(c, c->d_assign_score.grow((size_t)c->n));
     HIP_TRY(c, c->d_assign_out.grow((size_t)assign_out_words(kAssignMaxModels)));
     HIP_TRY(c, c->h_assign_out.grow((size_t)assign_out_words(kAssignMaxModels)));
-    for (int k = 0; k < K; ++k) {   // set_model's warp (optimizer_rolling.h:289-299), sine and cosine from the host's libm
-        const bf_model& m = models[k];
-        set_warp(c->h_assign_wp[k], -m.total_dx, -m.total_dy, m.cx, m.cy, m.total_div, -m.total_rot);
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_assign_wp, c->h_assign_wp, (size_t)K * sizeof(WarpParams), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_assign_votes, 0, words * sizeof(uint32_t), s));
     HIP_TRY(c, hipMemsetAsync(c->d_assign_out, 0, (size_t)nout * sizeof(uint32_t), s));
-
-    const bf_ctx::EvSet& e = c->set[c->cs];
-    AssignArgs a;
-    a.xy = e.xy; a.t = e.t;
-    a.perm = c->has_perm ? e.perm.get() : nullptr;
-    a.wp = c->d_assign_wp;
-    a.prior = o->use_prior ? c->d_group_id.get() : nullptr;
-    a.n = c->n;
-    a.K = K; a.scale = o->scale;
-    a.x_sh = (int)w.x_shift;   // double -> int parameter conversion of accel_lib.h:147
-    a.y_sh = (int)w.y_shift;
-    a.wsx = w.metric_wsizex; a.wsy = w.metric_wsizey;
-    a.R = R; a.C = C;
     {
         ProfScope ps(c, 3);
         launch_assign_vote(a, c->d_assign_votes, s);
-        if (o->scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, R, C, o->scale, s);
-        launch_assign_pick(a, o->scale > 1 ? c->d_assign_box.get() : c->d_assign_votes.get(), o->min_score, c->d_assign_gid,
-                           c->d_assign_score, c->d_assign_out, s);
+        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
+        launch_assign_pick(a, vote_planes_summed(c, vp), o->min_score, c->d_assign_gid, c->d_assign_score, c->d_assign_out, s);
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(c->h_assign_out, c->d_assign_out, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -100,11 +141,84 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
         for (int k = 0; k <= K; ++k) counts_out[k] = (int32_t)r[k];
     if (info) {
         info->models = K;
-        info->rows = R; info->cols = C;
+        info->rows = vp.R; info->cols = vp.C;
         info->unassigned = (int32_t)r[K];
         info->assigned = (int32_t)(c->n - (long long)r[K]);
         info->changed = (int32_t)r[K + 1];
         info->max_score = (int32_t)r[K + 2];
+    }
+    return BF_OK;
+}
+
+int bf_project_groups(bf_ctx* c, const bf_project_opts* o, const bf_model* models, int32_t n_models, uint32_t* count_out,
+                      int32_t* label_out, uint8_t* bgr_out, bf_group_score* scores_out, bf_project_info* info) {
+    if (!c) return BF_ERR_ARG;
+    if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_project_groups before bf_upload_events");
+    if (!o || !models) return fail(c, BF_ERR_ARG, "bf_project_groups: opts %p, models %p", (const void*)o, (const void*)models);
+    VotePlanes vp;
+    int rc = vote_planes_check(c, "bf_project_groups", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "gain", o->gain,
+                               n_models, "", vp);   // (the held grouping is required: here an event's ONE model)
+    if (rc != BF_OK) return rc;
+    const AssignArgs& a = vp.a;
+    const int K = a.K;
+    const size_t plane = vp.plane;
+
+    if (scores_out) memset(scores_out, 0, (size_t)K * sizeof(bf_group_score));
+    if (info) memset(info, 0, sizeof(*info));
+    if (c->n == 0) {   // N == 0 everywhere
+        if (count_out) memset(count_out, 0, plane * sizeof(uint32_t));
+        if (label_out) memset(label_out, 0xff, plane * sizeof(int32_t));
+        if (bgr_out) memset(bgr_out, 0, 3 * plane);
+        return BF_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+
+    const int nout = project_out_words(K);
+    rc = vote_planes_stage(c, models, true, vp);
+    if (rc != BF_OK) return rc;
+    HIP_TRY(c, c->d_project_count.grow(plane));
+    HIP_TRY(c, c->d_project_label.grow(plane));
+    HIP_TRY(c, c->d_project_bgr.grow(3 * plane));
+    HIP_TRY(c, c->d_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
+    HIP_TRY(c, c->h_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
+    HIP_TRY(c, hipMemsetAsync(c->d_project_out, 0, (size_t)nout * sizeof(unsigned long long), s));
+    {
+        ProfScope ps(c, 3);
+        launch_project_vote(a, c->d_assign_votes, c->d_project_out, s);
+        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
+        launch_project_compose(vote_planes_summed(c, vp), K, vp.R, vp.C, o->gain, c->d_project_count, c->d_project_label,
+                               c->d_project_bgr, c->d_project_out, s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->h_project_out, c->d_project_out, (size_t)nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, c->d_project_count, plane * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (label_out) HIP_TRY(c, hipMemcpyAsync(label_out, c->d_project_label, plane * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (bgr_out) HIP_TRY(c, hipMemcpyAsync(bgr_out, c->d_project_bgr, 3 * plane, hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const unsigned long long* h = c->h_project_out;
+    auto r = [h](int word) { return h[(size_t)word * kProjectStride]; };
+    long long outside = 0;
+    for (int k = 0; k < K; ++k) {
+        outside += (long long)r(k) - (long long)r(K + k);
+        if (!scores_out) continue;
+        bf_group_score& g = scores_out[k];
+        g.events = (int32_t)r(k);
+        g.inside = (int32_t)r(K + k);
+        g.pixels_hit = (int32_t)r(2 * K + k);
+        g.pixels_owned = (int32_t)r(3 * K + k);
+        g.max = (int32_t)r(4 * K + k);
+        g.sum_sq = r(5 * K + k);
+    }
+    if (info) {
+        const int t = kProjectTables * K;
+        info->models = K;
+        info->rows = vp.R; info->cols = vp.C;
+        info->unassigned = (int32_t)r(t);
+        info->outside = (int32_t)outside;
+        info->pixels = (int32_t)r(t + 1);
+        info->sum = r(t + 2);
+        info->sum_sq = r(t + 3);
     }
     return BF_OK;
 }

@@ -1,5 +1,5 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp, bf_propose_abi.cpp, bf_project_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
+// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp, bf_propose_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
 // (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
@@ -463,6 +463,11 @@ void set_warp(WarpParams& w, double dnx, double dny, double cx, double cy, doubl
     w.dnx = dnx; w.dny = dny; w.cx = cx; w.cy = cy; w.div = div;
     w.c = std::cos(angle);
     w.s = std::sin(angle);
+}
+// set_model's warp (optimizer_rolling.h:289-299): the ONE place a bf_model becomes a warp (bf_set_model, a tile's warm start,
+// the K models of bf_assign_groups / bf_project_groups)
+void set_model_warp(WarpParams& w, const bf_model& m) {
+    set_warp(w, -m.total_dx, -m.total_dy, m.cx, m.cy, m.total_div, -m.total_rot);
 }
 
 WarpParams identity_warp() {

@@ -1,4 +1,6 @@
-// bf_device_fns.h -- device-side helpers shared by the kernel files.
+// bf_device_fns.h -- device-side helpers shared by the kernel files.  Of the event-group stages (bf_segment.hip, bf_assign.hip,
+// bf_propose.hip, bf_project.hip): the wave reductions, the tally per distinct key of a wave (for_each_wave_key) and the box sum
+// of a tile (box_sum_tile).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <limits.h>
@@ -158,6 +160,71 @@ __device__ __forceinline__ long long wave_sum(long long v) {
 __device__ __forceinline__ double wave_sum(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
+}
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_down(v, o, 64));
+    return v;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long w = (unsigned long long)__shfl_down((long long)v, o, 64);
+        v = w > v ? w : v;
+    }
+    return v;
+}
+
+// f(k0, same) once per distinct key of the wave, in the order of each key's first lane: k0 the key, `same` the ballot of the lanes
+// that hold it.  A key below 0 is no key.  EVERY lane of the wave must reach the call (no caller branches around it on anything
+// that differs between lanes), so the ballots see all 64; `pending` is then the same in all 64 lanes, the loop is wave-uniform,
+// and it ends after at most 64 rounds: every round clears at least the leader's bit.  f runs in all lanes (a lane belongs to
+// the round iff key == k0) and may itself ballot, reduce over the wave and keep wave-uniform state across rounds.
+template <class F>
+__device__ __forceinline__ void for_each_wave_key(int key, F&& f) {
+    unsigned long long pending = __ballot(key >= 0);
+    while (pending) {
+        const int k0 = __shfl(key, __ffsll((long long)pending) - 1, 64);
+        const unsigned long long same = __ballot(key == k0);
+        f(k0, same);
+        pending &= ~same;
+    }
+}
+
+// The box sum of one 32 x 64 tile: dst = the (2 hs + 1)^2 box sum of src (R x C words, zero beyond the plane) at the tile whose
+// origin is (tr0, tc0); every word of dst inside the plane is written.  The tile plus a halo of hs <= MAXH in LDS, row sums, then
+// column sums; the whole work-group (kThreads) calls it.  k_assign_box and k_propose_box differ in MAXH and in how a
+// work-group finds its plane and tile.
+constexpr int kBoxTR = 32, kBoxTC = 64;
+template <int MAXH>
+__device__ __forceinline__ void box_sum_tile(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int R, int C, int hs,
+                                             int tr0, int tc0) {
+    __shared__ uint32_t s_in[(kBoxTR + 2 * MAXH) * (kBoxTC + 2 * MAXH)];
+    __shared__ uint32_t s_row[(kBoxTR + 2 * MAXH) * kBoxTC];
+    const int IR = kBoxTR + 2 * hs, IC = kBoxTC + 2 * hs;
+    for (int idx = threadIdx.x; idx < IR * IC; idx += kThreads) {
+        const int lr = idx / IC, lc = idx - lr * IC;
+        const int gr = tr0 - hs + lr, gc = tc0 - hs + lc;
+        s_in[idx] = (gr >= 0 && gr < R && gc >= 0 && gc < C) ? src[(size_t)gr * C + gc] : 0u;   // (zero beyond the plane)
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < IR * kBoxTC; idx += kThreads) {
+        const int lr = idx / kBoxTC, lc = idx % kBoxTC;
+        uint32_t sum = 0;
+        for (int d = 0; d <= 2 * hs; ++d) sum += s_in[lr * IC + lc + d];
+        s_row[idx] = sum;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < kBoxTR * kBoxTC; idx += kThreads) {
+        const int lr = idx / kBoxTC, lc = idx % kBoxTC;
+        const int gr = tr0 + lr, gc = tc0 + lc;
+        if (gr >= R || gc >= C) continue;
+        uint32_t sum = 0;
+        for (int d = 0; d <= 2 * hs; ++d) sum += s_row[(lr + d) * kBoxTC + lc];
+        dst[(size_t)gr * C + gc] = sum;
+    }
 }
 
 // Row -> bin row of the tile-binned loops: exact division by the (not necessarily power-of-two) tile height.

@@ -335,7 +335,7 @@ int bf_run_groups(bf_ctx* c, const bf_group_opts* o, const bf_model* warm, int32
         auto warm_state = [&](const bf_model& m) {   // bf_set_model (optimizer_rolling.h:289-299) on the reset state
             DevState w = tmpl;
             w.model = m;
-            set_warp(w.hot.wp, -m.total_dx, -m.total_dy, m.cx, m.cy, m.total_div, -m.total_rot);
+            set_model_warp(w.hot.wp, m);
             return w;
         };
         // the claim order: descending event count, so that the longest loops start first

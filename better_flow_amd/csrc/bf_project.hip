@@ -1,7 +1,8 @@
 // bf_project.hip -- the slice with every event warped by its OWN group's model: the picture and the objective of motion
 // segmentation by motion compensation.  The definitions are in include/bf_accel.h ("event groups: projection") and DESIGN.md
-// section 17; the C-ABI around these kernels is in bf_project_abi.cpp.  After an event's pixel everything is an integer count, a
-// sum, a maximum or a smallest index, so no result depends on the order work-groups or waves run in.
+// section 17; the C-ABI around these kernels is in bf_assign_abi.cpp.  After an event's pixel everything is an integer count, a
+// sum, a maximum or a smallest index, so no result depends on the order work-groups or waves run in.  The per-id tallies are
+// for_each_wave_key's and the wave reductions bf_device_fns.h's.
 //
 //   P1 k_project_vote     four events per thread.  The model differs per event (ids are interleaved in upload order), so the K
 //                         warps sit in LDS and each lane reads its group's (a loop over the wave's distinct ids with the warp on
@@ -33,15 +34,6 @@ constexpr int kComposeThreads = 1024;
 constexpr int kComposeMaxGroups = 512;
 
 __constant__ uint8_t c_palette[BF_PROJECT_PALETTE_SIZE][3] = BF_PROJECT_PALETTE;
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_down(v, o, 64));
-    return v;
-}
 
 __global__ __launch_bounds__(kThreads) void k_project_vote(AssignArgs a, uint32_t* __restrict__ V,
                                                            unsigned long long* __restrict__ out) {
@@ -76,19 +68,14 @@ __global__ __launch_bounds__(kThreads) void k_project_vote(AssignArgs a, uint32_
             key = assign_pixel(wp, v, t, a.scale, a.x_sh, a.y_sh, a.wsx, a.wsy, a.C);
             if (key >= 0) atomicAdd(V + (size_t)slot * plane + key, 1u);
         }
-        // one round per distinct id of the wave.  `pending` is the same in all 64 lanes: the loop is wave-uniform and ends after
-        // at most 64 rounds (every round clears at least the leader's bit)
-        unsigned long long pending = __ballot(slot >= 0);
-        while (pending) {
-            const int k0 = __shfl(slot, __ffsll((long long)pending) - 1, 64);
-            const unsigned long long same = __ballot(slot == k0);
+        // one round per distinct id of the wave
+        for_each_wave_key(slot, [&](int k0, unsigned long long same) {
             const unsigned long long in = __ballot(slot == k0 && key >= 0);
             if ((threadIdx.x & 63) == 0) {
                 atomicAdd(&s_cnt[k0], (uint32_t)__popcll(same));
                 if (in) atomicAdd(&s_cnt[K + 1 + k0], (uint32_t)__popcll(in));   // (k0 < K: an unassigned event has no key)
             }
-            pending &= ~same;
-        }
+        });
     }
     __syncthreads();
     for (int w = threadIdx.x; w < 2 * K + 1; w += kThreads) {
@@ -144,13 +131,9 @@ __global__ __launch_bounds__(kComposeThreads) void k_project_compose(const uint3
 #pragma unroll
             for (int c = 0; c < 3; ++c) bgr[3 * (size_t)p + c] = (uint8_t)((uint32_t)c_palette[col][c] * level / 255u);
         }
-        unsigned long long pending = __ballot(arg >= 0);   // one LDS add per distinct label of the wave, as above
-        while (pending) {
-            const int k0 = __shfl(arg, __ffsll((long long)pending) - 1, 64);
-            const unsigned long long same = __ballot(arg == k0);
+        for_each_wave_key(arg, [&](int k0, unsigned long long same) {   // one LDS add per distinct label of the wave
             if (leader) atomicAdd(&s_own[k0], (uint32_t)__popcll(same));
-            pending &= ~same;
-        }
+        });
         t_px += N > 0;
         t_sum += N;
         t_sq += (unsigned long long)N * N;

@@ -11,8 +11,8 @@
 //                        global  the tables read from memory, one global atomic without a return value per vote.
 //                      (Folding the lanes that share the wave's most frequent bins into one add each is the BF_PROPOSE_FOLD
 //                      build: DESIGN section 16 has the A/B.)
-//   P2 k_propose_box   B = the (2 r + 1)^2 box sum of H: a 32 x 64 tile plus a halo of r in LDS, row sums, then column sums --
-//                      the shape of k_assign_box.  Every word of B is written.
+//   P2 k_propose_box   B = the (2 r + 1)^2 box sum of H: box_sum_tile (bf_device_fns.h), k_assign_box's routine, with a halo of
+//                      at most kProposeMaxRadius and all tiles on one grid axis.  Every word of B is written.
 //   P3 k_propose_pick  one work-group of 1024 threads, max_models rounds over B: per thread the largest (B, lowest index) of its
 //                      words that no earlier pick suppresses (the list of picks is in LDS; a word is tested against it only when
 //                      it would beat the thread's best), then a wave and a work-group maximum of the 64-bit key.  A lattice of at
@@ -31,7 +31,6 @@ namespace {
 
 constexpr int kProposeEv = 4;                     // events per thread and round
 constexpr int kProposeBlocks = 512;               // at most: the work-groups stride over the slice
-constexpr int kPBoxTR = 32, kPBoxTC = 64;         // tile of k_propose_box
 constexpr int kPickThreads = 1024;
 constexpr int kPickRegs = 16;                     // words of B a thread of k_propose_pick keeps in registers (small lattices)
 
@@ -151,45 +150,15 @@ __global__ __launch_bounds__(kThreads) void k_propose_vote_global(ProposeArgs a,
 }
 
 __global__ __launch_bounds__(kThreads) void k_propose_box(const uint32_t* __restrict__ H, uint32_t* __restrict__ B, int R, int C, int hs) {
-    __shared__ uint32_t s_in[(kPBoxTR + 2 * kProposeMaxRadius) * (kPBoxTC + 2 * kProposeMaxRadius)];
-    __shared__ uint32_t s_row[(kPBoxTR + 2 * kProposeMaxRadius) * kPBoxTC];
     // (the tiles as one grid axis, row of tiles major: a lattice of 2^22 x 1 has more tile rows than a grid's second axis takes)
-    const int tiles_c = (C + kPBoxTC - 1) / kPBoxTC;
-    const int tr0 = (int)(blockIdx.x / (unsigned)tiles_c) * kPBoxTR, tc0 = (int)(blockIdx.x % (unsigned)tiles_c) * kPBoxTC;
-    const int IR = kPBoxTR + 2 * hs, IC = kPBoxTC + 2 * hs;
-    for (int idx = threadIdx.x; idx < IR * IC; idx += kThreads) {
-        const int lr = idx / IC, lc = idx - lr * IC;
-        const int gr = tr0 - hs + lr, gc = tc0 - hs + lc;
-        s_in[idx] = (gr >= 0 && gr < R && gc >= 0 && gc < C) ? H[(size_t)gr * C + gc] : 0u;   // (zero outside the lattice)
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < IR * kPBoxTC; idx += kThreads) {
-        const int lr = idx / kPBoxTC, lc = idx % kPBoxTC;
-        uint32_t sum = 0;
-        for (int d = 0; d <= 2 * hs; ++d) sum += s_in[lr * IC + lc + d];
-        s_row[idx] = sum;
-    }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < kPBoxTR * kPBoxTC; idx += kThreads) {
-        const int lr = idx / kPBoxTC, lc = idx % kPBoxTC;
-        const int gr = tr0 + lr, gc = tc0 + lc;
-        if (gr >= R || gc >= C) continue;
-        uint32_t sum = 0;
-        for (int d = 0; d <= 2 * hs; ++d) sum += s_row[(lr + d) * kPBoxTC + lc];
-        B[(size_t)gr * C + gc] = sum;
-    }
+    const int tiles_c = (C + kBoxTC - 1) / kBoxTC;
+    box_sum_tile<kProposeMaxRadius>(H, B, R, C, hs, (int)(blockIdx.x / (unsigned)tiles_c) * kBoxTR,
+                                    (int)(blockIdx.x % (unsigned)tiles_c) * kBoxTC);
 }
 
 // The key of a word: the larger B wins, among equals the lower index; 0: nothing (an index is below 2^22, so a key never is 0).
 __device__ __forceinline__ unsigned long long pick_key(uint32_t b, int idx) {
     return ((unsigned long long)b << 32) | (unsigned long long)(0xffffffffu - (uint32_t)idx);
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long w = (unsigned long long)__shfl_down((long long)v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
 }
 
 // One word of B against the thread's best so far: it replaces it when its key is larger and none of the p picks suppresses it.
@@ -275,7 +244,7 @@ int launch_propose_vote(const ProposeArgs& a, uint32_t* H, uint32_t* out, hipStr
 }
 
 void launch_propose_box(const uint32_t* H, uint32_t* B, int n_x, int n_y, int radius, hipStream_t s) {
-    const dim3 grid((unsigned)((n_y + kPBoxTC - 1) / kPBoxTC) * (unsigned)((n_x + kPBoxTR - 1) / kPBoxTR));
+    const dim3 grid((unsigned)((n_y + kBoxTC - 1) / kBoxTC) * (unsigned)((n_x + kBoxTR - 1) / kBoxTR));
     hipLaunchKernelGGL(k_propose_box, grid, dim3(kThreads), 0, s, H, B, n_x, n_y, radius);
 }
 

@@ -543,7 +543,7 @@ int bf_set_model(bf_ctx* c, const bf_model* model) {
     }
     // optimizer_rolling.h:289-299: model <- m; warp(-total_dx, -total_dy, cx, cy, total_div, -total_rot)
     c->hst.model = *model;
-    set_warp(c->hst.hot.wp, -model->total_dx, -model->total_dy, model->cx, model->cy, model->total_div, -model->total_rot);
+    set_model_warp(c->hst.hot.wp, *model);
     c->pending_warp = true;
     return BF_OK;
 }

@@ -26,6 +26,7 @@
 //   S8 k_seg_events   four events per thread: the scatter kernel's own pixel, cl_id through perm, the components' event counts --
 //                     counted per distinct component of the wave with ballots, kept in registers while consecutive rounds name
 //                     the same component, then one atomic.
+// The three folds over a wave's distinct roots / components (S5, S7, S8) are for_each_wave_key's rounds (bf_device_fns.h).
 #include <hip/hip_runtime.h>
 #include <limits.h>
 
@@ -244,17 +245,11 @@ __global__ __launch_bounds__(kThreads) void k_seg_flatten(int32_t* lab, int32_t*
         }
         ++run;
     }
-    // the last run of every lane, folded per root over the wave: one atomic per distinct root.  (No lane has left the kernel;
-    // `pending` is the same in all 64 lanes, so the loop is wave-uniform and ends after at most 64 rounds: every round clears
-    // at least the leader's bit.)
-    unsigned long long pending = __ballot(cur >= 0);
-    while (pending) {
-        const int k0 = __shfl(cur, __ffsll((long long)pending) - 1, 64);
-        const bool mine = cur == k0;
-        const long long n = wave_sum((long long)(mine ? run : 0));
+    // the last run of every lane, folded per root over the wave: one atomic per distinct root.  (No lane has left the kernel.)
+    for_each_wave_key(cur, [&](int k0, unsigned long long) {
+        const long long n = wave_sum((long long)(cur == k0 ? run : 0));
         if ((threadIdx.x & 63) == 0) atomicAdd(&sz[k0], (int)n);
-        pending &= ~__ballot(mine);
-    }
+    });
 }
 
 // (found << 32 | kept) of the 8 consecutive pixels of a thread
@@ -384,22 +379,17 @@ __global__ __launch_bounds__(kThreads) void k_seg_stats(const int32_t* __restric
         if (++c == C) { c = 0; ++r; }
     }
     // the last run of every lane, folded per component over the wave with shuffles: one set of atomics per distinct component
-    // (one inside a large one).  No lane has left the kernel; `pending` is the same in all 64 lanes, so the loop is
-    // wave-uniform and ends after at most 64 rounds: every round clears at least the leader's bit.
-    unsigned long long pending = __ballot(cur >= 0);
-    while (pending) {
-        const int k0 = __shfl(cur, __ffsll((long long)pending) - 1, 64);
-        const bool mine = cur == k0;
+    // (one inside a large one).  No lane has left the kernel.
+    for_each_wave_key(cur, [&](int k0, unsigned long long) {
         SegAcc b;
         seg_acc_clear(b);
-        if (mine) b = a;
+        if (cur == k0) b = a;
         b.pixels = (int)wave_sum((long long)b.pixels);
         b.rmin = wave_min(b.rmin); b.rmax = wave_max(b.rmax);
         b.cmin = wave_min(b.cmin); b.cmax = wave_max(b.cmax);
         b.rsum = wave_sum(b.rsum); b.csum = wave_sum(b.csum); b.qsum = wave_sum(b.qsum);
         if ((threadIdx.x & 63) == 0) seg_acc_flush(table + k0, b);
-        pending &= ~__ballot(mine);
-    }
+    });
 }
 
 constexpr int kSegEvPerThread = 4;   // events per thread of k_seg_events (a work-group's are consecutive per round)
@@ -425,20 +415,15 @@ __global__ __launch_bounds__(kThreads) void k_seg_events(SegEvents e, const int3
             cl_id[up] = k;
         }
         if (!table) continue;
-        // one count per distinct component of the wave.  `pending` is the same in all 64 lanes: the loop is wave-uniform and
-        // ends after at most 64 rounds (every round clears at least the leader's bit).
-        unsigned long long pending = __ballot(k >= 0);
-        while (pending) {
-            const int k0 = __shfl(k, __ffsll((long long)pending) - 1, 64);
-            const unsigned long long same = __ballot(k == k0);
+        // one count per distinct component of the wave (`table` is a kernel argument: the whole wave is here or skipped it)
+        for_each_wave_key(k, [&](int k0, unsigned long long same) {
             if (k0 != acc_key) {
                 if (acc_cnt && (threadIdx.x & 63) == 0) atomicAdd(&table[acc_key].events, acc_cnt);
                 acc_key = k0;
                 acc_cnt = 0;
             }
             acc_cnt += __popcll(same);
-            pending &= ~same;
-        }
+        });
     }
     if (table && acc_cnt && (threadIdx.x & 63) == 0) atomicAdd(&table[acc_key].events, acc_cnt);
 }

@@ -169,6 +169,28 @@ def test_a_pile_beyond_sixteen_bits(accel_mod):
         a.close()
 
 
+@pytest.mark.parametrize("scale,margin", [(9, 1), (1, 0)])
+def test_a_small_odd_sensor_at_the_largest_scale(accel_mod, scale, margin):
+    """The smallest shape with the largest halo of k_assign_box (scale 9: 4 words), tiles cut on both axes of the 315 x 603 window
+    (9 x 32 + 27 rows, 9 x 64 + 27 columns) and a last wave of 44 events; scale 1 is the same slice without the box sum."""
+    res, n = (33, 65), 300
+    rng = np.random.default_rng(11)
+    sl = dict(fr_x=rng.integers(0, res[0], n).astype(np.int32), fr_y=rng.integers(0, res[1], n).astype(np.int32),
+              t=np.sort(rng.integers(0, 30_000_000, n)).astype(np.int64))
+    ms = [gr.oracle.Model(), ar.model_of_velocity((150.0, -80.0)), ar.model_of_velocity((-90.0, 40.0))]
+    a = accel_mod.Accel(device=0, max_events=n, max_rows=640, max_cols=640)
+    try:
+        upload(a, sl)
+        r1 = ar.assign(sl, ms, scale, res, margin)
+        assert (r1[3]["rows"], r1[3]["cols"]) == (scale * (res[0] - 1 + 2 * margin) + scale, scale * (res[1] - 1 + 2 * margin) + scale)
+        assert len(set(r1[0].tolist())) > 1, "the models must compete"
+        same(a.assign_groups(to_accel(accel_mod, ms), scale, res, margin=margin), r1, "first round")
+        r2 = ar.assign(sl, ms, scale, res, margin, prior=r1[0])
+        same(a.assign_groups(to_accel(accel_mod, ms), scale, res, margin=margin, use_prior=True), r2, "round with a prior")
+    finally:
+        a.close()
+
+
 # ---- 4. storage order, repeatability, state ----
 
 def test_sorted_storage_gives_the_same_bytes_and_two_runs_agree(accel_mod, sc, acc):
