@@ -145,6 +145,35 @@ __device__ __forceinline__ T sload(const T* p) {
     return out;
 }
 
+// The kernel's own argument block, for a branch that is rarely taken (or for the kernel's tail): a struct argument is fetched
+// into scalar registers at the kernel's entry, every field any path uses, and held to its last use -- the pointers of the
+// overflow path, say, across the whole event loop.  A CU admits 8 waves per SIMD only up to 80 scalar registers
+// (MI355X_MICROARCH.md, "Residency"), so such fields are read again WHERE they are used, with scalar loads from the argument
+// block (a line of the scalar cache the entry's loads have already brought in).  `offset`: the struct argument's byte offset
+// among the kernel's arguments.  The empty asm pins the address to the place of the call: without it the loads -- from memory
+// that is known to be readable and constant -- are hoisted to the entry again.
+template <class A>
+__device__ __forceinline__ const A* late_args(unsigned offset) {
+    uintptr_t k = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr());
+    asm volatile("" : "+s"(k));
+    return reinterpret_cast<const A*>(k + offset);
+}
+
+// A pointer read through late_args is one to global memory, as every pointer among the kernels' arguments is, but the compiler
+// no longer knows (it would access it with flat instructions, a full 64-bit vector address each): say so.
+template <class T>
+__device__ __forceinline__ T* as_global(T* p) {
+    typedef __attribute__((address_space(1))) T* gptr;
+    return (T*)reinterpret_cast<gptr>(reinterpret_cast<uintptr_t>(p));   // (by way of the integer: a cast pair would be folded away)
+}
+
+// A uniform value, held in scalar registers, that the optimizer must take as made HERE: it cannot look through to the loads
+// the value came from (and, say, combine them with a neighbour's into a vector operation).  No instruction.
+template <class T>
+__device__ __forceinline__ void uniform_here(T& v) {
+    asm volatile("" : "+s"(v));
+}
+
 __device__ __forceinline__ int wave_min(int v) {
     for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_down(v, o, 64));
     return v;

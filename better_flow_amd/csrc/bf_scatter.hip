@@ -77,17 +77,32 @@ __device__ __forceinline__ bool event_target(const ScatterHot& hs, float2* p, ui
     // accel_lib.h:157-158: hsc <= X < wsx + hsc and the same for Y -- one unsigned compare each
     return (unsigned)(X - hsc) < (unsigned)hs.wsx && (unsigned)(Y - hsc) < (unsigned)hs.wsy;
 }
+// BinScatterArgs follows the scatter kernels' three leading pointers (24 bytes) in the argument block: late_args
+constexpr unsigned kScatterArgsOffset = 24;
+static_assert(alignof(BinScatterArgs) == 8, "the argument struct starts right behind the three leading pointers");
 // the exact slow path: straight into the overflow planes
+// (LATE: its four arguments are fetched here, not held in scalar registers across the event loop -- late_args)
+template <bool LATE>
 __device__ __forceinline__ void overflow_add(const ScatterHot& hs, const BinScatterArgs& a, int X, int Y, unsigned long long dt) {
+    unsigned long long* ovf_plane = a.ovf_plane;
+    uint32_t *ovf_cplane = a.ovf_cplane, *ovf_bits = a.ovf_bits;
+    int ovf_pitch = a.ovf_pitch;
+    if constexpr (LATE) {
+        const BinScatterArgs* la = late_args<BinScatterArgs>(kScatterArgsOffset);
+        ovf_plane = as_global(sload(&la->ovf_plane));
+        ovf_cplane = as_global(sload(&la->ovf_cplane));
+        ovf_bits = as_global(sload(&la->ovf_bits));
+        ovf_pitch = sload(&la->ovf_pitch);
+    }
     const size_t kk = (size_t)X * (size_t)hs.C + (size_t)Y;
-    atomicAdd(&a.ovf_plane[kk], dt);
-    atomicAdd(&a.ovf_cplane[kk], 1u);
+    atomicAdd(&ovf_plane[kk], dt);
+    atomicAdd(&ovf_cplane[kk], 1u);
     // (the stencil kernel reads the planes only around pixels flagged here)
-    atomicOr(&a.ovf_bits[(size_t)X * (size_t)a.ovf_pitch + (size_t)(Y >> 5) + 1], 1u << (Y & 31));
+    atomicOr(&ovf_bits[(size_t)X * (size_t)ovf_pitch + (size_t)(Y >> 5) + 1], 1u << (Y & 31));
 }
 
 // Dense slabs: accumulate in the bin's LDS tile.
-template <bool WARP>
+template <bool WARP, bool LATE = false>
 __device__ __forceinline__ void scatter_event(const ScatterHot& hs, const ScatterGeo& sg, unsigned long long* s_tile,
                                               const BinScatterArgs& a, float2* p, uint32_t i, uint32_t v, int32_t ti,
                                               double pr_x, double pr_y, uint32_t& n_ovf) {
@@ -98,7 +113,7 @@ __device__ __forceinline__ void scatter_event(const ScatterHot& hs, const Scatte
     if (hs.bin_ok && (unsigned)lx < (unsigned)sg.LR && (unsigned)ly < (unsigned)sg.L) {
         atomicAdd(&s_tile[__mul24(lx, sg.L) + ly], (1ull << hs.bin_tbits) + dt);
     } else {   // drifted out of this bin's tile: exact, slow path
-        overflow_add(hs, a, X, Y, dt);
+        overflow_add<LATE>(hs, a, X, Y, dt);
         ++n_ovf;
     }
 }
@@ -133,7 +148,7 @@ __device__ __forceinline__ uint32_t list_event(const ScatterHot& hs, const Scatt
         return (uint32_t)(__mul24(lx, sg.L) + ly);
     }
     if (take_overflow) {
-        overflow_add(hs, a, X, Y, (unsigned long long)((long long)ti - hs.tmin));
+        overflow_add<false>(hs, a, X, Y, (unsigned long long)((long long)ti - hs.tmin));
         ++n_ovf;
     }
     return kNoEntry;
@@ -172,7 +187,7 @@ __device__ __forceinline__ void list_put(const ScatterHot& hs, const ScatterGeo&
         cidx[slot] = (uint16_t)code;
     } else {
         const int lx = row >= 2 * sg.LR ? row - 2 * sg.LR : (row >= sg.LR ? row - sg.LR : row);   // (key -> tile row; without zones key < LR)
-        overflow_add(hs, a, sg.X0 + lx, sg.Y0 + (int)code - __mul24(lx, sg.L), dt);
+        overflow_add<false>(hs, a, sg.X0 + lx, sg.Y0 + (int)code - __mul24(lx, sg.L), dt);
         ++n_ovf;
     }
 }
@@ -524,6 +539,21 @@ __global__ __launch_bounds__(THREADS) void k_bin_warp_scatter_lean(const uint32_
     ScatterHot hs;
     hs.done = h0.done; hs.bin_tbits = h0.bin_tbits; hs.bin_ok = h0.bin_ok; hs.fmt = h0.fmt; hs.scale = h0.scale; hs.C = h0.C;
     hs.wsx = h0.wsx; hs.wsy = h0.wsy; hs.x_sh = h0.x_sh; hs.y_sh = h0.y_sh; hs.tmin = h0.tmin; hs.wp = h0.wp;
+    // DIET: the instantiations the co-scheduled dense loop runs in every iteration but the first, kept under 80 scalar registers
+    // without a spill (8 waves per SIMD whatever shares the CU: MI355X_MICROARCH.md, "Residency"; the compiler had taken 98 - 106).
+    // Three things, none of which changes an arithmetic expression:
+    //  * the overflow path fetches its four arguments itself (overflow_add<true>) instead of holding them across the event loop;
+    //  * a dead slot is clamped and skipped by two separate tests (load_pass, scatter_pass), not one shared lane mask per event;
+    //  * the warp parameters and shifts are opaque to the optimizer from here on (uniform_here).  Seeing them as adjacent loads, the
+    //    SLP vectoriser turned the LAST event of a pass -- that one only -- into <2 x double> operations on (x, y), whose uniform
+    //    operands (c, c), (s, c), (div, div) and the f32 constants of div_127 were built in scalar registers ahead of the loop
+    //    and held across it for that one event: 12 registers.
+    constexpr bool DIET = WARP && FMT == 0 && U >= 4;
+    if constexpr (DIET) {
+        uniform_here(hs.wp.dnx); uniform_here(hs.wp.dny); uniform_here(hs.wp.cx); uniform_here(hs.wp.cy);
+        uniform_here(hs.wp.div); uniform_here(hs.wp.c); uniform_here(hs.wp.s);
+        uniform_here(hs.x_sh); uniform_here(hs.y_sh);
+    }
     const EvSetPtrs ev = a.sets.s[h0.cs ^ h0.flip];
     const uint32_t* __restrict__ xy = ev.xy;
     const int32_t* __restrict__ t = ev.t;
@@ -534,11 +564,17 @@ __global__ __launch_bounds__(THREADS) void k_bin_warp_scatter_lean(const uint32_
     uint32_t vxy[U];
     int32_t vt[U];
     float2 vp[U];
+    // (DIET) A dead slot (i >= end) loads the bin's LAST event -- what it loads is never used, any readable index serves -- and is
+    // skipped by a compare of its own, against a constant the instruction carries (scatter_pass): with `i < end` shared between
+    // the clamp and the skip, one lane mask per event -- two scalar registers -- stayed live from the loads to the event's
+    // turn, 2 U in all.  Same number of vector instructions per event either way.
+    const uint32_t last = end > beg ? end - 1 : beg;
     auto load_pass = [&](uint32_t base) {
 #pragma unroll
         for (int k = 0; k < U; ++k) {
             uint32_t i = base + k * THREADS + tid;
-            i = i < end ? i : beg;
+            if constexpr (DIET) i = min(i, last);
+            else i = i < end ? i : beg;
             vxy[k] = ld_idx(xy, i);
             vt[k] = ld_idx(t, i);
             vp[k] = ld_idx(p, i);
@@ -589,12 +625,16 @@ __global__ __launch_bounds__(THREADS) void k_bin_warp_scatter_lean(const uint32_
         return;
     }
     auto scatter_pass = [&](uint32_t base) {
+        // (DIET) this thread's slots 0 .. nslot - 1 hold events, i.e. base + k THREADS + tid < end (a bin holds < 2^29 events;
+        // nslot <= 0: none)
+        static_assert((THREADS & (THREADS - 1)) == 0, "slots by a shift");
+        const int nslot = ((int)(end - base) - tid + (THREADS - 1)) >> (31 - __builtin_clz(THREADS));
 #pragma unroll
         for (int k = 0; k < U; ++k) {
             const uint32_t i = base + k * THREADS + tid;
-            if (i >= end) continue;
-            scatter_event<WARP>(hs, sg, s_tile, a, p, i, vxy[k], vt[k], pr_from_p(vxy[k] & 0xffffu, vp[k].x),
-                                pr_from_p(vxy[k] >> 16, vp[k].y), n_ovf);
+            if (DIET ? k >= nslot : i >= end) continue;
+            scatter_event<WARP, DIET>(hs, sg, s_tile, a, p, i, vxy[k], vt[k], pr_from_p(vxy[k] & 0xffffu, vp[k].x),
+                                      pr_from_p(vxy[k] >> 16, vp[k].y), n_ovf);
         }
     };
     if constexpr (SPLIT) {

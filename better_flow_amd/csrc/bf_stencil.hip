@@ -44,6 +44,9 @@ struct K3Pre {
     int R, C, D, lg, nbc, nbr, LR, L, TSR;
     uint32_t mul_r;
 };
+// StencilArgs follows the twelve leading arguments (two pointers, ten words: 56 bytes) in the argument block: late_args
+constexpr unsigned kStencilArgsOffset = 56;
+static_assert(sizeof(K3Pre) == kStencilArgsOffset && alignof(StencilArgs) == 8, "the argument struct starts right behind the leading arguments");
 template <int HS, int MODE, int NT>   // MODE: what the scatter kernel wrote -- 0 dense slabs, 1 lists, 2 interior + margin plane
 __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const K3Pre& pre) {
     constexpr bool COMPACT = MODE == 1;
@@ -316,20 +319,31 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
     // zeroed, the execution mask saved and restored around each conditional load, three adds).  Integer sums: same bits.
     const uint32_t vo_lo = c_in ? (uint32_t)c_lo * 8u : 0u;
     const uint32_t vo_hi = (c_in && c_two) ? (uint32_t)c_hi * 8u : 0u;
-    bool rin[KR], rtwo[KR];   // (uniform)
+    // What the sums below need to know of a row -- inside the image (bit k), a second bin row (bit 8 + k) -- is kept as ONE word
+    // of bits: a uniform bool that lives across basic blocks is a lane mask, a PAIR of scalar registers, and the 2 KR of them
+    // (plus KR for "the wave has this row", which the sums now form again from the wave's number) were 30 of this kernel's
+    // scalar registers from the first load to the last sum.  Scalar-unit instructions either way.
+    static_assert(KR <= 8, "row bits");
+    uint32_t rowbits = 0;
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
+        bool r_in, r_two;   // (uniform)
         int r_lo, r_hi;
-        row_of(wv + k * NW, rin[k], rtwo[k], r_lo, r_hi);   // (uniform: scalar unit)
-        if (rin[k]) {
+        row_of(wv + k * NW, r_in, r_two, r_lo, r_hi);   // (uniform: scalar unit)
+        if (r_in) {
+            rowbits |= 1u << k;
             w[k][0] = buf_ld_u64(slab_buf, vo_lo, (uint32_t)r_lo * 8u);
             w[k][1] = buf_ld_u64(slab_buf, vo_hi, (uint32_t)r_lo * 8u);
-            if (rtwo[k]) {
+            if (r_two) {
+                rowbits |= 0x100u << k;
                 w[k][2] = buf_ld_u64(slab_buf, vo_lo, (uint32_t)r_hi * 8u);
                 w[k][3] = buf_ld_u64(slab_buf, vo_hi, (uint32_t)r_hi * 8u);
             }
         }
     }
+    int wv_s = wv;   // (the wave's number as the sums see it: not the value the row tests above were formed from)
+    uniform_here(rowbits);
+    uniform_here(wv_s);
 #pragma unroll
     for (int x = 0; x < XE; ++x) {   // the columns beyond the 64th: per-lane rows, so per-lane conditions as before
         const int e = lane + 64 * x;
@@ -353,12 +367,12 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
     // are outside that bound (they come from any bin): their planes are read unpacked below, only when there are any.
 #pragma unroll
     for (int k = 0; k < KR; ++k) {
-        const int pr = wv + k * NW;
+        const int pr = wv_s + k * NW;
         if (pr < PR) {
             unsigned long long sum = 0ull;
-            if (rin[k]) {
+            if (rowbits & (1u << k)) {
                 sum = w[k][0] + w[k][1];
-                if (rtwo[k]) sum += w[k][2] + w[k][3];
+                if (rowbits & (0x100u << k)) sum += w[k][2] + w[k][3];
             }
             s_acc[pr * PC + lane] = sum;
         }
@@ -416,14 +430,18 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
                 box_dirty = any != 0;
             }
             if (box_dirty) {   // rare: the overflow planes (u64 time sums, u32 counts) straight from memory, box by box
+                // (their addresses are fetched here, not held in scalar registers through the pixel loops: late_args)
+                const StencilArgs* la = late_args<StencilArgs>(kStencilArgsOffset);
+                const unsigned long long* const plane = as_global(sload(&la->plane));
+                const uint32_t* const cplane = as_global(sload(&la->cplane));
 #pragma unroll
                 for (int da = -HS; da <= HS; ++da)
 #pragma unroll
                     for (int db = -HS; db <= HS; ++db) {
                         const int pr_ = gr + da, pc_ = gc + db;
                         if (pr_ >= 0 && pr_ < R && pc_ >= 0 && pc_ < C) {
-                            acc += a.plane[(uint32_t)(__mul24(pr_, C) + pc_)];
-                            cacc += a.cplane[(uint32_t)(__mul24(pr_, C) + pc_)];
+                            acc += plane[(uint32_t)(__mul24(pr_, C) + pc_)];
+                            cacc += cplane[(uint32_t)(__mul24(pr_, C) + pc_)];
                         }
                     }
             }
@@ -476,17 +494,29 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
             if (tr < TH) time_px(tr, 64 + lane % XT, box_at(tr, 64 + lane % XT));
         }
     }
+    // The tail takes its arguments from the argument block again (late_args): two dozen scalar registers of pointers and switches
+    // that nothing above reads would otherwise be held from the kernel's entry, through the slab loads and the pixel loops, to
+    // here.  Requested ahead of the barrier, whose wait covers the fetch (the scalar cache holds the block since the entry).
+    StencilArgs ta = sload(late_args<StencilArgs>(kStencilArgsOffset));
+    ta.st = as_global(ta.st); ta.acc = as_global(ta.acc); ta.acc_zero = as_global(ta.acc_zero);
+    ta.ovf_cur = as_global(ta.ovf_cur); ta.ovf_prev = as_global(ta.ovf_prev); ta.ovf_next = as_global(ta.ovf_next);
+    ta.zero_plane = as_global(ta.zero_plane); ta.zero_cplane = as_global(ta.zero_cplane); ta.zero_bits = as_global(ta.zero_bits);
+    ta.ticket = as_global(ta.ticket); ta.st_rw = as_global(ta.st_rw); ta.snap = as_global(ta.snap);
+    ta.trace = as_global(ta.trace); ta.tl = as_global(ta.tl);
     __syncthreads();
-    tl_stamp(a.tl, a.tl_launch, 4);
-    const bool do_zero = a.zero_plane && sload(a.ovf_prev) != 0;   // the other plane buffer is dirty: clear it for the next iteration
+    tl_stamp(ta.tl, ta.tl_launch, 4);
+    const bool do_zero = ta.zero_plane && sload(ta.ovf_prev) != 0;   // the other plane buffer is dirty: clear it for the next iteration
     // (the accumulator plane is free from here on: the wave totals of the moment sums go through it)
     static_assert((size_t)PR * PC >= (size_t)(NT / 64) * 192, "the reduction's scratch fits the accumulator plane");
-    stencil_tail<TR, TC, NT, false>(a, s_time, s_red, r0, c0, do_zero, reinterpret_cast<double*>(s_acc));
+    stencil_tail<TR, TC, NT, false>(ta, s_time, s_red, r0, c0, do_zero, reinterpret_cast<double*>(s_acc));
 }
 
-// Two builds of each: as the compiler allocates it (~100 scalar registers: the rows live in the scalar unit), and with
+// Two builds of each: as the compiler allocates it (72 - 78 scalar registers without a spill since the row flags became bits
+// of one word and the tail fetches its own arguments; ~100 before), and with
 // the scalar registers capped at what lets a CU hold 8 work-groups of 256 threads (<= 80: 7 up to 96, 6 up to 112 --
-// MI355X_MICROARCH.md "Residency"; the surplus is spilled into vector-register lanes).  A launch that fills the GPU
+// MI355X_MICROARCH.md "Residency"; the surplus is spilled into vector-register lanes: none left for HS <= 1, where the two
+// builds are now the same code -- the split stays until a change of its own removes it).  The measurements below are of the
+// ~100-register plain build against the spilling capped one.  A launch that fills the GPU
 // several times over runs the capped build: measured on one box, same inputs, eight config-2 slices side by side 60.8
 // -> 56.2 us, 1280x720 (event lists) 57.4 -> 50.3 us per launch.  A launch of a few work-groups per CU is one
 // work-group's latency chain long and the spills only lengthen it (346x260: 13.4 -> 13.8 us): the plain build.
