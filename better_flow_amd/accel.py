@@ -266,6 +266,8 @@ BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
 BF_FLOW_FRAME_FLO = 4               # ... and bf_flow_frame_create's third
 BF_FLOW_LAST_UPLOADED, BF_FLOW_FIRST_UPLOADED = 0, 1   # owner_rule of the per-pixel flow
 BF_GLOBAL_HOLD_CELLS, BF_GLOBAL_HOLD_FIELD = 1, 2      # mode of bf_global_hold_field
+# bf_get_stat "loop_form": the loop the last bf_run took
+BF_LOOP_ATOMIC, BF_LOOP_BINNED, BF_LOOP_ONE_KERNEL, BF_LOOP_PERSISTENT, BF_LOOP_DELTA = 0, 1, 2, 3, 4
 
 _lib = None
 

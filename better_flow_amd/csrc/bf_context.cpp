@@ -204,6 +204,10 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         *value = plan_persistent(c) ? 1 : 0;
         return BF_OK;
     }
+    if (!strcmp(key, "loop_form")) {   // which loop the last bf_run took (BF_LOOP_*; -1: none yet, or the run was skipped)
+        *value = c->last_loop;
+        return BF_OK;
+    }
     if (!strcmp(key, "persist_giveups")) {   // launches of the persistent loop kernel that gave up and undid themselves
         *value = c->persist_giveups;
         return BF_OK;
@@ -257,6 +261,11 @@ int bf_set_option(bf_ctx* c, const char* key, int64_t value) {
             HIP_TRY(c, s.in16.grow((size_t)c->cap_events * 2));
             HIP_TRY(c, s.noise.grow((size_t)c->cap_events));   // (else: first use, possibly in the middle of a solve)
         }
+        return BF_OK;
+    }
+    if (!strcmp(key, "delta_scatter")) {
+        if (value < 0 || value > 2) return fail(c, BF_ERR_ARG, "delta_scatter must be 0 (never), 1 (auto) or 2 (always)");
+        c->opt_delta = (int)value;
         return BF_OK;
     }
     if (!strcmp(key, "sep_update")) {

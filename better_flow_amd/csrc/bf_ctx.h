@@ -202,6 +202,10 @@ struct bf_ctx {
     // staging kernels, the events: ~25 us of host time) are issued by the next bf_run once that run's first batch of kernels is in
     // the queue -- or by whoever needs the slot sooner (bf_commit_upload, bf_wait_uploads).  For a single-threaded caller
     // driving one warm-started chain those 25 us otherwise sit between two runs, with the GPU idle.
+    // delta scatter (bf_kernels.hip: k_warp_scatter_delta): the global-atomic loop on ONE plane buffer that is kept from launch
+    // to launch -- 0 never, 1 where it is the faster loop (bf_plan.cpp: plan_run), 2 whenever the slice has no noise mask
+    int opt_delta = 1;
+    int last_loop = -1;              // the loop form of the last bf_run (bf_get_stat "loop_form": BF_LOOP_*; -1: no run yet)
     int opt_sep_update = 1;          // co-scheduled contexts: the update as a kernel of its own -- 0 never, 1 for event lists, 2 always (plan_run)
     bool opt_defer_uploads = false;
     std::mutex stats_mu;                          // fold_stats: bf_set_cloud's thread and an uploading thread (stage_early) may both fold
@@ -348,6 +352,7 @@ struct SlicePlan {
 };
 struct RunPlan {
     bool fused = false, binned = false, persist = false;   // one-kernel iteration, tile-binned (either loop), persistent kernel
+    bool delta = false;              // the global-atomic loop (binned == false) as delta scatter: one plane buffer, kept up to date
     bool head_update = false, sep_update = false;   // the update at the next scatter launch's head / in k_finish_update
     bool split = false;              // the two-kernel loop on own pixels + margin plane (fmt 3)
     int bin_threads = 0, ev_per_thread = 8;   // the scatter kernel's work-group size and events per thread

@@ -132,6 +132,9 @@ void launch_project_dn(const uint32_t* xy, const int32_t* t, float2* p, double2*
 void launch_final_warp(const WarpScatterArgs& a, hipStream_t s);
 void launch_warp_scatter(const WarpScatterArgs& a, bool warp, bool scatter, bool write_n,
                          hipStream_t s);
+// delta scatter: warp, and move the events whose pixel changed on a plane that holds the image of the stored products
+// (xy, t, p, plane, cplane, st, n, check_done, packed of `a`; no noise mask, no permutation)
+void launch_warp_scatter_delta(const WarpScatterArgs& a, hipStream_t s);
 void launch_prepare(const int32_t* fr_x, const int32_t* fr_y, const int32_t* t_in, uint32_t* xy,
                     int32_t* t_out, float2* p, long long n, long long n_pad, SliceStats* stats,
                     hipStream_t s);
@@ -188,6 +191,8 @@ void launch_group_rest(const uint32_t* perm, const uint32_t* start, int K, doubl
 
 // bf_rebin.hip / bf_scatter.hip / bf_stencil.hip / bf_fused.hip (the tile-binned loops)
 int bin_kernel_setup();
+// k_stencil_binned on the packed image-linear plane `a.plane` (src 4 of launch_stencil; R * C * 8 < 2^31: 32-bit byte offsets)
+void launch_stencil_plane(const StencilArgs& a, dim3 grid, hipStream_t s);
 void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n_cus);   // (the build: bf_rules::stencil_capped)
 // interior + margin format: clear what the bins' lists name in `mplane`, empty the lists (a run that cannot rely on the
 // loop's own clean-up: the dirty margin plane is the one its first iteration adds to, or the bin grid changes)

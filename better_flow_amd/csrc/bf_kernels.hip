@@ -113,6 +113,98 @@ __global__ __launch_bounds__(kThreads) void k_warp_scatter(
     }
 }
 
+// ---- delta scatter ------------------------------------------------------------------------------------------------------
+// The plane words are exact integers (count << tbits | sum(t - tmin), or the two split planes), so an image that is kept
+// from launch to launch -- every event that changes its pixel taken off the old one and added to the new one -- holds the
+// bits a rebuilt one holds, in any order.  About one event in twenty changes its pixel per iteration of a cold run
+// (profiles/mover_fraction_config2.txt): the other nineteen cost their loads, the warp and the store of the products.
+constexpr uint32_t kNoPixel = 0xffffffffu;   // (R, C <= 65535: a linear pixel index stays below it)
+
+// The scatter pixel the stored products give (accel_lib.h:154-158; the expression of event_body), kNoPixel outside the window.
+__device__ __forceinline__ uint32_t scatter_pixel(uint32_t fx, uint32_t fy, const float2& p, const HotState& st) {
+    const int s = st.scale, hs = s / 2;
+    const int X = trunc_scatter(pr_from_p(fx, p.x) * (double)s + (double)st.x_sh);
+    const int Y = trunc_scatter(pr_from_p(fy, p.y) * (double)s + (double)st.y_sh);
+    if ((X >= st.wsx + hs) || (X < hs) || (Y >= st.wsy + hs) || (Y < hs)) return kNoPixel;
+    return (uint32_t)X * (uint32_t)st.C + (uint32_t)Y;
+}
+
+template <bool PACKED>
+__device__ __forceinline__ void event_delta(uint32_t xy, int32_t t, float2& p, bool live, unsigned long long* plane,
+                                            uint32_t* cplane, const HotState& st) {
+    const uint32_t fx = xy & 0xffffu, fy = xy >> 16;
+    const uint32_t k_old = scatter_pixel(fx, fy, p, st);   // where the previous launch left the event
+    double nx, ny;
+    warp_products(st.wp, pr_from_p(fx, p.x), pr_from_p(fy, p.y), t, p, nx, ny);
+    const uint32_t k_new = scatter_pixel(fx, fy, p, st);
+    if (!live || k_old == k_new) return;
+    const unsigned long long dt = (unsigned long long)((long long)t - st.tmin);
+    const unsigned long long w = PACKED ? (1ull << st.tbits) + dt : dt;
+    if (k_old != kNoPixel) {   // two's complement: the sum modulo 2^64 (2^32) is the sum
+        (void)__hip_atomic_fetch_add(&plane[k_old], 0ull - w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!PACKED) (void)__hip_atomic_fetch_add(&cplane[k_old], 0u - 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (k_new != kNoPixel) {
+        (void)__hip_atomic_fetch_add(&plane[k_new], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (!PACKED) (void)__hip_atomic_fetch_add(&cplane[k_new], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// K1 of the delta-scatter loop: k_warp_scatter<true, true, false> on a plane that already holds the image of the stored
+// products.  No noise mask (bf_plan.cpp: such slices keep the plain loop).  The products go out write-through, as the
+// tile-binned kernel's do (bf_scatter.hip, flush_tile): 8 MB of plain stores sit dirty in the L2s until the kernel ends.
+template <bool PACKED, int EV>
+__global__ __launch_bounds__(kThreads) void k_warp_scatter_delta(const uint32_t* __restrict__ xy, const int32_t* __restrict__ t,
+                                                                 float2* __restrict__ p, unsigned long long* __restrict__ plane,
+                                                                 uint32_t* __restrict__ cplane, const DevState* __restrict__ st,
+                                                                 long long n, int check_done) {
+    static_assert(EV == 2 || EV == 4, "16-byte stores of the products: two events each");
+    const HotState hs = st->hot;
+    if (check_done == 1 && hs.done) return;
+    const long long base = ((long long)blockIdx.x * kThreads + threadIdx.x) * EV;
+    if (base >= n) return;
+    // arrays are padded to a multiple of kEvPerThread * kThreads elements
+    uint32_t vxy[EV];
+    int32_t vt[EV];
+    float2 q[EV];
+    if (EV == 4) {
+        *reinterpret_cast<uint4*>(vxy) = *reinterpret_cast<const uint4*>(xy + base);
+        *reinterpret_cast<int4*>(vt) = *reinterpret_cast<const int4*>(t + base);
+    } else {
+        *reinterpret_cast<uint2*>(vxy) = *reinterpret_cast<const uint2*>(xy + base);
+        *reinterpret_cast<int2*>(vt) = *reinterpret_cast<const int2*>(t + base);
+    }
+#pragma unroll
+    for (int k = 0; k < EV; k += 2) {
+        const float4 pa = *reinterpret_cast<const float4*>(p + base + k);
+        q[k] = make_float2(pa.x, pa.y);
+        q[k + 1] = make_float2(pa.z, pa.w);
+    }
+#pragma unroll
+    for (int k = 0; k < EV; ++k) event_delta<PACKED>(vxy[k], vt[k], q[k], base + k < n, plane, cplane, hs);
+#pragma unroll
+    for (int k = 0; k < EV; k += 2) {
+        const bf_u32x4 v = {__float_as_uint(q[k].x), __float_as_uint(q[k].y), __float_as_uint(q[k + 1].x), __float_as_uint(q[k + 1].y)};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1" :: "v"(p + base + k), "v"(v) : "memory");
+    }
+}
+
+// Events per thread of the delta-scatter kernel.  Two: 7800 waves per 1M events to interleave the warp's dependent f64 chain
+// (k_final_warp has the arithmetic), 8-byte loads of xy and t, and the products still leave 16 bytes wide.  With four -- the
+// plain kernel's 16-byte loads throughout, half the waves -- config 2 under four contexts ran 204-205 Mevents/s against
+// 240 with two and 218 for the tile-binned loop (experiments/round_8.md).
+constexpr int kDeltaEv = 2;
+
+void launch_warp_scatter_delta(const WarpScatterArgs& a, hipStream_t s) {
+    const long long per_block = (long long)kThreads * kDeltaEv;
+    const dim3 grid((unsigned)((a.n + per_block - 1) / per_block));
+    if (grid.x == 0) return;
+    if (a.packed)
+        hipLaunchKernelGGL((k_warp_scatter_delta<true, kDeltaEv>), grid, dim3(kThreads), 0, s, a.xy, a.t, a.p, a.plane, a.cplane, a.st, a.n, a.check_done);
+    else
+        hipLaunchKernelGGL((k_warp_scatter_delta<false, kDeltaEv>), grid, dim3(kThreads), 0, s, a.xy, a.t, a.p, a.plane, a.cplane, a.st, a.n, a.check_done);
+}
+
 // AccelLib::project_4param (accel_lib.h:275-281) -> Event::project_4param (event.h:88-96): the INCREMENTAL warp -- the same dn as
 // project_4param_reinit from the previous pr, but ADDED to the event's (nx, ny) (Event::project_dn, event.h:72-76) before
 // apply_project.  Dead in the reference (its only call is commented out, optimizer_rolling.h:333-339); exported for signature
@@ -475,6 +567,7 @@ void launch_stencil(const StencilArgs& a, int src, hipStream_t s, int n_cus) {
     stencil_grid(a.R, a.C, &gx, &gy);
     dim3 grid(gx, gy);
     if (src == 3) { launch_stencil_binned(a, grid, s, n_cus); return; }
+    if (src == 4) { launch_stencil_plane(a, grid, s); return; }
     if (src == 0) hipLaunchKernelGGL((k_stencil<0, kThreads>), grid, dim3(kThreads), 0, s, a);
     else if (src == 1) hipLaunchKernelGGL((k_stencil<1, kThreads>), grid, dim3(kThreads), 0, s, a);
     else hipLaunchKernelGGL((k_stencil<2, kThreads>), grid, dim3(kThreads), 0, s, a);

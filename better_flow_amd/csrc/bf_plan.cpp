@@ -125,9 +125,24 @@ bool plan_persistent(const bf_ctx* c) {
 
 RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     RunPlan p;
-    p.fused = plan_one_kernel(c);
-    p.binned = c->use_binned || p.fused;
-    p.persist = plan_persistent(c);
+    // Delta scatter (bf_kernels.hip: k_warp_scatter_delta), a form of the global-atomic loop: any slice without a noise mask can
+    // take it, and it then stands in for whichever loop the slice would run.  "auto" takes it where it was measured against the
+    // loop it replaces (experiments/round_8.md): cold runs of contexts that share the GPU ("co_schedule") on slices that would
+    // run the two-kernel loop on dense slabs by "auto"'s own choice, with packed planes and at least one event per image pixel
+    // -- config 2 under four contexts 218 -> 240 Mevents/s: the loop is bound by bytes there, and the slab hand-off is half of
+    // them.  A context alone (a latency chain: 101.5 against 102 Mevents/s, no gain), warm starts (a handful of iterations
+    // would pay for a full first scatter of global atomics) and the event-list geometries keep their loops; so does a
+    // context whose loop an option forces.  Nor a run capped below 200 iterations: the run's first two launches -- the full
+    // scatter and the first warp, which moves every event -- cost ~0.3 ms more than the tile-binned loop's (max_iter = 10 under
+    // four contexts: 0.69 -> 1.03 ms per slice), and an iteration saves ~3 us.
+    const double Pdelta = (double)c->win.scale_img_x * (double)c->win.scale_img_y;
+    const bool delta_pays = c->opt_co_schedule && !c->pending_warp && c->opt_binned == 1 && c->opt_fused != 2 && c->use_binned &&
+                            c->fmt == 0 && c->packed && !plan_one_kernel(c) && (double)c->n >= Pdelta && Pdelta < (double)(1u << 28) &&
+                            (o.max_iter <= 0 || o.max_iter >= 200);
+    p.delta = !c->has_noise && c->n > 0 && (c->opt_delta == 2 || (c->opt_delta == 1 && delta_pays));
+    p.fused = !p.delta && plan_one_kernel(c);
+    p.binned = !p.delta && (c->use_binned || p.fused);
+    p.persist = !p.delta && plan_persistent(c);
     // (g_live_ctx only knows this process: another process's kernels -- or anything else that keeps work-groups from becoming
     // resident -- shows as a launch that gives up after 0.2 s.  The context then stays away from the kernel for a while.)
     if (p.persist && c->persist_skip > 0) { --c->persist_skip; p.persist = false; }
@@ -139,7 +154,7 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     // (the persistent loop re-bins AT the request -- it returns for it --, the other loops one or two batches of launches
     // after it: the same effective threshold)
     if (p.binned) p.drift_limit = c->opt_bin_predict ? (p.persist ? 0.85 : 0.6) * (double)(p.fused ? c->fgrid.D : c->grid.D) : 1e300;
-    p.split = c->use_binned && !p.fused && c->fmt == 3;
+    p.split = p.binned && !p.fused && c->fmt == 3;
     // Where the model / loop update runs.  One slice context alone: at the head of the next warp+scatter launch (every
     // work-group for itself; shortest iteration).  Several contexts sharing the GPU ("co_schedule"): in the last
     // work-group of the stencil kernel -- a serial tail on ONE CU that the other contexts' kernels fill, instead of
@@ -190,6 +205,7 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     // host round trip every other iteration (22 instead of 14 us per iteration on a 50 000-event slice).
     p.quick_warm = p.warm_start && c->warm_iters_hint < 3 * o.poll_interval;
     // A tile-binned run that is not a quick warm start reads its progress from the pinned snapshot (bf_run.cpp: wait_snapshot).
-    p.snap_polled = p.binned && !p.quick_warm;
+    // ... and so does delta scatter, whose stencil kernel writes the same snapshot.
+    p.snap_polled = (p.binned || p.delta) && !p.quick_warm;
     return p;
 }

@@ -1,5 +1,5 @@
 // bf_run.cpp -- C-ABI: the fused OptimizerRolling::set_model / run (optimizer_rolling.h:48-125,289-347): the host side of the device loops
-// (two-kernel tile-binned loop, one-kernel iteration, persistent loop kernel, global-atomic fallback; plan_run picks one) and bf_run_many.
+// (two-kernel tile-binned loop, one-kernel iteration, persistent loop kernel, global-atomic fallback and its delta-scatter form; plan_run picks one) and bf_run_many.
 #include "bf_ctx.h"
 
 namespace {
@@ -40,7 +40,7 @@ struct RunLoop {
     DevState fin;                    // the final state (snapshot-polled: read by run_end)
     bf_run_info inf{0, 0, 1.0f, 1.0f, 10000.0f, 10000.0f};   // (rc, iterations, the four dividers)
     HostTiming ht;
-    DevState* state_of(int j) const { return c->d_state + (p.sep_update ? 0 : (j & 1)); }
+    DevState* state_of(int j) const { return c->d_state + ((p.sep_update || !p.binned) ? 0 : (j & 1)); }
     MomentAcc* acc_of(int j) const { return c->d_acc + (size_t)(p.fused ? ((j % 3) + 3) % 3 : (j & 1)) * kAccGroups; }
     uint32_t* ovf_of(int j) const { return c->d_ovf + (((j % 3) + 3) % 3) * kOvfSlotWords; }
     int finish(const DevState& s, bool warped) { fin = s; done = true; final_done = warped; return BF_OK; }   // the loop is over
@@ -222,7 +222,11 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
         HIP_TRY(c, launch_fused_pass(fa, c->win.scale / 2, c->fgrid.TSR, c->stream));
         L.inf.launches += 1;
     } else {
-        const int buf = L.buf;
+        // Delta scatter: every launch of the run works on the buffer the first one filled -- the first is the plain loop's full
+        // scatter into a clean buffer (its stencil launch clears the other one, which an earlier run or operator may have left
+        // dirty), every later one moves the events whose pixel changed, and its stencil launch clears nothing.
+        const bool delta_step = p.delta && !L.first;
+        const int buf = p.delta ? L.b0 : L.buf;
         if (p.sep_update) {   // the pending update of iteration j - 1 (none at j = 0: the state's own counter says so)
             launch_finish_update(L.state_of(j), L.acc_of(j - 1), L.ovf_of(j - 1), j, buf ^ 1, L.trace, snap, c->stream);
             L.inf.launches++;
@@ -251,10 +255,12 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
             c->launched.k1_threads = p.bin_threads; c->launched.k1_per_thread = p.ev_per_thread; c->launched.k1_head = p.head_update ? 1 : 0;
         } else {
             ProfScope ps(c, 0, c->n);
-            launch_warp_scatter(ws_args(c, buf, 1), warp, true, false, c->stream);
+            if (delta_step) launch_warp_scatter_delta(ws_args(c, buf, 1), c->stream);
+            else launch_warp_scatter(ws_args(c, buf, 1), warp, true, false, c->stream);
         }
         // stencil + moments; its last work-group reduces and runs the model / loop update
         StencilArgs a = st_args(c, buf, 1);
+        if (delta_step) a.zero_plane = nullptr, a.zero_cplane = nullptr;
         if (p.binned) {
             a.ovf_bits = c->d_ovf_bits[buf]; a.zero_bits = c->d_ovf_bits[buf ^ 1]; a.ovf_pitch = c->ovf_pitch;
             a.zero_full = j == 0 ? 1 : 0;   // (what an earlier operator left in the other buffer is not in the bitmap)
@@ -283,6 +289,7 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
             a.acc = c->d_acc;
             a.ticket = c->d_ticket;
             a.st_rw = c->d_state;
+            if (p.delta) a.snap = snap;   // (polled like the tile-binned loop: wait_snapshot)
         }
         a.trace = L.trace;
         a.update_mode = 1;
@@ -296,7 +303,12 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
         // instruction diet the kernel gains less from two more work-groups per CU than it loses to the spills.)
         const bool shared_lists = c->opt_co_schedule && c->fmt == 2 && g_live_ctx[c->device & 63].load() > 1;
         const int k3_cus = shared_lists ? 1 : c->n_cus;
-        launch_stencil(a, stencil_src(c, p.binned), c->stream, k3_cus);
+        // Delta scatter on a packed plane: the tile-binned loop's stencil kernel reading the plane itself (one load per pixel
+        // of the halo plane where it merges 2 x 2 slabs), in banded tile order when contexts share the GPU -- k_stencil takes
+        // half as long again per launch (experiments/round_8.md).  Split planes keep k_stencil.
+        const bool plane_k3 = p.delta && c->packed && (unsigned long long)a.R * (unsigned long long)a.C < (1ull << 28);
+        if (plane_k3) a.tile_bands = c->opt_co_schedule ? 1 : 0;
+        launch_stencil(a, plane_k3 ? 4 : stencil_src(c, p.binned), c->stream, k3_cus);
         if (p.binned) {   // (launch_stencil_binned picks its build by the same rule from the same numbers)
             c->launched.k3_half_scale = bf_rules::stencil_half_scale(a.scale);
             c->launched.k3_mode = bf_rules::stencil_mode(a.compact);
@@ -305,7 +317,7 @@ int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
         L.inf.launches += 2;
     }
     L.first = false;
-    L.buf ^= 1;
+    if (!p.delta) L.buf ^= 1;
     ++L.launched_iters;
     return BF_OK;
 }
@@ -516,7 +528,8 @@ int run_end(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, bf_mo
     // iterations executed alternate buffers starting at b0; the next scatter goes to the
     // buffer the last stencil left clean.  (The one-kernel loop touches neither plane buffer: what was dirty stays dirty,
     // hot.ovf_cnt came back from the device as it went.)
-    c->cur = p.fused ? L.b0 : (L.b0 ^ (d.hot.it & 1));
+    // (Delta scatter: b0 holds the last image, the first stencil launch cleared the other one and nobody has touched it since.)
+    c->cur = p.fused ? L.b0 : p.delta ? (d.hot.it > 0 ? L.b0 ^ 1 : L.b0) : (L.b0 ^ (d.hot.it & 1));
     c->trace_valid = d.hot.it < o.trace_cap ? d.hot.it : o.trace_cap;
     L.inf.rc = d.rc;
     L.inf.iterations = d.hot.it;
@@ -563,6 +576,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
     if (noise || c->n < (long long)o.min_events) {
         if (model_out) *model_out = c->hst.model;
         if (info) *info = bf_run_info{BF_SKIPPED, 0, 1.0f, 1.0f, 10000.0f, 10000.0f};
+        c->last_loop = -1;
         return BF_SKIPPED;
     }
 
@@ -573,6 +587,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
     int rc = run_begin(c, o, p, L);
     if (rc == BF_OK && p.persist) rc = run_persistent(c, o, p, L);
     if (rc != BF_OK) return rc;
+    c->last_loop = p.delta ? BF_LOOP_DELTA : L.done ? BF_LOOP_PERSISTENT : p.fused ? BF_LOOP_ONE_KERNEL : p.binned ? BF_LOOP_BINNED : BF_LOOP_ATOMIC;
     // Pipelined polling: batch b+1 is enqueued BEFORE the host waits for the state snapshot
     // taken after batch b, so the GPU never idles on the host (a blocking poll costs ~25 us of
     // idle GPU).  Kernels launched after `done` was set return at once (~1 us each).

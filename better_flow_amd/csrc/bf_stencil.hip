@@ -47,7 +47,9 @@ struct K3Pre {
 // StencilArgs follows the twelve leading arguments (two pointers, ten words: 56 bytes) in the argument block: late_args
 constexpr unsigned kStencilArgsOffset = 56;
 static_assert(sizeof(K3Pre) == kStencilArgsOffset && alignof(StencilArgs) == 8, "the argument struct starts right behind the leading arguments");
-template <int HS, int MODE, int NT>   // MODE: what the scatter kernel wrote -- 0 dense slabs, 1 lists, 2 interior + margin plane
+// MODE: what the scatter kernel wrote -- 0 dense slabs, 1 lists, 2 interior + margin plane, 3 the packed image-linear plane itself
+// (delta scatter: `slabs` is the plane, and of the grid only the banded-order bit of `lg` is read)
+template <int HS, int MODE, int NT>
 __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const K3Pre& pre) {
     constexpr bool COMPACT = MODE == 1;
     tl_stamp(a.tl, a.tl_launch, 0);
@@ -98,10 +100,11 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
     }
     BinGrid g = a.g;  // (the fields the slab addresses use come from the preloaded arguments)
     g.D = pre.D; g.lg = pre.lg & (kTileBandsBit - 1); g.nbc = pre.nbc; g.nbr = pre.nbr; g.LR = pre.LR; g.L = pre.L; g.TSR = pre.TSR; g.mul_r = pre.mul_r;
-    const int bt = hs.bin_tbits;
+    const int bt = MODE == 3 ? hs.tbits : hs.bin_tbits;   // (the plane's words are packed for the whole slice: bf_set_cloud)
     const unsigned long long bm = (1ull << bt) - 1ull;
     // (static indices only: a runtime index would push the HotState copy into scratch memory)
-    const bool ovf = sload(a.ovf_cur) != 0;   // events of this iteration took the overflow path (uniform)
+    bool ovf = false;   // events of this iteration took the overflow path (uniform; the plain plane has none)
+    if constexpr (MODE != 3) ovf = sload(a.ovf_cur) != 0;
     const int LLi = g.LR * g.L;
 
     constexpr bool compact = COMPACT;
@@ -266,6 +269,37 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
     for (int x = 0; x < XE; ++x) {
         const int e = lane + 64 * x, pr = wv + (e / XC) * NW;
         if (e < KR * XC && pr < PR) s_acc[pr * PC + 64 + e % XC] = we[x][0] + we[x][1];
+    }
+    } else if constexpr (MODE == 3) {
+    // The packed plane of the global-atomic loop, image-linear: ONE word per pixel of the halo plane, no merge.  Thread mapping
+    // as in the dense form below -- a wave takes whole rows (the row's offset is uniform), one column per lane.
+    unsigned long long w[KR], we[XE];
+    const __amdgpu_buffer_rsrc_t plane_buf = buf_of(pre.slabs);
+    const int c_gc = c0 - H + lane;
+    const bool c_in = c_gc >= 0 && c_gc < C;
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        const int pr = wv + k * NW, gr = r0 - H + pr;   // (uniform: scalar unit)
+        w[k] = 0ull;
+        if (pr < PR && gr >= 0 && gr < R && c_in) w[k] = buf_ld_u64(plane_buf, (uint32_t)c_gc * 8u, (uint32_t)__mul24(gr, C) * 8u);
+    }
+#pragma unroll
+    for (int x = 0; x < XE; ++x) {   // the columns beyond the 64th: lanes 0 .. KR XC - 1 of every wave, for the wave's own rows
+        const int e = lane + 64 * x;
+        const int pr = wv + (e / XC) * NW, gr = r0 - H + pr, gc = c0 - H + 64 + e % XC;
+        we[x] = 0ull;
+        if (e < KR * XC && pr < PR && gr >= 0 && gr < R && gc >= 0 && gc < C) we[x] = pre.slabs[(uint32_t)(__mul24(gr, C) + gc)];
+    }
+    if (a.check_done && hs.done) return;   // (uniform; before the first barrier -- the loads above are already out)
+#pragma unroll
+    for (int k = 0; k < KR; ++k) {
+        const int pr = wv + k * NW;
+        if (pr < PR) s_acc[pr * PC + lane] = w[k];
+    }
+#pragma unroll
+    for (int x = 0; x < XE; ++x) {
+        const int e = lane + 64 * x, pr = wv + (e / XC) * NW;
+        if (e < KR * XC && pr < PR) s_acc[pr * PC + 64 + e % XC] = we[x];
     }
     } else {
     static_assert(TR + 2 * H <= 32, "a tile plus halo must fit the smallest bin height (32)");
@@ -505,7 +539,8 @@ __device__ __forceinline__ void stencil_binned_body(const StencilArgs& a, const 
     ta.trace = as_global(ta.trace); ta.tl = as_global(ta.tl);
     __syncthreads();
     tl_stamp(ta.tl, ta.tl_launch, 4);
-    const bool do_zero = ta.zero_plane && sload(ta.ovf_prev) != 0;   // the other plane buffer is dirty: clear it for the next iteration
+    bool do_zero = ta.zero_plane != nullptr;   // the other plane buffer is dirty: clear it for the next iteration
+    if constexpr (MODE != 3) do_zero = do_zero && sload(ta.ovf_prev) != 0;   // (the plain plane: whenever the host names one)
     // (the accumulator plane is free from here on: the wave totals of the moment sums go through it)
     static_assert((size_t)PR * PC >= (size_t)(NT / 64) * 192, "the reduction's scratch fits the accumulator plane");
     stencil_tail<TR, TC, NT, false>(ta, s_time, s_red, r0, c0, do_zero, reinterpret_cast<double*>(s_acc));
@@ -557,6 +592,22 @@ void launch_stencil_binned(const StencilArgs& a, dim3 tiles, hipStream_t s, int 
     }
 #undef BF_K3
 #undef BF_K3_PRE
+}
+
+// The same kernel on the packed plane of the global-atomic loop (MODE 3; the delta-scatter loop's K3).  Its halo plane is one
+// load per pixel, and it never spills (72 scalar registers): one build.
+void launch_stencil_plane(const StencilArgs& a, dim3 tiles, hipStream_t s) {
+    const dim3 grid = a.tile_bands ? dim3(tiles.x * tiles.y) : tiles;
+#define BF_K3P(HS_) launch_timed(k_stencil_binned<HS_, 3, kThreads>, grid, dim3(kThreads), 0, s, a.plane, a.st, a.R, a.C, 0, \
+                                 a.tile_bands ? kTileBandsBit : 0, 0, 0, 0, 0, 0, 0u, a)
+    switch (bf_rules::stencil_half_scale(a.scale)) {
+        case 0: BF_K3P(0); break;
+        case 1: BF_K3P(1); break;
+        case 2: BF_K3P(2); break;
+        case 3: BF_K3P(3); break;
+        default: BF_K3P(4); break;
+    }
+#undef BF_K3P
 }
 
 }  // namespace bf

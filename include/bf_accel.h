@@ -213,13 +213,23 @@ int bf_abi_struct_sizes(int32_t *out, int32_t n);
  *                  words its events left in the tile's margin to a margin plane (device atomics; the bin clears them again
  *                  at its next launch): 0.6 x the bytes, a quarter of the stencil kernel's loads; 1 (default): the second
  *                  form for a context that has the GPU to itself on an image of >= 1.5 M pixels (640x480 scale 3, 1M
- *                  events: 37.2 -> 32.9 us per iteration), the first otherwise.  Bit-identical results. */
+ *                  events: 37.2 -> 32.9 us per iteration), the first otherwise.  Bit-identical results.
+ *   "delta_scatter"  the global-atomic loop on ONE plane buffer that is kept from launch to launch: the run's first launch
+ *                  scatters every event, every later one warps the events and moves only those whose pixel changed (one atomic
+ *                  that takes the event's word off the old pixel, one that adds it to the new one; about one event in twenty
+ *                  per iteration of a cold run).  The plane words are exact integers, so the image -- and every bit behind it --
+ *                  is the rebuilt one's.  0 never, 2 whenever the slice has no noise mask (it then replaces whichever loop
+ *                  the slice would take), 1 (default): where it was measured to be the faster loop -- cold runs of a
+ *                  "co_schedule" context on a slice that would otherwise run the two-kernel loop on dense slabs by default
+ *                  ("binned" = 1), with packed planes and at least one event per image pixel (config 2 under four contexts:
+ *                  218 -> 240 Mevents/s).  A slice with a noise mask keeps the plain global-atomic loop. */
 int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
 
 /* Diagnostics (no reference counterpart).  Keys:
  *   "scatter_format"  what the last bf_set_cloud chose for the tile-binned loop: 0 dense slabs, 2 event
  *                     lists, 3 own pixels + margin plane ("bin_split"); -1 when the slice does not take that loop.
  *   "one_kernel"      1 when bf_run would take the one-kernel iteration for the slice staged now, else 0.
+ *   "loop_form"       the loop the last bf_run took (BF_LOOP_*); -1 before the first run and after a skipped one.
  *   "persistent"      1 when bf_run, called now, would run it as the persistent kernel ("persist"), else 0.
  *   "persist_giveups" launches of the persistent kernel on this context that gave up (a work-group waited 0.2 s for others
  *                     that were not resident: something else holds part of the GPU) and undid themselves; the run they
@@ -238,6 +248,11 @@ int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
  *                     atomic per vote; 0 when it launched none (no call yet, or no events).
  * BF_ERR_ARG for an unknown key. */
 int bf_get_stat(bf_ctx *ctx, const char *key, int64_t *value);
+#define BF_LOOP_ATOMIC 0      /* one global atomic per event and iteration, two plane buffers */
+#define BF_LOOP_BINNED 1      /* the two-kernel tile-binned loop (slabs, lists or own pixels + margin plane) */
+#define BF_LOOP_ONE_KERNEL 2  /* the one-kernel iteration */
+#define BF_LOOP_PERSISTENT 3  /* ... as the persistent loop kernel (a run whose launch gave up reports the loop that finished it) */
+#define BF_LOOP_DELTA 4       /* delta scatter */
 
 /* ---- slice set-up -------------------------------------------------------------- */
 
