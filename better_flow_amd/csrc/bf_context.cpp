@@ -197,11 +197,11 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         return BF_OK;
     }
     if (!strcmp(key, "one_kernel")) {
-        *value = plan_one_kernel(c) ? 1 : 0;
+        *value = bf_rules::one_kernel_ok(loop_facts(c, -1, false)) ? 1 : 0;
         return BF_OK;
     }
     if (!strcmp(key, "persistent")) {   // would bf_run, called now, take the persistent loop kernel?
-        *value = plan_persistent(c) ? 1 : 0;
+        *value = bf_rules::persistent_ok(loop_facts(c, -1, false)) ? 1 : 0;   // (the back-off after a launch gave up is plan_run's)
         return BF_OK;
     }
     if (!strcmp(key, "loop_form")) {   // which loop the last bf_run took (BF_LOOP_*; -1: none yet, or the run was skipped)

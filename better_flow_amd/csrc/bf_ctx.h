@@ -40,7 +40,7 @@ using bf_mem::MappedArray;
 using bf_mem::Stream;
 
 // Contexts alive per device in this process (defined in bf_context.cpp): the persistent loop kernel is for a context alone on its
-// device (plan_persistent).
+// device (bf_rules::persistent_ok).
 extern std::atomic<int> g_live_ctx[64];
 
 struct GlobalSearch;   // bf_global_search.cpp: the exhaustive search's window, scratch and per-event state
@@ -351,19 +351,31 @@ struct SlicePlan {
     int fmt = 0, zw = 0;             // bf_ctx: fmt, grid.zw
 };
 struct RunPlan {
-    bool fused = false, binned = false, persist = false;   // one-kernel iteration, tile-binned (either loop), persistent kernel
-    bool delta = false;              // the global-atomic loop (binned == false) as delta scatter: one plane buffer, kept up to date
-    bool head_update = false, sep_update = false;   // the update at the next scatter launch's head / in k_finish_update
-    bool split = false;              // the two-kernel loop on own pixels + margin plane (fmt 3)
+    using Form = bf_rules::LoopForm;
+    using Home = bf_rules::UpdateHome;
+    Form form = Form::atomic;        // the loop, picked with the home of its model update by bf_rules::loop_choice
+    Home home = Home::tail;
+    // What the driver asks of the two, each said once.  (The scatter format stays in bf_ctx::fmt.)
+    bool kept_plane() const { return form == Form::delta; }             // delta scatter: one plane buffer, kept up to date
+    bool loop_kernel() const { return form == Form::persistent; }       // the persistent loop kernel
+    bool one_kernel() const { return form == Form::one_kernel || form == Form::persistent; }   // (a persistent launch that gives up goes on one launch at a time)
+    bool two_kernel() const { return form == Form::binned; }
+    bool bin_grid() const { return one_kernel() || two_kernel(); }      // the events are sorted by tile: bf_ctx::fgrid / grid
+    bool accumulate_only() const { return home != Home::tail; }          // the stencil kernel leaves the update to the next launch
+    bool head() const { return home == Home::head; }
+    bool separate() const { return home == Home::separate; }
+    bool one_state() const { return separate() || !bin_grid(); }         // one state buffer (else launch j reads [j & 1], writes the other)
+    bool acc_ring3() const { return one_kernel(); }                      // moment accumulators: the launch number mod 3 (else its parity)
+    bool snapshot_a_launch_early() const { return one_kernel() || !accumulate_only(); }   // iteration count L shows in launch L - 1's snapshot, not L's
     int bin_threads = 0, ev_per_thread = 8;   // the scatter kernel's work-group size and events per thread
     bool warm_start = false, prewarp = false, first_warp = false;   // bf_set_model's warp: by the first counting sort / iteration
     bool quick_warm = false, snap_polled = false;   // polled batch by batch (a warm start expected to converge soon) / from the pinned snapshot
     double drift_limit = 1e300;      // tile-binned loops: the drift since the sort that asks for a re-bin
-    bool head_like() const { return head_update || sep_update; }   // (the stencil kernel only accumulates)
 };
 SlicePlan plan_slice(const bf_ctx* c, const bf_window& w);
-bool plan_one_kernel(const bf_ctx* c);   // (and bf_get_stat)
-bool plan_persistent(const bf_ctx* c);   // (and bf_get_stat: without the back-off after a launch gave up)
+// What bf_rules::loop_choice decides on, read off the context; max_iter: the run's.  (bf_get_stat "one_kernel" / "persistent" ask
+// the same rules of the same facts as plan_run, with for_run = false, without taking a run of the back-off after a launch gave up.)
+bf_rules::LoopFacts loop_facts(const bf_ctx* c, int max_iter, bool for_run);
 RunPlan plan_run(bf_ctx* c, const bf_run_opts& o);   // (takes one run of that back-off)
 
 // The asynchronous uploads (bf_upload.cpp): the copy stream, the slots' events and arrays (on first use); the HIP side of the
@@ -554,8 +566,8 @@ StencilArgs st_args(bf_ctx* c, int buf, int check_done) {
     return a;
 }
 
-// which k_stencil instantiation reads the scatter result of the current mode
-int stencil_src(const bf_ctx* c, bool binned_pass) { return binned_pass ? 3 : (c->packed ? 0 : 1); }
+// which k_stencil instantiation reads the plane buffers of the current slice
+StencilSrc plane_src(const bf_ctx* c) { return c->packed ? StencilSrc::packed_plane : StencilSrc::split_planes; }
 
 // grow(n), and zero the array on the context's stream when that allocated it
 template <class T> hipError_t grow_zeroed(bf_ctx* c, DevArray<T>& a, size_t n) {

@@ -143,7 +143,15 @@ void launch_local_time(const unsigned long long* ts, unsigned long long t0, int3
 void launch_local_time16(const unsigned long long* ts, bool ts32, const uint16_t* row, const uint16_t* col, unsigned long long t0,
                          int32_t* x_out, int32_t* y_out, int32_t* t_out, long long n, hipStream_t s);
 void stencil_grid(int R, int C, int* gx, int* gy);
-void launch_stencil(const StencilArgs& a, int src, hipStream_t s, int n_cus = 0);   // n_cus: lets the tile-binned form pick its build by how often the grid fills the GPU
+// what a stencil launch reads: the first three are k_stencil's sources, the last two k_stencil_binned's
+enum class StencilSrc {
+    packed_plane,   // one u64 plane: count << tbits | time sum
+    split_planes,   // a u64 sum plane and a u32 count plane
+    time_image,     // an f32 time image (a.time_in)
+    binned,         // the tile-binned scatter's slabs, lists or own pixels + margin plane
+    plane_binned,   // the packed plane through k_stencil_binned (launch_stencil_plane)
+};
+void launch_stencil(const StencilArgs& a, StencilSrc src, hipStream_t s, int n_cus = 0);   // n_cus: lets the tile-binned form pick its build by how often the grid fills the GPU
 // applies a pending update (sums in `acc`) to `st` in place: the tile-binned loop's update outside a warp+scatter launch
 // (snap_seq / seq: after the snapshot has been stored and fenced, `seq` goes to the pinned word the host spins on)
 void launch_finish_update(DevState* st, MomentAcc* acc, const uint32_t* ovf_prev, int j, int cur_prev, bf_trace_rec* trace,
@@ -191,7 +199,7 @@ void launch_group_rest(const uint32_t* perm, const uint32_t* start, int K, doubl
 
 // bf_rebin.hip / bf_scatter.hip / bf_stencil.hip / bf_fused.hip (the tile-binned loops)
 int bin_kernel_setup();
-// k_stencil_binned on the packed image-linear plane `a.plane` (src 4 of launch_stencil; R * C * 8 < 2^31: 32-bit byte offsets)
+// k_stencil_binned on the packed image-linear plane `a.plane` (StencilSrc::plane_binned; R * C * 8 < 2^31: 32-bit byte offsets)
 void launch_stencil_plane(const StencilArgs& a, dim3 grid, hipStream_t s);
 void launch_stencil_binned(const StencilArgs& a, dim3 grid, hipStream_t s, int n_cus);   // (the build: bf_rules::stencil_capped)
 // interior + margin format: clear what the bins' lists name in `mplane`, empty the lists (a run that cannot rely on the

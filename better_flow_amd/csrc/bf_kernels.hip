@@ -562,15 +562,17 @@ void stencil_grid(int R, int C, int* gx, int* gy) {
     *gy = (R + kTileR - 1) / kTileR;
 }
 
-void launch_stencil(const StencilArgs& a, int src, hipStream_t s, int n_cus) {
+void launch_stencil(const StencilArgs& a, StencilSrc src, hipStream_t s, int n_cus) {
     int gx, gy;
     stencil_grid(a.R, a.C, &gx, &gy);
     dim3 grid(gx, gy);
-    if (src == 3) { launch_stencil_binned(a, grid, s, n_cus); return; }
-    if (src == 4) { launch_stencil_plane(a, grid, s); return; }
-    if (src == 0) hipLaunchKernelGGL((k_stencil<0, kThreads>), grid, dim3(kThreads), 0, s, a);
-    else if (src == 1) hipLaunchKernelGGL((k_stencil<1, kThreads>), grid, dim3(kThreads), 0, s, a);
-    else hipLaunchKernelGGL((k_stencil<2, kThreads>), grid, dim3(kThreads), 0, s, a);
+    switch (src) {
+        case StencilSrc::binned: launch_stencil_binned(a, grid, s, n_cus); break;
+        case StencilSrc::plane_binned: launch_stencil_plane(a, grid, s); break;
+        case StencilSrc::packed_plane: hipLaunchKernelGGL((k_stencil<0, kThreads>), grid, dim3(kThreads), 0, s, a); break;
+        case StencilSrc::split_planes: hipLaunchKernelGGL((k_stencil<1, kThreads>), grid, dim3(kThreads), 0, s, a); break;
+        case StencilSrc::time_image: hipLaunchKernelGGL((k_stencil<2, kThreads>), grid, dim3(kThreads), 0, s, a); break;
+    }
 }
 
 void launch_compute_uv(const double2* nxny, double2* uv, long long n, hipStream_t s) {

@@ -221,7 +221,7 @@ int ctx_time_img_pass(bf_ctx* c, const char* who) {
     a.zero_cplane = c->d_cplane[buf ^ 1];   // may be NULL (never allocated): nothing to clear
     {
         ProfScope ps(c, 1);
-        launch_stencil(a, stencil_src(c, false), c->stream, c->n_cus);
+        launch_stencil(a, plane_src(c), c->stream, c->n_cus);
     }
     HIP_TRY(c, hipGetLastError());
     c->cur = buf ^ 1;   // the stencil zeroed the other buffer; `buf` is cleared by the next pass
@@ -262,7 +262,7 @@ static int image_pass(bf_ctx* c, const float* d_src, int rows, int cols, bool gr
         a.update_mode = 0;
     }
     ProfScope ps(c, 1);
-    launch_stencil(a, 2, c->stream);
+    launch_stencil(a, StencilSrc::time_image, c->stream);
     return BF_OK;
 }
 

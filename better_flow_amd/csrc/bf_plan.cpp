@@ -104,72 +104,67 @@ SlicePlan plan_slice(const bf_ctx* c, const bf_window& w) {
     return p;
 }
 
-bool plan_one_kernel(const bf_ctx* c) {
-    // One slice context alone on the GPU: the one-kernel iteration when the slice qualifies (plan_slice), else the
-    // two-kernel tile-binned loop when the slice is dense enough for it, else global atomics.
-    return c->fused_ok && (!c->opt_co_schedule || c->fused_shared);
-}
-
-bool plan_persistent(const bf_ctx* c) {
-    // The persistent form of the one-kernel loop (bf_loop.hip): the work-groups stay resident over many iterations and
-    // exchange their moment sums through memory -- for a context that has the GPU to itself (two such kernels from two
-    // contexts could each hold half of the CUs and wait for the other half), when all tiles can be resident at once.
-    // A cold run re-bins a dozen times in its first iterations, and every re-bin ends a launch of the persistent kernel with
-    // a host round trip (measured on 50 000 events, 240x180: 25 us per iteration against 17); a warm-started slice of a stream
-    // -- the reference's own mode, ~115 iterations and one or two re-bins -- is where it pays (11.1 against 12.2 us per
-    // iteration all in): "auto" takes it for warm starts.
-    return plan_one_kernel(c) && !c->opt_co_schedule && (c->opt_persist == 2 || (c->opt_persist == 1 && c->pending_warp)) &&
-           g_live_ctx[c->device & 63].load() == 1 &&
-           fused_loop_resident(c->win.scale / 2, c->fgrid.TSR, c->n_cus, c->fgrid.nbr * c->fgrid.nbc);   // (else: one launch per iteration)
+// The loop form and the update's home: bf_rules::loop_choice (bf_plan_rules.h) of the facts below.  Why its thresholds are what they are:
+// One slice context alone on the GPU: the one-kernel iteration when the slice qualifies (plan_slice), else the
+// two-kernel tile-binned loop when the slice is dense enough for it, else global atomics.
+// The persistent form of the one-kernel loop (bf_loop.hip): the work-groups stay resident over many iterations and
+// exchange their moment sums through memory -- for a context that has the GPU to itself (two such kernels from two
+// contexts could each hold half of the CUs and wait for the other half), when all tiles can be resident at once.
+// A cold run re-bins a dozen times in its first iterations, and every re-bin ends a launch of the persistent kernel with
+// a host round trip (measured on 50 000 events, 240x180: 25 us per iteration against 17); a warm-started slice of a stream
+// -- the reference's own mode, ~115 iterations and one or two re-bins -- is where it pays (11.1 against 12.2 us per
+// iteration all in): "auto" takes it for warm starts.  (else: one launch per iteration)
+// Delta scatter (bf_kernels.hip: k_warp_scatter_delta), a form of the global-atomic loop: any slice without a noise mask can
+// take it, and it then stands in for whichever loop the slice would run.  "auto" takes it where it was measured against the
+// loop it replaces (experiments/round_8.md): cold runs of contexts that share the GPU ("co_schedule") on slices that would
+// run the two-kernel loop on dense slabs by "auto"'s own choice, with packed planes and at least one event per image pixel
+// -- config 2 under four contexts 218 -> 240 Mevents/s: the loop is bound by bytes there, and the slab hand-off is half of
+// them.  A context alone (a latency chain: 101.5 against 102 Mevents/s, no gain), warm starts (a handful of iterations
+// would pay for a full first scatter of global atomics) and the event-list geometries keep their loops; so does a
+// context whose loop an option forces.  Nor a run capped below 200 iterations: the run's first two launches -- the full
+// scatter and the first warp, which moves every event -- cost ~0.3 ms more than the tile-binned loop's (max_iter = 10 under
+// four contexts: 0.69 -> 1.03 ms per slice), and an iteration saves ~3 us.
+// Where the model / loop update runs.  One slice context alone: at the head of the next warp+scatter launch (every
+// work-group for itself; shortest iteration).  Several contexts sharing the GPU ("co_schedule"): in the last
+// work-group of the stencil kernel -- a serial tail on ONE CU that the other contexts' kernels fill, instead of
+// ~1.5 us on all 256 CUs.  (the one-kernel loop has no other form than the head)
+// A third home ("sep_update", round 6): contexts that share the GPU run the lean scatter kernel and a stencil kernel that
+// only ACCUMULATES (no drain of its atomics, no ticket, no serial tail), and the update is a kernel of its own
+// (k_finish_update: one wave) ahead of every scatter launch, on ONE state buffer (nobody reads the state while that kernel
+// writes it).  Bookkeeping -- accumulator parities, overflow slots, when a snapshot is behind a re-bin -- is the head
+// form's.  A stencil work-group that has to see its fifteen atomics acknowledged and then wait for its ticket holds its LDS and a
+// wave slot ~1 us longer -- 10 % of its life: with thousands of work-groups per launch (event lists: 8100 tiles at 1280x720)
+// the third launch per iteration is the cheaper way (stencil kernel 42.7 -> 37.9 us under co_schedule, config 5's batch +2.7 %);
+// with a few hundred (config 2: 752) the launch costs more than the tickets (bench 206.7 -> 200.9): "auto" takes it for event
+// lists only.  Same bits either way.
+bf_rules::LoopFacts loop_facts(const bf_ctx* c, int max_iter, bool for_run) {
+    bf_rules::LoopFacts f;
+    f.opt_binned = c->opt_binned; f.opt_fused = c->opt_fused; f.opt_persist = c->opt_persist; f.opt_delta = c->opt_delta;
+    f.opt_sep_update = c->opt_sep_update; f.co_schedule = c->opt_co_schedule;
+    f.pixels = (double)c->win.scale_img_x * (double)c->win.scale_img_y;
+    f.n = c->n; f.max_iter = max_iter;
+    f.has_noise = c->has_noise; f.packed = c->packed; f.warm = c->pending_warp; f.live_ctx = g_live_ctx[c->device & 63].load();
+    f.grid_ok = c->use_binned; f.fused_ok = c->fused_ok; f.fused_shared = c->fused_shared; f.fmt = c->fmt;
+    // (the device is asked -- an occupancy query, the kernel's code object loaded -- only where its answer decides: not for a run delta scatter takes)
+    f.resident = !bf_rules::persistent_ok(f) || (for_run && bf_rules::delta_ok(f)) || fused_loop_resident(c->win.scale / 2, c->fgrid.TSR, c->n_cus, c->fgrid.nbr * c->fgrid.nbc);
+    return f;
 }
 
 RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     RunPlan p;
-    // Delta scatter (bf_kernels.hip: k_warp_scatter_delta), a form of the global-atomic loop: any slice without a noise mask can
-    // take it, and it then stands in for whichever loop the slice would run.  "auto" takes it where it was measured against the
-    // loop it replaces (experiments/round_8.md): cold runs of contexts that share the GPU ("co_schedule") on slices that would
-    // run the two-kernel loop on dense slabs by "auto"'s own choice, with packed planes and at least one event per image pixel
-    // -- config 2 under four contexts 218 -> 240 Mevents/s: the loop is bound by bytes there, and the slab hand-off is half of
-    // them.  A context alone (a latency chain: 101.5 against 102 Mevents/s, no gain), warm starts (a handful of iterations
-    // would pay for a full first scatter of global atomics) and the event-list geometries keep their loops; so does a
-    // context whose loop an option forces.  Nor a run capped below 200 iterations: the run's first two launches -- the full
-    // scatter and the first warp, which moves every event -- cost ~0.3 ms more than the tile-binned loop's (max_iter = 10 under
-    // four contexts: 0.69 -> 1.03 ms per slice), and an iteration saves ~3 us.
-    const double Pdelta = (double)c->win.scale_img_x * (double)c->win.scale_img_y;
-    const bool delta_pays = c->opt_co_schedule && !c->pending_warp && c->opt_binned == 1 && c->opt_fused != 2 && c->use_binned &&
-                            c->fmt == 0 && c->packed && !plan_one_kernel(c) && (double)c->n >= Pdelta && Pdelta < (double)(1u << 28) &&
-                            (o.max_iter <= 0 || o.max_iter >= 200);
-    p.delta = !c->has_noise && c->n > 0 && (c->opt_delta == 2 || (c->opt_delta == 1 && delta_pays));
-    p.fused = !p.delta && plan_one_kernel(c);
-    p.binned = !p.delta && (c->use_binned || p.fused);
-    p.persist = !p.delta && plan_persistent(c);
+    const bf_rules::LoopChoice choice = bf_rules::loop_choice(loop_facts(c, o.max_iter, true));
+    p.form = choice.form; p.home = choice.home;
     // (g_live_ctx only knows this process: another process's kernels -- or anything else that keeps work-groups from becoming
     // resident -- shows as a launch that gives up after 0.2 s.  The context then stays away from the kernel for a while.)
-    if (p.persist && c->persist_skip > 0) { --c->persist_skip; p.persist = false; }
+    if (p.loop_kernel() && c->persist_skip > 0) { --c->persist_skip; p.form = RunPlan::Form::one_kernel; }
     // Tile-binned mode sorts the events by the tile of their CURRENT target, so a warm-start
     // warp (bf_set_model) is applied before the sort rather than inside the first iteration.
     p.warm_start = c->pending_warp;
-    p.prewarp = p.binned && c->pending_warp;   // fused into the first counting sort (k_bin_count<true>)
+    p.prewarp = p.bin_grid() && c->pending_warp;   // fused into the first counting sort (k_bin_count<true>)
     p.first_warp = c->pending_warp && !p.prewarp;
     // (the persistent loop re-bins AT the request -- it returns for it --, the other loops one or two batches of launches
     // after it: the same effective threshold)
-    if (p.binned) p.drift_limit = c->opt_bin_predict ? (p.persist ? 0.85 : 0.6) * (double)(p.fused ? c->fgrid.D : c->grid.D) : 1e300;
-    p.split = p.binned && !p.fused && c->fmt == 3;
-    // Where the model / loop update runs.  One slice context alone: at the head of the next warp+scatter launch (every
-    // work-group for itself; shortest iteration).  Several contexts sharing the GPU ("co_schedule"): in the last
-    // work-group of the stencil kernel -- a serial tail on ONE CU that the other contexts' kernels fill, instead of
-    // ~1.5 us on all 256 CUs.
-    p.head_update = p.fused || (p.binned && !c->opt_co_schedule);   // (the one-kernel loop has no other form)
-    // A third home ("sep_update", round 6): contexts that share the GPU run the lean scatter kernel and a stencil kernel that
-    // only ACCUMULATES (no drain of its atomics, no ticket, no serial tail), and the update is a kernel of its own
-    // (k_finish_update: one wave) ahead of every scatter launch, on ONE state buffer (nobody reads the state while that kernel
-    // writes it).  Bookkeeping -- accumulator parities, overflow slots, when a snapshot is behind a re-bin -- is the head
-    // form's.  A stencil work-group that has to see its fifteen atomics acknowledged and then wait for its ticket holds its LDS and a
-    // wave slot ~1 us longer -- 10 % of its life: with thousands of work-groups per launch (event lists: 8100 tiles at 1280x720)
-    // the third launch per iteration is the cheaper way (stencil kernel 42.7 -> 37.9 us under co_schedule, config 5's batch +2.7 %);
-    // with a few hundred (config 2: 752) the launch costs more than the tickets (bench 206.7 -> 200.9): "auto" takes it for event
-    // lists only.  Same bits either way.
-    p.sep_update = p.binned && !p.fused && !p.head_update && (c->opt_sep_update == 2 || (c->opt_sep_update == 1 && c->fmt == 2));
+    if (p.bin_grid()) p.drift_limit = c->opt_bin_predict ? (p.loop_kernel() ? 0.85 : 0.6) * (double)(p.one_kernel() ? c->fgrid.D : c->grid.D) : 1e300;
     // Work-group size of the scatter kernel (bf_rules::scatter_size).  Dense tiles: 1024 threads for a context that
     // has the GPU to itself and bins of thousands of events (8.0 against 8.9 us per launch at config 2; at 640x480, bins of
     // ~1500 events, 512 threads: 11.7 against 17.4 us), 512 for contexts sharing the GPU ("co_schedule": a
@@ -179,7 +174,7 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     // work-groups (16.6 against 18.6 us per scatter launch there at 1 M events, 8.2 against 13.3 at 100 k); with a couple of
     // bins per CU -- 640x480, 540 bins -- 512 threads stay ahead (6.3 against 8.2).  (512 rather than 1024 where a bin holds a few
     // hundred events -- large images --: twice as many bins in flight per CU, 84 instead of 91 us per iteration at 1280x720.)
-    if (p.binned) {
+    if (p.two_kernel()) {
         // events a scatter thread keeps in flight:
         // (event lists: registers, not LDS, set the occupancy there -- two events per thread keep four work-groups on a
         // CU, and a bin above the pass size takes a second pass; measured at 1280x720: 512 x 2 69.8 us, 512 x 4 73.5)
@@ -195,7 +190,7 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
         // 877 in the fullest: four per thread cover every bin in one pass, 14.3-14.6 -> 13.5 us per launch; the head form, whose
         // registers also hold the update, loses with four: 14.8 -> 16.5)
         // (the arithmetic of all of the above: bf_plan_rules.h)
-        const bf_rules::ScatterSize k1 = bf_rules::scatter_size(c->fmt, p.head_update, c->grid.nbins, c->n, c->n_cus);
+        const bf_rules::ScatterSize k1 = bf_rules::scatter_size(c->fmt, p.head(), c->grid.nbins, c->n, c->n_cus);
         p.bin_threads = k1.threads;
         p.ev_per_thread = k1.per_thread;
     }
@@ -206,6 +201,6 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o) {
     p.quick_warm = p.warm_start && c->warm_iters_hint < 3 * o.poll_interval;
     // A tile-binned run that is not a quick warm start reads its progress from the pinned snapshot (bf_run.cpp: wait_snapshot).
     // ... and so does delta scatter, whose stencil kernel writes the same snapshot.
-    p.snap_polled = (p.binned || p.delta) && !p.quick_warm;
+    p.snap_polled = (p.bin_grid() || p.kept_plane()) && !p.quick_warm;
     return p;
 }

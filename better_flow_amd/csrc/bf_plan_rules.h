@@ -1,5 +1,5 @@
 // bf_plan_rules.h -- the arithmetic that picks the kernel variants of the two-kernel tile-binned loop, as pure functions of plain
-// numbers: no bf_ctx, no HIP, nothing but <cstddef> / <cstdint>.  bf_plan.cpp (plan_slice, plan_run), the launchers
+// numbers: no bf_ctx, no HIP, nothing but <cstddef> / <cstdint> and the ABI's constants.  bf_plan.cpp (plan_slice, plan_run), the launchers
 // (launch_bin_warp_scatter, launch_stencil_binned) and bf_run's record of what it launched (bf_get_stat "k1_*" / "k3_*") all
 // call these, so the plan, the dispatch and the report cannot disagree; tests/cpp/test_plan.cpp sweeps them on the host and
 // holds the set of variants they can return to tests/variants_reachable.txt.  Why each threshold is what it is stands next to
@@ -7,6 +7,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+
+#include "../../include/bf_accel.h"   // BF_LOOP_*
 
 namespace bf_rules {
 
@@ -131,5 +133,59 @@ BF_RULES_HD inline int tile_of_block(int b, int ntiles) {
 }
 inline int stencil_half_scale(int scale) { return scale / 2 < 4 ? scale / 2 : 4; }   // HS
 inline int stencil_mode(int fmt) { return fmt == 3 ? 2 : (fmt ? 1 : 0); }            // MODE: 0 dense slabs, 1 lists, 2 own pixels + margin plane
+
+// ---- which loop a run takes, and where its model update runs ----------------------------------------------------------------
+// One value each: a run has exactly one form and one home, and every question bf_run asks is answered from the two (RunPlan,
+// bf_ctx.h).  The forms are bf_get_stat "loop_form"'s values.
+enum class LoopForm : int {
+    atomic = BF_LOOP_ATOMIC,           // global atomics into alternating plane buffers
+    binned = BF_LOOP_BINNED,           // the two-kernel tile-binned loop
+    one_kernel = BF_LOOP_ONE_KERNEL,   // the one-kernel iteration, one launch per iteration
+    persistent = BF_LOOP_PERSISTENT,   // ... as the persistent loop kernel
+    delta = BF_LOOP_DELTA,             // global atomics on ONE plane buffer that is kept up to date
+};
+enum class UpdateHome : int {
+    tail,       // the stencil kernel's last work-group
+    head,       // the head of the next scatter launch (the one-kernel loops have no other)
+    separate,   // k_finish_update ahead of every scatter launch, the stencil kernel only accumulates
+};
+struct LoopChoice {
+    LoopForm form;
+    UpdateHome home;
+};
+// What the choice depends on.  The options: 0 never, 1 "auto", 2 whenever possible.
+struct LoopFacts {
+    int opt_binned = 1, opt_fused = 1, opt_persist = 1, opt_delta = 1, opt_sep_update = 1;
+    bool co_schedule = false;     // the context shares the GPU with others
+    double pixels = 0;            // of the scaled image
+    long long n = 0;              // events
+    int max_iter = -1;            // the run's cap (<= 0: none)
+    bool has_noise = false, packed = true;
+    bool warm = false;            // bf_set_model's warp is pending
+    int live_ctx = 1;             // contexts of this process alive on the device
+    // what plan_slice found possible: the two-kernel loop's grid, the one-kernel iteration's (and whether that loop is also the one
+    // to take under "co_schedule"), the scatter format
+    bool grid_ok = false, fused_ok = false, fused_shared = false;
+    int fmt = 0;
+    bool resident = true;         // every tile of the one-kernel grid can be resident at once (the persistent kernel)
+};
+inline bool one_kernel_ok(const LoopFacts& f) { return f.fused_ok && (!f.co_schedule || f.fused_shared); }
+inline bool persistent_ok(const LoopFacts& f) {
+    return one_kernel_ok(f) && !f.co_schedule && (f.opt_persist == 2 || (f.opt_persist == 1 && f.warm)) && f.live_ctx == 1 && f.resident;
+}
+inline bool delta_ok(const LoopFacts& f) {
+    const bool pays = f.co_schedule && !f.warm && f.opt_binned == 1 && f.opt_fused != 2 && f.grid_ok && f.fmt == 0 && f.packed && !one_kernel_ok(f) &&
+                      (double)f.n >= f.pixels && f.pixels < (double)(1u << 28) && (f.max_iter <= 0 || f.max_iter >= 200);
+    return !f.has_noise && f.n > 0 && (f.opt_delta == 2 || (f.opt_delta == 1 && pays));
+}
+inline LoopChoice loop_choice(const LoopFacts& f) {
+    if (delta_ok(f)) return {LoopForm::delta, UpdateHome::tail};
+    if (persistent_ok(f)) return {LoopForm::persistent, UpdateHome::head};
+    if (one_kernel_ok(f)) return {LoopForm::one_kernel, UpdateHome::head};
+    if (!f.grid_ok) return {LoopForm::atomic, UpdateHome::tail};
+    if (!f.co_schedule) return {LoopForm::binned, UpdateHome::head};
+    const bool separate = f.opt_sep_update == 2 || (f.opt_sep_update == 1 && f.fmt == 2);
+    return {LoopForm::binned, separate ? UpdateHome::separate : UpdateHome::tail};
+}
 
 }  // namespace bf_rules

@@ -21,11 +21,20 @@ struct RunLoop {
     bf_ctx* c;
     const RunPlan& p;
     // Tile-binned loop: the update of iteration j runs at the head of warp+scatter launch j + 1, so the state ping-pongs between
-    // two buffers (launch j reads [j & 1], writes [(j + 1) & 1]; sep_update: ONE buffer), the moment accumulators alternate with the
+    // two buffers (launch j reads [j & 1], writes [(j + 1) & 1]; update in k_finish_update: ONE buffer), the moment accumulators alternate with the
     // iteration's parity (one-kernel loop: the launch number mod 3), and the overflow events of iteration j are counted in slot
     // j % 3 (slot 2 stands for "iteration -1": is plane buffer b0 ^ 1 still dirty from an earlier operator?).
+    // The plane buffers alternate: an iteration scatters into `buf`, its stencil launch clears the other one, the next iteration takes
+    // that one.  Delta scatter keeps b0: its first launch is the plain loop's (the other buffer may be dirty from earlier), every later
+    // one moves the events that changed pixel and its stencil launch clears nothing.  The one-kernel loops touch neither buffer.
     int b0 = 0, buf = 0;             // plane buffer of the first iteration / of the next one
     bool first = true;               // no iteration launched yet
+    bool delta_step() const { return p.kept_plane() && !first; }
+    void next_buf() { if (!p.kept_plane()) buf ^= 1; }
+    int cur_after(int it) const {    // the clean buffer after `it` executed iterations: where the next scatter goes
+        if (p.one_kernel()) return b0;
+        return p.kept_plane() ? (it > 0 ? b0 ^ 1 : b0) : b0 ^ (it & 1);
+    }
     int launched_iters = 0;
     bool prewarp_done = false;       // a persistent round has fused the warm start's warp into its counting sort
     bf_trace_rec* trace = nullptr;
@@ -40,8 +49,9 @@ struct RunLoop {
     DevState fin;                    // the final state (snapshot-polled: read by run_end)
     bf_run_info inf{0, 0, 1.0f, 1.0f, 10000.0f, 10000.0f};   // (rc, iterations, the four dividers)
     HostTiming ht;
-    DevState* state_of(int j) const { return c->d_state + ((p.sep_update || !p.binned) ? 0 : (j & 1)); }
-    MomentAcc* acc_of(int j) const { return c->d_acc + (size_t)(p.fused ? ((j % 3) + 3) % 3 : (j & 1)) * kAccGroups; }
+    bool split() const { return p.two_kernel() && c->fmt == 3; }   // own pixels + margin plane
+    DevState* state_of(int j) const { return c->d_state + (p.one_state() ? 0 : (j & 1)); }
+    MomentAcc* acc_of(int j) const { return c->d_acc + (size_t)(p.acc_ring3() ? ((j % 3) + 3) % 3 : (j & 1)) * kAccGroups; }
     uint32_t* ovf_of(int j) const { return c->d_ovf + (((j % 3) + 3) % 3) * kOvfSlotWords; }
     int finish(const DevState& s, bool warped) { fin = s; done = true; final_done = warped; return BF_OK; }   // the loop is over
 };
@@ -62,13 +72,13 @@ int run_begin(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L) {
     h.max_iter = o.max_iter;
     h.hard_cap = o.hard_iter_cap;
     h.trace_cap = o.trace_cap;
-    h.hot.binned = p.binned ? 1 : 0;
-    h.hot.need_rebin = p.binned ? 1 : 0;   // the first enqueued re-bin builds the bins
+    h.hot.binned = p.bin_grid() ? 1 : 0;
+    h.hot.need_rebin = p.bin_grid() ? 1 : 0;   // the first enqueued re-bin builds the bins
     h.hot.rebins = 0; h.ovf_total = 0;
     h.hot.cs = c->cs; h.hot.flip = 0;
     h.hot.pp = 0; h.hot.redo = 0; h.hot.pend = 0; h.last_j = -1;
     h.hot.spare_ = 0;   // launches of the persistent loop kernel completed in THIS run (with run_tag: the launch's id)
-    if (p.binned) h.drift_limit = p.drift_limit;
+    if (p.bin_grid()) h.drift_limit = p.drift_limit;
     // A warm start keeps bf_set_model's warp in hot.wp: the first iteration applies it, or the first counting sort does (prewarp).  In
     // that case the bins are built for the positions THAT warp gives, so it is the reference the drift bound measures from
     // (k_bin_scan: ref_wp <- hot.wp; the first pass does not warp, and the first update overwrites hot.wp).  With the identity there,
@@ -77,20 +87,20 @@ int run_begin(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L) {
     // with its host round trip.
     if (!p.warm_start) h.hot.wp = identity_warp();
     h.ref_wp = h.hot.wp;
-    launch_run_init(c->d_state, h, c->d_ovf, h.hot.ovf_cnt[L.b0 ^ 1] ? 1u : 0u, c->d_acc, p.binned || c->acc_dirty, c->stream);
+    launch_run_init(c->d_state, h, c->d_ovf, h.hot.ovf_cnt[L.b0 ^ 1] ? 1u : 0u, c->d_acc, p.bin_grid() || c->acc_dirty, c->stream);
     c->acc_dirty = false;
     // Interior + margin format: iteration j adds to margin plane b0 ^ (j & 1) and clears, bin by bin, what the lists say the
     // previous executed launch left in the other one.  That works across runs as long as the plane the lists describe is not
     // the one the first iteration adds to; otherwise (or after a run that did not complete) it is cleared up front.
-    if (p.split) {
+    if (L.split()) {
         if (c->m_unknown || c->m_dirty_plane == L.b0) {
             int rcm = margin_reset(c);
             if (rcm != BF_OK) return rcm;
         }
         c->m_unknown = true;   // (until this run has completed)
     }
-    if (p.head_like()) c->acc_dirty = true;   // (the sums of the last iteration are consumed, not cleared)
-    if (p.persist) {
+    if (p.accumulate_only()) c->acc_dirty = true;   // (the sums of the last iteration are consumed, not cleared)
+    if (p.loop_kernel()) {
         const size_t nrec = (size_t)c->fgrid.nbr * c->fgrid.nbc * (c->fgrid.TSR / 16);
         HIP_TRY(c, grow_zeroed(c, c->d_xrec, 2 * nrec * 32));
         HIP_TRY(c, grow_zeroed(c, c->d_xred, 2 * 16 * 32));
@@ -110,7 +120,7 @@ void enqueue_final_warp(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLo
     ProfScope ps(c, 3);
     WarpScatterArgs fa = ws_args(c, L.buf, check_done);
     fa.st = st;                         // (after `done` every launch keeps both buffers identical)
-    fa.pick_set = p.binned ? 1 : 0;     // the device knows which set holds the (tile-sorted) events
+    fa.pick_set = p.bin_grid() ? 1 : 0;     // the device knows which set holds the (tile-sorted) events
     fa.sorted_out = 1;
     if (o.want_uv) fa.uv = c->d_uv;     // Event::compute_uv (event.h:135-142) in the same pass
     launch_final_warp(fa, c->stream);
@@ -199,125 +209,126 @@ int run_persistent(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L
     }
 }
 
-// One iteration of the planned loop: the one-kernel pass, or [k_finish_update +] binned or global-atomic scatter + stencil kernel.
+// One iteration of each loop: j its number, `warp` whether its launch warps the events, `snap` the pinned snapshot whoever
+// computes the new state writes it to as well (null: a quick warm start).
+// The one-kernel pass: warp + scatter + stencil + moments in one launch; the update at the head of the next.
+int enqueue_one_kernel(bf_ctx* c, RunLoop& L, int j, bool warp, DevState* snap) {
+    FusedArgs fa;
+    fa.sets = ev_sets(c); fa.ftab = c->d_ftab;
+    fa.st_in = L.state_of(j); fa.st_out = L.state_of(j + 1);
+    fa.snap = snap;
+    fa.acc_in = L.acc_of(j - 1); fa.acc_out = L.acc_of(j); fa.acc_zero = L.acc_of(j + 1);
+    fa.lost = lost_flag(c); fa.trace = L.trace;
+    fa.nbr = c->fgrid.nbr; fa.nbc = c->fgrid.nbc;
+    fa.R = c->win.scale_img_x; fa.C = c->win.scale_img_y;
+    fa.j = j; fa.warp = warp ? 1 : 0; fa.tl = c->d_tl;
+    ProfScope ps(c, 0, c->n);
+    HIP_TRY(c, launch_fused_pass(fa, c->win.scale / 2, c->fgrid.TSR, c->stream));
+    L.inf.launches += 1;
+    return BF_OK;
+}
+
+// What the two pairs' stencil launches share: the end of the arguments, the launch and the pair's accounting.
+void launch_pair_stencil(bf_ctx* c, RunLoop& L, StencilArgs& a, StencilSrc src, int j, int n_cus) {
+    a.trace = L.trace; a.update_mode = 1;
+    a.tl = c->d_tl; a.tl_launch = j;
+    ProfScope ps(c, 1);
+    launch_stencil(a, src, c->stream, n_cus);
+    L.inf.launches += 2;
+}
+
+// The tile-binned pair: [k_finish_update +] warp + scatter by bin, then stencil + moments.
+int enqueue_binned_pair(bf_ctx* c, const RunPlan& p, RunLoop& L, int j, bool warp, DevState* snap) {
+    const int buf = L.buf;
+    if (p.separate()) {   // the pending update of iteration j - 1 (none at j = 0: the state's own counter says so)
+        launch_finish_update(L.state_of(j), L.acc_of(j - 1), L.ovf_of(j - 1), j, buf ^ 1, L.trace, snap, c->stream);
+        L.inf.launches++;
+    }
+    BinScatterArgs ba;
+    ba.sets = ev_sets(c); ba.bin_start = c->d_bin_start; ba.slabs = c->d_slabs;
+    ba.cidx = c->d_cidx; ba.chdr = c->d_chdr;
+    ba.compact = c->fmt;
+    ba.ovf_plane = c->d_plane[buf]; ba.ovf_cplane = c->d_cplane[buf];
+    ba.ovf_bits = c->d_ovf_bits[buf]; ba.ovf_pitch = c->ovf_pitch;
+    ba.st_in = L.state_of(j); ba.st_out = L.state_of(j + 1);
+    ba.acc = p.head() ? L.acc_of(j - 1) : nullptr;
+    ba.ovf_cur = L.ovf_of(j); ba.ovf_prev = L.ovf_of(j - 1);
+    ba.snap = snap; ba.trace = L.trace; ba.g = c->grid;
+    ba.cur = buf; ba.j = j;
+    ba.tl = c->d_tl ? c->d_tl + 64 * 2 * 16 : nullptr;
+    ba.m_cur = c->d_mplane[buf]; ba.m_prev = c->d_mplane[buf ^ 1];
+    ba.mlist = c->d_mlist; ba.mcount = c->d_mcount; ba.mcap = c->m_cap;
+    { ProfScope ps(c, 0, c->n); HIP_TRY(c, launch_bin_warp_scatter(ba, warp, p.bin_threads, p.ev_per_thread, c->stream)); }
+    c->launched.k1_threads = p.bin_threads; c->launched.k1_per_thread = p.ev_per_thread; c->launched.k1_head = p.head() ? 1 : 0;
+    StencilArgs a = st_args(c, buf, 1);
+    a.ovf_bits = c->d_ovf_bits[buf]; a.zero_bits = c->d_ovf_bits[buf ^ 1]; a.ovf_pitch = c->ovf_pitch;
+    a.zero_full = j == 0 ? 1 : 0;   // (what an earlier operator left in the other buffer is not in the bitmap)
+    a.ovf_cur = L.ovf_of(j); a.ovf_prev = L.ovf_of(j - 1); a.ovf_next = L.ovf_of(j + 1);
+    // Which work-group takes which tile (same bits either way).  Bands of tile rows per residue class mod 8 of the launch
+    // id -- neighbouring tiles' shared halo then meets in one L2 -- for the slab formats of contexts that share the GPU:
+    // config 2 with four contexts in flight 206.3 -> 212.3 Mevents/s, the stencil kernel 15.7 -> 15.1 us and the lean
+    // scatter kernel 14.3 -> 14.1 us per launch.  Launch order where the bands LOST (experiments/tile_order.md): a context
+    // alone on the GPU (the scatter launch that FOLLOWS a banded stencil launch is 1.5 - 1.7 us slower there, 8.3 -> 9.8
+    // and 9.3 -> 11.0 us, against 0.4 - 0.7 us gained in the stencil kernel) and event lists (config 5, 16 slices: 3.63 ->
+    // 3.57 Mevents/s).
+    a.tile_bands = (!p.head() && c->fmt != 2) ? 1 : 0;
+    if (p.accumulate_only()) {   // the update runs at the head of the next warp+scatter launch (or in its own kernel)
+        a.st = L.state_of(j + 1);
+        a.acc = L.acc_of(j); a.acc_zero = L.acc_of(j + 1);
+    } else {   // "co_schedule": the last work-group of the stencil kernel updates
+        a.acc = c->d_acc; a.ticket = c->d_ticket;
+        // it reads the state the (lean) scatter kernel read and writes the new one where the next scatter
+        // launch looks for it -- and to the pinned snapshot the host polls; nobody copies the state in between
+        a.st = L.state_of(j); a.st_rw = L.state_of(j + 1);
+        a.snap = snap;
+    }
+    // (contexts of this process sharing the GPU -- g_live_ctx, read per launch: they come and go -- hold CU slots too.  For event
+    // lists (large sparse images) count the GPU as full whatever this grid's size, i.e. take the stencil kernel's build that fits 8
+    // work-groups per CU: config 5 with four contexts 3.27 against 2.90 Mevents/s.  Dense tiles on a grid that does not fill
+    // the GPU by itself keep the plain build: config 2 with four contexts 208.3 against 206.5, round 5 -- since its
+    // instruction diet the kernel gains less from two more work-groups per CU than it loses to the spills.)
+    const bool shared_lists = c->opt_co_schedule && c->fmt == 2 && g_live_ctx[c->device & 63].load() > 1;
+    const int k3_cus = shared_lists ? 1 : c->n_cus;
+    launch_pair_stencil(c, L, a, StencilSrc::binned, j, k3_cus);
+    // (launch_stencil_binned picks its build by the same rule from the same numbers)
+    c->launched.k3_half_scale = bf_rules::stencil_half_scale(a.scale);
+    c->launched.k3_mode = bf_rules::stencil_mode(a.compact);
+    c->launched.k3_capped = bf_rules::stencil_capped(bf_rules::stencil_tiles(a.R, a.C), k3_cus) ? 1 : 0;
+    return BF_OK;
+}
+
+// The plane pair: warp + scatter with one global atomic per event (a delta step: per event that changed pixel), then stencil +
+// moments, whose last work-group reduces and runs the model / loop update.
+void enqueue_plane_pair(bf_ctx* c, const RunPlan& p, RunLoop& L, int j, bool warp, DevState* snap) {
+    {
+        ProfScope ps(c, 0, c->n);
+        if (L.delta_step()) launch_warp_scatter_delta(ws_args(c, L.buf, 1), c->stream);
+        else launch_warp_scatter(ws_args(c, L.buf, 1), warp, true, false, c->stream);
+    }
+    StencilArgs a = st_args(c, L.buf, 1);
+    if (L.delta_step()) a.zero_plane = nullptr, a.zero_cplane = nullptr;
+    a.acc = c->d_acc; a.ticket = c->d_ticket; a.st_rw = c->d_state;
+    if (p.kept_plane()) a.snap = snap;   // (polled like the tile-binned loop: wait_snapshot)
+    // Delta scatter on a packed plane: the tile-binned loop's stencil kernel reading the plane itself (one load per pixel
+    // of the halo plane where it merges 2 x 2 slabs), in banded tile order when contexts share the GPU -- k_stencil takes
+    // half as long again per launch (experiments/round_8.md).  Split planes keep k_stencil.
+    const bool plane_k3 = p.kept_plane() && c->packed && (unsigned long long)a.R * (unsigned long long)a.C < (1ull << 28);
+    if (plane_k3) a.tile_bands = c->opt_co_schedule ? 1 : 0;
+    launch_pair_stencil(c, L, a, plane_k3 ? StencilSrc::plane_binned : plane_src(c), j, c->n_cus);
+}
+
 int enqueue_iteration(bf_ctx* c, const RunPlan& p, RunLoop& L) {
     const bool warp = L.first ? p.first_warp : true;
     const int j = L.launched_iters;
     DevState* const snap = p.quick_warm ? nullptr : &c->h_state[0];
-    if (p.fused) {   // warp + scatter + stencil + moments in one launch; the update at the head of the next
-        FusedArgs fa;
-        fa.sets = ev_sets(c);
-        fa.ftab = c->d_ftab;
-        fa.st_in = L.state_of(j); fa.st_out = L.state_of(j + 1);
-        fa.snap = snap;
-        fa.acc_in = L.acc_of(j - 1); fa.acc_out = L.acc_of(j); fa.acc_zero = L.acc_of(j + 1);
-        fa.lost = lost_flag(c);
-        fa.trace = L.trace;
-        fa.nbr = c->fgrid.nbr; fa.nbc = c->fgrid.nbc;
-        fa.R = c->win.scale_img_x; fa.C = c->win.scale_img_y;
-        fa.j = j;
-        fa.warp = warp ? 1 : 0;
-        fa.tl = c->d_tl;
-        ProfScope ps(c, 0, c->n);
-        HIP_TRY(c, launch_fused_pass(fa, c->win.scale / 2, c->fgrid.TSR, c->stream));
-        L.inf.launches += 1;
-    } else {
-        // Delta scatter: every launch of the run works on the buffer the first one filled -- the first is the plain loop's full
-        // scatter into a clean buffer (its stencil launch clears the other one, which an earlier run or operator may have left
-        // dirty), every later one moves the events whose pixel changed, and its stencil launch clears nothing.
-        const bool delta_step = p.delta && !L.first;
-        const int buf = p.delta ? L.b0 : L.buf;
-        if (p.sep_update) {   // the pending update of iteration j - 1 (none at j = 0: the state's own counter says so)
-            launch_finish_update(L.state_of(j), L.acc_of(j - 1), L.ovf_of(j - 1), j, buf ^ 1, L.trace, snap, c->stream);
-            L.inf.launches++;
-        }
-        if (p.binned) {
-            BinScatterArgs ba;
-            ba.sets = ev_sets(c);
-            ba.bin_start = c->d_bin_start;
-            ba.slabs = c->d_slabs;
-            ba.cidx = c->d_cidx; ba.chdr = c->d_chdr;
-            ba.compact = c->fmt;
-            ba.ovf_plane = c->d_plane[buf]; ba.ovf_cplane = c->d_cplane[buf];
-            ba.ovf_bits = c->d_ovf_bits[buf]; ba.ovf_pitch = c->ovf_pitch;
-            ba.st_in = L.state_of(j); ba.st_out = L.state_of(j + 1);
-            ba.acc = p.head_update ? L.acc_of(j - 1) : nullptr;
-            ba.ovf_cur = L.ovf_of(j); ba.ovf_prev = L.ovf_of(j - 1);
-            ba.snap = snap;
-            ba.trace = L.trace;
-            ba.g = c->grid;
-            ba.cur = buf; ba.j = j;
-            ba.tl = c->d_tl ? c->d_tl + 64 * 2 * 16 : nullptr;
-            ba.m_cur = c->d_mplane[buf]; ba.m_prev = c->d_mplane[buf ^ 1];
-            ba.mlist = c->d_mlist; ba.mcount = c->d_mcount; ba.mcap = c->m_cap;
-            ProfScope ps(c, 0, c->n);
-            HIP_TRY(c, launch_bin_warp_scatter(ba, warp, p.bin_threads, p.ev_per_thread, c->stream));
-            c->launched.k1_threads = p.bin_threads; c->launched.k1_per_thread = p.ev_per_thread; c->launched.k1_head = p.head_update ? 1 : 0;
-        } else {
-            ProfScope ps(c, 0, c->n);
-            if (delta_step) launch_warp_scatter_delta(ws_args(c, buf, 1), c->stream);
-            else launch_warp_scatter(ws_args(c, buf, 1), warp, true, false, c->stream);
-        }
-        // stencil + moments; its last work-group reduces and runs the model / loop update
-        StencilArgs a = st_args(c, buf, 1);
-        if (delta_step) a.zero_plane = nullptr, a.zero_cplane = nullptr;
-        if (p.binned) {
-            a.ovf_bits = c->d_ovf_bits[buf]; a.zero_bits = c->d_ovf_bits[buf ^ 1]; a.ovf_pitch = c->ovf_pitch;
-            a.zero_full = j == 0 ? 1 : 0;   // (what an earlier operator left in the other buffer is not in the bitmap)
-            a.st = L.state_of(j + 1);
-            a.ovf_cur = L.ovf_of(j); a.ovf_prev = L.ovf_of(j - 1); a.ovf_next = L.ovf_of(j + 1);
-            // Which work-group takes which tile (same bits either way).  Bands of tile rows per residue class mod 8 of the launch
-            // id -- neighbouring tiles' shared halo then meets in one L2 -- for the slab formats of contexts that share the GPU:
-            // config 2 with four contexts in flight 206.3 -> 212.3 Mevents/s, the stencil kernel 15.7 -> 15.1 us and the lean
-            // scatter kernel 14.3 -> 14.1 us per launch.  Launch order where the bands LOST (experiments/tile_order.md): a context
-            // alone on the GPU (the scatter launch that FOLLOWS a banded stencil launch is 1.5 - 1.7 us slower there, 8.3 -> 9.8
-            // and 9.3 -> 11.0 us, against 0.4 - 0.7 us gained in the stencil kernel) and event lists (config 5, 16 slices: 3.63 ->
-            // 3.57 Mevents/s).
-            a.tile_bands = (!p.head_update && c->fmt != 2) ? 1 : 0;
-        }
-        if (p.head_like()) {   // accumulate only: the update runs at the head of the next warp+scatter launch (or in its own kernel)
-            a.acc = L.acc_of(j); a.acc_zero = L.acc_of(j + 1);
-        } else if (p.binned) {   // "co_schedule": the last work-group of the stencil kernel updates
-            a.acc = c->d_acc;
-            a.ticket = c->d_ticket;
-            // it reads the state the (lean) scatter kernel read and writes the new one where the next scatter
-            // launch looks for it -- and to the pinned snapshot the host polls; nobody copies the state in between
-            a.st = L.state_of(j);
-            a.st_rw = L.state_of(j + 1);
-            a.snap = snap;
-        } else {        // the last work-group reduces and updates
-            a.acc = c->d_acc;
-            a.ticket = c->d_ticket;
-            a.st_rw = c->d_state;
-            if (p.delta) a.snap = snap;   // (polled like the tile-binned loop: wait_snapshot)
-        }
-        a.trace = L.trace;
-        a.update_mode = 1;
-        a.tl = c->d_tl;
-        a.tl_launch = j;
-        ProfScope ps(c, 1);
-        // (contexts of this process sharing the GPU -- g_live_ctx, read per launch: they come and go -- hold CU slots too.  For event
-        // lists (large sparse images) count the GPU as full whatever this grid's size, i.e. take the stencil kernel's build that fits 8
-        // work-groups per CU: config 5 with four contexts 3.27 against 2.90 Mevents/s.  Dense tiles on a grid that does not fill
-        // the GPU by itself keep the plain build: config 2 with four contexts 208.3 against 206.5, round 5 -- since its
-        // instruction diet the kernel gains less from two more work-groups per CU than it loses to the spills.)
-        const bool shared_lists = c->opt_co_schedule && c->fmt == 2 && g_live_ctx[c->device & 63].load() > 1;
-        const int k3_cus = shared_lists ? 1 : c->n_cus;
-        // Delta scatter on a packed plane: the tile-binned loop's stencil kernel reading the plane itself (one load per pixel
-        // of the halo plane where it merges 2 x 2 slabs), in banded tile order when contexts share the GPU -- k_stencil takes
-        // half as long again per launch (experiments/round_8.md).  Split planes keep k_stencil.
-        const bool plane_k3 = p.delta && c->packed && (unsigned long long)a.R * (unsigned long long)a.C < (1ull << 28);
-        if (plane_k3) a.tile_bands = c->opt_co_schedule ? 1 : 0;
-        launch_stencil(a, plane_k3 ? 4 : stencil_src(c, p.binned), c->stream, k3_cus);
-        if (p.binned) {   // (launch_stencil_binned picks its build by the same rule from the same numbers)
-            c->launched.k3_half_scale = bf_rules::stencil_half_scale(a.scale);
-            c->launched.k3_mode = bf_rules::stencil_mode(a.compact);
-            c->launched.k3_capped = bf_rules::stencil_capped(bf_rules::stencil_tiles(a.R, a.C), k3_cus) ? 1 : 0;
-        }
-        L.inf.launches += 2;
+    int rc = BF_OK;
+    switch (p.form) {
+        case RunPlan::Form::one_kernel: case RunPlan::Form::persistent: rc = enqueue_one_kernel(c, L, j, warp, snap); break;
+        case RunPlan::Form::binned: rc = enqueue_binned_pair(c, p, L, j, warp, snap); break;
+        case RunPlan::Form::atomic: case RunPlan::Form::delta: enqueue_plane_pair(c, p, L, j, warp, snap); break;
     }
-    L.first = false;
-    if (!p.delta) L.buf ^= 1;
+    if (rc != BF_OK) return rc;
+    L.first = false; L.next_buf();
     ++L.launched_iters;
     return BF_OK;
 }
@@ -329,15 +340,15 @@ int enqueue_batch(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L,
     // when a polled snapshot shows the update asking for one.  The request is predictive
     // (0.6 x margin of drift), which covers the one-to-two batches of polling lag; anything
     // that still escapes takes the exact overflow path.
-    if (p.binned && (batch == 0 || L.want_rebin)) {
+    if (p.bin_grid() && (batch == 0 || L.want_rebin)) {
         int rc = enqueue_rebin(c, L.state_of(L.launched_iters), c->has_perm, (p.prewarp && batch == 0 && !L.prewarp_done) ? &c->hst.hot.wp : nullptr,
-                               p.fused, L.launched_iters);
+                               p.one_kernel(), L.launched_iters);
         if (rc != BF_OK) return rc;
         L.inf.launches += 3;
         L.want_rebin = false;
         L.skip_rebin_checks = 1;   // the next snapshot predates this re-bin
         L.last_rebin_at = L.launched_iters;
-        if (p.fused && batch > 0) L.stall_allowance += 3 * o.poll_interval;
+        if (p.one_kernel() && batch > 0) L.stall_allowance += 3 * o.poll_interval;
     }
     int batch_len = o.poll_interval;
     if (p.quick_warm) {
@@ -361,13 +372,13 @@ int enqueue_batch(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L,
         // set on the device: when the batch was enough -- the usual case -- nothing is left to launch
         // after the poll (a blocking poll + launch costs ~20 us of idle GPU).
         const int n = L.launched_iters;
-        if (p.head_like()) {   // `done` of the batch's last iteration: apply its update now (normally the next launch would)
+        if (p.accumulate_only()) {   // `done` of the batch's last iteration: apply its update now (normally the next launch would)
             L.seq_wait = ++c->seq_counter;
             launch_finish_update(L.state_of(n), L.acc_of(n - 1), L.ovf_of(n - 1), n, L.buf ^ 1, L.trace, &c->h_state[batch & 1], c->stream,
-                                 p.fused ? lost_flag(c) + (n + 2) % 3 : nullptr, c->h_seq, L.seq_wait);
+                                 p.one_kernel() ? lost_flag(c) + (n + 2) % 3 : nullptr, c->h_seq, L.seq_wait);
             L.inf.launches++;
         }
-        enqueue_final_warp(c, o, p, L, 2, L.state_of(p.binned ? n : 0));
+        enqueue_final_warp(c, o, p, L, 2, L.state_of(n));
     }
     if (batch == 0) {   // ("defer_uploads": the next slice's copies and staging go out now, under this batch)
         const int rcd = issue_deferred_uploads(c);
@@ -409,7 +420,7 @@ int wait_snapshot(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L)
         gpu_it = (sdone == 0) ? sit : 0;
         // (one-kernel iteration: progress is counted in LAUNCHES -- passes that wait for a re-bin, or repeat one,
         // do not advance the iteration counter)
-        if (p.fused) {
+        if (p.one_kernel()) {
             const unsigned long long wj = *lastj_p;   // (run_tag, last_j): one 8-byte store of the device
             gpu_it = ((int32_t)(uint32_t)(wj & 0xffffffffull) == tag) ? (int32_t)(uint32_t)(wj >> 32) + 1 : 0;
         }
@@ -430,7 +441,7 @@ int wait_snapshot(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L)
     // (a snapshot older than the last re-bin does not count.  With the update at the scatter head the snapshot of
     // iteration count L is written by launch L itself, behind a re-bin enqueued at L; with the update in the stencil
     // tail -- and in the one-kernel loop -- it is written by launch L - 1, ahead of that re-bin)
-    if (((p.fused || !p.head_like()) ? gpu_it > L.last_rebin_at : gpu_it >= L.last_rebin_at) && gpu_it > 0 && *rebin_p) L.want_rebin = true;
+    if ((p.snapshot_a_launch_early() ? gpu_it > L.last_rebin_at : gpu_it >= L.last_rebin_at) && gpu_it > 0 && *rebin_p) L.want_rebin = true;
     return check_iteration_cap(c, o, L);
 }
 
@@ -438,9 +449,8 @@ int wait_snapshot(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L)
 // the pinned snapshot itself and, behind a system-scope fence, this batch's sequence number -- the host spins on that word and has
 // the model while the final warp (whose results stay on the device) is still running.  A bounded spin: past 2 ms the event decides.
 int wait_quick_warm(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, int batch) {
-    if (!p.head_like())   // (else k_finish_update has written the state to the pinned copy itself)
-        HIP_TRY(c, hipMemcpyAsync(&c->h_state[batch & 1], L.state_of(p.binned ? L.launched_iters : 0), sizeof(DevState),
-                                  hipMemcpyDeviceToHost, c->stream));
+    if (!p.accumulate_only())   // (else k_finish_update has written the state to the pinned copy itself)
+        HIP_TRY(c, hipMemcpyAsync(&c->h_state[batch & 1], L.state_of(L.launched_iters), sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->poll_ev[batch & 1], c->stream));
     bool seen = false;
     if (L.seq_wait) {
@@ -462,15 +472,14 @@ int wait_quick_warm(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& 
     // (a warm start's follow-up batches are two iterations long: a re-bin -- three kernels, ~30 us on a large image --
     // pays only where the overflow path would cost more, i.e. when a good part of the events took it)
     // (the one-kernel loop has no overflow path: it WAITS for the re-bin it asks for)
-    if (p.binned && ws.hot.need_rebin && (p.fused || (unsigned long long)ws.last_ovf * 8ull > (unsigned long long)ws.n_events)) L.want_rebin = true;
+    if (p.bin_grid() && ws.hot.need_rebin && (p.one_kernel() || (unsigned long long)ws.last_ovf * 8ull > (unsigned long long)ws.n_events)) L.want_rebin = true;
     return check_iteration_cap(c, o, L);
 }
 
 // A cold run that is not snapshot-polled is polled one batch behind the launches, so its wait can sleep (the wake-up latency hides
 // behind the batch already queued) instead of burning a host core per slice context.
 int wait_one_batch_behind(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, int batch) {
-    HIP_TRY(c, hipMemcpyAsync(&c->h_state[batch & 1], L.state_of(p.binned ? L.launched_iters : 0), sizeof(DevState),
-                              hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&c->h_state[batch & 1], L.state_of(L.launched_iters), sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipEventRecord(c->poll_ev[batch & 1], c->stream));
     if (batch == 0) return BF_OK;
     L.ht.lap(L.ht.launch);
@@ -481,7 +490,7 @@ int wait_one_batch_behind(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, Run
     const DevState& snap = c->h_state[(batch - 1) & 1];
     if (snap.hot.done) return L.finish(snap, false);
     if (L.skip_rebin_checks > 0) --L.skip_rebin_checks;
-    else if (p.binned && snap.hot.need_rebin) L.want_rebin = true;
+    else if (p.bin_grid() && snap.hot.need_rebin) L.want_rebin = true;
     return check_iteration_cap(c, o, L);
 }
 
@@ -489,7 +498,7 @@ int wait_one_batch_behind(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, Run
 int run_end(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, bf_model* model_out, bf_run_info* info) {
     if (L.ht.on)
         fprintf(stderr, "bf_run host time: launching %.3f ms, waiting %.3f ms, %d launches\n", 1e3 * L.ht.launch, 1e3 * L.ht.wait, (int)L.inf.launches);
-    if (!L.final_done) enqueue_final_warp(c, o, p, L, 0, L.state_of(p.binned ? L.launched_iters : 0));
+    if (!L.final_done) enqueue_final_warp(c, o, p, L, 0, L.state_of(L.launched_iters));
     if (L.snap_polled) {   // the final state, consistently: behind everything that is queued
         HIP_TRY(c, hipMemcpyAsync(&c->h_state[1], L.state_of(L.launched_iters), sizeof(DevState), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipEventRecord(c->poll_ev[1], c->stream));
@@ -499,7 +508,7 @@ int run_end(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, bf_mo
         }
         L.fin = c->h_state[1];
     }
-    if (p.binned) {   // the device chose which set holds the (tile-sorted) events
+    if (p.bin_grid()) {   // the device chose which set holds the (tile-sorted) events
         c->cs = L.fin.hot.cs;
         c->has_perm = true;
     }
@@ -516,20 +525,16 @@ int run_end(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, bf_mo
     DevState& h = c->hst;
     h = d;   // model, dividers, warp parameters, plane-buffer dirtiness
     h.hot.pp = 0; h.hot.redo = 0; h.hot.pend = 0;   // (the final warp left the products in the set's first array)
-    if (p.split) {   // the last executed iteration added to margin plane b0 ^ ((it - 1) & 1), and the lists name those pixels
+    if (L.split()) {   // the last executed iteration added to margin plane b0 ^ ((it - 1) & 1), and the lists name those pixels
         if (d.hot.it > 0) c->m_dirty_plane = L.b0 ^ ((d.hot.it - 1) & 1);
         c->m_unknown = d.rc < 0;   // (a run stopped at the iteration cap may have one executed launch more than `it` counts)
     }
-    if (p.binned && !p.fused) {   // the last iteration scattered its overflow events into buffer b0 ^ ((it - 1) & 1); the other one is clean
+    if (p.two_kernel()) {   // the last iteration scattered its overflow events into buffer b0 ^ ((it - 1) & 1); the other one is clean
         h.hot.ovf_cnt[L.b0 ^ (d.hot.it & 1)] = 0;
         h.hot.ovf_cnt[L.b0 ^ (d.hot.it & 1) ^ 1] = d.last_ovf ? 1u : 0u;
     }
 
-    // iterations executed alternate buffers starting at b0; the next scatter goes to the
-    // buffer the last stencil left clean.  (The one-kernel loop touches neither plane buffer: what was dirty stays dirty,
-    // hot.ovf_cnt came back from the device as it went.)
-    // (Delta scatter: b0 holds the last image, the first stencil launch cleared the other one and nobody has touched it since.)
-    c->cur = p.fused ? L.b0 : p.delta ? (d.hot.it > 0 ? L.b0 ^ 1 : L.b0) : (L.b0 ^ (d.hot.it & 1));
+    c->cur = L.cur_after(d.hot.it);   // the next scatter goes to the clean buffer (one-kernel loops: hot.ovf_cnt came back as it went)
     c->trace_valid = d.hot.it < o.trace_cap ? d.hot.it : o.trace_cap;
     L.inf.rc = d.rc;
     L.inf.iterations = d.hot.it;
@@ -585,9 +590,9 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
     c->launched = bf_ctx::Launched{};
     RunLoop L{c, p};
     int rc = run_begin(c, o, p, L);
-    if (rc == BF_OK && p.persist) rc = run_persistent(c, o, p, L);
+    if (rc == BF_OK && p.loop_kernel()) rc = run_persistent(c, o, p, L);
     if (rc != BF_OK) return rc;
-    c->last_loop = p.delta ? BF_LOOP_DELTA : L.done ? BF_LOOP_PERSISTENT : p.fused ? BF_LOOP_ONE_KERNEL : p.binned ? BF_LOOP_BINNED : BF_LOOP_ATOMIC;
+    c->last_loop = (int)((p.loop_kernel() && !L.done) ? RunPlan::Form::one_kernel : p.form);   // (a persistent launch gave up: the loop that finishes the run)
     // Pipelined polling: batch b+1 is enqueued BEFORE the host waits for the state snapshot
     // taken after batch b, so the GPU never idles on the host (a blocking poll costs ~25 us of
     // idle GPU).  Kernels launched after `done` was set return at once (~1 us each).
