@@ -212,6 +212,17 @@ class ProjectInfo(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class MergeOpts(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("sensor_res_x", C.c_int32), ("sensor_res_y", C.c_int32), ("margin", C.c_int32),
+                ("targets_per_pass", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class MergeInfo(C.Structure):
+    _fields_ = [("models", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("unassigned", C.c_int32),
+                ("passes", C.c_int32), ("reserved0", C.c_int32), ("sum", C.c_uint64), ("sum_sq", C.c_uint64),
+                ("reserved", C.c_int32 * 2)]
+
+
 # BF_PROJECT_PALETTE of include/bf_accel.h: the (B, G, R) of group k is PROJECT_PALETTE[k % 12]
 PROJECT_PALETTE = ((255, 255, 255), (0, 0, 255), (0, 255, 0), (255, 0, 0), (0, 255, 255), (255, 0, 255), (255, 255, 0),
                    (0, 128, 255), (255, 128, 0), (128, 0, 255), (0, 255, 128), (128, 128, 255))
@@ -259,7 +270,7 @@ EXPORTS = [
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
     "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups", "bf_assign_groups",
-    "bf_propose_models", "bf_project_groups",
+    "bf_propose_models", "bf_project_groups", "bf_merge_scores",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -405,6 +416,8 @@ def load(path=None):
                                        C.POINTER(AssignInfo)]
         L.bf_project_groups.argtypes = [C.c_void_p, C.POINTER(ProjectOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.POINTER(ProjectInfo)]
+        L.bf_merge_scores.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.POINTER(MergeInfo)]
         L.bf_propose_models.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(AccelProposeOpts), C.c_void_p, C.c_void_p,
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ProposeInfo)]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -995,6 +1008,21 @@ class Accel:
         self._chk(self.L.bf_project_groups(self.h, C.byref(o), ms, K, _ptr(img.get("count")), _ptr(img.get("label")),
                                            _ptr(img.get("bgr")), scores, C.byref(info)))
         return img, list(scores)[:K], info
+
+    def merge_scores(self, models, scale, sensor_res, margin=0, targets_per_pass=0):
+        """bf_merge_scores: for every ordered pair (b, a) of the held grouping's groups, what the events of b add to the
+        contrast sum N^2 under model a (`models`, one Model per group).  Returns (gain uint64 [K, K], inside int32 [K, K],
+        events int32 [K], MergeInfo), the matrices indexed [b, a]: after "b adopts model a" the objective is
+        info.sum_sq - gain[b, b] + gain[b, a]."""
+        K = len(models)
+        o = MergeOpts(scale, sensor_res[0], sensor_res[1], margin, targets_per_pass)
+        ms = (Model * max(K, 1))(*models)
+        gain = np.zeros((K, K), dtype=np.uint64)
+        inside = np.zeros((K, K), dtype=np.int32)
+        events = np.zeros(K, dtype=np.int32)
+        info = MergeInfo()
+        self._chk(self.L.bf_merge_scores(self.h, C.byref(o), ms, K, _ptr(gain), _ptr(inside), _ptr(events), C.byref(info)))
+        return gain, inside, events, info
 
     def propose_models(self, opts=None, radius=1, suppress=2, max_models=8, min_votes=1, want_planes=False):
         """bf_propose_models: the modes of the per-event best flow global_search left over the lattice `opts` (a

@@ -76,4 +76,28 @@ void launch_project_vote(const AssignArgs& a, uint32_t* V, unsigned long long* o
 void launch_project_compose(const uint32_t* B, int K, int R, int C, int gain, uint32_t* count, int32_t* label, uint8_t* bgr,
                             unsigned long long* out, hipStream_t s);
 
+// The merge-gain kernels (bf_merge.hip; include/bf_accel.h, "event groups: merge gains").  The base planes B_k are the
+// projection's (launch_project_vote, launch_assign_box); a pass holds the trial planes of `targets` target models, plane
+// (a_local * K + b) the events of group b under model a0 + a_local.
+// The result block, 64-bit words, each on a line of its own as the projection's: gain[K x K] (word b * K + a), inside[K x K],
+// then sum, sum_sq.
+constexpr int kMergeTail = 2;
+inline int merge_out_words(int K) { return (2 * K * K + kMergeTail) * kProjectStride; }
+// A = min(K, targets_per_pass or K, floor(2^27 / (K R C))): the target models of one pass (K R C <= 2^27, so A >= 1).
+inline int merge_targets_per_pass(int K, long long plane, int targets_per_pass) {
+    long long A = kAssignMaxWords / ((long long)K * plane);
+    if (A > K) A = K;
+    if (targets_per_pass >= 1 && A > targets_per_pass) A = targets_per_pass;
+    return (int)A;
+}
+// N = sum_k B_k, every word written; out (zero) += sum, sum_sq.
+void launch_merge_total(const uint32_t* B, int K, int R, int C, uint32_t* N, unsigned long long* out, hipStream_t s);
+// T (targets x K x R x C words, zero) += one vote per event with an id other than the target's on plane (a_local, id) under
+// model a0 + a_local; out += inside[id][a0 + a_local].  The diagonal stays zero: it is the base pass's.
+void launch_merge_vote(const AssignArgs& a, int a0, int targets, uint32_t* T, unsigned long long* out, hipStream_t s);
+// out += gain[b][a0 + a_local] from the trial planes T (box-summed when scale > 1; plane b == a read from B), the base planes B
+// and N.
+void launch_merge_gain(const uint32_t* T, const uint32_t* B, const uint32_t* N, int K, int a0, int targets, int R, int C,
+                       unsigned long long* out, hipStream_t s);
+
 }  // namespace bf

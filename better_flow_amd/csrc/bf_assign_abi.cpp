@@ -1,9 +1,12 @@
-// bf_assign_abi.cpp -- C-ABI of the two entries that work on the K models' vote planes (include/bf_accel.h, "event groups:
-// assignment" and "event groups: projection"; kernels in bf_assign.hip and bf_project.hip):
+// bf_assign_abi.cpp -- C-ABI of the entries that work on the K models' vote planes (include/bf_accel.h, "event groups:
+// assignment", "event groups: projection" and "event groups: merge gains"; kernels in bf_assign.hip, bf_project.hip and
+// bf_merge.hip):
 //   bf_assign_groups   gives every event of the uploaded slice to one of K candidate models, and may install the result as the
 //                      context's grouping for bf_run_groups;
 //   bf_project_groups  renders the slice with every event warped by its own group's model -- per pixel the event count, the
 //                      owning group and its colour -- and scores it: per group and overall the integer moments of that image.
+//   bf_merge_scores    says, for every ordered pair (b, a) of groups, how much of the contrast sum N^2 the events of group b
+//                      add under model a: the projection's planes once, then the trial planes of A target models per pass.
 // What they share is here once: the option checks, the window of the widened sensor and its capacity check (vote_planes_check),
 // and the planes, the staged warps and the kernels' AssignArgs (vote_planes_stage).  Between the two each entry zeroes its own
 // outputs and applies its own rule for a slice without events.
@@ -219,6 +222,87 @@ int bf_project_groups(bf_ctx* c, const bf_project_opts* o, const bf_model* model
         info->pixels = (int32_t)r(t + 1);
         info->sum = r(t + 2);
         info->sum_sq = r(t + 3);
+    }
+    return BF_OK;
+}
+
+int bf_merge_scores(bf_ctx* c, const bf_merge_opts* o, const bf_model* models, int32_t n_models, uint64_t* gain_out,
+                    int32_t* inside_out, int32_t* events_out, bf_merge_info* info) {
+    if (!c) return BF_ERR_ARG;
+    if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_merge_scores before bf_upload_events");
+    if (!o || !models) return fail(c, BF_ERR_ARG, "bf_merge_scores: opts %p, models %p", (const void*)o, (const void*)models);
+    if (o->targets_per_pass < 0) return fail(c, BF_ERR_ARG, "bf_merge_scores: targets_per_pass %d (>= 0)", o->targets_per_pass);
+    VotePlanes vp;
+    int rc = vote_planes_check(c, "bf_merge_scores", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "targets_per_pass + 1",
+                               o->targets_per_pass + 1, n_models, "", vp);   // (the held grouping is required, as for the projection)
+    if (rc != BF_OK) return rc;
+    const AssignArgs& a = vp.a;
+    const int K = a.K;
+    const size_t plane = vp.plane;
+    const size_t pairs = (size_t)K * (size_t)K;
+
+    if (gain_out) memset(gain_out, 0, pairs * sizeof(uint64_t));
+    if (inside_out) memset(inside_out, 0, pairs * sizeof(int32_t));
+    if (events_out) memset(events_out, 0, (size_t)K * sizeof(int32_t));
+    if (info) memset(info, 0, sizeof(*info));
+    if (c->n == 0) return BF_OK;   // everything zero
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t s = c->stream;
+
+    const int A = merge_targets_per_pass(K, (long long)plane, o->targets_per_pass);
+    const int passes = (K + A - 1) / A;
+    const size_t trial = (size_t)A * (size_t)K * plane;
+    const int nbase = project_out_words(K), nout = merge_out_words(K);
+    rc = vote_planes_stage(c, models, true, vp);
+    if (rc != BF_OK) return rc;
+    HIP_TRY(c, c->d_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
+    HIP_TRY(c, c->h_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
+    HIP_TRY(c, c->d_merge_n.grow(plane));
+    HIP_TRY(c, c->d_merge_votes.grow(trial));
+    if (a.scale > 1) HIP_TRY(c, c->d_merge_box.grow(trial));
+    HIP_TRY(c, c->d_merge_out.grow((size_t)merge_out_words(kAssignMaxModels)));
+    HIP_TRY(c, c->h_merge_out.grow((size_t)merge_out_words(kAssignMaxModels)));
+    HIP_TRY(c, hipMemsetAsync(c->d_project_out, 0, (size_t)nbase * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(c->d_merge_out, 0, (size_t)nout * sizeof(unsigned long long), s));
+    {
+        ProfScope ps(c, 3);
+        // the base planes: every group under its own model, exactly the projection's
+        launch_project_vote(a, c->d_assign_votes, c->d_project_out, s);
+        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
+        const uint32_t* B = vote_planes_summed(c, vp);
+        launch_merge_total(B, K, vp.R, vp.C, c->d_merge_n, c->d_merge_out, s);
+        for (int a0 = 0; a0 < K; a0 += A) {   // (the passes follow each other on the stream: they share the trial planes)
+            const int targets = K - a0 < A ? K - a0 : A;
+            const size_t words = (size_t)targets * (size_t)K * plane;
+            HIP_TRY(c, hipMemsetAsync(c->d_merge_votes, 0, words * sizeof(uint32_t), s));
+            launch_merge_vote(a, a0, targets, c->d_merge_votes, c->d_merge_out, s);
+            if (a.scale > 1) launch_assign_box(c->d_merge_votes, c->d_merge_box, targets * K, vp.R, vp.C, a.scale, s);
+            launch_merge_gain(a.scale > 1 ? c->d_merge_box.get() : c->d_merge_votes.get(), B, c->d_merge_n, K, a0, targets, vp.R,
+                              vp.C, c->d_merge_out, s);
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(c->h_project_out, c->d_project_out, (size_t)nbase * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(c->h_merge_out, c->d_merge_out, (size_t)nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipStreamSynchronize(s));
+    const unsigned long long* hb = c->h_project_out;
+    const unsigned long long* hm = c->h_merge_out;
+    auto r = [hm](size_t word) { return hm[word * kProjectStride]; };
+    for (size_t w = 0; w < pairs; ++w) {
+        if (gain_out) gain_out[w] = r(w);
+        if (inside_out) inside_out[w] = (int32_t)r(pairs + w);
+    }
+    if (inside_out)   // the diagonal is the base pass's: events of k inside under their own model
+        for (int k = 0; k < K; ++k) inside_out[(size_t)k * K + k] = (int32_t)hb[(size_t)(K + k) * kProjectStride];
+    if (events_out)
+        for (int k = 0; k < K; ++k) events_out[k] = (int32_t)hb[(size_t)k * kProjectStride];
+    if (info) {
+        info->models = K;
+        info->rows = vp.R; info->cols = vp.C;
+        info->unassigned = (int32_t)hb[(size_t)(kProjectTables * K) * kProjectStride];
+        info->passes = passes;
+        info->sum = r(2 * pairs);
+        info->sum_sq = r(2 * pairs + 1);
     }
     return BF_OK;
 }

@@ -151,6 +151,12 @@ struct bf_ctx {
     DevArray<uint8_t> d_project_bgr;
     DevArray<unsigned long long> d_project_out;
     HostArray<unsigned long long> h_project_out;
+    // merge gains (bf_merge_scores): the base planes, warps and their result block are the projection's; the N plane, the trial
+    // planes of one pass and their box sums (A x K x R x C words each), and the result block of 64-bit words (bf_assign.h:
+    // merge_out_words); grown on first use
+    DevArray<uint32_t> d_merge_n, d_merge_votes, d_merge_box;
+    DevArray<unsigned long long> d_merge_out;
+    HostArray<unsigned long long> h_merge_out;
     // candidate models (bf_propose_models): the lattice's value tables (n_x doubles, then n_y), the vote plane H and its box
     // sums B (n_x * n_y words each), the result block (counts, proposals); grown on first use
     DevArray<double> d_propose_tab;

@@ -212,7 +212,8 @@ void DVS_flow<MAX_SZ, SPAN>::render_flow_frame(OptimizerRolling<LinearEventPtrs>
 
 // The moving objects of the slice (better_flow/object_finder.h) as objects_N.txt: one line per group -- id, events, the
 // median (u, v) of its events under its model in px / s, the model's fields (cx cy dx dy rot div cnt total_dx total_dy total_rot
-// total_div), the votes of the proposal it started from --, then a last line "unassigned <events>".  Event::t holds the
+// total_div), the votes of the proposal it started from --, then a last line "unassigned <events>".  With --objects-merge the groups are
+// those bf::ObjectMerger left, and objects_N.merge.txt lists its steps.  Event::t holds the
 // slice-local time (set_time).  With --objects-img also the slice under its objects' models (better_flow/object_render.h).
 template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(LinearEventPtrs &slice) {
     std::vector<int32_t> fx, fy, ft;
@@ -241,10 +242,13 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
         const bf_model &m = finder.models[k];
         std::fprintf(f, "%zu %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u %.17g %.17g %.17g %.17g %d\n", k, (int)finder.counts[k],
                      finder.flow_u[k], finder.flow_v[k], m.cx, m.cy, m.dx, m.dy, m.rot, m.div, (unsigned)m.cnt, m.total_dx, m.total_dy,
-                     m.total_rot, m.total_div, k < finder.proposals.size() ? (int)finder.proposals[k].votes : 0);
+                     m.total_rot, m.total_div, (size_t)finder.origin[k] < finder.proposals.size() ? (int)finder.proposals[(size_t)finder.origin[k]].votes : 0);
     }
     std::fprintf(f, "unassigned %d\n", finder.counts.empty() ? 0 : (int)finder.counts.back());
     std::fclose(f);
+    // (--objects-merge) what the merger did to the proposed groups, and the contrast sum N^2 of the grouping it left
+    if (finder.merge_num > 0 && !bf::ObjectMerger::write_steps(base + ".merge.txt", finder.steps, finder.models.size(), finder.merged_sum_sq) && !quiet)
+        std::cerr << "cannot write " << base << ".merge.txt\n";
     if (!generate_objects_img || finder.models.empty()) return;   // (no object: nothing to project)
     // find() leaves the context holding one group's events (its flows re-upload): the renderer uploads the slice again and
     // holds the final ids as its grouping

@@ -97,13 +97,19 @@ class MotionAssigner {
     // this membership -- or after max_alternations.  A group whose window exceeds the device path's LDS (BF_ERR_CAPACITY in its
     // info) is refit through ObjectTasks' one-after-the-other path on `helper` (a second context with room for the slice; null:
     // it keeps its model); a group a guard skipped keeps its model.  o.use_prior and o.install are set here.
+    // start_prior: ids (-1 .. K-1, upload order) the very first assignment takes as its prior (null: it has none).
     int alternate(bf_ctx *ctx, const Slice &s, const std::vector<bf_model> &start, bf_assign_opts o, int rounds_per_fit,
-                  int max_alternations, bf_ctx *helper = nullptr, bool force_host = false) {
+                  int max_alternations, bf_ctx *helper = nullptr, bool force_host = false,
+                  const std::vector<int32_t> *start_prior = nullptr) {
         models = start;
         records.clear();
         const size_t K = models.size();
         std::vector<int32_t> prior;
         bool have = false;
+        if (start_prior) {
+            prior = *start_prior;
+            have = true;
+        }
         o.install = 1;
         for (int a = 0; a < max_alternations; ++a) {
             int rc = upload(ctx, s);   // (a refit leaves a subset, or the slice sorted, behind)

@@ -1,7 +1,9 @@
 // object_finder.h -- bf::ObjectFinder: the moving objects of one slice without a hint from the caller:
 //   1. bf_global_set_window + bf_global_search over a lattice: every event's sharpest candidate;
 //   2. bf::ModelProposer::propose: the modes of that per-event best flow as K candidate models;
-//   3. bf::MotionAssigner::alternate from them: assignment and grouped refit until no id changes.
+//   3. bf::MotionAssigner::alternate from them: assignment and grouped refit until no id changes;
+//   4. (merge_num > 0) bf::ObjectMerger::reduce: groups that are one motion are merged, so the K proposed is "at most K"
+//      (DESIGN section 18).
 // It needs the device library: the CPU stand-in the tests build has no bf_global_*.  Against a C-ABI that lacks an entry find()
 // returns BF_ERR_STATE and `error` names the entry.
 #ifndef BF_HOST_OBJECT_FINDER_H
@@ -9,6 +11,7 @@
 
 #include <better_flow/model_proposer.h>
 #include <better_flow/motion_assign.h>
+#include <better_flow/object_merge.h>
 
 #include <string>
 
@@ -30,6 +33,11 @@ class ObjectFinder {
     bf_assign_opts assign;
     bf_group_opts fit;
     int rounds_per_fit = 2, max_alternations = 5;
+    // merging (bf::ObjectMerger::reduce after the alternation): a group adopts another's model when it keeps merge_num /
+    // merge_den of its contrast; merge_num == 0: off, nothing changes.  A group below dissolve_below events is dissolved.
+    uint64_t merge_num = 0, merge_den = 1;
+    int32_t dissolve_below = 0;
+    int merge_max_steps = 64;
 
     // what find() leaves: K models, the ids in upload order (-1: unassigned), K + 1 counts (last: unassigned), the proposals
     // the models started from and one record per alternation
@@ -38,6 +46,9 @@ class ObjectFinder {
     std::vector<bf_proposal> proposals;
     std::vector<MotionAssigner::Record> records;
     std::vector<double> flow_u, flow_v;   // per group: the median (u, v) in px / s of its events under its model's warp
+    std::vector<ObjectMerger::Step> steps;   // (merging) what reduce() did, and the final grouping's contrast sum N^2
+    uint64_t merged_sum_sq = 0;
+    std::vector<int32_t> origin;          // per group: the proposal it started from
     std::string error;
 
     ObjectFinder() : lattice(ModelProposer::default_lattice()), propose(ModelProposer::default_opts()), assign() {
@@ -48,10 +59,11 @@ class ObjectFinder {
     }
 
     // The entry the linked C-ABI lacks, or null.
-    static const char *missing_entry() {
+    static const char *missing_entry(bool merging = false) {
         if (!bf_propose_models) return "bf_propose_models";
         if (!bf_global_search || !bf_global_set_window) return "bf_global_search";
         if (!MotionAssigner::device_available()) return "bf_assign_groups";
+        if (merging && !ObjectMerger::device_available()) return "bf_merge_scores";
         return nullptr;
     }
 
@@ -59,7 +71,10 @@ class ObjectFinder {
     int find(bf_ctx *ctx, const MotionAssigner::Slice &s, bf_ctx *helper = nullptr) {
         models.clear(); gid.clear(); counts.clear(); proposals.clear(); records.clear(); error.clear();
         flow_u.clear(); flow_v.clear();
-        if (const char *m = missing_entry()) {
+        steps.clear();
+        merged_sum_sq = 0;
+        origin.clear();
+        if (const char *m = missing_entry(merge_num > 0)) {
             error = std::string("bf::ObjectFinder: the linked library has no ") + m;
             return BF_ERR_STATE;
         }
@@ -71,6 +86,7 @@ class ObjectFinder {
         if (rc < 0) return fail(ctx, rc);
         proposals = mp.result.proposals;
         models = mp.result.models;
+        for (size_t k = 0; k < models.size(); ++k) origin.push_back((int32_t)k);
         gid.assign(s.n, -1);
         counts.assign(models.size() + 1, 0);
         counts.back() = (int32_t)s.n;
@@ -85,6 +101,25 @@ class ObjectFinder {
         gid = ma.gid;
         counts = ma.counts;
         records = ma.records;
+        if (merge_num > 0) {
+            ObjectMerger om;
+            om.opts.scale = assign.scale;
+            om.opts.sensor_res_x = assign.sensor_res_x; om.opts.sensor_res_y = assign.sensor_res_y;
+            om.opts.margin = assign.margin;
+            om.assign = assign;
+            om.fit = fit;
+            om.rounds_per_fit = rounds_per_fit;
+            rc = om.reduce(ctx, s, models, gid, merge_num, merge_den, dissolve_below, merge_max_steps, helper);
+            if (rc < 0) return fail(ctx, rc);
+            models = om.models;
+            gid = om.gid;
+            counts = om.counts;
+            steps = om.steps;
+            origin = om.origin;
+            merged_sum_sq = om.info.sum_sq;
+            flow_u.assign(models.size(), 0.0);
+            flow_v.assign(models.size(), 0.0);
+        }
         rc = group_flows(ctx, s);
         return rc < 0 ? fail(ctx, rc) : BF_OK;
     }

@@ -44,6 +44,9 @@ struct Options {
     double objects_range = 600.0, objects_step = 30.0;   // the search lattice in px / s
     bool objects_img = false;                    // --objects-img: objects_N.ppm / .pgm / .score.txt per slice
     int objects_img_gain = 8;
+    bool objects_merge = false, objects_merge_bad = false;   // --objects-merge[=<num>/<den>]: objects_N.merge.txt per slice
+    unsigned long long objects_merge_num = 9, objects_merge_den = 10;
+    int objects_min_events = -1;                 // --objects-min-events=<n> (-1: the refit's min_events)
     int objects_radius = 1, objects_suppress = 2, objects_min_votes = 1, objects_scale = 3;
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
@@ -65,6 +68,17 @@ struct Options {
     int threads = 0;                       // reader / writer threads (0: one per core, at most 4 -- measured: 2.4 / 2.3 / 2.1 / 1.9
                                            // Gevents/s from a binary file with 2 / 4 / 8 / 16 reader threads)
 };
+
+// "<num>/<den>", two runs of digits: the threshold of --objects-merge
+bool parse_fraction(const char *v, unsigned long long &num, unsigned long long &den) {
+    const char *slash = std::strchr(v, '/');
+    if (!slash || slash == v || !slash[1] || slash - v > 18 || std::strlen(slash + 1) > 18) return false;
+    for (const char *p = v; *p; ++p)
+        if (p != slash && (*p < '0' || *p > '9')) return false;
+    num = std::strtoull(v, nullptr, 10);
+    den = std::strtoull(slash + 1, nullptr, 10);
+    return true;
+}
 
 // "0-3", "0,2,5", "1": the HIP devices of --devices
 std::vector<int> parse_device_list(const char *v) {
@@ -134,6 +148,15 @@ const std::vector<Flag> &flag_table() {
          "model, coloured by object; objects_N.pgm: 16-bit owner per pixel, id + 1; objects_N.score.txt: per object id events inside "
          "pixels_hit pixels_owned max sum_sq, then the info line with the slice's contrast sum N^2)"},
         {"--objects-img-gain", Arg::Inline, [](Options &o, const char *v) { o.objects_img_gain = atoi(v); }, "<n>", "... 255 / n events on a pixel saturate an object's colour (8)"},
+        {"--objects-merge", Arg::None, [](Options &o, const char *) { o.objects_merge = true; }, "",
+         "with --objects: K is then \"at most K\": a group whose events keep 9/10 of their contrast (their share of the slice's sum N^2) "
+         "under a larger group's model adopts that model, one pair at a time with a reassignment and refit after each, and groups too "
+         "small for a refit are dissolved (objects_N.merge.txt: merge|dissolve b a gain_ba gain_bb events_b K_after per step, then "
+         "info K sum_sq); the default 9/10 rests on one synthetic scene"},
+        {"--objects-merge", Arg::Inline, [](Options &o, const char *v) { o.objects_merge = true; o.objects_merge_bad = !parse_fraction(v, o.objects_merge_num, o.objects_merge_den); },
+         "<num>/<den>", "... at this threshold instead (0/1: no merging)"},
+        {"--objects-min-events", Arg::Inline, [](Options &o, const char *v) { o.objects_min_events = atoi(v); }, "<n>",
+         "with --objects-merge: dissolve groups with fewer events (default: the refit's own min_events guard: a group it skips has no model of its own)"},
         {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
         {"--video", Arg::None, [](Options &o, const char *) { o.video = true; }, "", "write the frames to a video (uncompressed AVI)"},
         {"--video-name", Arg::Next, [](Options &o, const char *v) { o.video_name = v; }, "<file>", "name of that video"},
@@ -253,6 +276,15 @@ int parse(int argc, char **argv, Options &o) {
                              "--objects-suppress 0..64, --objects-min-votes >= 1, an odd --objects-scale up to 9\n");
         return 1;
     }
+    if (o.objects_merge && !o.objects_flag) { std::fprintf(stderr, "--objects-merge merges the objects --objects=<K> finds: give both\n"); return 1; }
+    if (o.objects_merge && (o.objects_merge_bad || o.objects_merge_den < 1 || o.objects_merge_num > o.objects_merge_den)) {
+        std::fprintf(stderr, "--objects-merge=<num>/<den>: two non-negative integers, num <= den, den >= 1 (default 9/10)\n");
+        return 1;
+    }
+    if (o.objects_min_events != -1 && (!o.objects_merge || o.objects_min_events < 0)) {
+        std::fprintf(stderr, "--objects-min-events=<n> (>= 0) sets what --objects-merge dissolves: give both\n");
+        return 1;
+    }
     if (o.objects_img && !o.objects_flag) { std::fprintf(stderr, "--objects-img renders the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_img && o.objects_img_gain < 1) { std::fprintf(stderr, "--objects-img-gain must be at least 1\n"); return 1; }
     // (--img / --video / --flow-img / --flow-field run on both engines; without --engine they keep the reference ring)
@@ -327,7 +359,8 @@ int run_ring(const Options &o) {
         estimator.set_generate_segments(so, o.frame_prefix);
     }
     if (o.objects_flag) {
-        if (const char *missing = bf::ObjectFinder::missing_entry()) {   // (before any slice: no file is written)
+        const bool merging = o.objects_merge && o.objects_merge_num > 0;
+        if (const char *missing = bf::ObjectFinder::missing_entry(merging)) {   // (before any slice: no file is written)
             std::fprintf(stderr, "--objects needs %s, which this build of the library does not have\n", missing);
             return 2;
         }
@@ -339,6 +372,10 @@ int run_ring(const Options &o) {
         cfg.propose.radius = o.objects_radius; cfg.propose.suppress = o.objects_suppress;
         cfg.propose.max_models = o.objects; cfg.propose.min_votes = o.objects_min_votes;
         cfg.assign.scale = cfg.fit.scale = o.objects_scale;
+        if (merging) {
+            cfg.merge_num = o.objects_merge_num; cfg.merge_den = o.objects_merge_den;
+            cfg.dissolve_below = o.objects_min_events >= 0 ? o.objects_min_events : cfg.fit.min_events;
+        }
         estimator.set_generate_objects(cfg, o.frame_prefix);
         if (o.objects_img) {
             if (!bf::ObjectRenderer::device_available()) {

@@ -549,6 +549,52 @@ int bf_project_groups(bf_ctx *ctx, const bf_project_opts *opts, const bf_model *
                       uint32_t *count_out /* R x C */, int32_t *label_out /* R x C */, uint8_t *bgr_out /* R x C x 3 */,
                       bf_group_score *scores_out /* K */, bf_project_info *info);
 
+/* ---- event groups: merge gains -- how much of a group's contrast survives under another group's model ----
+ *
+ * The last decision of the object pipeline: which groups are one motion, and with it the number of objects.  For every ordered
+ * pair (b, a) of groups it gives the exact change of bf_project_groups' objective, info.sum_sq, under the merge "group b adopts
+ * model a" (DESIGN section 18).  Everything after an event's pixel is an integer count or a sum: the bytes do not depend on
+ * the order events are stored or work-groups run in, and no tolerance is involved.
+ *
+ *   grouping  exactly bf_project_groups': the held grouping, ids -1 .. K-1 in upload order; n_models must equal K.
+ *   window    exactly bf_project_groups': the whole sensor widened by `margin`.
+ *   pixel_k(i)  exactly bf_assign_groups'.
+ *   trial     T[b][a][p] = the s x s box sum (zero beyond the plane; at scale 1 the plane itself) of the events with id b that
+ *             are inside under MODEL a at p.
+ *   base      B_b = T[b][b]: bf_project_groups' planes.  N[p] = sum_k B_k[p].
+ *   unassigned  an event with id -1 is in no plane and counts in info.unassigned.
+ *   gain      gain_out[b * K + a] = sum_p T[b][a][p] * (2 * (N[p] - B_b[p]) + T[b][a][p]), as uint64.
+ *   reading   gain[b][b] is what the objective loses when the events of b are deleted; gain[b][a] is what they add back under
+ *             model a: after "b adopts model a" the objective is S - gain[b][b] + gain[b][a], S = info.sum_sq.
+ *   inside    inside_out[b * K + a] = the events of b that are inside under model a.
+ *   events    events_out[b] = the events with id b.
+ *   info      models = K, rows = R, cols = C, unassigned, passes (below), sum = sum_p N[p], sum_sq = S = sum_p N[p]^2.
+ *   overflow  the uint64 sums wrap by definition.  A gain is at most the objective after its merge, which is <= (s^2 n)^2 with
+ *             s <= 9: none can wrap while the slice has fewer than 2^32 / 81 = 53 024 287 events (bf_project_groups' bound).
+ *   passes    one pass holds the trial planes of A = min(K, targets_per_pass or K, floor(2^27 / (K R C))) target models;
+ *             info.passes = ceil(K / A).  The result does not depend on A.
+ *   state     exactly bf_project_groups' list: reads the events' addresses and times, the permutation and the held grouping
+ *             only; nothing of the context's state is written.  The base planes are bf_assign_groups' (each call of the three
+ *             entries clears them first); the trial planes are buffers of their own.
+ *   errors    those of bf_project_groups (without gain); BF_ERR_ARG for targets_per_pass < 0; BF_ERR_CAPACITY when
+ *             K R C > 2^27.  Zero events: BF_OK, every output zero (info too).
+ * Any output may be NULL.  Blocking.  Which pair to merge is the caller's policy (bf::ObjectMerger, object_merge.h). */
+typedef struct bf_merge_opts {         /* 32 bytes */
+    int32_t scale;                     /* odd, scale/2 <= 4 */
+    int32_t sensor_res_x, sensor_res_y;
+    int32_t margin;                    /* >= 0 sensor pixels added on every side of the sensor box */
+    int32_t targets_per_pass;          /* 0: as many target models per launch as fit; >= 1: at most that many */
+    int32_t reserved[3];
+} bf_merge_opts;
+typedef struct bf_merge_info {         /* 48 bytes */
+    int32_t models, rows, cols, unassigned, passes, reserved0;
+    uint64_t sum, sum_sq;
+    int32_t reserved[2];
+} bf_merge_info;
+int bf_merge_scores(bf_ctx *ctx, const bf_merge_opts *opts, const bf_model *models, int32_t n_models,
+                    uint64_t *gain_out /* K x K, [b * K + a] */, int32_t *inside_out /* K x K */,
+                    int32_t *events_out /* K */, bf_merge_info *info);
+
 /* A batch of independent slices -- the reference's queue of (events, model) tasks (dvs_flow.h:200-231, executed there
  * one after the other) -- solved together: bf_run on each of the n contexts, all in flight at once (one host thread per
  * context inside the library; the contexts' streams share the GPU, set "co_schedule" on them when n > 1).  Every
