@@ -103,12 +103,7 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
     if (c->n == 0) {   // every output zero; an installed result is the empty grouping
-        if (o->install) {
-            HIP_TRY(c, c->d_group_id.grow(1));
-            c->groups_K = K;
-            c->groups_valid = true;
-        }
-        return BF_OK;
+        return o->install ? install_grouping(c, nullptr, hipMemcpyDeviceToDevice, K) : BF_OK;
     }
 
     const int nout = assign_out_words(K);
@@ -131,13 +126,7 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
         HIP_TRY(c, hipMemcpyAsync(group_id_out, c->d_assign_gid, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     if (score_out)
         HIP_TRY(c, hipMemcpyAsync(score_out, c->d_assign_score, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (o->install) {   // the rule of bf_set_groups: the context's own plane, held until the next upload
-        c->groups_valid = false;
-        HIP_TRY(c, c->d_group_id.grow((size_t)c->n));
-        HIP_TRY(c, hipMemcpyAsync(c->d_group_id, c->d_assign_gid, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        c->groups_K = K;
-        c->groups_valid = true;
-    }
+    if (o->install && (rc = install_grouping(c, c->d_assign_gid, hipMemcpyDeviceToDevice, K)) != BF_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
     const uint32_t* r = c->h_assign_out;
     if (counts_out)

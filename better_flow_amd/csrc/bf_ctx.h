@@ -1,11 +1,13 @@
-// bf_ctx.h -- private to the C-ABI implementation files (bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
-// bf_extras.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp, bf_propose_abi.cpp): the context structure behind `bf_ctx`, and the small helpers they share
-// (error text, profiling brackets, kernel-argument builders, the buffers allocated on first use).  Every HIP resource of a
+// bf_ctx.h -- private to the C-ABI implementation files (bf_ctx.cpp, bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
+// bf_tiles_abi.cpp, bf_local_abi.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp,
+// bf_propose_abi.cpp): the context structure behind `bf_ctx` and the declarations of the small helpers they share (error text,
+// profiling brackets, kernel-argument builders, the buffers allocated on first use; defined in bf_ctx.cpp, but for the few that
+// bf_run.cpp calls once per kernel launch, which are inline here).  What the context knows about its slice -- the flags every
+// entry reads -- is the base struct bf_state::SliceState (bf_ctx_state.h), changed through its named transitions only.  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
 // (bf_ctx::UploadSlot).  Nothing here is part of the ABI (include/bf_accel.h).
 #pragma once
-#pragma clang diagnostic ignored "-Wunused-function"   // (every file uses its own subset of the helpers below)
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "bf_assign.h"
+#include "bf_ctx_state.h"
 #include "bf_device.h"
 #include "bf_kernels.h"
 #include "bf_mem.h"
@@ -46,22 +49,18 @@ extern std::atomic<int> g_live_ctx[64];
 struct GlobalSearch;   // bf_global_search.cpp: the exhaustive search's window, scratch and per-event state
 struct GlobalSearchFree { void operator()(GlobalSearch* g) const; };   // (defined where the type is complete)
 
-namespace {
-
 struct ProfRec {
     Event a, b;
     int cat;
     long long nev;
 };
 
-}  // namespace
-
 // Margins of the tile-binned loops (bf_plan_rules.h).  The tile shape, the scatter work-groups' size and their events per thread
 // are chosen per slice (bf_plan.cpp, by the rules of bf_plan_rules.h): the options that overrode them went in round 5.
 using bf_rules::kBinMargin;
 using bf_rules::kFusedMargin;
 
-struct bf_ctx {
+struct bf_ctx : bf_state::SliceState {
     int device = 0;
     Stream stream;                   // created, or the caller's (bf_create)
 
@@ -72,9 +71,7 @@ struct bf_ctx {
 
     // two event sets: the tile-binned mode ping-pongs between them on every re-bin
     struct EvSet { DevArray<uint32_t> xy; DevArray<int32_t> t; DevArray<float2> p; DevArray<uint32_t> perm; DevArray<float2> p2; };
-    EvSet set[2];
-    int cs = 0;                      // set holding the live events
-    bool has_perm = false;           // set[cs] is permuted; perm[] gives the upload index
+    EvSet set[2];                    // (SliceState: cs is the set holding the live events, has_perm says it is permuted)
     DevArray<uint8_t> d_noise;
     // tile-binned scatter
     int opt_binned = 1;              // 0 never, 1 when it pays (dense enough), 2 whenever possible
@@ -82,14 +79,11 @@ struct bf_ctx {
     bool opt_co_schedule = false;    // several slice contexts share the GPU: the update runs in the stencil kernel's last work-group
     int opt_bin_pack_limit = 64;     // bits available to the per-bin packing (lower only to test the fallback)
     int n_cus = 0;
-    bool use_binned = false;         // decided per slice (plan_slice)
-    BinGrid grid;
+    BinGrid grid;                    // the slice's bin grid where plan_slice chose the loop (SliceState::use_binned)
     // one-kernel iteration (k_fused_pass): the loop of a context that has the GPU to itself
     int opt_fused = 1;               // 0 never, 1 where it is the faster loop (small slices on small images; sparser ones only when
                                      // the context is co-scheduled with others), 2 whenever possible
-    bool fused_ok = false;           // decided per slice (plan_slice)
-    bool fused_shared = false;       // ... and it is also the loop to take when the context shares the GPU ("co_schedule")
-    BinGrid fgrid;                   // its sort grid: keys = (tile, zone)
+    BinGrid fgrid;                   // its sort grid, keys = (tile, zone), where plan_slice allows the loop (SliceState::fused_ok)
     DevArray<uint32_t> d_ftab;       // FusedTab per tile
     // persistent form of that loop (k_fused_loop, bf_loop.hip): a context ALONE on the GPU keeps the work-groups resident
     bool counted = false;            // in g_live_ctx
@@ -134,8 +128,6 @@ struct bf_ctx {
     // groups' fr boxes (x min, x max, y min, y max), the claim order (descending event count) and the claim counter
     DevArray<int32_t> d_group_id, d_group_box;
     DevArray<uint32_t> d_group_order, d_group_counter;
-    int groups_K = 0;
-    bool groups_valid = false;       // a grouping of the uploaded slice is held (every upload clears it)
     int groups_lds = 0, groups_per_cu = 0;   // what the last bf_run_groups launched: dynamic LDS bytes, work-groups per CU (bf_get_stat)
     // assignment (bf_assign_groups): the K vote planes and their box sums (K x R x C words each), the K warps, the ids and scores
     // in upload order, the result block (counts, changed, max_score); grown on first use
@@ -244,11 +236,9 @@ struct bf_ctx {
     DevArray<uint8_t> d_flow;                     // flow field / colour-coded flow / flow frame scratch (bf_flow_abi.cpp: FlowScratch)
     HostArray<unsigned long long> h_lscore;
     bf_local_window lwin;
-    bool have_lwin = false;
     int lcur = 0;
     // exhaustive search (bf_global.hip / bf_global_search.cpp)
     std::unique_ptr<GlobalSearch, GlobalSearchFree> glob;
-    bool glob_valid = false;         // bf_global_set_window ran on the slice uploaded now (every upload clears it)
     // segmentation (bf_segment.hip / bf_segment_abi.cpp): label, size and id planes of the image, the scan's per-work-group words,
     // the scalars, the component table (seg_K rows) and the per-event ids; grown on first use, sized from the image / the slice
     DevArray<int32_t> d_seg_lab, d_seg_sz, d_seg_nid, d_seg_cl;
@@ -257,10 +247,8 @@ struct bf_ctx {
     HostArray<SegDev> h_seg_dev;
     DevArray<bf_component> d_seg_table;
     DevArray<uint8_t> d_seg_mask;    // bf_label_image: the host mask
-    bool seg_valid = false;          // a segmentation of the current window is held (an upload, bf_set_cloud and every warp clear it)
     int seg_K = 0;
     SliceStats stats;                // folded k_prepare statistics of the uploaded slice
-    bool stats_valid = false;
 
     HostArray<DevState> h_state;     // D2H target only: 2 slots (pipelined polling), then h_seq
     unsigned long long* h_seq = nullptr;   // in h_state (not owned): "snapshot complete" sequence number of a warm start's batch (k_finish_update)
@@ -271,19 +259,12 @@ struct bf_ctx {
 
     DevState hst;                    // authoritative host mirror outside bf_run
     bf_window win;
-    bool uploaded = false, have_window = false;
-    bool has_noise = false, all_noise = false;
+    bool has_noise = false;
     bool packed = true;
     bool force_split = false;
-    bool degenerate = false;         // window with R <= 0 or C <= 0 (empty slice)
-    bool pending_warp = false;       // bf_set_model's warp not applied yet
-    bool n_valid = false;            // d_nxny holds the n of the last warp
     uint32_t run_counter = 0;
     int warm_iters_hint = 6;         // iterations the previous warm-started run needed
-    bool p_clean = false;            // p is all zero (Event::reset state): set by the upload, cleared by any warp
-    bool out_sorted = false;         // d_nxny (and d_uv) are in slot order: un-permute with set[cs].perm before reading back
-    DevArray<double2> d_out_tmp;     // second buffer for that un-permutation
-    bool uv_valid = false;           // d_uv holds compute_uv of that n (fused into bf_run's final warp)
+    DevArray<double2> d_out_tmp;     // second buffer for un-permuting outputs left in slot order (SliceState::out_sorted)
     int cur = 0;                     // plane buffer that is guaranteed all-zero
     bool planes_unknown = true;      // both buffers must be cleared before use
     int last_R = 0, last_C = 0;
@@ -335,7 +316,7 @@ int global_best_state(bf_ctx* c, const bf_global_search_opts* lattice, std::vect
                       GlobalBestState* out);
 void global_cand_uv(double nx, double ny, double nz, double* u, double* v);
 
-// The two frame tiles of the live slice (bf_extras.cpp), ENQUEUED on the context stream into device memory: the 8-bit projection
+// The two frame tiles of the live slice (bf_local_abi.cpp, bf_frame_abi.cpp), ENQUEUED on the context stream into device memory: the 8-bit projection
 // image, (scale res_x) x (scale res_y), and the colour-coded time image, (scale res_x + scale) x (scale res_y + scale) BGR.  A
 // pending bf_set_model warp is applied first.  bf_projection_img / bf_color_time_img are these, a copy and a sync; bf_frame_render
 // runs them into its own tiles.
@@ -391,18 +372,10 @@ int streaming_setup(bf_ctx* c);
 int issue_deferred_uploads(bf_ctx* c);
 void drop_uploads(bf_ctx* c, int k);
 
-namespace {
+// ---- shared helpers (bf_ctx.cpp) ----
 
-int fail(bf_ctx* c, int code, const char* fmt, ...) {
-    if (c) {
-        va_list ap;
-        va_start(ap, fmt);
-        std::lock_guard<std::mutex> g(c->err_mu);
-        vsnprintf(c->err, sizeof(c->err), fmt, ap);
-        va_end(ap);
-    }
-    return code;
-}
+// stores the message in the context (c may be null) and returns `code`
+int fail(bf_ctx* c, int code, const char* fmt, ...);
 
 #define HIP_TRY(c, expr)                                                                      \
     do {                                                                                      \
@@ -412,7 +385,47 @@ int fail(bf_ctx* c, int code, const char* fmt, ...) {
                         __FILE__, __LINE__);                                                  \
     } while (0)
 
-Event get_event(bf_ctx* c) {
+int prof_fold(bf_ctx* c);                     // the pending ProfScope brackets into bf_ctx::prof (synchronises the stream)
+long long pad_events(long long n);            // n events padded to whole k_prepare work-groups (the event arrays' granule)
+int bit_length(unsigned long long v);
+// a warp by (dnx, dny) about (cx, cy), divergence div, rotation `angle` (cos / sin evaluated on the host: event.h:91-92,102-103)
+void set_warp(WarpParams& w, double dnx, double dny, double cx, double cy, double div, double angle);
+// set_model's warp (optimizer_rolling.h:289-299): the ONE place a bf_model becomes a warp (bf_set_model, a tile's warm start,
+// the K models of bf_assign_groups / bf_project_groups)
+void set_model_warp(WarpParams& w, const bf_model& m);
+WarpParams identity_warp();
+// OptimizerRolling::set_cloud's window (optimizer_rolling.h:263-282) of a bounding box in sensor pixels: the ONE place this
+// arithmetic lives on the host (bf_set_cloud on the events' seeded box, bf_assign_groups on the widened sensor box).
+bf_window window_of_box(int scale, int x_min, int x_max, int y_min, int y_max);
+
+// Buffers allocated on first use.  The second event set and both permutations are shared by the tile-binned loops and
+// bf_run_tiles: whichever comes first allocates them, and the other finds them (with the slice's events possibly IN the second set).
+int ensure_cplanes(bf_ctx* c);
+int ensure_ovf_bits(bf_ctx* c, int R, int C);   // dirty bitmaps of the overflow planes for an R x C image
+int ensure_second_set(bf_ctx* c);
+int ensure_bin_buffers(bf_ctx* c, const BinGrid& g);
+int ensure_margin_buffers(bf_ctx* c, const BinGrid& g);   // margin planes and per-bin lists of the interior + margin format
+int clear_planes(bf_ctx* c);
+int margin_reset(bf_ctx* c);
+// grow(n), and zero the array on the context's stream when that allocated it (instantiated in bf_ctx.cpp for the element types in use)
+template <class T> hipError_t grow_zeroed(bf_ctx* c, DevArray<T>& a, size_t n);
+
+// Device-conditional counting sort of the live events by the image tile of their current target (runs only when hot.need_rebin
+// is set); no host synchronisation.
+int enqueue_rebin(bf_ctx* c, DevState* st, bool has_perm_at_start, const WarpParams* prewarp = nullptr, bool fused = false, int launch_no = 0);
+int flush_pending(bf_ctx* c);                 // applies the warp bf_set_model left pending (optimizer_rolling.h:294-298)
+// Waits for an event without occupying a host core: query, sleep ~20 us (+ the kernel's timer slack), repeat.
+int wait_event_sleeping(bf_ctx* c, hipEvent_t ev);
+// Folds the per-work-group min / max / sum records k_prepare wrote for the uploaded slice (one device-to-host copy per slice,
+// cached).  With `overwritten`, a record about to be reused: only if the slice's statistics are still unread in that record.
+int fold_stats(bf_ctx* c, const SliceStats* overwritten = nullptr);
+// Installs n group ids (n = c->n; `src` on the host or on the device, as `kind` says; not read when the slice is empty) as the
+// held grouping of K groups: the context's own plane, held until the next upload.  A host source is free again on return.
+int install_grouping(bf_ctx* c, const int32_t* src, hipMemcpyKind kind, int K);
+
+// ---- what bf_run.cpp calls once per kernel launch: inline, the host's launch time is on a warm-started chain's critical path ----
+
+inline Event get_event(bf_ctx* c) {
     Event e;
     if (c->ev_pool.empty()) {
         (void)e.create();
@@ -449,78 +462,7 @@ struct ProfScope {
     }
 };
 
-int prof_fold(bf_ctx* c) {
-    if (c->prof_pending.empty()) return BF_OK;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (auto& r : c->prof_pending) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, r.a, r.b);
-        switch (r.cat) {
-            case 0: c->prof.warp_scatter_ms += ms; c->prof.warp_scatter_launches++;
-                    c->prof.warp_scatter_events += (uint64_t)r.nev; break;
-            case 1: c->prof.stencil_ms += ms; c->prof.stencil_launches++; break;
-            case 2: c->prof.update_ms += ms; c->prof.update_launches++; break;
-            default: c->prof.other_ms += ms; c->prof.other_launches++; break;
-        }
-        c->ev_pool.push_back(std::move(r.a));
-        c->ev_pool.push_back(std::move(r.b));
-    }
-    c->prof_pending.clear();
-    return BF_OK;
-}
-
-// n events padded to whole k_prepare work-groups (the event arrays' granule)
-long long pad_events(long long n) {
-    constexpr long long gran = (long long)kThreads * kEvPerThread;
-    return (n + gran - 1) / gran * gran;
-}
-
-int bit_length(unsigned long long v) {
-    int b = 0;
-    while (v) { ++b; v >>= 1; }
-    return b;
-}
-
-// a warp by (dnx, dny) about (cx, cy), divergence div, rotation `angle` (cos / sin evaluated on the host: event.h:91-92,102-103)
-void set_warp(WarpParams& w, double dnx, double dny, double cx, double cy, double div, double angle) {
-    w.dnx = dnx; w.dny = dny; w.cx = cx; w.cy = cy; w.div = div;
-    w.c = std::cos(angle);
-    w.s = std::sin(angle);
-}
-// set_model's warp (optimizer_rolling.h:289-299): the ONE place a bf_model becomes a warp (bf_set_model, a tile's warm start,
-// the K models of bf_assign_groups / bf_project_groups)
-void set_model_warp(WarpParams& w, const bf_model& m) {
-    set_warp(w, -m.total_dx, -m.total_dy, m.cx, m.cy, m.total_div, -m.total_rot);
-}
-
-WarpParams identity_warp() {
-    WarpParams w;
-    w.dnx = w.dny = w.cx = w.cy = w.div = 0.0;
-    w.c = 1.0;
-    w.s = 0.0;
-    return w;
-}
-
-// OptimizerRolling::set_cloud's window (optimizer_rolling.h:263-282) of a bounding box in sensor pixels: the ONE place this
-// arithmetic lives on the host (bf_set_cloud on the events' seeded box, bf_assign_groups on the widened sensor box).
-bf_window window_of_box(int scale, int x_min, int x_max, int y_min, int y_max) {
-    bf_window w;
-    memset(&w, 0, sizeof(w));
-    w.scale = scale;
-    w.x_min = x_min; w.y_min = y_min; w.x_max = x_max; w.y_max = y_max;
-    w.metric_wsizex = scale * (w.x_max - w.x_min);   // :263
-    w.metric_wsizey = scale * (w.y_max - w.y_min);   // :264
-    w.scale_img_x = w.metric_wsizex + scale;         // :276
-    w.scale_img_y = w.metric_wsizey + scale;         // :277
-    // :279-282, both "/ 2" are integer divisions
-    w.x_shift = -double((w.x_max - w.x_min) / 2 + w.x_min) * double(scale) +
-                double(w.metric_wsizex) / 2.0 + scale / 2;
-    w.y_shift = -double((w.y_max - w.y_min) / 2 + w.y_min) * double(scale) +
-                double(w.metric_wsizey) / 2.0 + scale / 2;
-    return w;
-}
-
-EvSets ev_sets(const bf_ctx* c) {
+inline EvSets ev_sets(const bf_ctx* c) {
     EvSets e;
     for (int i = 0; i < 2; ++i) {
         e.s[i].xy = c->set[i].xy; e.s[i].t = c->set[i].t; e.s[i].p = c->set[i].p; e.s[i].perm = c->set[i].perm;
@@ -529,7 +471,7 @@ EvSets ev_sets(const bf_ctx* c) {
     return e;
 }
 
-WarpScatterArgs ws_args(bf_ctx* c, int buf, int check_done) {
+inline WarpScatterArgs ws_args(bf_ctx* c, int buf, int check_done) {
     WarpScatterArgs a;
     const bf_ctx::EvSet& e = c->set[c->cs];
     a.xy = e.xy; a.t = e.t; a.p = e.p;
@@ -549,7 +491,7 @@ WarpScatterArgs ws_args(bf_ctx* c, int buf, int check_done) {
     return a;
 }
 
-StencilArgs st_args(bf_ctx* c, int buf, int check_done) {
+inline StencilArgs st_args(bf_ctx* c, int buf, int check_done) {
     StencilArgs a;
     memset(&a, 0, sizeof(a));
     a.st = c->d_state;
@@ -573,204 +515,8 @@ StencilArgs st_args(bf_ctx* c, int buf, int check_done) {
 }
 
 // which k_stencil instantiation reads the plane buffers of the current slice
-StencilSrc plane_src(const bf_ctx* c) { return c->packed ? StencilSrc::packed_plane : StencilSrc::split_planes; }
+inline StencilSrc plane_src(const bf_ctx* c) { return c->packed ? StencilSrc::packed_plane : StencilSrc::split_planes; }
 
-// grow(n), and zero the array on the context's stream when that allocated it
-template <class T> hipError_t grow_zeroed(bf_ctx* c, DevArray<T>& a, size_t n) {
-    bool fresh;
-    const hipError_t e = a.grow(n, &fresh);
-    return (e == hipSuccess && fresh) ? hipMemsetAsync(a, 0, n * sizeof(T), c->stream) : e;
-}
+// the word behind the moment accumulators that the one-kernel loops set when an event is lost
+inline uint32_t* lost_flag(const bf_ctx* c) { return reinterpret_cast<uint32_t*>(c->d_acc.get() + 3 * kAccGroups); }
 
-int ensure_cplanes(bf_ctx* c) {
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, grow_zeroed(c, c->d_cplane[i], c->cap_px));
-    return BF_OK;
-}
-
-int clear_planes(bf_ctx* c) {
-    for (int i = 0; i < 2; ++i) {
-        HIP_TRY(c, hipMemsetAsync(c->d_plane[i], 0, c->cap_px * sizeof(unsigned long long), c->stream));
-        if (c->d_cplane[i])
-            HIP_TRY(c, hipMemsetAsync(c->d_cplane[i], 0, c->cap_px * sizeof(uint32_t), c->stream));
-        if (c->d_ovf_bits[i])
-            HIP_TRY(c, hipMemsetAsync(c->d_ovf_bits[i], 0, c->d_ovf_bits[i].size() * sizeof(uint32_t), c->stream));
-    }
-    c->planes_unknown = false;
-    c->cur = 0;
-    c->hst.hot.ovf_cnt[0] = c->hst.hot.ovf_cnt[1] = 0;
-    return BF_OK;
-}
-
-// Dirty bitmaps of the overflow planes for an R x C image (a change of R or C clears planes and bitmaps: bf_set_cloud).
-int ensure_ovf_bits(bf_ctx* c, int R, int C) {
-    const int pitch = (C + 31) / 32 + 3;
-    const size_t need = (size_t)R * (size_t)pitch;
-    for (int i = 0; i < 2; ++i) {
-        bool fresh;
-        HIP_TRY(c, c->d_ovf_bits[i].grow(need, &fresh));
-        if (fresh) c->planes_unknown = true;   // (fresh bitmaps: cleared with the planes below)
-    }
-    if (pitch != c->ovf_pitch) c->planes_unknown = true;   // (bits set under another row pitch mean other pixels)
-    c->ovf_pitch = pitch;
-    return BF_OK;
-}
-
-// The second event set and both permutations, shared by the tile-binned loops and bf_run_tiles: whichever comes first allocates
-// them, and the other finds them (with the slice's events possibly IN the second set).
-int ensure_second_set(bf_ctx* c) {
-    const size_t ne = (size_t)c->cap_events;
-    HIP_TRY(c, c->set[1].xy.grow(ne));
-    HIP_TRY(c, c->set[1].t.grow(ne));
-    HIP_TRY(c, c->set[1].p.grow(ne));
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, c->set[i].perm.grow(ne));
-    return BF_OK;
-}
-
-int ensure_bin_buffers(bf_ctx* c, const BinGrid& g) {
-    if (!c->bin_setup_done) {
-        if (bin_kernel_setup() != 0) return fail(c, BF_ERR_HIP, "cannot raise the dynamic LDS limit");
-        c->bin_setup_done = true;
-    }
-    const size_t ne = (size_t)c->cap_events;
-    HIP_TRY(c, c->d_binid.grow(ne));
-    HIP_TRY(c, grow_zeroed(c, c->d_armed, 16));
-    const int rc = ensure_second_set(c);
-    if (rc != BF_OK) return rc;
-    const size_t nb = (size_t)g.nbins + 1;
-    HIP_TRY(c, grow_zeroed(c, c->d_hist_cnt, kHistCopies * nb));
-    HIP_TRY(c, c->d_bin_start.grow(nb));
-    HIP_TRY(c, c->d_cursor.grow(nb));
-    HIP_TRY(c, c->d_chdr.grow(nb * 580));   // event lists: 3 LR + 1 <= 577 key offsets per bin ((column zone, row) keys)
-    const size_t need = (size_t)g.nbins * (size_t)g.LR * (size_t)g.L;
-    HIP_TRY(c, c->d_slabs.grow(need));
-    HIP_TRY(c, c->d_cidx.grow(need));
-    return BF_OK;
-}
-
-// Margin planes and per-bin lists of the interior + margin format.  Iteration j of a run adds to margin plane b0 ^ (j & 1) and
-// clears, bin by bin, what the lists say the previous executed launch left in the other one (flush_split); the host keeps
-// track of which plane the lists describe.  The lists name pixels by their linear index, so what an earlier bin grid left
-// behind is cleared with the earlier grid's list layout before the buffers change hands.
-int margin_reset(bf_ctx* c) {
-    if (c->m_unknown) {
-        for (int i = 0; i < 2; ++i)
-            if (c->d_mplane[i]) HIP_TRY(c, hipMemsetAsync(c->d_mplane[i], 0, c->cap_px * sizeof(unsigned long long), c->stream));
-        if (c->d_mcount) HIP_TRY(c, hipMemsetAsync(c->d_mcount, 0, c->d_mcount.size() * sizeof(uint32_t), c->stream));
-        c->m_unknown = false;
-    } else if (c->m_dirty_plane >= 0) {
-        launch_margin_clean(c->d_mplane[c->m_dirty_plane], c->d_mlist, c->d_mcount, c->m_nbins, c->m_cap, c->stream);
-        HIP_TRY(c, hipGetLastError());
-    }
-    c->m_dirty_plane = -1;
-    return BF_OK;
-}
-int ensure_margin_buffers(bf_ctx* c, const BinGrid& g) {
-    const int mcap = g.LR * g.L - g.TSR * g.TS;
-    if (c->m_unknown || g.nbins != c->m_nbins || mcap != c->m_cap) {
-        int rc = margin_reset(c);
-        if (rc != BF_OK) return rc;
-    }
-    for (int i = 0; i < 2; ++i) HIP_TRY(c, grow_zeroed(c, c->d_mplane[i], c->cap_px));
-    HIP_TRY(c, grow_zeroed(c, c->d_mcount, (size_t)g.nbins));
-    HIP_TRY(c, c->d_mlist.grow((size_t)g.nbins * (size_t)mcap));
-    c->m_nbins = g.nbins;
-    c->m_cap = mcap;
-    return BF_OK;
-}
-
-// Device-conditional counting sort of the live events by the image tile of their current
-// target (runs only when hot.need_rebin is set); no host synchronisation.
-uint32_t* lost_flag(const bf_ctx* c) { return reinterpret_cast<uint32_t*>(c->d_acc.get() + 3 * kAccGroups); }
-
-int enqueue_rebin(bf_ctx* c, DevState* st, bool has_perm_at_start, const WarpParams* prewarp = nullptr, bool fused = false, int launch_no = 0) {
-    ProfScope ps(c, 3);
-    launch_rebin(ev_sets(c), has_perm_at_start ? 1 : 0, c->n, st, fused ? c->fgrid : c->grid, c->d_binid, c->d_hist_cnt,
-                 c->d_bin_start, c->d_cursor, c->d_armed, prewarp, c->opt_bin_pack_limit, c->stream,
-                 fused ? c->d_ftab : nullptr, fused ? lost_flag(c) + (launch_no + 2) % 3 : nullptr);   // (the last pass's word)
-    HIP_TRY(c, hipGetLastError());
-    return BF_OK;
-}
-
-// Apply the warp bf_set_model left pending (optimizer_rolling.h:294-298).
-int flush_pending(bf_ctx* c) {
-    if (!c->pending_warp) return BF_OK;
-    launch_set_state(c->d_state, c->hst, c->stream);
-    {
-        ProfScope ps(c, 3);
-        launch_warp_scatter(ws_args(c, c->cur, 0), true, false, true, c->stream);
-    }
-    c->pending_warp = false;
-    c->p_clean = false;
-    c->seg_valid = false;
-    c->n_valid = true;
-    c->uv_valid = false;
-    c->out_sorted = false;
-    HIP_TRY(c, hipGetLastError());
-    return BF_OK;
-}
-
-// Waits for an event without occupying a host core: query, sleep ~20 us (+ the kernel's timer slack), repeat.
-// hipEventSynchronize spins here whatever the event's flags say (measured: one full core per waiting thread).
-int wait_event_sleeping(bf_ctx* c, hipEvent_t ev) {
-    bool waited = false;
-    for (;;) {
-        const hipError_t e = hipEventQuery(ev);
-        if (e == hipSuccess) break;
-        if (e != hipErrorNotReady) HIP_TRY(c, e);
-        waited = true;
-        struct timespec ts = {0, 20000};
-        nanosleep(&ts, nullptr);
-    }
-    if (waited) (void)hipGetLastError();   // "not ready" is recorded as the thread's last error: it is not one
-    return BF_OK;
-}
-
-// Folds the per-work-group min / max / sum records k_prepare wrote for the uploaded slice (one
-// device-to-host copy per slice, cached).  With `overwritten`, a record about to be reused: only if the slice's statistics are
-// still unread in that record.
-int fold_stats(bf_ctx* c, const SliceStats* overwritten = nullptr) {
-    // (one folder at a time: with early staging the thread that uploads the NEXT slice into this record's slot folds the current
-    // slice's statistics first if nobody has -- bf_upload.cpp: stage_early -- while bf_set_cloud may be doing the same)
-    std::lock_guard<std::mutex> lk(c->stats_mu);
-    if (c->stats_valid) return BF_OK;
-    if (overwritten && (!c->uploaded || c->stats_src != overwritten)) return BF_OK;
-    // (the records are in pinned host memory once k_prepare has completed: on the compute stream, or -- early staging -- on the
-    // copy stream, usually long ago)
-    if (c->stats_event) HIP_TRY(c, hipEventSynchronize(c->stats_event));
-    else HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const SliceStats* src = c->stats_src ? c->stats_src : c->h_stats;
-    SliceStats s = src[0];
-    for (int k = 1; k < kPrepBlocks; ++k) {
-        const SliceStats& q = src[k];
-        if (q.xmin < s.xmin) s.xmin = q.xmin;
-        if (q.xmax > s.xmax) s.xmax = q.xmax;
-        if (q.ymin < s.ymin) s.ymin = q.ymin;
-        if (q.ymax > s.ymax) s.ymax = q.ymax;
-        if (q.tmin < s.tmin) s.tmin = q.tmin;
-        if (q.tmax > s.tmax) s.tmax = q.tmax;
-        s.tsum += q.tsum;
-    }
-    c->stats = s;
-    c->stats_valid = true;
-    return BF_OK;
-}
-
-int after_upload(bf_ctx* c, long long n) {
-    c->p_clean = true;   // k_prepare wrote p = 0
-    c->stats_valid = false;
-    c->have_lwin = false;
-    c->glob_valid = false;
-    c->seg_valid = false;
-    c->groups_valid = false;
-    c->n = n;
-    c->uploaded = true;
-    c->have_window = false;
-    c->all_noise = false;
-    c->pending_warp = false;
-    c->n_valid = false;
-    c->uv_valid = false;
-    c->out_sorted = false;
-    return BF_OK;
-}
-
-}  // namespace

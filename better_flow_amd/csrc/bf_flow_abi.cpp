@@ -1,7 +1,7 @@
 // bf_flow_abi.cpp -- C-ABI of the per-pixel flow field, its colour coding (EventFile::color_flow_img, event_file.h:318-350)
 // and the flow frame of --flow-img / --flow-field (include/bf_accel.h, "per-pixel flow"): render_flow_field enqueues the owner
 // scatter and the per-pixel pass (bf_flowimg.hip) on the context stream; bf_flow_field / bf_color_flow_img are that, a copy
-// and a sync; bf_flow_frame_render runs it next to the two scale-1 projection images (render_projection_img, bf_extras.cpp)
+// and a sync; bf_flow_frame_render runs it next to the two scale-1 projection images (render_projection_img, bf_local_abi.cpp)
 // and composes the three tiles straight into a pinned, device-mapped slot in the byte layout of the files, with the ticket /
 // wait / release protocol of bf_frame_* (bf_frame_abi.cpp).  Every render takes its events either from the live slice (the
 // rolling optimiser's state: bf_flow_*) or from the held flow of the exhaustive search (bf_global_*, "the held flow" in

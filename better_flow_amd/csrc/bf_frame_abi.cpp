@@ -1,7 +1,7 @@
 // bf_frame_abi.cpp -- C-ABI of the device-composed frame of --img / --video (include/bf_accel.h, "per-slice frames on the
-// device"): four tiles rendered on the context stream (render_projection_img / render_color_time_img, bf_extras.cpp), the
+// device"): four tiles rendered on the context stream (render_projection_img, bf_local_abi.cpp; render_color_time_img, below), the
 // mosaic composed by k_frame_compose (bf_frame.hip) straight into a pinned, device-mapped slot in the byte layout of the file,
-// and the ticket / wait / release calls around the slots.
+// and the ticket / wait / release calls around the slots.  The colour-coded time image on its own is bf_color_time_img.
 #include "bf_ctx.h"
 
 #include <cmath>
@@ -25,6 +25,56 @@ struct bf_frame {
     hipStream_t last_stream = nullptr;       // the stream of the newest render, and its slot's event
     hipEvent_t last = nullptr;
 };
+
+extern "C" {
+
+// EventFile::color_time_img (event_file.h:649-747) of the live slice into d_bgr ((scale res_x + scale) x (scale res_y + scale)
+// x 3 bytes), enqueued on the context stream.  Arguments checked by the callers (scale already mapped from 0 to 11).
+int render_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* d_bgr) {
+    ColorGeom g;
+    memset(&g, 0, sizeof(g));
+    g.scale = scale; g.show_final = show_final ? 1 : 0;
+    g.mx = scale * res_x; g.my = scale * res_y;
+    g.R = g.mx + scale; g.C = g.my + scale;
+    const size_t px = (size_t)g.R * (size_t)g.C;
+    int rc = flush_pending(c);   // a pending bf_set_model warp moves the events first
+    if (rc != BF_OK) return rc;
+    if (c->n > 0) {
+        rc = fold_stats(c);
+        if (rc != BF_OK) return rc;
+        g.t_min = c->stats.tmin;                                             // :659-662: t_max starts at 0
+        g.t_range = std::max<long long>(c->stats.tmax, 0) - g.t_min;
+    }
+    g.x_shift = -double(res_x / 2) * double(scale) + double(g.mx) / 2.0;     // :677-678 with x_min = 0, x_max = RES_X
+    g.y_shift = -double(res_y / 2) * double(scale) + double(g.my) / 2.0;
+    HIP_TRY(c, c->d_col_planes.grow(c->cap_px * 20));   // 2 x i64 sums + u32 count per pixel
+    HIP_TRY(c, hipMemsetAsync(c->d_col_planes, 0, px * 20, c->stream));
+    const bf_ctx::EvSet& e = c->set[c->cs];
+    unsigned long long* sums = reinterpret_cast<unsigned long long*>(c->d_col_planes.get());
+    launch_color_time(e.xy, e.t, e.p, c->has_noise ? c->d_noise : nullptr, c->n, g,
+                      reinterpret_cast<uint32_t*>(sums + 2 * px), sums, sums + px, d_bgr, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return BF_OK;
+}
+
+int bf_color_time_img(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, int32_t show_final, uint8_t* bgr_out) {
+    if (!c || !bgr_out) return BF_ERR_ARG;
+    if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_color_time_img before bf_upload_events");
+    if (scale == 0) scale = 11;   // event_file.h:650
+    if (scale < 1 || scale > 15) return fail(c, BF_ERR_ARG, "scale must be in 1..15 (got %d)", scale);
+    if (res_x < 1 || res_y < 1) return fail(c, BF_ERR_ARG, "bad sensor size");
+    const size_t px = (size_t)(scale * res_x + scale) * (size_t)(scale * res_y + scale);
+    if (px > c->cap_px) return fail(c, BF_ERR_CAPACITY, "image %d x %d exceeds the image capacity", scale * res_x + scale, scale * res_y + scale);
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_col_img.grow(c->cap_px * 3));
+    int rc = render_color_time_img(c, scale, res_x, res_y, show_final, c->d_col_img);
+    if (rc != BF_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(bgr_out, c->d_col_img, px * 3, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return BF_OK;
+}
+
+}  // extern "C"
 
 namespace {
 

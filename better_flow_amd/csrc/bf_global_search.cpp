@@ -464,7 +464,7 @@ int bf_global_set_window(bf_ctx* c, int32_t scale, int32_t metric_wsize, bf_glob
     gs->have = false;
     gs->cells.have = false;
     gs->held.mode = 0;
-    c->glob_valid = false;
+    c->global_window_dropped();
     HIP_TRY(c, gs->d_state.grow((size_t)c->cap_events * 6));   // (n <= cap_events: one allocation for every slice)
     GlobalGeom& g = gs->g;
     g.scale = scale; g.mw = metric_wsize;
@@ -479,7 +479,7 @@ int bf_global_set_window(bf_ctx* c, int32_t scale, int32_t metric_wsize, bf_glob
     gs->w = w;
     gs->n = c->n;
     gs->have = true;
-    c->glob_valid = true;
+    c->global_window_held();
     if (out) *out = w;
     return BF_OK;
 }

@@ -1,4 +1,4 @@
-// bf_kernels.h -- launch interface between the C-ABI files (bf_context / bf_upload / bf_operators / bf_run / bf_extras .cpp) and
+// bf_kernels.h -- launch interface between the C-ABI files (bf_context / bf_upload / bf_operators / bf_run / bf_tiles_abi / bf_local_abi .cpp) and
 // bf_kernels.hip (gfx950 kernels).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -13,7 +13,7 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
     int rc = fold_stats(c);
     if (rc != BF_OK) return rc;
     const SliceStats s = c->stats;
-    c->seg_valid = false;
+    c->segmentation_dropped();
     // optimizer_rolling.h:252-260: min seeded with RES, max with 0
     int x_min = res_x, y_min = res_y, x_max = 0, y_max = 0;
     if (c->n > 0) {
@@ -31,14 +31,11 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
         // e.g. an empty slice: x_min = RES_X > x_max = 0.  The reference carries on and run()
         // returns 1 at the window guard (:49-55); no image operator is usable on it.
         c->win = w;
-        c->have_window = true;
-        c->degenerate = true;
+        c->window_set(true);
         memset(&c->hst.model, 0, sizeof(c->hst.model));
-        c->pending_warp = false;
         if (window_out) *window_out = w;
         return BF_OK;
     }
-    c->degenerate = false;
     if ((size_t)w.scale_img_x * (size_t)w.scale_img_y > c->cap_px)
         return fail(c, BF_ERR_CAPACITY, "window %d x %d exceeds the image capacity", w.scale_img_x, w.scale_img_y);
     if (w.scale_img_x > 65535 || w.scale_img_y > 65535)   // 16-bit pixel coordinates in the packed moment sums
@@ -61,8 +58,12 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
         tbits = 64;
     }
 
+    // Event::reset for every event (set_cloud :260).  bf_upload_events already reset p.
+    if (!c->p_clean) HIP_TRY(c, hipMemsetAsync(c->set[c->cs].p, 0, (size_t)c->n_pad * sizeof(float2), c->stream));
+    // The window and everything the flags say about it change together, once nothing can refuse the call any more: a
+    // bf_set_cloud refused above (capacity) leaves the previous window as it was, its `degenerate` included.
     c->win = w;
-    c->have_window = true;
+    c->window_set(false);
     DevState& h = c->hst;
     h.hot.scale = scale;
     h.hot.R = w.scale_img_x; h.hot.C = w.scale_img_y;
@@ -76,17 +77,9 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
     memset(&h.model, 0, sizeof(h.model));   // a fresh OptimizerRolling has a zero ObjectModel
     h.hot.wp = identity_warp();
     h.hot.it = 0; h.hot.done = 0; h.rc = 0;
-    c->pending_warp = false;
-    c->all_noise = false;
-    // Event::reset for every event (set_cloud :260).  bf_upload_events already reset p.
-    if (!c->p_clean) HIP_TRY(c, hipMemsetAsync(c->set[c->cs].p, 0, (size_t)c->n_pad * sizeof(float2), c->stream));
-    c->p_clean = true;
-    c->n_valid = false;
-    c->uv_valid = false;
-    c->out_sorted = false;
     // The slice's bin grids and scatter format (plan_slice); the buffers they need are allocated here, in this order.
     const SlicePlan p = plan_slice(c, w);
-    c->use_binned = p.binned;
+    c->planned_binned(p.binned);
     if (c->use_binned) {
         rc = ensure_cplanes(c);
         if (rc == BF_OK) rc = ensure_bin_buffers(c, p.grid);
@@ -94,7 +87,7 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
         if (rc != BF_OK) return rc;
         c->grid = p.grid;
     }
-    c->fused_ok = false;
+    c->planned_one_kernel(false);
     if (p.fused_ok) {
         rc = ensure_cplanes(c);
         if (rc == BF_OK) rc = ensure_bin_buffers(c, p.fgrid);
@@ -102,8 +95,8 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
         HIP_TRY(c, c->d_ftab.grow((size_t)p.fgrid.nbr * p.fgrid.nbc * kFusedTabWords));
         for (int i = 0; i < 2; ++i) HIP_TRY(c, c->set[i].p2.grow((size_t)c->cap_events));
         c->fgrid = p.fgrid;
-        c->fused_ok = true;
-        c->fused_shared = p.fused_shared;
+        c->planned_one_kernel(true);
+        c->planned_one_kernel_shared(p.fused_shared);
     }
     h.hot.binned = (c->use_binned || c->fused_ok) ? 1 : 0;
     h.hot.pp = 0; h.hot.redo = 0; h.hot.pend = 0; h.last_j = -1;
@@ -141,7 +134,7 @@ int bf_set_cloud(bf_ctx* c, int32_t scale, int32_t res_x, int32_t res_y, bf_wind
 // when somebody reads them.
 static int materialize_outputs(bf_ctx* c) {
     if (!c->out_sorted) return BF_OK;
-    c->out_sorted = false;
+    c->outputs_materialised();
     if (!c->has_perm || c->n == 0) return BF_OK;
     HIP_TRY(c, c->d_out_tmp.grow((size_t)c->cap_events));
     const uint32_t* perm = c->set[c->cs].perm;
@@ -174,11 +167,7 @@ int bf_project_4param_reinit(bf_ctx* c, double dnx_, double dny_, double cx, dou
         ProfScope ps(c, 0, c->n);
         launch_warp_scatter(ws_args(c, c->cur, 0), true, false, true, c->stream);
     }
-    c->p_clean = false;
-    c->seg_valid = false;
-    c->n_valid = true;
-    c->uv_valid = false;
-    c->out_sorted = false;
+    c->events_warped();
     HIP_TRY(c, hipGetLastError());
     return BF_OK;
 }
@@ -195,11 +184,7 @@ int bf_project_4param(bf_ctx* c, double dnx_, double dny_, double cx, double cy,
         ProfScope ps(c, 0, c->n);
         launch_project_dn(e.xy, e.t, e.p, c->d_nxny, c->has_perm ? e.perm : nullptr, c->n_valid ? 1 : 0, c->d_state, c->n, c->stream);
     }
-    c->p_clean = false;
-    c->seg_valid = false;
-    c->n_valid = true;
-    c->uv_valid = false;
-    c->out_sorted = false;
+    c->events_warped();
     HIP_TRY(c, hipGetLastError());
     return BF_OK;
 }
@@ -322,7 +307,7 @@ static int ensure_uv(bf_ctx* c) {
     if (!c->uv_valid) {
         ProfScope ps(c, 3);
         launch_compute_uv(c->d_nxny, c->d_uv, c->n, c->stream);
-        c->uv_valid = true;
+        c->uv_computed();
     }
     HIP_TRY(c, hipGetLastError());
     return BF_OK;
@@ -375,7 +360,7 @@ int bf_writeout_events(bf_ctx* c, double* pr_x, double* pr_y, double* nx, double
     rc = materialize_outputs(c);
     if (rc != BF_OK) return rc;
     if (pr_x || pr_y) {
-        c->uv_valid = false;   // d_uv is the staging buffer of the expanded positions below
+        c->uv_buffer_reused();   // d_uv is the staging buffer of the expanded positions below
         {
             ProfScope ps(c, 3);
             launch_expand_pr(c->set[c->cs].xy, c->set[c->cs].p, c->has_perm ? c->set[c->cs].perm : nullptr,

@@ -1,5 +1,6 @@
 // bf_run.cpp -- C-ABI: the fused OptimizerRolling::set_model / run (optimizer_rolling.h:48-125,289-347): the host side of the device loops
-// (two-kernel tile-binned loop, one-kernel iteration, persistent loop kernel, global-atomic fallback and its delta-scatter form; plan_run picks one) and bf_run_many.
+// (two-kernel tile-binned loop, one-kernel iteration, persistent loop kernel, global-atomic fallback and its delta-scatter form; plan_run picks one), bf_run_many,
+// and bf_get_trace of the last run's per-iteration records.
 #include "bf_ctx.h"
 
 namespace {
@@ -61,9 +62,7 @@ int run_begin(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L) {
     DevState& h = c->hst;
     L.b0 = L.buf = c->cur;
     L.trace = o.trace_cap > 0 ? c->d_trace : nullptr;
-    c->p_clean = false;   // the loop warps the events
-    c->seg_valid = false;
-    c->pending_warp = false;
+    c->run_began();   // the loop warps the events
     h.x_div = h.y_div = 1.0f;            // :61
     h.rot_div = h.div_div = 10000.0f;    // :62-63
     h.old_dx = h.old_dy = h.old_rot = h.old_div = 0.f;
@@ -508,14 +507,9 @@ int run_end(bf_ctx* c, const bf_run_opts& o, const RunPlan& p, RunLoop& L, bf_mo
         }
         L.fin = c->h_state[1];
     }
-    if (p.bin_grid()) {   // the device chose which set holds the (tile-sorted) events
-        c->cs = L.fin.hot.cs;
-        c->has_perm = true;
-    }
+    if (p.bin_grid()) c->sorted_by_plan(L.fin.hot.cs);   // the device chose which set holds the (tile-sorted) events
     if (p.warm_start) c->warm_iters_hint = L.fin.hot.it;
-    c->n_valid = true;
-    c->uv_valid = o.want_uv != 0;
-    c->out_sorted = true;
+    c->run_ended(o.want_uv != 0);
     HIP_TRY(c, hipGetLastError());
     // (want_uv: the final warp writes the per-event flow into d_uv; whoever reads it -- bf_compute_uv, bf_compute_uv_ring, the
     // writers -- does so on this stream, behind it: the run does not wait for it.  It used to drain the stream here, which kept a
@@ -562,7 +556,7 @@ int bf_set_model(bf_ctx* c, const bf_model* model) {
     // optimizer_rolling.h:289-299: model <- m; warp(-total_dx, -total_dy, cx, cy, total_div, -total_rot)
     c->hst.model = *model;
     set_model_warp(c->hst.hot.wp, *model);
-    c->pending_warp = true;
+    c->warp_pending();
     return BF_OK;
 }
 
@@ -577,7 +571,7 @@ int bf_run(bf_ctx* c, const bf_run_opts* opts_in, bf_model* model_out, bf_run_in
 
     // optimizer_rolling.h:49-55 (integer arithmetic) and :57-58
     const bool noise = (w.scale_img_x < w.scale * o.res_x / 15) && (w.scale_img_y < w.scale * o.res_y / 15);
-    if (noise) c->all_noise = true;   // "for (auto &e : *events) e.noise = true;"
+    if (noise) c->all_noise_marked();   // "for (auto &e : *events) e.noise = true;"
     if (noise || c->n < (long long)o.min_events) {
         if (model_out) *model_out = c->hst.model;
         if (info) *info = bf_run_info{BF_SKIPPED, 0, 1.0f, 1.0f, 10000.0f, 10000.0f};
@@ -633,6 +627,18 @@ int bf_run_many(bf_ctx* const* ctxs, int32_t n, const bf_run_opts* opts, bf_mode
     for (auto& t : th) t.join();
     for (int i = 0; i < n; ++i)
         if (rc[(size_t)i] < 0) return rc[(size_t)i];
+    return BF_OK;
+}
+
+int bf_get_trace(bf_ctx* c, bf_trace_rec* out, int32_t cap, int32_t* written) {
+    if (!c || !out || cap < 0) return BF_ERR_ARG;
+    int n = c->trace_valid < cap ? c->trace_valid : cap;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (n > 0) {
+        HIP_TRY(c, hipMemcpyAsync(out, c->d_trace, (size_t)n * sizeof(bf_trace_rec), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    if (written) *written = n;
     return BF_OK;
 }
 

@@ -72,7 +72,7 @@ int bf_segment(bf_ctx* c, const bf_segment_opts* opts, bf_segment_info* info) {
     if (o.min_count < 1 || o.min_pixels < 1 || (o.connectivity != 4 && o.connectivity != 8))
         return fail(c, BF_ERR_ARG, "bf_segment: min_count %d, min_pixels %d (both >= 1), connectivity %d (4 or 8)", o.min_count,
                     o.min_pixels, o.connectivity);
-    c->seg_valid = false;
+    c->segmentation_dropped();
     int rc = ctx_time_img_pass(c, "bf_segment");
     if (rc != BF_OK) return rc;
     const int R = c->win.scale_img_x, C = c->win.scale_img_y;
@@ -103,7 +103,7 @@ int bf_segment(bf_ctx* c, const bf_segment_opts* opts, bf_segment_info* info) {
             HIP_TRY(c, hipGetLastError());
         }
     }
-    c->seg_valid = true;
+    c->segmentation_held();
     if (info) {
         const SegDev& d = c->h_seg_dev[0];
         memset(info, 0, sizeof(*info));
@@ -141,7 +141,7 @@ int bf_label_image(bf_ctx* c, const uint8_t* mask, int32_t rows, int32_t cols, i
     const size_t P = (size_t)rows * (size_t)cols;
     if (P > c->cap_px || P > (size_t)INT_MAX) return fail(c, BF_ERR_CAPACITY, "image %d x %d exceeds capacity", rows, cols);
     HIP_TRY(c, hipSetDevice(c->device));
-    c->seg_valid = false;   // (the planes change hands)
+    c->segmentation_dropped();   // (the planes change hands)
     int rc = seg_prepare(c, P);
     if (rc != BF_OK) return rc;
     HIP_TRY(c, c->d_seg_mask.grow(P));

@@ -36,12 +36,12 @@ static int stage(bf_ctx* c, UploadSlot& s, hipStream_t st, bf_ctx::EvSet& dst, S
 // The slice of n events is staged (or being staged) in set[0]; its statistics are in `stats` once `ev` has completed (null: the
 // compute stream).
 static int slice_staged(bf_ctx* c, long long n, const SliceStats* stats, hipEvent_t ev) {
+    c->n = n;
     c->n_pad = pad_events(n);
-    c->cs = 0;
-    c->has_perm = false;
     c->stats_src = stats;
     c->stats_event = ev;
-    return after_upload(c, n);
+    c->slice_uploaded();
+    return BF_OK;
 }
 
 // Early staging of slot s (no noise ring, a context alone on the GPU): stage() on the COPY stream, behind the copies, into the

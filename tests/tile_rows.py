@@ -11,7 +11,7 @@ import numpy as np
 
 from better_flow_amd import synth
 
-LDS_PLANE_BYTES = 156 * 1024    # bf_extras.cpp, tiles_prepare: max_px * 16 must fit
+LDS_PLANE_BYTES = 156 * 1024    # bf_tiles_abi.cpp, tiles_prepare: max_px * 16 must fit
 TILE_REGISTER_EVENTS = 4096     # bf_tiles.hip: kTileUR * THREADS
 LOCAL_REGISTER_EVENTS = 2048    # bf_local.hip: the window optimizer's register file
 
@@ -115,7 +115,7 @@ def tile_order(sl, H, W, gr, gc):
 
 
 def max_px(H, W, s, gr, gc):
-    """The largest window a tile can have, in scaled pixels (bf_extras.cpp, tiles_prepare)."""
+    """The largest window a tile can have, in scaled pixels (bf_tiles_abi.cpp, tiles_prepare)."""
     tr, tc = -(-H // gr) + 1, -(-W // gc) + 1
     return (s * tr + s) * (s * tc + s)
 
