@@ -270,7 +270,7 @@ EXPORTS = [
     "bf_global_flow_frame_render", "bf_global_render_flow_frame", "bf_global_emit_slice",
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
     "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups", "bf_assign_groups",
-    "bf_propose_models", "bf_project_groups", "bf_merge_scores",
+    "bf_propose_models", "bf_project_groups", "bf_merge_scores", "bf_hold_groups", "bf_group_flow_medians",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -481,6 +481,8 @@ def load(path=None):
         L.bf_global_hold_field.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_int32]
         L.bf_global_hold_best.argtypes = [C.c_void_p]
         L.bf_global_get_flow.argtypes = [C.c_void_p] + [C.c_void_p] * 6
+        L.bf_hold_groups.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
+        L.bf_group_flow_medians.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.bf_global_flow_field.argtypes = L.bf_flow_field.argtypes
         L.bf_global_color_flow_img.argtypes = L.bf_color_flow_img.argtypes
         L.bf_global_flow_frame_render.argtypes = L.bf_flow_frame_render.argtypes
@@ -1023,6 +1025,27 @@ class Accel:
         info = MergeInfo()
         self._chk(self.L.bf_merge_scores(self.h, C.byref(o), ms, K, _ptr(gain), _ptr(inside), _ptr(events), C.byref(info)))
         return gain, inside, events, info
+
+    def hold_groups(self, models):
+        """bf_hold_groups: every event of the held grouping under its own group's model (`models`, one Model per group) becomes
+        the held flow that global_get_flow, global_flow_field, global_color_flow_img, global_render_flow_frame and
+        global_emit_slice read; an event of no group is held with zero flow.  Needs global_set_window on the slice."""
+        K = len(models)
+        ms = (Model * max(K, 1))(*models)
+        self._chk(self.L.bf_hold_groups(self.h, ms, K))
+
+    def group_flow_medians(self):
+        """bf_group_flow_medians: per group of the held grouping the median per axis of the held flow's (u, v) over its events
+        (the mean of the two middle values of an even count, 0 for an empty group).  Returns (u_med float64[K],
+        v_med float64[K], counts int32[K + 1] (last: the events of no group))."""
+        k = C.c_int64(0)
+        self._chk(self.L.bf_get_stat(self.h, b"groups_held", C.byref(k)))
+        K = max(int(k.value), 0)
+        u = np.zeros(K, dtype=np.float64)
+        v = np.zeros(K, dtype=np.float64)
+        counts = np.zeros(K + 1, dtype=np.int32)
+        self._chk(self.L.bf_group_flow_medians(self.h, _ptr(u), _ptr(v), _ptr(counts)))
+        return u, v, counts
 
     def propose_models(self, opts=None, radius=1, suppress=2, max_models=8, min_votes=1, want_planes=False):
         """bf_propose_models: the modes of the per-event best flow global_search left over the lattice `opts` (a

@@ -4,8 +4,12 @@
 // candidate, the objective S, the objective per cell, the candidate set of a pyramid level, the piecewise projection, the
 // interpolated field, the held flow) are stated in include/bf_accel.h and DESIGN.md.
 #include "bf_ctx.h"
+#include "bf_hold_groups.h"
 
 constexpr int kGlobalHoldBest = 3;   // GlobalSearch::Held::mode after bf_global_hold_best (1, 2: BF_GLOBAL_HOLD_CELLS / _FIELD)
+constexpr int kGlobalHoldGroups = 4; // ... after bf_hold_groups
+// a hold that keeps its own copy of the slot order (d_xy / d_idx): it outlives the cells and every later re-sort of the context
+constexpr bool global_hold_own_order(int mode) { return mode == kGlobalHoldBest || mode == kGlobalHoldGroups; }
 
 struct GlobalSearch {
     // the window of bf_global_set_window, the per-event state and the buffers of one batch of candidates
@@ -54,16 +58,18 @@ struct GlobalSearch {
         DevArray<double> d_state_save;
     } pyr;
 
-    // The held flow (bf_global_hold_field / bf_global_hold_best), of the slice the window was set on: valid while `have` and
+    // The held flow (bf_global_hold_field / bf_global_hold_best / bf_hold_groups), of the slice the window was set on: valid while `have` and
     // mode != 0.  bf_global_set_window drops it, bf_global_set_cells drops one of the grid modes (whose address words and
     // upload indices are the cells' own d_cxy / d_cidx); an upload invalidates it with the window (bf_ctx::glob_valid).
     // The nz it was formed with (one for a grid mode, best_nz per event for the snapshot) is spent at the hold: d_p and
     // d_uv carry it.
     struct Held {
-        int mode = 0;                      // 0: none, BF_GLOBAL_HOLD_CELLS, BF_GLOBAL_HOLD_FIELD or kGlobalHoldBest
+        int mode = 0;                      // 0: none, BF_GLOBAL_HOLD_CELLS, BF_GLOBAL_HOLD_FIELD, kGlobalHoldBest or kGlobalHoldGroups
         DevArray<double2> d_nxny, d_uv;    // upload order
-        DevArray<float2> d_p;              // the hold's source order: the cells', or (kGlobalHoldBest) that of d_xy / d_idx
-        DevArray<uint32_t> d_xy, d_idx;    // kGlobalHoldBest: the context's slot order at the hold
+        DevArray<float2> d_p;              // the hold's source order: the cells', or (global_hold_own_order) that of d_xy / d_idx
+        DevArray<uint32_t> d_xy, d_idx;    // global_hold_own_order: the context's slot order at the hold
+        DevArray<uint8_t> d_med;           // bf_group_flow_medians: the select's state (bf_hold_groups.h: MedianState)
+        HostArray<uint8_t> h_med;          // ... and the pinned copy of all of it but the digit counts
         DevArray<double2> d_pr;            // bf_global_get_flow: the positions, upload order
         HostArray<double2> h_stage;        // ... and its pinned staging, 3 n pairs
         Event landed[3];                   // ... one per array: its copy has landed in h_stage
@@ -535,7 +541,7 @@ int bf_global_set_cells(bf_ctx* c, int32_t res_x, int32_t res_y, int32_t cell_ro
     GlobalSearch* gs = c->glob.get();
     GlobalSearch::Cells& cs = gs->cells;
     cs.have = false;
-    if (gs->held.mode != kGlobalHoldBest) gs->held.mode = 0;   // (a grid hold lives in the cells' order)
+    if (!global_hold_own_order(gs->held.mode)) gs->held.mode = 0;   // (a grid hold lives in the cells' order)
     if (res_x <= 0 || res_y <= 0 || cell_rows <= 0 || cell_cols <= 0)
         return fail(c, BF_ERR_ARG, "sensor %d x %d, cells %d x %d: every size must be positive", res_x, res_y, cell_rows, cell_cols);
     if (gs->n > 0 && (gs->w.x_max >= res_x || gs->w.y_max >= res_y))   // (addresses are unsigned: x_min, y_min >= 0)
@@ -958,6 +964,93 @@ int bf_global_hold_best(bf_ctx* c) {
     return BF_OK;
 }
 
+int bf_hold_groups(bf_ctx* c, const bf_model* models, int32_t n_models) {
+    if (!c) return BF_ERR_ARG;
+    if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_hold_groups before bf_upload_events");
+    GlobalSearch* gs = c->glob.get();
+    if (!gs || !gs->have || !c->glob_valid || c->n != gs->n)
+        return fail(c, BF_ERR_STATE, "bf_hold_groups: no window of the uploaded slice: call bf_global_set_window first");
+    if (!models) return fail(c, BF_ERR_ARG, "bf_hold_groups: models %p", (const void*)models);
+    if (n_models < 1 || n_models > kAssignMaxModels) return fail(c, BF_ERR_ARG, "bf_hold_groups: %d models (1 .. %d)", n_models, kAssignMaxModels);
+    if (c->has_noise) return fail(c, BF_ERR_ARG, "bf_hold_groups does not take a noise mask");
+    if (!c->groups_valid) return fail(c, BF_ERR_STATE, "bf_hold_groups: no grouping of the uploaded slice is held");
+    const int K = n_models;
+    if (c->groups_K != K) return fail(c, BF_ERR_ARG, "bf_hold_groups: the held grouping has %d groups, %d models given", c->groups_K, K);
+    HIP_TRY(c, hipSetDevice(c->device));
+    gs->held.mode = 0;   // (a failure below leaves no held flow)
+    if (gs->n > 0) {
+        GlobalHeld h;
+        int rc = ensure_held(c, gs, true, h);
+        if (rc != BF_OK) return rc;
+        HIP_TRY(c, c->d_assign_wp.grow((size_t)kAssignMaxModels));
+        HIP_TRY(c, c->h_assign_wp.grow((size_t)kAssignMaxModels));
+        for (int k = 0; k < K; ++k) set_model_warp(c->h_assign_wp[k], models[k]);   // (sine and cosine from the host's libm)
+        HIP_TRY(c, hipMemcpyAsync(c->d_assign_wp, c->h_assign_wp, (size_t)K * sizeof(WarpParams), hipMemcpyHostToDevice, c->stream));
+        const bf_ctx::EvSet& e = c->set[c->cs];
+        {
+            ProfScope ps(c, 3);
+            launch_hold_groups(e.xy, e.t, c->has_perm ? e.perm.get() : nullptr, c->d_group_id, c->d_assign_wp, K, gs->n, h, c->stream);
+        }
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the staged warps are the assignment's too: free again from here)
+    }
+    gs->held.mode = kGlobalHoldGroups;
+    return BF_OK;
+}
+
+int bf_group_flow_medians(bf_ctx* c, double* u_med, double* v_med, int32_t* counts) {
+    if (!c) return BF_ERR_ARG;
+    GlobalHeldFlow f;
+    int rc = global_held_flow(c, "bf_group_flow_medians", &f);
+    if (rc != BF_OK) return rc;
+    if (!c->groups_valid) return fail(c, BF_ERR_STATE, "bf_group_flow_medians: no grouping of the uploaded slice is held");
+    const int K = c->groups_K;
+    if (K > kAssignMaxModels) return fail(c, BF_ERR_CAPACITY, "bf_group_flow_medians: %d groups (at most %d)", K, kAssignMaxModels);
+    for (int k = 0; k < K; ++k) {
+        if (u_med) u_med[k] = 0.0;
+        if (v_med) v_med[k] = 0.0;
+        if (counts) counts[k] = 0;
+    }
+    if (counts) counts[K] = (int32_t)f.n;
+    if (f.n == 0 || K == 0) return BF_OK;   // every group empty
+    HIP_TRY(c, hipSetDevice(c->device));
+    GlobalSearch::Held& hd = c->glob->held;
+    // the state: prefix, median, rank, count -- the part read back -- then the digit counts
+    const size_t head = median_state_head(K), bytes = median_state_bytes(K);
+    HIP_TRY(c, hd.d_med.grow(median_state_bytes(kAssignMaxModels)));
+    HIP_TRY(c, hd.h_med.grow(median_state_head(kAssignMaxModels)));
+    uint8_t* b = hd.d_med;
+    MedianState st;
+    st.prefix = reinterpret_cast<unsigned long long*>(b);
+    st.median = reinterpret_cast<double*>(st.prefix + 4 * K);
+    st.rank = reinterpret_cast<uint32_t*>(st.median + 2 * K);
+    st.count = st.rank + 4 * K;
+    st.hist = reinterpret_cast<uint32_t*>(b + head);   // (16-byte aligned: the pick reads four counts at a time)
+    HIP_TRY(c, hipMemsetAsync(b, 0, bytes, c->stream));
+    {
+        ProfScope ps(c, 3);
+        for (int pass = 0; pass < 8; ++pass) {   // (the picks narrow the ranks on the device: no wait in between)
+            if (pass > 0) HIP_TRY(c, hipMemsetAsync(st.hist, 0, (size_t)K * 4 * 256 * sizeof(uint32_t), c->stream));
+            launch_median_pass(f.uv, c->d_group_id, f.n, K, pass, st, c->stream);
+        }
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(hd.h_med, b, head, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint8_t* hb = hd.h_med;
+    const double* med = reinterpret_cast<const double*>(hb + (size_t)K * 4 * 8);
+    const uint32_t* cnt = reinterpret_cast<const uint32_t*>(hb + (size_t)K * (4 * 8 + 2 * 8 + 4 * 4));
+    long long assigned = 0;
+    for (int k = 0; k < K; ++k) {
+        if (u_med) u_med[k] = med[2 * k];
+        if (v_med) v_med[k] = med[2 * k + 1];
+        if (counts) counts[k] = (int32_t)cnt[2 * k];
+        assigned += (long long)cnt[2 * k];
+    }
+    if (counts) counts[K] = (int32_t)(f.n - assigned);
+    return BF_OK;
+}
+
 int bf_global_get_flow(bf_ctx* c, double* nx, double* ny, double* u, double* v, double* pr_x, double* pr_y) {
     if (!c) return BF_ERR_ARG;
     GlobalHeldFlow f;
@@ -1016,14 +1109,14 @@ void global_cand_uv(double nx, double ny, double nz, double* u, double* v) { can
 int global_held_flow(bf_ctx* c, const char* who, GlobalHeldFlow* out) {
     GlobalSearch* gs = c->glob.get();
     if (!gs || !gs->have || !gs->held.mode)
-        return fail(c, BF_ERR_STATE, "%s: no held flow: call bf_global_hold_field or bf_global_hold_best first", who);
+        return fail(c, BF_ERR_STATE, "%s: no held flow: call bf_global_hold_field, bf_global_hold_best or bf_hold_groups first", who);
     if (!c->uploaded || !c->glob_valid || c->n != gs->n)
         return fail(c, BF_ERR_STATE, "%s: events were uploaded since the flow was held", who);
     const GlobalSearch::Held& hd = gs->held;
     std::memset(out, 0, sizeof(*out));
     out->n = gs->n;
     if (gs->n <= 0) return BF_OK;
-    const bool best = hd.mode == kGlobalHoldBest;
+    const bool best = global_hold_own_order(hd.mode);
     out->xy = best ? hd.d_xy.get() : gs->cells.d_cxy.get();
     out->idx = best ? hd.d_idx.get() : gs->cells.d_cidx.get();
     out->p = hd.d_p;

@@ -64,6 +64,7 @@ protected:
     bf_ctx *objects_helper = nullptr;          // the refit of a group too large for the grouped solve runs here
     bool generate_objects_img = false;         // --objects-img: objects_N.ppm / objects_N.pgm / objects_N.score.txt
     bf::ObjectRenderer renderer;
+    bool generate_objects_flow = false;        // --objects-flow: objects_N.flo / objects_N.flow.ppm / objects_N.events.txt
     bf::AviWriter flowvideo;
     ull flow_count = 0;
     bool stm_disable;
@@ -125,6 +126,9 @@ public:
     // ... and their picture and score (objects_N.ppm, objects_N.pgm, objects_N.score.txt): the slice with every event under
     // its own object's model, in the assignment's window; a box sum of 255 / gain saturates an object's colour
     void set_generate_objects_img(int gain) { generate_objects_img = true; renderer.opts.gain = gain; }
+    // ... and their per-event flow (objects_N.flo, objects_N.flow.ppm, objects_N.events.txt): every event under its own
+    // object's model, held on the device by the finder (bf::ObjectFinder::hold_flow) and read through the held flow's outputs
+    void set_generate_objects_flow() { generate_objects_flow = true; finder.hold_flow = true; }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
 
@@ -249,6 +253,25 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
     // (--objects-merge) what the merger did to the proposed groups, and the contrast sum N^2 of the grouping it left
     if (finder.merge_num > 0 && !bf::ObjectMerger::write_steps(base + ".merge.txt", finder.steps, finder.models.size(), finder.merged_sum_sq) && !quiet)
         std::cerr << "cannot write " << base << ".merge.txt\n";
+    // (--objects-flow) the finder left the slice, the grouping and the held flow on the context: the flow field and the flow
+    // frame as render_flow_frame writes the rolling optimiser's (oldest event owns a pixel), and one line per event.  A slice
+    // without an object has no model to hold a flow under (bf::ObjectFinder::hold_flow): like --objects-img it writes nothing
+    if (generate_objects_flow && !finder.models.empty()) {
+        std::vector<uint8_t> ppm((size_t)RES_X * (size_t)(3 * RES_Y) * 3);
+        std::vector<float> flo((size_t)RES_X * (size_t)RES_Y * 2);
+        std::vector<double> u(sl.n), v(sl.n);
+        int frc = bf_global_render_flow_frame(ctx, RES_X, RES_Y, BF_FLOW_LAST_UPLOADED, ppm.data(), nullptr, flo.data());
+        if (frc >= 0) frc = bf_global_get_flow(ctx, nullptr, nullptr, u.data(), v.data(), nullptr, nullptr);
+        if (frc < 0) throw bf::AccelError(frc, std::string("--objects-flow: ") + bf_last_error(ctx));
+        bool w = bf::write_flo(base + ".flo", RES_X, RES_Y, flo.data()) && bf::write_ppm_raw(base + ".flow.ppm", RES_X, 3 * RES_Y, ppm.data());
+        FILE *ef = std::fopen((base + ".events.txt").c_str(), "w");
+        if (ef) {
+            for (size_t i = 0; i < sl.n; ++i)
+                std::fprintf(ef, "%d %d %d %d %.9f %.9f\n", (int)ft[i], (int)fx[i], (int)fy[i], (int)finder.gid[i], u[i], v[i]);
+            w = (std::fclose(ef) == 0) && w;
+        }
+        if ((!w || !ef) && !quiet) std::cerr << "cannot write " << base << ".flo / .flow.ppm / .events.txt\n";
+    }
     if (!generate_objects_img || finder.models.empty()) return;   // (no object: nothing to project)
     // find() leaves the context holding one group's events (its flows re-upload): the renderer uploads the slice again and
     // holds the final ids as its grouping

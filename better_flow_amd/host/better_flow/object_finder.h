@@ -4,6 +4,9 @@
 //   3. bf::MotionAssigner::alternate from them: assignment and grouped refit until no id changes;
 //   4. (merge_num > 0) bf::ObjectMerger::reduce: groups that are one motion are merged, so the K proposed is "at most K"
 //      (DESIGN section 18).
+// With hold_flow it ends with every event's flow under its own object's model held on the device (bf_hold_groups, DESIGN
+// section 19): the per-object median flow comes from there, and the context is left holding the slice, the grouping and that flow
+// for the readers of the held flow (bf_global_get_flow, bf_global_flow_field, bf_global_render_flow_frame, ...).
 // It needs the device library: the CPU stand-in the tests build has no bf_global_*.  Against a C-ABI that lacks an entry find()
 // returns BF_ERR_STATE and `error` names the entry.
 #ifndef BF_HOST_OBJECT_FINDER_H
@@ -20,6 +23,11 @@ extern "C" {
 int bf_global_set_window(bf_ctx *ctx, int32_t scale, int32_t metric_wsize, bf_global_window *out) __attribute__((weak));
 int bf_global_search(bf_ctx *ctx, const bf_global_search_opts *opts, bf_global_result *out, int64_t *surface_out,
                      int64_t surface_cap) __attribute__((weak));
+int bf_hold_groups(bf_ctx *ctx, const bf_model *models, int32_t n_models) __attribute__((weak));
+int bf_group_flow_medians(bf_ctx *ctx, double *u_med, double *v_med, int32_t *counts) __attribute__((weak));
+int bf_global_get_flow(bf_ctx *ctx, double *nx, double *ny, double *u, double *v, double *pr_x, double *pr_y) __attribute__((weak));
+int bf_global_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32_t owner_rule, uint8_t *ppm_out, uint8_t *avi_out,
+                                float *flo_out) __attribute__((weak));
 }
 
 namespace bf {
@@ -38,6 +46,13 @@ class ObjectFinder {
     uint64_t merge_num = 0, merge_den = 1;
     int32_t dissolve_below = 0;
     int merge_max_steps = 64;
+    // false: the groups' median flows come from one upload and write-out per group, and the context is left holding the last
+    // group's events.  true: ONE upload of the slice, then bf_global_set_window, bf_set_groups(gid), bf_hold_groups(models) and
+    // bf_group_flow_medians; the context is left holding the slice, the grouping and the held flow.  When no group is left
+    // (nothing scored, or the merger dissolved every group) there is no model to hold a flow under: find() returns BF_OK with
+    // empty models and flows as without hold_flow, nothing is held, and the readers of the held flow return BF_ERR_STATE
+    // (every path to that end has uploaded events since any earlier hold).
+    bool hold_flow = false;
 
     // what find() leaves: K models, the ids in upload order (-1: unassigned), K + 1 counts (last: unassigned), the proposals
     // the models started from and one record per alternation
@@ -59,11 +74,12 @@ class ObjectFinder {
     }
 
     // The entry the linked C-ABI lacks, or null.
-    static const char *missing_entry(bool merging = false) {
+    static const char *missing_entry(bool merging = false, bool holding = false) {
         if (!bf_propose_models) return "bf_propose_models";
         if (!bf_global_search || !bf_global_set_window) return "bf_global_search";
         if (!MotionAssigner::device_available()) return "bf_assign_groups";
         if (merging && !ObjectMerger::device_available()) return "bf_merge_scores";
+        if (holding && (!bf_hold_groups || !bf_group_flow_medians || !bf_set_groups)) return "bf_hold_groups";
         return nullptr;
     }
 
@@ -74,7 +90,7 @@ class ObjectFinder {
         steps.clear();
         merged_sum_sq = 0;
         origin.clear();
-        if (const char *m = missing_entry(merge_num > 0)) {
+        if (const char *m = missing_entry(merge_num > 0, hold_flow)) {
             error = std::string("bf::ObjectFinder: the linked library has no ") + m;
             return BF_ERR_STATE;
         }
@@ -120,7 +136,7 @@ class ObjectFinder {
             flow_u.assign(models.size(), 0.0);
             flow_v.assign(models.size(), 0.0);
         }
-        rc = group_flows(ctx, s);
+        rc = hold_flow && !models.empty() ? held_flows(ctx, s) : group_flows(ctx, s);   // (no group: group_flows does nothing)
         return rc < 0 ? fail(ctx, rc) : BF_OK;
     }
 
@@ -148,6 +164,17 @@ class ObjectFinder {
             flow_v[k] = median(v);
         }
         return BF_OK;
+    }
+    // The same figure from the held flow: the slice once, every event under its own group's model on the device, the medians
+    // by the device's select (include/bf_accel.h, "the held flow of a grouping").
+    int held_flows(bf_ctx *ctx, const MotionAssigner::Slice &s) {
+        const int32_t K = (int32_t)models.size();
+        int rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
+        if (rc >= 0) rc = bf_global_set_window(ctx, search_scale, search_wsize, nullptr);
+        if (rc >= 0) rc = bf_set_groups(ctx, gid.data(), K);
+        if (rc >= 0) rc = bf_hold_groups(ctx, models.data(), K);
+        if (rc >= 0) rc = bf_group_flow_medians(ctx, flow_u.data(), flow_v.data(), nullptr);
+        return rc;
     }
     static double median(std::vector<double> &a) {
         std::sort(a.begin(), a.end());

@@ -44,6 +44,7 @@ struct Options {
     double objects_range = 600.0, objects_step = 30.0;   // the search lattice in px / s
     bool objects_img = false;                    // --objects-img: objects_N.ppm / .pgm / .score.txt per slice
     int objects_img_gain = 8;
+    bool objects_flow = false;                   // --objects-flow: objects_N.flo / .flow.ppm / .events.txt per slice
     bool objects_merge = false, objects_merge_bad = false;   // --objects-merge[=<num>/<den>]: objects_N.merge.txt per slice
     unsigned long long objects_merge_num = 9, objects_merge_den = 10;
     int objects_min_events = -1;                 // --objects-min-events=<n> (-1: the refit's min_events)
@@ -148,6 +149,11 @@ const std::vector<Flag> &flag_table() {
          "model, coloured by object; objects_N.pgm: 16-bit owner per pixel, id + 1; objects_N.score.txt: per object id events inside "
          "pixels_hit pixels_owned max sum_sq, then the info line with the slice's contrast sum N^2)"},
         {"--objects-img-gain", Arg::Inline, [](Options &o, const char *v) { o.objects_img_gain = atoi(v); }, "<n>", "... 255 / n events on a pixel saturate an object's colour (8)"},
+        {"--objects-flow", Arg::None, [](Options &o, const char *) { o.objects_flow = true; }, "",
+         "with --objects: the per-event flow of every slice under its objects' models (objects_N.flo: the flow field, the oldest event "
+         "owning a pixel; objects_N.flow.ppm: compensated events | colour-coded flow | raw events; objects_N.events.txt: per event "
+         "t_local_ns row col object u v in px/s, -1 and zero flow for an event of no object); a slice in which no object is found "
+         "gets none of the three, as it gets no --objects-img files"},
         {"--objects-merge", Arg::None, [](Options &o, const char *) { o.objects_merge = true; }, "",
          "with --objects: K is then \"at most K\": a group whose events keep 9/10 of their contrast (their share of the slice's sum N^2) "
          "under a larger group's model adopts that model, one pair at a time with a reassignment and refit after each, and groups too "
@@ -286,6 +292,7 @@ int parse(int argc, char **argv, Options &o) {
         return 1;
     }
     if (o.objects_img && !o.objects_flag) { std::fprintf(stderr, "--objects-img renders the objects --objects=<K> finds: give both\n"); return 1; }
+    if (o.objects_flow && !o.objects_flag) { std::fprintf(stderr, "--objects-flow writes the flow of the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_img && o.objects_img_gain < 1) { std::fprintf(stderr, "--objects-img-gain must be at least 1\n"); return 1; }
     // (--img / --video / --flow-img / --flow-field run on both engines; without --engine they keep the reference ring)
     const bool needs_ring = o.frames || o.video || o.flow_img || o.flow_field || o.interactive || o.segments || o.objects_flag;
@@ -360,7 +367,7 @@ int run_ring(const Options &o) {
     }
     if (o.objects_flag) {
         const bool merging = o.objects_merge && o.objects_merge_num > 0;
-        if (const char *missing = bf::ObjectFinder::missing_entry(merging)) {   // (before any slice: no file is written)
+        if (const char *missing = bf::ObjectFinder::missing_entry(merging, o.objects_flow)) {   // (before any slice: no file is written)
             std::fprintf(stderr, "--objects needs %s, which this build of the library does not have\n", missing);
             return 2;
         }
@@ -377,6 +384,13 @@ int run_ring(const Options &o) {
             cfg.dissolve_below = o.objects_min_events >= 0 ? o.objects_min_events : cfg.fit.min_events;
         }
         estimator.set_generate_objects(cfg, o.frame_prefix);
+        if (o.objects_flow) {
+            if (!bf_global_render_flow_frame || !bf_global_get_flow) {
+                std::fprintf(stderr, "--objects-flow needs bf_global_render_flow_frame, which this build of the library does not have\n");
+                return 2;
+            }
+            estimator.set_generate_objects_flow();
+        }
         if (o.objects_img) {
             if (!bf::ObjectRenderer::device_available()) {
                 std::fprintf(stderr, "--objects-img needs bf_project_groups, which this build of the library does not have\n");

@@ -246,6 +246,8 @@ int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
  *                     launch of >= 8 tiles per CU takes; -1 as above.
  *   "propose_form"    the vote kernel the last bf_propose_models launched: 1 a histogram per work-group in LDS, 2 one global
  *                     atomic per vote; 0 when it launched none (no call yet, or no events).
+ *   "groups_held"     the groups K of the grouping held for the uploaded slice (bf_set_groups, bf_set_groups_from_segments,
+ *                     bf_assign_groups with install); -1 when none is held.
  * BF_ERR_ARG for an unknown key. */
 int bf_get_stat(bf_ctx *ctx, const char *key, int64_t *value);
 #define BF_LOOP_ATOMIC 0      /* one global atomic per event and iteration, two plane buffers */
@@ -1129,6 +1131,37 @@ int bf_global_render_flow_frame(bf_ctx *ctx, int32_t res_x, int32_t res_y, int32
                                 float *flo_out);
 int bf_global_emit_slice(bf_ctx *ctx, bf_emit *emit, int64_t n, uint64_t first, uint64_t start_time, int32_t lead, uint64_t lead_t,
                          int32_t lead_row, int32_t lead_col, int64_t *ticket_out);
+
+/* ---- the held flow of a grouping: every event under its own object's model, and the per-group median of a held flow ----
+ * A further definition of this build.  The object pipeline ends with a grouping (an id per event) and
+ * one four-parameter model per group; these two entries turn that into the per-event flow every reader of the held flow
+ * above works on unchanged, and into the one per-object figure the host used to compute with K uploads.
+ *
+ *   bf_hold_groups  a fourth way to fill the context's ONE held flow.  Needs, in this order of checks: an uploaded slice
+ *       (BF_ERR_STATE), bf_global_set_window on it (BF_ERR_STATE: the rule every reader is gated on), models != NULL,
+ *       1 <= n_models <= 64, no noise mask (BF_ERR_ARG each), a held grouping (BF_ERR_STATE) of exactly n_models groups
+ *       (BF_ERR_ARG).  Per event i with id k >= 0, in upload order: from the reset state (pr = fr) ONE
+ *       warp_reinit(-total_dx, -total_dy, cx, cy, total_div, -total_rot) of models[k] -- set_model's warp, its sine and
+ *       cosine from the host's libm, exactly the (nx, ny) bf_assign_groups and bf_project_groups form for pixel_k(i) -- then
+ *       kx = (float)((double)(float)nx / 127), ky likewise, p = (kx * float(t), ky * float(t)) (two f32 products, nz = 127),
+ *       pr = float(fr) - (double)p / 10000.0, and (u, v) = Event::compute_uv of (nx, ny): the bits of bf_compute_uv.  An
+ *       event with id -1 is held with zero flow, p = 0 and pr = fr -- bf_global_hold_best's convention for an event no
+ *       candidate was accepted for; it is still an event for the owner plane.  Zero events: BF_OK and an empty held flow.
+ *       Like the snapshot of bf_global_hold_best the hold keeps its own copy of the slot order, so it survives a later
+ *       bf_run / bf_run_groups re-sort, bf_set_groups, bf_assign_groups with install and bf_global_set_cells; it is dropped
+ *       by bf_global_set_window and invalidated by any upload.  A refused call leaves the previous held flow as it was; a
+ *       failure after the checks leaves none.  Nothing else is written: not the events' products, the rolling (nx, ny), the
+ *       time image, the grouping, the vote planes or the per-event best state.  Blocking.
+ *   bf_group_flow_medians  per group of the held grouping the median of the held u and of the held v over the group's
+ *       events.  Needs a held flow of ANY mode and a held grouping of K groups on the same slice (BF_ERR_STATE otherwise);
+ *       K > 64: BF_ERR_CAPACITY.  u_med and v_med: K doubles; counts: K + 1 words, counts[k] the events with id k, counts[K]
+ *       those with id -1; each may be NULL.  The median orders the values by the total order
+ *       key(x) = bits(x) ^ (sign(x) ? ~0 : 1 << 63) on the 64-bit pattern, so -0.0 sorts below +0.0; an odd count c gives
+ *       element c / 2, an even count 0.5 * (a[c/2 - 1] + a[c/2]) as one f64 add and one f64 multiply, an empty group 0.0.
+ *       The result is a function of the multiset of values alone: whatever order the events are stored in, the bits are
+ *       those of sorting the keys.  On the device an 8-pass radix select; the host waits once.  Blocking. */
+int bf_hold_groups(bf_ctx *ctx, const bf_model *models, int32_t n_models);
+int bf_group_flow_medians(bf_ctx *ctx, double *u_med, double *v_med, int32_t *counts);
 
 /* ---- event groups: candidate models -- the modes of the per-event best flow of the exhaustive search ----
  *
