@@ -223,6 +223,16 @@ class MergeInfo(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class TrackOpts(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("sensor_res_x", C.c_int32), ("sensor_res_y", C.c_int32), ("margin", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+class TrackInfo(C.Structure):
+    _fields_ = [("models", C.c_int32), ("kept_models", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32),
+                ("unassigned", C.c_int32), ("outside", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # BF_PROJECT_PALETTE of include/bf_accel.h: the (B, G, R) of group k is PROJECT_PALETTE[k % 12]
 PROJECT_PALETTE = ((255, 255, 255), (0, 0, 255), (0, 255, 0), (255, 0, 0), (0, 255, 255), (255, 0, 255), (255, 255, 0),
                    (0, 128, 255), (255, 128, 0), (128, 0, 255), (0, 255, 128), (128, 128, 255))
@@ -271,6 +281,7 @@ EXPORTS = [
     "bf_segment_opts_default", "bf_segment", "bf_segment_get", "bf_label_image",
     "bf_set_groups", "bf_set_groups_from_segments", "bf_run_groups", "bf_assign_groups",
     "bf_propose_models", "bf_project_groups", "bf_merge_scores", "bf_hold_groups", "bf_group_flow_medians",
+    "bf_track_keep", "bf_track_overlap", "bf_track_drop",
 ]
 
 BF_FRAME_PPM, BF_FRAME_AVI = 1, 2   # bf_frame_create layouts
@@ -418,6 +429,10 @@ def load(path=None):
                                         C.c_void_p, C.POINTER(ProjectInfo)]
         L.bf_merge_scores.argtypes = [C.c_void_p, C.POINTER(MergeOpts), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.POINTER(MergeInfo)]
+        L.bf_track_keep.argtypes = [C.c_void_p, C.POINTER(TrackOpts), C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(TrackInfo)]
+        L.bf_track_overlap.argtypes = [C.c_void_p, C.POINTER(TrackOpts), C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.POINTER(TrackInfo)]
+        L.bf_track_drop.argtypes = [C.c_void_p]
         L.bf_propose_models.argtypes = [C.c_void_p, C.POINTER(GlobalSearchOpts), C.POINTER(AccelProposeOpts), C.c_void_p, C.c_void_p,
                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ProposeInfo)]
         L.bf_sobel.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
@@ -1025,6 +1040,46 @@ class Accel:
         info = MergeInfo()
         self._chk(self.L.bf_merge_scores(self.h, C.byref(o), ms, K, _ptr(gain), _ptr(inside), _ptr(events), C.byref(info)))
         return gain, inside, events, info
+
+    def track_keep(self, models, scale, sensor_res, margin=0, want_plane=True):
+        """bf_track_keep: the owner plane of the held grouping under `models` (project_groups' "label") is kept on the device
+        across the next uploads, with its window and its number of groups, for track_overlap.  Returns (plane int32 [R, C] or
+        None, TrackInfo)."""
+        K = len(models)
+        o = TrackOpts(scale, sensor_res[0], sensor_res[1], margin)
+        ms = (Model * max(K, 1))(*models)
+        plane = None
+        if want_plane:
+            R, C_ = max(scale * (sensor_res[0] + 2 * margin), 0), max(scale * (sensor_res[1] + 2 * margin), 0)   # the header's window
+            if R * C_ > (1 << 27):   # (the entry refuses it: BF_ERR_ARG or BF_ERR_CAPACITY)
+                R = C_ = 0
+            plane = np.zeros((R, C_), dtype=np.int32)
+        info = TrackInfo()
+        self._chk(self.L.bf_track_keep(self.h, C.byref(o), ms, K, _ptr(plane), C.byref(info)))
+        return plane, info
+
+    def track_overlap(self, models, dt_ns, scale, sensor_res, margin=0):
+        """bf_track_overlap: the events of every group of the held grouping, carried back by dt_ns (this slice's time origin
+        minus the kept slice's) under the group's own model, counted by the owner of the kept plane's pixel they land on.
+        Returns (overlap int32 [K, Kp + 1] (last column: a pixel nobody owns), inside int32 [K], TrackInfo)."""
+        K = len(models)
+        Kp = max(self.tracks_held, 0)
+        o = TrackOpts(scale, sensor_res[0], sensor_res[1], margin)
+        ms = (Model * max(K, 1))(*models)
+        overlap = np.zeros((K, Kp + 1), dtype=np.int32)
+        inside = np.zeros(K, dtype=np.int32)
+        info = TrackInfo()
+        self._chk(self.L.bf_track_overlap(self.h, C.byref(o), ms, K, int(dt_ns), _ptr(overlap), _ptr(inside), C.byref(info)))
+        return overlap, inside, info
+
+    def track_drop(self):
+        """bf_track_drop: releases the kept plane."""
+        self._chk(self.L.bf_track_drop(self.h))
+
+    @property
+    def tracks_held(self):
+        """The groups Kp of the kept plane, -1 without one (bf_get_stat "tracks_held")."""
+        return self.get_stat("tracks_held")
 
     def hold_groups(self, models):
         """bf_hold_groups: every event of the held grouping under its own group's model (`models`, one Model per group) becomes

@@ -10,20 +10,13 @@
 // What they share is here once: the option checks, the window of the widened sensor and its capacity check (vote_planes_check),
 // and the planes, the staged warps and the kernels' AssignArgs (vote_planes_stage).  Between the two each entry zeroes its own
 // outputs and applies its own rule for a slice without events.
+// (bf_track_keep, bf_track_abi.cpp, drives the projection's kernels through the same three helpers: declared in bf_ctx.h.)
 #include "bf_ctx.h"
-
-namespace {
-
-// The K-model vote planes of one call: the kernels' arguments, and the R x C window with its words per plane.
-struct VotePlanes {
-    AssignArgs a;
-    int R, C;
-    size_t plane;
-};
 
 // The checks both entries make after those of their own pointers, in their order; `who`: the entry point's name; `knob`: the
 // entry's own option, which must be >= 1, and its name; `prior`: null when the held grouping is not read, else what the message
 // says before "no grouping ... is held".  Then the window and the capacity check.  Fills everything of vp but a's pointers.
+// vote_planes_window: the window alone, of options that have passed these checks (bf_track_overlap: the kept plane's).
 int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_y, int margin, const char* knob_name, int knob,
                       int n_models, const char* prior, VotePlanes& vp) {
     if (scale < 1 || scale % 2 == 0 || scale / 2 > kMaxHalfScale)
@@ -38,13 +31,18 @@ int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_
         if (!c->groups_valid) return fail(c, BF_ERR_STATE, "%s: %sno grouping of the uploaded slice is held", who, prior);
         if (c->groups_K != K) return fail(c, BF_ERR_ARG, "%s: the held grouping has %d groups, %d models given", who, c->groups_K, K);
     }
+    vote_planes_window(c, scale, res_x, res_y, margin, K, vp);
+    if ((long long)K * (long long)vp.plane > kAssignMaxWords)
+        return fail(c, BF_ERR_CAPACITY, "%s: %d planes of %d x %d exceed 2^27 words", who, K, vp.R, vp.C);
+    return BF_OK;
+}
+
+void vote_planes_window(const bf_ctx* c, int scale, int res_x, int res_y, int margin, int K, VotePlanes& vp) {
     // the window of the whole sensor widened by the margin (optimizer_rolling.h:248-283): the same for every call on a sensor
     const bf_window w = window_of_box(scale, -margin, res_x - 1 + margin, -margin, res_y - 1 + margin);
     vp.R = w.scale_img_x;
     vp.C = w.scale_img_y;
     vp.plane = (size_t)vp.R * (size_t)vp.C;
-    if ((long long)K * (long long)vp.plane > kAssignMaxWords)
-        return fail(c, BF_ERR_CAPACITY, "%s: %d planes of %d x %d exceed 2^27 words", who, K, vp.R, vp.C);
     AssignArgs& a = vp.a;
     a.xy = nullptr; a.t = nullptr; a.perm = nullptr; a.wp = nullptr;
     a.prior = nullptr;
@@ -54,7 +52,6 @@ int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_
     a.y_sh = (int)w.y_shift;
     a.wsx = w.metric_wsizex; a.wsy = w.metric_wsizey;
     a.R = vp.R; a.C = vp.C;
-    return BF_OK;
 }
 
 // (n > 0, the device set) The vote planes grown and V cleared, the box planes grown when they are used, the K warps staged, and
@@ -81,8 +78,6 @@ int vote_planes_stage(bf_ctx* c, const bf_model* models, bool prior, VotePlanes&
 const uint32_t* vote_planes_summed(bf_ctx* c, const VotePlanes& vp) {
     return vp.a.scale > 1 ? c->d_assign_box.get() : c->d_assign_votes.get();
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -1,6 +1,6 @@
 // bf_ctx.h -- private to the C-ABI implementation files (bf_ctx.cpp, bf_context.cpp, bf_upload.cpp, bf_operators.cpp, bf_plan.cpp, bf_run.cpp,
 // bf_tiles_abi.cpp, bf_local_abi.cpp, bf_global_search.cpp, bf_emit_abi.cpp, bf_frame_abi.cpp, bf_flow_abi.cpp, bf_segment_abi.cpp, bf_assign_abi.cpp,
-// bf_propose_abi.cpp): the context structure behind `bf_ctx` and the declarations of the small helpers they share (error text,
+// bf_propose_abi.cpp, bf_track_abi.cpp): the context structure behind `bf_ctx` and the declarations of the small helpers they share (error text,
 // profiling brackets, kernel-argument builders, the buffers allocated on first use; defined in bf_ctx.cpp, but for the few that
 // bf_run.cpp calls once per kernel launch, which are inline here).  What the context knows about its slice -- the flags every
 // entry reads -- is the base struct bf_state::SliceState (bf_ctx_state.h), changed through its named transitions only.  Every HIP resource of a
@@ -149,6 +149,18 @@ struct bf_ctx : bf_state::SliceState {
     DevArray<uint32_t> d_merge_n, d_merge_votes, d_merge_box;
     DevArray<unsigned long long> d_merge_out;
     HostArray<unsigned long long> h_merge_out;
+    // tracks (bf_track_keep / bf_track_overlap, bf_track_abi.cpp): the kept owner plane (R x C labels), a buffer of its own that
+    // no other entry writes, and the overlap's result block.  NOT slice state: an upload leaves it, bf_track_keep replaces it,
+    // bf_track_drop and bf_destroy release it -- so its validity is here and not in SliceState.
+    DevArray<int32_t> d_track_plane;
+    DevArray<uint32_t> d_track_out;
+    HostArray<uint32_t> h_track_out;
+    struct TrackKept {
+        bool valid = false;
+        int Kp = 0;                                          // the groups of the kept grouping
+        int scale = 0, res_x = 0, res_y = 0, margin = 0;     // the window's options ...
+        int R = 0, C = 0;                                    // ... and its planes
+    } track;
     // candidate models (bf_propose_models): the lattice's value tables (n_x doubles, then n_y), the vote plane H and its box
     // sums B (n_x * n_y words each), the result block (counts, proposals); grown on first use
     DevArray<double> d_propose_tab;
@@ -422,6 +434,25 @@ int fold_stats(bf_ctx* c, const SliceStats* overwritten = nullptr);
 // Installs n group ids (n = c->n; `src` on the host or on the device, as `kind` says; not read when the slice is empty) as the
 // held grouping of K groups: the context's own plane, held until the next upload.  A host source is free again on return.
 int install_grouping(bf_ctx* c, const int32_t* src, hipMemcpyKind kind, int K);
+
+// The K-model vote planes of one call (bf_assign_abi.cpp; shared with bf_track_abi.cpp): the kernels' arguments, and the R x C
+// window with its words per plane.
+struct VotePlanes {
+    AssignArgs a;
+    int R, C;
+    size_t plane;
+};
+// The option checks of the entries on the vote planes, in their order, then the window of the widened sensor and the capacity
+// check; fills everything of vp but a's pointers.  `knob`: the entry's own option, which must be >= 1; `prior`: null when the
+// held grouping is not read, else what the message says before "no grouping ... is held".
+int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_y, int margin, const char* knob_name, int knob,
+                      int n_models, const char* prior, VotePlanes& vp);
+// The window part of it alone (options that have passed those checks): everything of vp but a's pointers, a.K = K.
+void vote_planes_window(const bf_ctx* c, int scale, int res_x, int res_y, int margin, int K, VotePlanes& vp);
+// (n > 0, the device set) The vote planes grown and V cleared, the box planes grown when they are used, the K warps staged, a's pointers.
+int vote_planes_stage(bf_ctx* c, const bf_model* models, bool prior, VotePlanes& vp);
+// The planes the second kernel of an entry reads: the box sums, or V itself at scale 1.
+const uint32_t* vote_planes_summed(bf_ctx* c, const VotePlanes& vp);
 
 // ---- what bf_run.cpp calls once per kernel launch: inline, the host's launch time is on a warm-started chain's critical path ----
 

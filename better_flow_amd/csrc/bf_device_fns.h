@@ -95,8 +95,9 @@ __device__ __forceinline__ double pr_from_p(uint32_t fr, float prod) {
 // place this arithmetic lives.  In: the event's previous projected position (pr_x, pr_y) and slice-local time.
 // Out: the direction vector (nx, ny) and the two f32 products q = (kx * float(t), ky * float(t)) from which
 // pr is re-derived with pr_from_p.  No operation may be contracted (-ffp-contract=off).
-__device__ __forceinline__ void warp_products(const WarpParams& wp, double pr_x, double pr_y, int32_t t, float2& q,
-                                              double& nx, double& ny) {
+// warp_products_ft: with the time operand float(t) given by the caller (bf_track_overlap: the f32 nearest to t + dt).
+__device__ __forceinline__ void warp_products_ft(const WarpParams& wp, double pr_x, double pr_y, float ft, float2& q, double& nx,
+                                                 double& ny) {
     // event.h:100-108
     const double rx = pr_x - wp.cx, ry = pr_y - wp.cy;
     const double qx = wp.c * rx - wp.s * ry;
@@ -107,26 +108,34 @@ __device__ __forceinline__ void warp_products(const WarpParams& wp, double pr_x,
     // correctly rounded f32 division (double has >= 2 * 24 + 2 digits).
     const float kx = div_127((float)nx);
     const float ky = div_127((float)ny);
-    const float ft = (float)t;   // round-to-nearest int -> f32, as float(sll t)
     q.x = kx * ft;
     q.y = ky * ft;
 }
+__device__ __forceinline__ void warp_products(const WarpParams& wp, double pr_x, double pr_y, int32_t t, float2& q,
+                                              double& nx, double& ny) {
+    warp_products_ft(wp, pr_x, pr_y, (float)t, q, nx, ny);   // round-to-nearest int -> f32, as float(sll t)
+}
 
 // The event's pixel index in the R x C window under one warp from the reset state, or -1 when it is outside (accel_lib.h:157):
-// pixel_k(i) of bf_assign_groups and bf_project_groups (include/bf_accel.h, "event groups: assignment").
-__device__ __forceinline__ int assign_pixel(const WarpParams& wp, uint32_t v, int32_t t, int scale, int x_sh, int y_sh, int wsx,
-                                            int wsy, int C) {
+// pixel_k(i) of bf_assign_groups and bf_project_groups (include/bf_accel.h, "event groups: assignment").  assign_pixel_ft: with
+// the time operand float(t) given by the caller (bf_track_overlap's pixel_k(i; dt)).
+__device__ __forceinline__ int assign_pixel_ft(const WarpParams& wp, uint32_t v, float ft, int scale, int x_sh, int y_sh, int wsx,
+                                               int wsy, int C) {
     const uint32_t fx = v & 0xffffu, fy = v >> 16;
     float2 q;
     double nx, ny;
     // Event::reset (pr = fr), then set_model's warp_reinit (optimizer_rolling.h:289-299): event.h:99-110,164-168
-    warp_products(wp, (double)fx, (double)fy, t, q, nx, ny);
+    warp_products_ft(wp, (double)fx, (double)fy, ft, q, nx, ny);
     // accel_lib.h:154-158, as the scatter kernel forms it (bf_kernels.hip: event_body; bf_segment.hip: k_seg_events)
     const int X = trunc_scatter(pr_from_p(fx, q.x) * (double)scale + (double)x_sh);
     const int Y = trunc_scatter(pr_from_p(fy, q.y) * (double)scale + (double)y_sh);
     const int hs = scale / 2;
     if ((X >= wsx + hs) || (X < hs) || (Y >= wsy + hs) || (Y < hs)) return -1;
     return X * C + Y;
+}
+__device__ __forceinline__ int assign_pixel(const WarpParams& wp, uint32_t v, int32_t t, int scale, int x_sh, int y_sh, int wsx,
+                                            int wsy, int C) {
+    return assign_pixel_ft(wp, v, (float)t, scale, x_sh, y_sh, wsx, wsy, C);
 }
 
 // A load the compiler must issue on the SCALAR unit: through the constant address space.  For data that no work-group

@@ -16,6 +16,7 @@
 #include <better_flow/event_file.h>
 #include <better_flow/frame_writer.h>
 #include <better_flow/object_finder.h>
+#include <better_flow/object_tracker.h>
 #include <better_flow/object_render.h>
 #include <better_flow/optimizer_rolling.h>
 
@@ -62,6 +63,9 @@ protected:
     std::string objects_prefix;
     ull objects_count = 0;
     bf_ctx *objects_helper = nullptr;          // the refit of a group too large for the grouped solve runs here
+    bool generate_objects_track = false;       // --objects-track: identities carried across slices, objects_N.tracks.txt
+    bf::ObjectTracker tracker;
+    ull objects_origin = 0;                    // the previous slice's time origin
     bool generate_objects_img = false;         // --objects-img: objects_N.ppm / objects_N.pgm / objects_N.score.txt
     bf::ObjectRenderer renderer;
     bool generate_objects_flow = false;        // --objects-flow: objects_N.flo / objects_N.flow.ppm / objects_N.events.txt
@@ -76,7 +80,7 @@ protected:
     ull slice_origin();
     void render_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
     void render_flow_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
-    void write_objects(LinearEventPtrs &slice);
+    void write_objects(LinearEventPtrs &slice, ull origin);
 
 public:
     DVS_flow(ull on_ev_change_, ull on_time_change_, ull start_time = 0)
@@ -129,6 +133,11 @@ public:
     // ... and their per-event flow (objects_N.flo, objects_N.flow.ppm, objects_N.events.txt): every event under its own
     // object's model, held on the device by the finder (bf::ObjectFinder::hold_flow) and read through the held flow's outputs
     void set_generate_objects_flow() { generate_objects_flow = true; finder.hold_flow = true; }
+    // ... and their identities across slices (objects_N.tracks.txt): bf::ObjectTracker with the finder's configuration, a search
+    // every `research_every` slices (0: only when it must).  Call after set_generate_objects.
+    void set_generate_objects_track(int research_every) {
+        generate_objects_track = true; tracker.finder = finder; tracker.research_every = research_every;
+    }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
 
@@ -219,22 +228,31 @@ void DVS_flow<MAX_SZ, SPAN>::render_flow_frame(OptimizerRolling<LinearEventPtrs>
 // total_div), the votes of the proposal it started from --, then a last line "unassigned <events>".  With --objects-merge the groups are
 // those bf::ObjectMerger left, and objects_N.merge.txt lists its steps.  Event::t holds the
 // slice-local time (set_time).  With --objects-img also the slice under its objects' models (better_flow/object_render.h).
-template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(LinearEventPtrs &slice) {
+template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(LinearEventPtrs &slice, ull origin) {
+    bf::ObjectFinder &fd = generate_objects_track ? tracker.finder : finder;   // (tracking: the tracker's finder holds the slice's result)
     std::vector<int32_t> fx, fy, ft;
     fx.reserve(slice.size()); fy.reserve(slice.size()); ft.reserve(slice.size());
     for (auto &e : slice) {
         fx.push_back((int32_t)e.fr_x); fy.push_back((int32_t)e.fr_y); ft.push_back((int32_t)e.t);
     }
-    const int s = finder.fit.scale;
+    const int s = fd.fit.scale;
     bf_ctx *ctx = bf::DeviceContext::get((long long)MAX_SZ, s * RES_X + s, s * RES_Y + s);
     if (!objects_helper && bf_create(bf::DeviceContext::device(), (long long)MAX_SZ, s * RES_X + s, s * RES_Y + s, nullptr, &objects_helper) != BF_OK)
         objects_helper = nullptr;   // (a group too large for the grouped solve then keeps its model)
-    finder.assign.sensor_res_x = finder.fit.sensor_res_x = finder.fit.guard_res_x = RES_X;
-    finder.assign.sensor_res_y = finder.fit.sensor_res_y = finder.fit.guard_res_y = RES_Y;
+    fd.assign.sensor_res_x = fd.fit.sensor_res_x = fd.fit.guard_res_x = RES_X;
+    fd.assign.sensor_res_y = fd.fit.sensor_res_y = fd.fit.guard_res_y = RES_Y;
     bf::MotionAssigner::Slice sl;
     sl.fr_x = fx.data(); sl.fr_y = fy.data(); sl.t_ns = ft.data(); sl.n = fx.size();
-    const int rc = finder.find(ctx, sl, objects_helper);
-    if (rc < 0) throw bf::AccelError(rc, "--objects: " + finder.error);
+    int rc;
+    if (generate_objects_track) {   // dt: the difference of the two slices' time origins, the absolute time set_time subtracts
+        tracker.hold_flow = generate_objects_flow;
+        rc = tracker.next(ctx, sl, objects_count ? (int64_t)origin - (int64_t)objects_origin : 0, objects_helper);
+        objects_origin = origin;
+        if (rc < 0) throw bf::AccelError(rc, "--objects-track: " + tracker.error);
+    } else {
+        rc = fd.find(ctx, sl, objects_helper);
+        if (rc < 0) throw bf::AccelError(rc, "--objects: " + fd.error);
+    }
     const std::string base = objects_prefix + "/objects_" + std::to_string(objects_count++);
     const std::string path = base + ".txt";
     FILE *f = std::fopen(path.c_str(), "w");
@@ -242,21 +260,36 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
         if (!quiet) std::cerr << "cannot write " << path << "\n";
         return;
     }
-    for (size_t k = 0; k < finder.models.size(); ++k) {
-        const bf_model &m = finder.models[k];
-        std::fprintf(f, "%zu %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u %.17g %.17g %.17g %.17g %d\n", k, (int)finder.counts[k],
-                     finder.flow_u[k], finder.flow_v[k], m.cx, m.cy, m.dx, m.dy, m.rot, m.div, (unsigned)m.cnt, m.total_dx, m.total_dy,
-                     m.total_rot, m.total_div, (size_t)finder.origin[k] < finder.proposals.size() ? (int)finder.proposals[(size_t)finder.origin[k]].votes : 0);
+    for (size_t k = 0; k < fd.models.size(); ++k) {
+        const bf_model &m = fd.models[k];
+        std::fprintf(f, "%zu %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u %.17g %.17g %.17g %.17g %d\n", k, (int)fd.counts[k],
+                     fd.flow_u[k], fd.flow_v[k], m.cx, m.cy, m.dx, m.dy, m.rot, m.div, (unsigned)m.cnt, m.total_dx, m.total_dy,
+                     m.total_rot, m.total_div, (size_t)fd.origin[k] < fd.proposals.size() ? (int)fd.proposals[(size_t)fd.origin[k]].votes : 0);
     }
-    std::fprintf(f, "unassigned %d\n", finder.counts.empty() ? 0 : (int)finder.counts.back());
+    std::fprintf(f, "unassigned %d\n", fd.counts.empty() ? 0 : (int)fd.counts.back());
     std::fclose(f);
+    // (--objects-track) objects_N.tracks.txt: the path the slice took, then per group its track, the track's age, its events,
+    // those inside under its model carried back by dt and those of them on its own track's pixels, then the tracks that ended
+    if (generate_objects_track) {
+        FILE *tf = std::fopen((base + ".tracks.txt").c_str(), "w");
+        if (tf) {
+            std::fprintf(tf, "searched %d dt_ns %lld\n", tracker.searched ? 1 : 0, (long long)tracker.dt_ns);
+            for (size_t k = 0; k < tracker.tracks.size(); ++k)
+                std::fprintf(tf, "%zu %d %d %d %d %d\n", k, (int)tracker.tracks[k].id, (int)tracker.tracks[k].age, (int)tracker.tracks[k].events,
+                             tracker.inside.empty() ? 0 : (int)tracker.inside[k], (int)tracker.on_track[k]);
+            std::fprintf(tf, "ended");
+            for (int32_t id : tracker.ended) std::fprintf(tf, " %d", (int)id);
+            std::fprintf(tf, "\n");
+        }
+        if ((!tf || std::fclose(tf) != 0) && !quiet) std::cerr << "cannot write " << base << ".tracks.txt\n";
+    }
     // (--objects-merge) what the merger did to the proposed groups, and the contrast sum N^2 of the grouping it left
-    if (finder.merge_num > 0 && !bf::ObjectMerger::write_steps(base + ".merge.txt", finder.steps, finder.models.size(), finder.merged_sum_sq) && !quiet)
+    if (fd.merge_num > 0 && !bf::ObjectMerger::write_steps(base + ".merge.txt", fd.steps, fd.models.size(), fd.merged_sum_sq) && !quiet)
         std::cerr << "cannot write " << base << ".merge.txt\n";
     // (--objects-flow) the finder left the slice, the grouping and the held flow on the context: the flow field and the flow
     // frame as render_flow_frame writes the rolling optimiser's (oldest event owns a pixel), and one line per event.  A slice
     // without an object has no model to hold a flow under (bf::ObjectFinder::hold_flow): like --objects-img it writes nothing
-    if (generate_objects_flow && !finder.models.empty()) {
+    if (generate_objects_flow && !fd.models.empty()) {
         std::vector<uint8_t> ppm((size_t)RES_X * (size_t)(3 * RES_Y) * 3);
         std::vector<float> flo((size_t)RES_X * (size_t)RES_Y * 2);
         std::vector<double> u(sl.n), v(sl.n);
@@ -267,18 +300,18 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
         FILE *ef = std::fopen((base + ".events.txt").c_str(), "w");
         if (ef) {
             for (size_t i = 0; i < sl.n; ++i)
-                std::fprintf(ef, "%d %d %d %d %.9f %.9f\n", (int)ft[i], (int)fx[i], (int)fy[i], (int)finder.gid[i], u[i], v[i]);
+                std::fprintf(ef, "%d %d %d %d %.9f %.9f\n", (int)ft[i], (int)fx[i], (int)fy[i], (int)fd.gid[i], u[i], v[i]);
             w = (std::fclose(ef) == 0) && w;
         }
         if ((!w || !ef) && !quiet) std::cerr << "cannot write " << base << ".flo / .flow.ppm / .events.txt\n";
     }
-    if (!generate_objects_img || finder.models.empty()) return;   // (no object: nothing to project)
+    if (!generate_objects_img || fd.models.empty()) return;   // (no object: nothing to project)
     // find() leaves the context holding one group's events (its flows re-upload): the renderer uploads the slice again and
     // holds the final ids as its grouping
-    renderer.opts.scale = finder.assign.scale;
+    renderer.opts.scale = fd.assign.scale;
     renderer.opts.sensor_res_x = RES_X; renderer.opts.sensor_res_y = RES_Y;
-    renderer.opts.margin = finder.assign.margin;
-    const int prc = renderer.render(ctx, sl, finder.gid, finder.models);
+    renderer.opts.margin = fd.assign.margin;
+    const int prc = renderer.render(ctx, sl, fd.gid, fd.models);
     if (prc < 0) throw bf::AccelError(prc, std::string("--objects-img: ") + bf_last_error(ctx));
     if ((!renderer.write_ppm(base + ".ppm") || !renderer.write_label_pgm(base + ".pgm") || !renderer.write_scores(base + ".score.txt")) && !quiet)
         std::cerr << "cannot write " << base << ".ppm / .pgm / .score.txt\n";
@@ -322,7 +355,7 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::recompute() {
         info = optimizer.get_run_info();
     }
     // (after every other output, and after the optimizer: it uploads the slice again, and the next slice uploads its own)
-    if (generate_objects) write_objects(slice);
+    if (generate_objects) write_objects(slice, origin);
     ++slices_done;
     if (rc != 0) ++slices_skipped;
     iterations_total += (ull)info.iterations;

@@ -85,6 +85,29 @@ class ObjectFinder {
 
     // helper: a second context with room for the slice, for the refit of a group too large for the grouped solve (may be null)
     int find(bf_ctx *ctx, const MotionAssigner::Slice &s, bf_ctx *helper = nullptr) {
+        if (const int rc = begin()) return rc;
+        int rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
+        if (rc >= 0) rc = bf_global_set_window(ctx, search_scale, search_wsize, nullptr);
+        if (rc >= 0) rc = bf_global_search(ctx, &lattice, nullptr, nullptr, 0);
+        ModelProposer mp;
+        if (rc >= 0) rc = mp.propose(ctx, lattice, propose);
+        if (rc < 0) return fail(ctx, rc);
+        proposals = mp.result.proposals;
+        models = mp.result.models;
+        return refine(ctx, s, helper);
+    }
+
+    // find() without its search: the alternation starts from `candidates` (the previous slice's models: bf::ObjectTracker's
+    // warm path) instead of from proposals; no bf_global_set_window, bf_global_search or bf_propose_models runs.  Everything
+    // after the candidates is find()'s own code; `proposals` stays empty and origin[k] is the candidate group k started from.
+    int find_from(bf_ctx *ctx, const MotionAssigner::Slice &s, const std::vector<bf_model> &candidates, bf_ctx *helper = nullptr) {
+        if (const int rc = begin()) return rc;
+        models = candidates;
+        return refine(ctx, s, helper);
+    }
+
+  private:
+    int begin() {
         models.clear(); gid.clear(); counts.clear(); proposals.clear(); records.clear(); error.clear();
         flow_u.clear(); flow_v.clear();
         steps.clear();
@@ -94,14 +117,11 @@ class ObjectFinder {
             error = std::string("bf::ObjectFinder: the linked library has no ") + m;
             return BF_ERR_STATE;
         }
-        int rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
-        if (rc >= 0) rc = bf_global_set_window(ctx, search_scale, search_wsize, nullptr);
-        if (rc >= 0) rc = bf_global_search(ctx, &lattice, nullptr, nullptr, 0);
-        ModelProposer mp;
-        if (rc >= 0) rc = mp.propose(ctx, lattice, propose);
-        if (rc < 0) return fail(ctx, rc);
-        proposals = mp.result.proposals;
-        models = mp.result.models;
+        return BF_OK;
+    }
+    // From the candidates in `models`: the alternation, the merger when it is on, the groups' flows.
+    int refine(bf_ctx *ctx, const MotionAssigner::Slice &s, bf_ctx *helper) {
+        int rc;
         for (size_t k = 0; k < models.size(); ++k) origin.push_back((int32_t)k);
         gid.assign(s.n, -1);
         counts.assign(models.size() + 1, 0);
@@ -140,7 +160,6 @@ class ObjectFinder {
         return rc < 0 ? fail(ctx, rc) : BF_OK;
     }
 
-  private:
     // Per group its events alone under set_model's warp of its model (optimizer_rolling.h:289-299), Event::compute_uv of
     // what that leaves, and the median per axis (the mean of the two middle values of an even count).
     int group_flows(bf_ctx *ctx, const MotionAssigner::Slice &s) {

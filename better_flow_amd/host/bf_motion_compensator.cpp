@@ -48,6 +48,8 @@ struct Options {
     bool objects_merge = false, objects_merge_bad = false;   // --objects-merge[=<num>/<den>]: objects_N.merge.txt per slice
     unsigned long long objects_merge_num = 9, objects_merge_den = 10;
     int objects_min_events = -1;                 // --objects-min-events=<n> (-1: the refit's min_events)
+    bool objects_track = false;                  // --objects-track[=<N>]: objects_N.tracks.txt per slice, a search every N slices
+    int objects_track_every = 0;                 // (0: only when the tracker must)
     int objects_radius = 1, objects_suppress = 2, objects_min_votes = 1, objects_scale = 3;
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
@@ -161,6 +163,13 @@ const std::vector<Flag> &flag_table() {
          "info K sum_sq); the default 9/10 rests on one synthetic scene"},
         {"--objects-merge", Arg::Inline, [](Options &o, const char *v) { o.objects_merge = true; o.objects_merge_bad = !parse_fraction(v, o.objects_merge_num, o.objects_merge_den); },
          "<num>/<den>", "... at this threshold instead (0/1: no merging)"},
+        {"--objects-track", Arg::None, [](Options &o, const char *) { o.objects_track = true; }, "",
+         "with --objects: carry the objects' identities from slice to slice and start every slice from the previous slice's models, "
+         "searching only when no track is left or half a slice stays unassigned (objects_N.tracks.txt: \"searched 0|1 dt_ns <dt>\", per "
+         "group its track id, the track's age, events, events inside and events on its own track's pixels of the previous slice, then "
+         "\"ended <track ids>\")"},
+        {"--objects-track", Arg::Inline, [](Options &o, const char *v) { o.objects_track = true; o.objects_track_every = atoi(v); }, "<N>",
+         "... and search again every N slices"},
         {"--objects-min-events", Arg::Inline, [](Options &o, const char *v) { o.objects_min_events = atoi(v); }, "<n>",
          "with --objects-merge: dissolve groups with fewer events (default: the refit's own min_events guard: a group it skips has no model of its own)"},
         {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
@@ -291,6 +300,10 @@ int parse(int argc, char **argv, Options &o) {
         std::fprintf(stderr, "--objects-min-events=<n> (>= 0) sets what --objects-merge dissolves: give both\n");
         return 1;
     }
+    if (o.objects_track && (!o.objects_flag || o.objects_track_every < 0)) {
+        std::fprintf(stderr, "--objects-track[=<N>] (N >= 0) tracks the objects --objects=<K> finds: give both\n");
+        return 1;
+    }
     if (o.objects_img && !o.objects_flag) { std::fprintf(stderr, "--objects-img renders the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_flow && !o.objects_flag) { std::fprintf(stderr, "--objects-flow writes the flow of the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_img && o.objects_img_gain < 1) { std::fprintf(stderr, "--objects-img-gain must be at least 1\n"); return 1; }
@@ -397,6 +410,13 @@ int run_ring(const Options &o) {
                 return 2;
             }
             estimator.set_generate_objects_img(o.objects_img_gain);
+        }
+        if (o.objects_track) {   // (last: the tracker takes the finder's configuration as it stands)
+            if (const char *missing = bf::ObjectTracker::missing_entry(merging, o.objects_flow)) {
+                std::fprintf(stderr, "--objects-track needs %s, which this build of the library does not have\n", missing);
+                return 2;
+            }
+            estimator.set_generate_objects_track(o.objects_track_every);
         }
     }
     if (o.stm_disable) estimator.set_stm_disable(true);

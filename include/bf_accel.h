@@ -248,6 +248,7 @@ int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
  *                     atomic per vote; 0 when it launched none (no call yet, or no events).
  *   "groups_held"     the groups K of the grouping held for the uploaded slice (bf_set_groups, bf_set_groups_from_segments,
  *                     bf_assign_groups with install); -1 when none is held.
+ *   "tracks_held"     the groups Kp of the owner plane bf_track_keep kept; -1 when none is kept.  An upload does not change it.
  * BF_ERR_ARG for an unknown key. */
 int bf_get_stat(bf_ctx *ctx, const char *key, int64_t *value);
 #define BF_LOOP_ATOMIC 0      /* one global atomic per event and iteration, two plane buffers */
@@ -596,6 +597,63 @@ typedef struct bf_merge_info {         /* 48 bytes */
 int bf_merge_scores(bf_ctx *ctx, const bf_merge_opts *opts, const bf_model *models, int32_t n_models,
                     uint64_t *gain_out /* K x K, [b * K + a] */, int32_t *inside_out /* K x K */,
                     int32_t *events_out /* K */, bf_merge_info *info);
+
+/* ---- event groups: tracks -- which object of the previous slice is which object of this one ----
+ *
+ * The object pipeline numbers the groups of every slice anew.  To carry an identity from slice to slice, the owner plane of one
+ * slice's final grouping is KEPT on the device across the next upload, and the next slice's groups are counted against it: per
+ * group, on whose pixels its events land once they are carried back by the time between the two slices.
+ * Everything after an event's pixel is an integer count: the bytes do not depend on the order events are stored or work-groups
+ * run in.
+ *
+ * bf_track_keep
+ *   plane     R x C words: exactly bf_project_groups' label_out for the held grouping under `models` -- its window (the whole
+ *             sensor widened by `margin`), pixel_k(i), box sums B_k, label = the smallest k with the largest B_k[p], -1 where
+ *             N[p] == 0 -- and equal to it byte for byte on the same context.  plane_out may be NULL.
+ *   kept      the plane, Kp = K = n_models, and the window's options (scale, sensor sides, margin), in a buffer of the plane's
+ *             own.  It is NOT slice state: it survives bf_upload_events (that is its purpose), bf_set_cloud,
+ *             bf_global_set_window, every run, bf_segment, bf_set_groups and bf_assign_groups.  The next bf_track_keep replaces
+ *             it; bf_track_drop and bf_destroy release it.  bf_get_stat "tracks_held" gives Kp, -1 without a plane.
+ *   info      models = kept_models = K, rows = R, cols = C, unassigned (ids of -1), outside (events outside under their own
+ *             model).
+ *   state     writes nothing else: bf_project_groups' untouched list (the vote planes are shared and cleared, as there).
+ *   errors    exactly bf_project_groups', without gain.  A refused call leaves the previous plane as it was.  Zero events:
+ *             BF_OK, a kept plane of all -1 over the R x C window, info zero.
+ * bf_track_overlap
+ *   needs     a held grouping of K == n_models groups on the slice uploaded now, and a kept plane of the same window options.
+ *   dt_ns     the time origin of the slice uploaded now minus the kept slice's, in ns (the absolute times both slices' local
+ *             times were taken from); it may be negative; |dt_ns| <= 2^40.
+ *   pixel_k(i; dt)  exactly bf_assign_groups' pixel_k(i) -- ONE set_model warp of models[k] from the reset state, sine and cosine
+ *             from the host's libm, the scatter kernel's truncation, the window test -- with one change: the event's time
+ *             operand float(t_i) is the f32 nearest (ties to even) to the 64-bit integer t_i + dt_ns.  The event is carried
+ *             back, under its own model, to where it was in the kept slice's frame.  dt_ns = 0 gives bf_project_groups' pixel.
+ *   overlap   overlap_out[k * (Kp + 1) + j] = the events with id k that are inside and land on a pixel whose kept label is j;
+ *             j == Kp: on a pixel whose kept label is -1.  inside_out[k] = the row's sum.
+ *   info      models = K, kept_models = Kp, rows, cols, outside = the events of any group that are outside under their own model
+ *             and dt, unassigned = the events with id -1.
+ *   state     reads the events' addresses and times, the permutation, the held grouping and the kept plane; writes nothing of
+ *             the context's state and does not use the vote planes.
+ *   errors    BF_ERR_STATE before an upload, with no held grouping, or with no kept plane; BF_ERR_ARG for n_models < 1 or > 64
+ *             or different from the held K, NULL opts or models, a noise mask, options that differ from the kept plane's,
+ *             |dt_ns| > 2^40.  Zero events: BF_OK, every output zero (info too).
+ * All 32-bit counts.  Any output may be NULL.  Blocking.  Which group continues which track is the caller's policy
+ * (bf::ObjectTracker::match, object_tracker.h). */
+typedef struct bf_track_opts {         /* 32 bytes */
+    int32_t scale;                     /* odd, scale/2 <= 4 */
+    int32_t sensor_res_x, sensor_res_y;
+    int32_t margin;                    /* >= 0 sensor pixels added on every side of the sensor box */
+    int32_t reserved[4];
+} bf_track_opts;
+typedef struct bf_track_info {         /* 32 bytes */
+    int32_t models, kept_models, rows, cols, unassigned, outside;
+    int32_t reserved[2];
+} bf_track_info;
+int bf_track_keep(bf_ctx *ctx, const bf_track_opts *opts, const bf_model *models, int32_t n_models,
+                  int32_t *plane_out /* R x C */, bf_track_info *info);
+int bf_track_overlap(bf_ctx *ctx, const bf_track_opts *opts, const bf_model *models, int32_t n_models, int64_t dt_ns,
+                     int32_t *overlap_out /* K x (Kp + 1), [k * (Kp + 1) + j] */, int32_t *inside_out /* K */,
+                     bf_track_info *info);
+int bf_track_drop(bf_ctx *ctx);
 
 /* A batch of independent slices -- the reference's queue of (events, model) tasks (dvs_flow.h:200-231, executed there
  * one after the other) -- solved together: bf_run on each of the n contexts, all in flight at once (one host thread per
