@@ -60,6 +60,7 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
         else HIP_TRY(c, c->stream.create(hipStreamNonBlocking));
         c->cap_events = pad_events(max_events);
         c->cap_px = (size_t)max_rows * (size_t)max_cols;
+        c->max_rows = max_rows; c->max_cols = max_cols;
         int gx, gy;
         stencil_grid(max_rows, max_cols, &gx, &gy);
         // a window with the same pixel count but another aspect ratio can need more tiles
@@ -163,6 +164,10 @@ int bf_create(int32_t device, int64_t max_events, int32_t max_rows, int32_t max_
 // copy stream), drop the pending uploads (those only RECORDED go unrun), dump the debug timeline; the handles then free everything.
 void bf_destroy(bf_ctx* c) {
     if (!c) return;
+    if (c->wide_inner) {   // (first: it borrows this context's stream)
+        bf_destroy(c->wide_inner);
+        c->wide_inner = nullptr;
+    }
     if (c->counted) g_live_ctx[c->device & 63].fetch_sub(1);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -179,6 +184,24 @@ void bf_destroy(bf_ctx* c) {
     }
     delete c;
 }
+
+}  // extern "C"
+
+int ensure_wide_inner(bf_ctx* owner) {
+    if (owner->wide_inner) return BF_OK;
+    bf_ctx* in = nullptr;
+    const int rc = bf_create(owner->device, owner->cap_events, owner->max_rows, owner->max_cols, (void*)(hipStream_t)owner->stream, &in);
+    if (rc != BF_OK) return fail(owner, rc, "cannot create the inner context of the wide groups (%lld events, %d x %d)",
+                                 owner->cap_events, owner->max_rows, owner->max_cols);
+    // not a context of its own: it runs only inside its owner's bf_run_groups, never beside it (bf_rules::persistent_ok)
+    g_live_ctx[in->device & 63].fetch_sub(1);
+    in->counted = false;
+    in->opt_persist = 0;   // (a nested run has no use for the resident loop; every form gives the same bits)
+    owner->wide_inner = in;
+    return BF_OK;
+}
+
+extern "C" {
 
 const char* bf_last_error(const bf_ctx* c) {
     if (!c) return "null ctx";
@@ -221,6 +244,8 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         {"bin_margin", c->use_binned ? c->grid.D : 0}, {"bins", c->use_binned ? c->grid.nbins : 0},
         // ... and what the last bf_run_groups launched: the optimizers' dynamic LDS (bytes) and their work-groups per CU
         {"groups_lds", c->groups_lds}, {"groups_per_cu", c->groups_per_cu},
+        // ... and how many of its groups it solved on the chip-wide loop ("groups_wide" = 1; 0 before any call)
+        {"groups_wide", c->groups_wide},
         // ... and the groups of the grouping held for the uploaded slice (-1: none is held)
         {"groups_held", c->groups_valid ? c->groups_K : -1},
         // ... and the groups of the owner plane kept by bf_track_keep (-1: none is kept); not slice state
@@ -313,6 +338,11 @@ int bf_set_option(bf_ctx* c, const char* key, int64_t value) {
     if (!strcmp(key, "persist")) {
         if (value < 0 || value > 2) return fail(c, BF_ERR_ARG, "persist must be 0, 1 (auto) or 2");
         c->opt_persist = (int)value;
+        return BF_OK;
+    }
+    if (!strcmp(key, "groups_wide")) {   // read by the next bf_run_groups, not by bf_set_cloud
+        if (value < 0 || value > 1) return fail(c, BF_ERR_ARG, "groups_wide must be 0 or 1");
+        c->opt_groups_wide = value != 0;
         return BF_OK;
     }
     return fail(c, BF_ERR_ARG, "unknown option '%s'", key);

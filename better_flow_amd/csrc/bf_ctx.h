@@ -31,6 +31,7 @@
 #include "bf_assign.h"
 #include "bf_ctx_state.h"
 #include "bf_device.h"
+#include "bf_group_rules.h"
 #include "bf_kernels.h"
 #include "bf_mem.h"
 #include "bf_segment.h"
@@ -129,6 +130,13 @@ struct bf_ctx : bf_state::SliceState {
     DevArray<int32_t> d_group_id, d_group_box;
     DevArray<uint32_t> d_group_order, d_group_counter;
     int groups_lds = 0, groups_per_cu = 0;   // what the last bf_run_groups launched: dynamic LDS bytes, work-groups per CU (bf_get_stat)
+    // wide groups ("groups_wide", bf_group_rules.h): a group whose window does not fit the LDS runs the chip-wide loop on an inner
+    // context of this one's capacity on this one's stream, created at the first such group and released by bf_destroy.  It is not
+    // counted in g_live_ctx (it never runs beside its owner) and its "persist" is 0.
+    int max_rows = 0, max_cols = 0;          // bf_create's image capacity, per axis
+    bool opt_groups_wide = false;            // read by bf_run_groups
+    int groups_wide = 0;                     // groups the last bf_run_groups solved wide (bf_get_stat)
+    bf_ctx* wide_inner = nullptr;            // owned
     // assignment (bf_assign_groups): the K vote planes and their box sums (K x R x C words each), the K warps, the ids and scores
     // in upload order, the result block (counts, changed, max_score); grown on first use
     DevArray<uint32_t> d_assign_votes, d_assign_box, d_assign_out;
@@ -383,6 +391,10 @@ RunPlan plan_run(bf_ctx* c, const bf_run_opts& o);   // (takes one run of that b
 int streaming_setup(bf_ctx* c);
 int issue_deferred_uploads(bf_ctx* c);
 void drop_uploads(bf_ctx* c, int k);
+
+// The inner context of `owner`'s wide groups (bf_context.cpp): created on first use with the owner's device, event and image
+// capacity on the owner's stream, uncounted, "persist" 0.  A failure leaves the message in the owner.
+int ensure_wide_inner(bf_ctx* owner);
 
 // ---- shared helpers (bf_ctx.cpp) ----
 

@@ -196,6 +196,21 @@ void launch_group_boxes(const uint32_t* xy, const uint32_t* perm, const int32_t*
 int launch_group_optimizer(const TileArgs& a, const uint32_t* order, int K, bool warm, uint32_t* counter, int n_cus,
                            hipStream_t s, int* per_cu_out);
 void launch_group_rest(const uint32_t* perm, const uint32_t* start, int K, double2* nxny, hipStream_t s);
+// bf_groups_wide.hip -- a group solved by the chip-wide loop ("groups_wide"): slots beg .. beg + n of the sorted set into the three
+// int32 staging columns of the inner context (upload index j = slot beg + j), and the inner run's per-event results back.
+struct WideBack {
+    const uint32_t* in_perm;     // inner slot -> inner upload index (null: the identity)
+    const float2* in_p;          // inner products, inner slot order
+    const double2* in_nxny;      // inner (nx, ny): by inner slot (in_nxny_by_slot) or by inner upload index; null: zeros
+    int32_t in_nxny_by_slot;
+    uint32_t beg, n;             // the group's bucket of the outer set
+    const uint32_t* out_perm;    // outer slot -> outer upload index
+    float2* out_p;               // outer products, outer slot order
+    double2* out_nxny;           // outer (nx, ny), outer upload order
+};
+void launch_group_gather(const uint32_t* xy, const int32_t* t, uint32_t beg, uint32_t n, int32_t* ox, int32_t* oy, int32_t* ot,
+                         hipStream_t s);
+void launch_group_scatter_back(const WideBack& a, hipStream_t s);
 
 // bf_rebin.hip / bf_scatter.hip / bf_stencil.hip / bf_fused.hip (the tile-binned loops)
 int bin_kernel_setup();

@@ -110,6 +110,60 @@ void tiles_collect(bf_ctx* c, const std::vector<DevState>& st, int nt, bf_model*
     c->tile_run_collected();   // per-event read-back (bf_compute_uv / bf_writeout_events) is valid now
 }
 
+// One wide group of bf_run_groups ("groups_wide", include/bf_accel.h): slots beg .. beg + n of the sorted set `dst` through the
+// chip-wide loop on the inner context -- gather, bf_upload_events_device, bf_set_cloud, bf_set_model when warm, bf_run with the
+// group options' mapping (object_tasks.h: ObjectTasks::run), and the per-event results back into the outer context.  Everything
+// is enqueued on the one stream both contexts use.  BF_ERR_NOCONV of a run that ended is the group's own outcome (out.info.rc);
+// any other inner error fails the call with the inner message.
+struct WideResult {
+    bf_model model;
+    bf_run_info info;
+};
+int run_wide_group(bf_ctx* c, const bf_ctx::EvSet& dst, const bf_group_opts& o, int g, uint32_t beg, uint32_t n, const bf_model* warm,
+                   WideResult& out) {
+    int rc = ensure_wide_inner(c);
+    if (rc != BF_OK) return rc;
+    bf_ctx* in = c->wide_inner;
+    auto inner_failed = [&](int code, const char* step) {
+        char msg[sizeof(in->err)];
+        snprintf(msg, sizeof(msg), "%s", bf_last_error(in));
+        return fail(c, code, "bf_run_groups: wide group %d, %s: %s", g, step, msg);
+    };
+    bf_ctx::UploadSlot& stage = in->up.slot[0];   // (the blocking uploads' columns: the inner context takes no asynchronous upload)
+    launch_group_gather(dst.xy, dst.t, beg, n, stage.x, stage.y, stage.t, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    if ((rc = bf_upload_events_device(in, stage.x, stage.y, stage.t, (int64_t)n)) != BF_OK) return inner_failed(rc, "upload");
+    if ((rc = bf_set_cloud(in, o.scale, o.sensor_res_x, o.sensor_res_y, nullptr)) != BF_OK) return inner_failed(rc, "bf_set_cloud");
+    if (warm && (rc = bf_set_model(in, warm)) != BF_OK) return inner_failed(rc, "bf_set_model");
+    bf_run_opts ro;
+    bf_run_opts_default(&ro);
+    ro.max_iter = o.max_iter;
+    ro.min_events = o.min_events;
+    ro.res_x = o.guard_res_x; ro.res_y = o.guard_res_y;
+    ro.hard_iter_cap = o.hard_iter_cap;
+    memset(&out, 0, sizeof(out));
+    out.info.iterations = -1;   // (a run that ends says how many it took)
+    rc = bf_run(in, &ro, &out.model, &out.info);
+    const bool ended = out.info.iterations >= 0;
+    if (!(rc == BF_OK || rc == BF_SKIPPED || (rc == BF_ERR_NOCONV && ended))) return inner_failed(rc, "bf_run");
+    // what bf_writeout_events would read on the inner context: a warp still pending applied, then the products in the inner
+    // order and (nx, ny) wherever the run left them
+    if ((rc = flush_pending(in)) != BF_OK) return inner_failed(rc, "the pending warp");
+    const bf_ctx::EvSet& is = in->set[in->cs];
+    WideBack b;
+    b.in_perm = in->has_perm ? is.perm.get() : nullptr;
+    b.in_p = is.p;
+    b.in_nxny = in->n_valid ? in->d_nxny.get() : nullptr;
+    b.in_nxny_by_slot = (in->out_sorted && in->has_perm) ? 1 : 0;
+    b.beg = beg; b.n = n;
+    b.out_perm = dst.perm;
+    b.out_p = dst.p;
+    b.out_nxny = c->d_nxny;
+    launch_group_scatter_back(b, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return BF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -299,6 +353,8 @@ int bf_run_groups(bf_ctx* c, const bf_group_opts* o, const bf_model* warm, int32
     const int sc = o->scale;
     long long max_px = 1;
     std::vector<bf_group_info> gi((size_t)K);
+    std::vector<int> wide;   // the groups the chip-wide loop solves (bf_rules::group_route)
+    c->groups_wide = 0;
     for (int g = 0; g < K; ++g) {
         const int n = (int)(start[(size_t)g + 1] - start[(size_t)g]);
         int x_min = o->sensor_res_x, y_min = o->sensor_res_y, x_max = 0, y_max = 0;   // optimizer_rolling.h:252-253
@@ -312,9 +368,20 @@ int bf_run_groups(bf_ctx* c, const bf_group_opts* o, const bf_model* warm, int32
         q.events = n;
         q.row_min = x_min; q.row_max = x_max; q.col_min = y_min; q.col_max = y_max;
         q.rows = R; q.cols = C;
-        // the guards of run() as the kernel evaluates them (tile_optimizer_body): a group they skip needs no planes
-        const bool skipped = ((R < sc * o->guard_res_x / 15) && (C < sc * o->guard_res_y / 15)) || n < o->min_events;
-        if (!skipped && R > 0 && C > 0 && (long long)R * C * 16 <= (long long)kGroupLdsBudget) max_px = std::max(max_px, (long long)R * C);
+        // where the group is solved: a group the guards skip needs no planes, the launch's LDS is the largest window that runs
+        // in it, a wide group is marked for the caller
+        bf_rules::GroupFacts f;
+        f.rows = R; f.cols = C; f.events = n; f.scale = sc;
+        f.guard_res_x = o->guard_res_x; f.guard_res_y = o->guard_res_y; f.min_events = o->min_events;
+        f.lds_budget = kGroupLdsBudget;
+        f.max_rows = c->max_rows; f.max_cols = c->max_cols;
+        f.wide = c->opt_groups_wide;
+        const bf_rules::GroupRoute route = bf_rules::group_route(f);
+        if (route.path == bf_rules::GroupPath::lds) max_px = std::max(max_px, route.lds_bytes / 16);
+        if (route.path == bf_rules::GroupPath::wide) {
+            wide.push_back(g);
+            q.reserved = 1;
+        }
     }
     if (groups_out) for (int g = 0; g < K; ++g) groups_out[g] = gi[(size_t)g];
 
@@ -350,12 +417,25 @@ int bf_run_groups(bf_ctx* c, const bf_group_opts* o, const bf_model* warm, int32
         c->groups_lds = (int)(max_px * 16);
         c->groups_per_cu = per_cu;
     }
+    // the wide groups, one after the other behind the LDS groups' launch (which left them what set_model left), longest first
+    std::stable_sort(wide.begin(), wide.end(), [&](int a, int b) { return gi[(size_t)a].events > gi[(size_t)b].events; });
+    std::vector<WideResult> wres(wide.size());
+    for (size_t k = 0; k < wide.size(); ++k) {
+        const int g = wide[k];
+        const bf_model* wm = warm_count == 0 ? nullptr : &warm[warm_count == K ? g : 0];
+        if ((rc = run_wide_group(c, dst, *o, g, start[(size_t)g], (uint32_t)gi[(size_t)g].events, wm, wres[k])) != BF_OK) return rc;
+    }
+    c->groups_wide = (int)wide.size();
     launch_group_rest(dst.perm, c->d_tile_start, K, c->d_nxny, s);
     HIP_TRY(c, hipGetLastError());
     std::vector<DevState> st((size_t)K);
     if (K > 0) HIP_TRY(c, hipMemcpyAsync(st.data(), c->d_tile_states, (size_t)K * sizeof(DevState), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
     tiles_collect(c, st, K, models_out, infos_out);
+    for (size_t k = 0; k < wide.size(); ++k) {   // the inner run's outcome in place of the kernel's BF_ERR_CAPACITY
+        if (models_out) models_out[wide[k]] = wres[k].model;
+        if (infos_out) infos_out[wide[k]] = wres[k].info;
+    }
     return BF_OK;
 }
 

@@ -137,6 +137,7 @@ public:
     // every `research_every` slices (0: only when it must).  Call after set_generate_objects.
     void set_generate_objects_track(int research_every) {
         generate_objects_track = true; tracker.finder = finder; tracker.research_every = research_every;
+        tracker.wide_groups = finder.wide_groups;
     }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
@@ -237,7 +238,8 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(Li
     }
     const int s = fd.fit.scale;
     bf_ctx *ctx = bf::DeviceContext::get((long long)MAX_SZ, s * RES_X + s, s * RES_Y + s);
-    if (!objects_helper && bf_create(bf::DeviceContext::device(), (long long)MAX_SZ, s * RES_X + s, s * RES_Y + s, nullptr, &objects_helper) != BF_OK)
+    // (--objects-wide, bf::ObjectFinder::wide_groups: every group is refit inside the grouped solve -- no second context)
+    if (!finder.wide_groups && !objects_helper && bf_create(bf::DeviceContext::device(), (long long)MAX_SZ, s * RES_X + s, s * RES_Y + s, nullptr, &objects_helper) != BF_OK)
         objects_helper = nullptr;   // (a group too large for the grouped solve then keeps its model)
     fd.assign.sensor_res_x = fd.fit.sensor_res_x = fd.fit.guard_res_x = RES_X;
     fd.assign.sensor_res_y = fd.fit.sensor_res_y = fd.fit.guard_res_y = RES_Y;

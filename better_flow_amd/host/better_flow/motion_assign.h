@@ -42,6 +42,9 @@ class MotionAssigner {
     };
 
     bf_group_opts fit;                    // the refit's scale, seeds, guards and caps (bf::ObjectTasks)
+    // the refit solves a group whose window exceeds the LDS in its own bf_run_groups (ObjectTasks::wide): no group then comes back
+    // BF_ERR_CAPACITY unless it exceeds the context's image capacity, and alternate() does not touch `helper`
+    bool wide_groups = false;
     // what assign() leaves (upload order) ...
     std::vector<int32_t> gid, score, counts;
     bf_assign_info info;
@@ -135,6 +138,7 @@ class MotionAssigner {
                 if (gid[i] >= 0) ids[(size_t)gid[i]].push_back((int32_t)i);
             ObjectTasks q;
             q.opts = fit;
+            q.wide = wide_groups;
             for (size_t k = 0; k < K; ++k) q.push(ids[k], &models[k]);
             rc = q.run(ctx, s.fr_x, s.fr_y, s.t_ns, s.n, force_host);
             if (rc < 0) return rc;

@@ -41,6 +41,9 @@ class ObjectFinder {
     bf_assign_opts assign;
     bf_group_opts fit;
     int rounds_per_fit = 2, max_alternations = 5;
+    // the refits solve a group whose window exceeds the LDS inside their own bf_run_groups (bf::MotionAssigner::wide_groups,
+    // handed to the merger's alternations too): `helper` is then not touched
+    bool wide_groups = false;
     // merging (bf::ObjectMerger::reduce after the alternation): a group adopts another's model when it keeps merge_num /
     // merge_den of its contrast; merge_num == 0: off, nothing changes.  A group below dissolve_below events is dissolved.
     uint64_t merge_num = 0, merge_den = 1;
@@ -131,6 +134,7 @@ class ObjectFinder {
         if (models.empty()) return BF_OK;   // nothing scored: no object
         MotionAssigner ma;
         ma.fit = fit;
+        ma.wide_groups = wide_groups;
         rc = ma.alternate(ctx, s, models, assign, rounds_per_fit, max_alternations, helper);
         if (rc < 0) return fail(ctx, rc);
         models = ma.models;
@@ -145,6 +149,7 @@ class ObjectFinder {
             om.assign = assign;
             om.fit = fit;
             om.rounds_per_fit = rounds_per_fit;
+            om.wide_groups = wide_groups;
             rc = om.reduce(ctx, s, models, gid, merge_num, merge_den, dissolve_below, merge_max_steps, helper);
             if (rc < 0) return fail(ctx, rc);
             models = om.models;

@@ -43,6 +43,7 @@ class ObjectMerger {
     bf_assign_opts assign;                // the alternation's assignment ...
     bf_group_opts fit;                    // ... and refit (bf::MotionAssigner)
     int rounds_per_fit = 2;
+    bool wide_groups = false;             // handed to the alternation's refit (bf::MotionAssigner::wide_groups)
     // what scores() / scores_host() leave: K x K gains and inside counts, [b * K + a]; K event counts; the info
     std::vector<uint64_t> gain;
     std::vector<int32_t> inside, events;
@@ -285,6 +286,7 @@ class ObjectMerger {
     int one_alternation(bf_ctx *ctx, const MotionAssigner::Slice &s, bf_ctx *helper, bool force_host) {
         MotionAssigner ma;
         ma.fit = fit;
+        ma.wide_groups = wide_groups;
         const int rc = ma.alternate(ctx, s, models, assign, rounds_per_fit, 1, helper, force_host, &gid);
         if (rc < 0) return rc;
         models = ma.models;

@@ -9,7 +9,9 @@
 // An event belongs to at most one task (a second push of the same index is BF_ERR_ARG on either path).  A task without a
 // model starts cold; when only some tasks carry one, the others start from the zero model, whose set_model warp is the
 // identity.  The device path reports BF_ERR_CAPACITY in the info of a task whose window exceeds the LDS; the host path has no
-// such limit.  No membership policy lives here: which events form an object is the caller's decision.
+// such limit.  With `wide` the device path sets bf_set_option "groups_wide" around its bf_run_groups: such a task is then solved
+// in the same call by the chip-wide loop, unless its window exceeds the context's image capacity (include/bf_accel.h, "wide
+// groups").  No membership policy lives here: which events form an object is the caller's decision.
 #ifndef BF_HOST_OBJECT_TASKS_H
 #define BF_HOST_OBJECT_TASKS_H
 
@@ -36,6 +38,7 @@ class ObjectTasks {
     std::vector<bf_model> models;
     std::vector<bf_run_info> infos;
     std::vector<double> nx, ny;
+    bool wide = false;                    // device path: "groups_wide" = 1 for its bf_run_groups (the host path has no LDS limit)
 
     ObjectTasks() {   // the reference's constants (common.h:39-40, optimizer_rolling.h:57)
         opts.scale = 3;
@@ -82,9 +85,12 @@ class ObjectTasks {
         if (device_available() && !force_host) {
             int rc = bf_upload_events(ctx, fr_x, fr_y, t_ns, nullptr, (int64_t)n);
             if (rc >= 0) rc = bf_set_groups(ctx, gid.data(), (int32_t)K);
-            if (rc >= 0)
+            if (rc >= 0 && wide) rc = bf_set_option(ctx, "groups_wide", 1);
+            if (rc >= 0) {
                 rc = bf_run_groups(ctx, &opts, any_warm ? warm_.data() : nullptr, any_warm ? (int32_t)K : 0, models.data(),
                                    infos.data(), nullptr);
+                if (wide) (void)bf_set_option(ctx, "groups_wide", 0);   // (off again: the option is this queue's, not the context's other callers')
+            }
             if (rc >= 0 && n > 0) rc = bf_writeout_events(ctx, nullptr, nullptr, nx.data(), ny.data());
             return rc < 0 ? rc : BF_OK;
         }

@@ -43,6 +43,7 @@ class ObjectTracker {
     // wrong one at most 0.034; no other scene has been looked at.
     uint64_t match_num = 1, match_den = 2;
     bool hold_flow = false;
+    bool wide_groups = false;   // the finder's wide_groups, set by every next(): set this one
 
     struct Track {
         int32_t id;
@@ -113,6 +114,7 @@ class ObjectTracker {
         }
         searched = tracks.empty() || (research_every > 0 && since_search >= research_every) ||
                    last_unassigned * research_unassigned_den > last_events * research_unassigned_num;
+        finder.wide_groups = wide_groups;
         finder.hold_flow = false;   // (the flow is held below, after the keep: the overlap and the keep need the slice uploaded again)
         int rc;
         if (searched) {

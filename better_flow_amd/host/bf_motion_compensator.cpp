@@ -50,6 +50,7 @@ struct Options {
     int objects_min_events = -1;                 // --objects-min-events=<n> (-1: the refit's min_events)
     bool objects_track = false;                  // --objects-track[=<N>]: objects_N.tracks.txt per slice, a search every N slices
     int objects_track_every = 0;                 // (0: only when the tracker must)
+    bool objects_wide = false;                   // --objects-wide: groups too large for the LDS are refit inside bf_run_groups
     int objects_radius = 1, objects_suppress = 2, objects_min_votes = 1, objects_scale = 3;
     std::string frame_prefix = "./", video_name = "./out.avi";
     int video_fps = 60;
@@ -170,6 +171,10 @@ const std::vector<Flag> &flag_table() {
          "\"ended <track ids>\")"},
         {"--objects-track", Arg::Inline, [](Options &o, const char *v) { o.objects_track = true; o.objects_track_every = atoi(v); }, "<N>",
          "... and search again every N slices"},
+        {"--objects-wide", Arg::None, [](Options &o, const char *) { o.objects_wide = true; }, "",
+         "with --objects: a group too large for one work-group's LDS (the background, always) is refit inside the grouped solve by the "
+         "chip-wide loop (bf_set_option \"groups_wide\") instead of one after the other on a second context, which is then not created; "
+         "the files keep their bytes"},
         {"--objects-min-events", Arg::Inline, [](Options &o, const char *v) { o.objects_min_events = atoi(v); }, "<n>",
          "with --objects-merge: dissolve groups with fewer events (default: the refit's own min_events guard: a group it skips has no model of its own)"},
         {"--img-prefix", Arg::Next, [](Options &o, const char *v) { o.frame_prefix = v; }, "<dir>", "directory of those frames (and of flow_N.*)"},
@@ -304,6 +309,7 @@ int parse(int argc, char **argv, Options &o) {
         std::fprintf(stderr, "--objects-track[=<N>] (N >= 0) tracks the objects --objects=<K> finds: give both\n");
         return 1;
     }
+    if (o.objects_wide && !o.objects_flag) { std::fprintf(stderr, "--objects-wide refits the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_img && !o.objects_flag) { std::fprintf(stderr, "--objects-img renders the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_flow && !o.objects_flag) { std::fprintf(stderr, "--objects-flow writes the flow of the objects --objects=<K> finds: give both\n"); return 1; }
     if (o.objects_img && o.objects_img_gain < 1) { std::fprintf(stderr, "--objects-img-gain must be at least 1\n"); return 1; }
@@ -392,6 +398,7 @@ int run_ring(const Options &o) {
         cfg.propose.radius = o.objects_radius; cfg.propose.suppress = o.objects_suppress;
         cfg.propose.max_models = o.objects; cfg.propose.min_votes = o.objects_min_votes;
         cfg.assign.scale = cfg.fit.scale = o.objects_scale;
+        cfg.wide_groups = o.objects_wide;
         if (merging) {
             cfg.merge_num = o.objects_merge_num; cfg.merge_den = o.objects_merge_den;
             cfg.dissolve_below = o.objects_min_events >= 0 ? o.objects_min_events : cfg.fit.min_events;

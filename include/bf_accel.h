@@ -222,7 +222,11 @@ int bf_abi_struct_sizes(int32_t *out, int32_t n);
  *                  the slice would take), 1 (default): where it was measured to be the faster loop -- cold runs of a
  *                  "co_schedule" context on a slice that would otherwise run the two-kernel loop on dense slabs by default
  *                  ("binned" = 1), with packed planes and at least one event per image pixel (config 2 under four contexts:
- *                  218 -> 240 Mevents/s).  A slice with a noise mask keeps the plain global-atomic loop. */
+ *                  218 -> 240 Mevents/s).  A slice with a noise mask keeps the plain global-atomic loop.
+ *   "groups_wide"  bf_run_groups only; takes effect at the NEXT bf_run_groups, not at bf_set_cloud.  0 (default): a group whose
+ *                  window does not fit one work-group's LDS gets BF_ERR_CAPACITY in its own rc and is not solved.  1: such a
+ *                  group is solved inside the call by the chip-wide loop that bf_run is, as long as its window fits the
+ *                  context's own image capacity ("event groups", wide groups).  Anything else is BF_ERR_ARG. */
 int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
 
 /* Diagnostics (no reference counterpart).  Keys:
@@ -246,6 +250,7 @@ int bf_set_option(bf_ctx *ctx, const char *key, int64_t value);
  *                     launch of >= 8 tiles per CU takes; -1 as above.
  *   "propose_form"    the vote kernel the last bf_propose_models launched: 1 a histogram per work-group in LDS, 2 one global
  *                     atomic per vote; 0 when it launched none (no call yet, or no events).
+ *   "groups_wide"     the groups the last bf_run_groups solved on the chip-wide loop ("groups_wide" = 1); 0 before any call.
  *   "groups_held"     the groups K of the grouping held for the uploaded slice (bf_set_groups, bf_set_groups_from_segments,
  *                     bf_assign_groups with install); -1 when none is held.
  *   "tracks_held"     the groups Kp of the owner plane bf_track_keep kept; -1 when none is kept.  An upload does not change it.
@@ -427,7 +432,25 @@ int bf_run_tiles_many(bf_ctx *const *ctxs, int32_t n, const bf_tile_opts *opts, 
  *                                sized to the largest window that runs in THIS call (bf_get_stat "groups_lds",
  *                                "groups_per_cu").  Afterwards the context is in the state bf_run_tiles leaves it in.
  * The grouping holds until the next upload; bf_run_groups may be called again on it, e.g. with other warm models.
- * No membership policy is implied: which events form an object is the caller's decision. */
+ * No membership policy is implied: which events form an object is the caller's decision.
+ *
+ * Wide groups (bf_set_option "groups_wide" = 1).  A group is WIDE when the guards do not skip it, its
+ * rows * cols * 16 bytes exceed the LDS budget, and its window fits the context's own image capacity: rows <= max_rows and
+ * cols <= max_cols of bf_create.  A wide group is solved in the same call on the chip-wide loop; a group beyond the image
+ * capacity keeps BF_ERR_CAPACITY.  The result of a wide group g is what a FRESH context of the same capacity leaves after
+ *   1. bf_upload_events(E_g);  2. bf_set_cloud(scale, sensor_res_x, sensor_res_y);  3. bf_set_model(warm_g) when the call is warm;
+ *   4. bf_run with max_iter, min_events, res_x / res_y = guard_res_x / y and hard_iter_cap of the group options, everything
+ *      else bf_run_opts_default:
+ * the model; the bf_run_info (rc BF_OK or BF_ERR_NOCONV in the group's own rc while the call returns BF_OK, iterations, the
+ * four dividers; the diagnostic counters are the inner run's); and per event of the group what bf_writeout_events and
+ * bf_compute_uv read there.  Every loop form of bf_run gives the same bits from order-free integer accumulators, so this too
+ * is a function of the event set alone.  An inner error that is not a run's own outcome (BF_ERR_HIP, ...) fails the whole call
+ * with that code and the inner message.  groups_out[g].reserved is 1 for a group solved wide and 0 otherwise (always 0 with
+ * the option off); bf_get_stat "groups_wide" counts them for the last call.  The wide groups run one after the other, longest
+ * first, behind the LDS groups' launch, on an inner context the outer one owns (created at the first wide group, same device,
+ * capacity and stream; released by bf_destroy; not a context of its own for "persist"'s "only context on its device").  The
+ * context is left as by any bf_run_groups; the held grouping, a held flow of bf_hold_groups, the kept track plane, the vote
+ * planes and the per-event best state are untouched. */
 typedef struct bf_group_opts {            /* 32 bytes */
     int32_t scale;                        /* odd, scale/2 <= 4 */
     int32_t sensor_res_x, sensor_res_y;   /* seeds of set_cloud's bounding box */
@@ -437,7 +460,7 @@ typedef struct bf_group_opts {            /* 32 bytes */
     int32_t hard_iter_cap;
 } bf_group_opts;
 typedef struct bf_group_info {            /* what the device found per group before solving */
-    int32_t events, row_min, row_max, col_min, col_max, rows, cols, reserved;   /* fr bbox (set_cloud's, seeded); window R, C */
+    int32_t events, row_min, row_max, col_min, col_max, rows, cols, reserved;   /* fr bbox (set_cloud's, seeded); window R, C; reserved: 1 solved wide */
 } bf_group_info;
 int bf_set_groups(bf_ctx *ctx, const int32_t *group_id, int32_t groups);
 int bf_set_groups_from_segments(bf_ctx *ctx, int32_t *groups_out);
