@@ -15,7 +15,6 @@
 #include <better_flow/event.h>
 #include <better_flow/event_file.h>
 #include <better_flow/frame_writer.h>
-#include <better_flow/object_finder.h>
 #include <better_flow/object_tracker.h>
 #include <better_flow/object_render.h>
 #include <better_flow/optimizer_rolling.h>
@@ -59,12 +58,11 @@ protected:
     std::string segments_prefix;
     ull segments_count = 0;
     bool generate_objects = false;             // --objects: objects_N.txt
-    bf::ObjectFinder finder;
+    bf::ObjectTracker tracker;                 // its .finder is the finder, with or without tracking; .finder.refit is the refit policy
     std::string objects_prefix;
     ull objects_count = 0;
-    bf_ctx *objects_helper = nullptr;          // the refit of a group too large for the grouped solve runs here
+    bf_ctx *objects_helper = nullptr;          // owned; lent to the refit policy: a group too large for the grouped solve is refit here
     bool generate_objects_track = false;       // --objects-track: identities carried across slices, objects_N.tracks.txt
-    bf::ObjectTracker tracker;
     ull objects_origin = 0;                    // the previous slice's time origin
     bool generate_objects_img = false;         // --objects-img: objects_N.ppm / objects_N.pgm / objects_N.score.txt
     bf::ObjectRenderer renderer;
@@ -81,6 +79,7 @@ protected:
     void render_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
     void render_flow_frame(OptimizerRolling<LinearEventPtrs> &optimizer);
     void write_objects(LinearEventPtrs &slice, ull origin);
+    void write_object_files(bf_ctx *ctx, const bf::Slice &sl, const std::string &base);
 
 public:
     DVS_flow(ull on_ev_change_, ull on_time_change_, ull start_time = 0)
@@ -122,23 +121,20 @@ public:
     void set_generate_segments(const bf_segment_opts &opts, std::string prefix = "./") {
         generate_segments = true; segmenter.opts = opts; segments_prefix = prefix;
     }
-    // the moving objects of every slice (objects_N.txt under `prefix`): `cfg`'s search, proposal and alternation (its result
-    // fields are not read); the number of objects is cfg.propose.max_models
+    // the moving objects of every slice (objects_N.txt under `prefix`): `cfg`'s search, proposal, alternation and refit policy
+    // (its result fields, hold_flow and refit.helper are not read); the number of objects is cfg.propose.max_models
     void set_generate_objects(const bf::ObjectFinder &cfg, std::string prefix = "./") {
-        generate_objects = true; finder = cfg; objects_prefix = prefix;
+        generate_objects = true; tracker.finder = cfg; objects_prefix = prefix;
     }
     // ... and their picture and score (objects_N.ppm, objects_N.pgm, objects_N.score.txt): the slice with every event under
     // its own object's model, in the assignment's window; a box sum of 255 / gain saturates an object's colour
     void set_generate_objects_img(int gain) { generate_objects_img = true; renderer.opts.gain = gain; }
     // ... and their per-event flow (objects_N.flo, objects_N.flow.ppm, objects_N.events.txt): every event under its own
     // object's model, held on the device by the finder (bf::ObjectFinder::hold_flow) and read through the held flow's outputs
-    void set_generate_objects_flow() { generate_objects_flow = true; finder.hold_flow = true; }
-    // ... and their identities across slices (objects_N.tracks.txt): bf::ObjectTracker with the finder's configuration, a search
-    // every `research_every` slices (0: only when it must).  Call after set_generate_objects.
-    void set_generate_objects_track(int research_every) {
-        generate_objects_track = true; tracker.finder = finder; tracker.research_every = research_every;
-        tracker.wide_groups = finder.wide_groups;
-    }
+    void set_generate_objects_flow() { generate_objects_flow = true; }
+    // ... and their identities across slices (objects_N.tracks.txt): bf::ObjectTracker around the finder, a search every
+    // `research_every` slices (0: only when it must)
+    void set_generate_objects_track(int research_every) { generate_objects_track = true; tracker.research_every = research_every; }
     void set_stm_disable(bool off = true) { stm_disable = off; }
     void set_quiet(bool val = true) { this->quiet = val; }   // the reference parses --quiet but ignores it
 
@@ -224,96 +220,72 @@ void DVS_flow<MAX_SZ, SPAN>::render_flow_frame(OptimizerRolling<LinearEventPtrs>
     }
 }
 
-// The moving objects of the slice (better_flow/object_finder.h) as objects_N.txt: one line per group -- id, events, the
-// median (u, v) of its events under its model in px / s, the model's fields (cx cy dx dy rot div cnt total_dx total_dy total_rot
-// total_div), the votes of the proposal it started from --, then a last line "unassigned <events>".  With --objects-merge the groups are
-// those bf::ObjectMerger left, and objects_N.merge.txt lists its steps.  Event::t holds the
-// slice-local time (set_time).  With --objects-img also the slice under its objects' models (better_flow/object_render.h).
+// The moving objects of the slice (better_flow/object_finder.h) in three steps: the slice as arrays (Event::t holds the
+// slice-local time, set_time); bf::ObjectFinder::find on it, or with --objects-track bf::ObjectTracker::next -- either leaves the
+// slice's result in tracker.finder --; the files (write_object_files).
 template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::write_objects(LinearEventPtrs &slice, ull origin) {
-    bf::ObjectFinder &fd = generate_objects_track ? tracker.finder : finder;   // (tracking: the tracker's finder holds the slice's result)
     std::vector<int32_t> fx, fy, ft;
     fx.reserve(slice.size()); fy.reserve(slice.size()); ft.reserve(slice.size());
     for (auto &e : slice) {
         fx.push_back((int32_t)e.fr_x); fy.push_back((int32_t)e.fr_y); ft.push_back((int32_t)e.t);
     }
-    const int s = fd.fit.scale;
+    const bf::Slice sl = {fx.data(), fy.data(), ft.data(), fx.size()};
+    bf::ObjectFinder &fd = tracker.finder;   // (what is this class's to decide is set here, whatever order the setters were called in)
+    const int s = fd.refit.fit.scale;
     bf_ctx *ctx = bf::DeviceContext::get((long long)MAX_SZ, s * RES_X + s, s * RES_Y + s);
-    // (--objects-wide, bf::ObjectFinder::wide_groups: every group is refit inside the grouped solve -- no second context)
-    if (!finder.wide_groups && !objects_helper && bf_create(bf::DeviceContext::device(), (long long)MAX_SZ, s * RES_X + s, s * RES_Y + s, nullptr, &objects_helper) != BF_OK)
+    // (--objects-wide, bf::Refit::wide: every group is refit inside the grouped solve -- no second context)
+    if (!fd.refit.wide && !objects_helper && bf_create(bf::DeviceContext::device(), (long long)MAX_SZ, s * RES_X + s, s * RES_Y + s, nullptr, &objects_helper) != BF_OK)
         objects_helper = nullptr;   // (a group too large for the grouped solve then keeps its model)
-    fd.assign.sensor_res_x = fd.fit.sensor_res_x = fd.fit.guard_res_x = RES_X;
-    fd.assign.sensor_res_y = fd.fit.sensor_res_y = fd.fit.guard_res_y = RES_Y;
-    bf::MotionAssigner::Slice sl;
-    sl.fr_x = fx.data(); sl.fr_y = fy.data(); sl.t_ns = ft.data(); sl.n = fx.size();
-    int rc;
+    fd.refit.helper = objects_helper;
+    fd.assign.sensor_res_x = fd.refit.fit.sensor_res_x = fd.refit.fit.guard_res_x = RES_X;
+    fd.assign.sensor_res_y = fd.refit.fit.sensor_res_y = fd.refit.fit.guard_res_y = RES_Y;
+    fd.hold_flow = generate_objects_flow;
     if (generate_objects_track) {   // dt: the difference of the two slices' time origins, the absolute time set_time subtracts
-        tracker.hold_flow = generate_objects_flow;
-        rc = tracker.next(ctx, sl, objects_count ? (int64_t)origin - (int64_t)objects_origin : 0, objects_helper);
+        const int rc = tracker.next(ctx, sl, objects_count ? (int64_t)origin - (int64_t)objects_origin : 0);
         objects_origin = origin;
         if (rc < 0) throw bf::AccelError(rc, "--objects-track: " + tracker.error);
     } else {
-        rc = fd.find(ctx, sl, objects_helper);
+        const int rc = fd.find(ctx, sl);
         if (rc < 0) throw bf::AccelError(rc, "--objects: " + fd.error);
     }
-    const std::string base = objects_prefix + "/objects_" + std::to_string(objects_count++);
-    const std::string path = base + ".txt";
-    FILE *f = std::fopen(path.c_str(), "w");
-    if (!f) {
-        if (!quiet) std::cerr << "cannot write " << path << "\n";
+    write_object_files(ctx, sl, objects_prefix + "/objects_" + std::to_string(objects_count++));
+}
+
+// objects_N.txt; with --objects-track objects_N.tracks.txt; with --objects-merge the groups are those bf::ObjectMerger left, and
+// objects_N.merge.txt lists its steps; with --objects-flow the held flow's outputs; with --objects-img the slice under its objects' models.
+template <size_t MAX_SZ, sll SPAN>
+void DVS_flow<MAX_SZ, SPAN>::write_object_files(bf_ctx *ctx, const bf::Slice &sl, const std::string &base) {
+    const bf::ObjectFinder &fd = tracker.finder;
+    const bf::Grouping &g = fd.grouping;
+    if (!fd.write_objects(base + ".txt")) {
+        if (!quiet) std::cerr << "cannot write " << base << ".txt\n";
         return;
     }
-    for (size_t k = 0; k < fd.models.size(); ++k) {
-        const bf_model &m = fd.models[k];
-        std::fprintf(f, "%zu %d %.17g %.17g %.17g %.17g %.17g %.17g %.17g %.17g %u %.17g %.17g %.17g %.17g %d\n", k, (int)fd.counts[k],
-                     fd.flow_u[k], fd.flow_v[k], m.cx, m.cy, m.dx, m.dy, m.rot, m.div, (unsigned)m.cnt, m.total_dx, m.total_dy,
-                     m.total_rot, m.total_div, (size_t)fd.origin[k] < fd.proposals.size() ? (int)fd.proposals[(size_t)fd.origin[k]].votes : 0);
-    }
-    std::fprintf(f, "unassigned %d\n", fd.counts.empty() ? 0 : (int)fd.counts.back());
-    std::fclose(f);
-    // (--objects-track) objects_N.tracks.txt: the path the slice took, then per group its track, the track's age, its events,
-    // those inside under its model carried back by dt and those of them on its own track's pixels, then the tracks that ended
-    if (generate_objects_track) {
-        FILE *tf = std::fopen((base + ".tracks.txt").c_str(), "w");
-        if (tf) {
-            std::fprintf(tf, "searched %d dt_ns %lld\n", tracker.searched ? 1 : 0, (long long)tracker.dt_ns);
-            for (size_t k = 0; k < tracker.tracks.size(); ++k)
-                std::fprintf(tf, "%zu %d %d %d %d %d\n", k, (int)tracker.tracks[k].id, (int)tracker.tracks[k].age, (int)tracker.tracks[k].events,
-                             tracker.inside.empty() ? 0 : (int)tracker.inside[k], (int)tracker.on_track[k]);
-            std::fprintf(tf, "ended");
-            for (int32_t id : tracker.ended) std::fprintf(tf, " %d", (int)id);
-            std::fprintf(tf, "\n");
-        }
-        if ((!tf || std::fclose(tf) != 0) && !quiet) std::cerr << "cannot write " << base << ".tracks.txt\n";
-    }
+    if (generate_objects_track && !tracker.write_tracks(base + ".tracks.txt") && !quiet) std::cerr << "cannot write " << base << ".tracks.txt\n";
     // (--objects-merge) what the merger did to the proposed groups, and the contrast sum N^2 of the grouping it left
-    if (fd.merge_num > 0 && !bf::ObjectMerger::write_steps(base + ".merge.txt", fd.steps, fd.models.size(), fd.merged_sum_sq) && !quiet)
+    if (fd.merge_num > 0 && !bf::ObjectMerger::write_steps(base + ".merge.txt", fd.steps, g.models.size(), fd.merged_sum_sq) && !quiet)
         std::cerr << "cannot write " << base << ".merge.txt\n";
     // (--objects-flow) the finder left the slice, the grouping and the held flow on the context: the flow field and the flow
     // frame as render_flow_frame writes the rolling optimiser's (oldest event owns a pixel), and one line per event.  A slice
     // without an object has no model to hold a flow under (bf::ObjectFinder::hold_flow): like --objects-img it writes nothing
-    if (generate_objects_flow && !fd.models.empty()) {
+    if (generate_objects_flow && !g.models.empty()) {
         std::vector<uint8_t> ppm((size_t)RES_X * (size_t)(3 * RES_Y) * 3);
         std::vector<float> flo((size_t)RES_X * (size_t)RES_Y * 2);
         std::vector<double> u(sl.n), v(sl.n);
         int frc = bf_global_render_flow_frame(ctx, RES_X, RES_Y, BF_FLOW_LAST_UPLOADED, ppm.data(), nullptr, flo.data());
         if (frc >= 0) frc = bf_global_get_flow(ctx, nullptr, nullptr, u.data(), v.data(), nullptr, nullptr);
         if (frc < 0) throw bf::AccelError(frc, std::string("--objects-flow: ") + bf_last_error(ctx));
-        bool w = bf::write_flo(base + ".flo", RES_X, RES_Y, flo.data()) && bf::write_ppm_raw(base + ".flow.ppm", RES_X, 3 * RES_Y, ppm.data());
-        FILE *ef = std::fopen((base + ".events.txt").c_str(), "w");
-        if (ef) {
-            for (size_t i = 0; i < sl.n; ++i)
-                std::fprintf(ef, "%d %d %d %d %.9f %.9f\n", (int)ft[i], (int)fx[i], (int)fy[i], (int)fd.gid[i], u[i], v[i]);
-            w = (std::fclose(ef) == 0) && w;
-        }
-        if ((!w || !ef) && !quiet) std::cerr << "cannot write " << base << ".flo / .flow.ppm / .events.txt\n";
+        const bool w = bf::write_flo(base + ".flo", RES_X, RES_Y, flo.data()) && bf::write_ppm_raw(base + ".flow.ppm", RES_X, 3 * RES_Y, ppm.data());
+        const bool we = fd.write_events(base + ".events.txt", sl, u, v);
+        if (!(w && we) && !quiet) std::cerr << "cannot write " << base << ".flo / .flow.ppm / .events.txt\n";
     }
-    if (!generate_objects_img || fd.models.empty()) return;   // (no object: nothing to project)
+    if (!generate_objects_img || g.models.empty()) return;   // (no object: nothing to project)
     // find() leaves the context holding one group's events (its flows re-upload): the renderer uploads the slice again and
     // holds the final ids as its grouping
     renderer.opts.scale = fd.assign.scale;
     renderer.opts.sensor_res_x = RES_X; renderer.opts.sensor_res_y = RES_Y;
     renderer.opts.margin = fd.assign.margin;
-    const int prc = renderer.render(ctx, sl, fd.gid, fd.models);
+    const int prc = renderer.render(ctx, sl, g.gid, g.models);
     if (prc < 0) throw bf::AccelError(prc, std::string("--objects-img: ") + bf_last_error(ctx));
     if ((!renderer.write_ppm(base + ".ppm") || !renderer.write_label_pgm(base + ".pgm") || !renderer.write_scores(base + ".score.txt")) && !quiet)
         std::cerr << "cannot write " << base << ".ppm / .pgm / .score.txt\n";
@@ -328,8 +300,8 @@ template <size_t MAX_SZ, sll SPAN> void DVS_flow<MAX_SZ, SPAN>::recompute() {
     const bool frames = generate_video || generate_pictures;
     if (frames)   // the frames are rendered at scale 3 whatever `scale` is: make room once
         (void)bf::DeviceContext::get((long long)MAX_SZ, 3 * RES_X + 3, 3 * RES_Y + 3);
-    if (generate_objects)   // ... and the objects' refit at its own scale
-        (void)bf::DeviceContext::get((long long)MAX_SZ, finder.fit.scale * RES_X + finder.fit.scale, finder.fit.scale * RES_Y + finder.fit.scale);
+    const int os = tracker.finder.refit.fit.scale;   // ... and the objects' refit at its own scale
+    if (generate_objects) (void)bf::DeviceContext::get((long long)MAX_SZ, os * RES_X + os, os * RES_Y + os);
 
     LinearEventPtrs slice;                     // newest -> oldest, the ring's iteration order
     slice.reserve(ev_buffer.size());

@@ -31,28 +31,20 @@ namespace bf {
 
 class MotionAssigner {
   public:
-    struct Slice {                        // borrowed for the duration of a call
-        const int32_t *fr_x, *fr_y, *t_ns;
-        size_t n;
-    };
     struct Record {                       // one alternation
         int32_t changed;                  // ids the first assignment of the alternation changed
         std::vector<int32_t> counts;      // K + 1 of its last assignment (last: unassigned)
         std::vector<int32_t> iterations;  // per group of the refit; empty: the alternation ended without one
     };
 
-    bf_group_opts fit;                    // the refit's scale, seeds, guards and caps (bf::ObjectTasks)
-    // the refit solves a group whose window exceeds the LDS in its own bf_run_groups (ObjectTasks::wide): no group then comes back
-    // BF_ERR_CAPACITY unless it exceeds the context's image capacity, and alternate() does not touch `helper`
-    bool wide_groups = false;
+    Refit refit;                          // how alternate() refits; its force_host also takes assign() to the host path
     // what assign() leaves (upload order) ...
     std::vector<int32_t> gid, score, counts;
     bf_assign_info info;
-    // ... and alternate(): the models, gid above, and one record per alternation
-    std::vector<bf_model> models;
+    // ... and alternate(), beside the grouping it was given: one record per alternation
     std::vector<Record> records;
 
-    MotionAssigner() : info() { fit = ObjectTasks().opts; }
+    MotionAssigner() : info() {}
 
     static bool device_available() { return bf_assign_groups != nullptr; }
 
@@ -65,24 +57,24 @@ class MotionAssigner {
     }
 
     // The grouping a round with use_prior starts from (ids -1 .. groups - 1 in upload order), as bf_set_groups.
-    int set_prior(bf_ctx *ctx, const std::vector<int32_t> &ids, int32_t groups, bool force_host = false) {
+    int set_prior(bf_ctx *ctx, const std::vector<int32_t> &ids, int32_t groups) {
         if (ids.size() != n_) return BF_ERR_ARG;
         prior_ = ids;
         prior_K_ = groups;
         have_prior_ = true;
-        if (device_available() && !force_host && bf_set_groups) return bf_set_groups(ctx, ids.data(), groups);
+        if (device_available() && !refit.force_host && bf_set_groups) return bf_set_groups(ctx, ids.data(), groups);
         return BF_OK;
     }
 
     // One assignment of the uploaded slice (upload()); fills gid, score, counts, info.
-    int assign(bf_ctx *ctx, const std::vector<bf_model> &cand, const bf_assign_opts &o, bool force_host = false) {
+    int assign(bf_ctx *ctx, const std::vector<bf_model> &cand, const bf_assign_opts &o) {
         const size_t K = cand.size();
         gid.assign(n_, 0);
         score.assign(n_, 0);
         counts.assign(K + 1, 0);
         std::memset(&info, 0, sizeof(info));
         int rc;
-        if (device_available() && !force_host)
+        if (device_available() && !refit.force_host)
             rc = bf_assign_groups(ctx, &o, cand.data(), (int32_t)K, gid.data(), score.data(), counts.data(), &info);
         else
             rc = assign_host(ctx, cand, o);
@@ -94,38 +86,30 @@ class MotionAssigner {
         return rc;
     }
 
-    // Alternates assignment and refit on the slice, starting from `start`: per alternation rounds_per_fit assignments (the very
-    // first without a prior, every other with the one before it), then a refit of every group through bf::ObjectTasks, warm from
+    // Alternates assignment and refit on the slice, starting from g's models: per alternation rounds_per_fit assignments (the
+    // very first without a prior, every other with the one before it), then a refit of every group (bf::Refit::refit), warm from
     // its current model.  It ends when the first assignment after a refit changes no id -- the models are then the fit of exactly
-    // this membership -- or after max_alternations.  A group whose window exceeds the device path's LDS (BF_ERR_CAPACITY in its
-    // info) is refit through ObjectTasks' one-after-the-other path on `helper` (a second context with room for the slice; null:
-    // it keeps its model); a group a guard skipped keeps its model.  o.use_prior and o.install are set here.
-    // start_prior: ids (-1 .. K-1, upload order) the very first assignment takes as its prior (null: it has none).
-    int alternate(bf_ctx *ctx, const Slice &s, const std::vector<bf_model> &start, bf_assign_opts o, int rounds_per_fit,
-                  int max_alternations, bf_ctx *helper = nullptr, bool force_host = false,
-                  const std::vector<int32_t> *start_prior = nullptr) {
-        models = start;
+    // this membership -- or after max_alternations.  o.use_prior and o.install are set here.  It leaves g's models, ids and counts.
+    // from_ids: the very first assignment takes g's ids as its prior (false: it has none).
+    int alternate(bf_ctx *ctx, const Slice &s, Grouping &g, bf_assign_opts o, int rounds_per_fit, int max_alternations,
+                  bool from_ids = false) {
         records.clear();
-        const size_t K = models.size();
-        std::vector<int32_t> prior;
-        bool have = false;
-        if (start_prior) {
-            prior = *start_prior;
-            have = true;
-        }
+        const size_t K = g.models.size();
+        bool have = from_ids;
         o.install = 1;
         for (int a = 0; a < max_alternations; ++a) {
             int rc = upload(ctx, s);   // (a refit leaves a subset, or the slice sorted, behind)
-            if (rc >= 0 && have) rc = set_prior(ctx, prior, (int32_t)K, force_host);
+            if (rc >= 0 && have) rc = set_prior(ctx, g.gid, (int32_t)K);
             if (rc < 0) return rc;
             Record rec;
             rec.changed = 0;
             for (int r = 0; r < rounds_per_fit; ++r) {
                 o.use_prior = have ? 1 : 0;
-                rc = assign(ctx, models, o, force_host);
+                rc = assign(ctx, g.models, o);
                 if (rc < 0) return rc;
                 if (r == 0) rec.changed = info.changed;
-                prior = gid;
+                g.gid = gid;
+                g.counts = counts;
                 have = true;
             }
             rec.counts = counts;
@@ -133,39 +117,14 @@ class MotionAssigner {
                 records.push_back(rec);
                 break;
             }
-            std::vector<std::vector<int32_t>> ids(K);
-            for (size_t i = 0; i < s.n; ++i)
-                if (gid[i] >= 0) ids[(size_t)gid[i]].push_back((int32_t)i);
-            ObjectTasks q;
-            q.opts = fit;
-            q.wide = wide_groups;
-            for (size_t k = 0; k < K; ++k) q.push(ids[k], &models[k]);
-            rc = q.run(ctx, s.fr_x, s.fr_y, s.t_ns, s.n, force_host);
+            rc = refit.refit(ctx, s, g, rec.iterations);
             if (rc < 0) return rc;
-            rec.iterations.assign(K, 0);
-            std::vector<size_t> large;
-            for (size_t k = 0; k < K; ++k) {
-                rec.iterations[k] = q.infos[k].iterations;
-                if (q.infos[k].rc == BF_OK) models[k] = q.models[k];
-                else if (q.infos[k].rc == BF_ERR_CAPACITY && helper) large.push_back(k);
-            }
-            if (!large.empty()) {
-                ObjectTasks one;
-                one.opts = fit;
-                for (size_t k : large) one.push(ids[k], &models[k]);
-                rc = one.run(helper, s.fr_x, s.fr_y, s.t_ns, s.n, true);
-                if (rc < 0) return rc;
-                for (size_t j = 0; j < large.size(); ++j) {
-                    rec.iterations[large[j]] = one.infos[j].iterations;
-                    if (one.infos[j].rc == BF_OK) models[large[j]] = one.models[j];
-                }
-            }
             records.push_back(rec);
         }
         return BF_OK;
     }
 
-    // The host paths' pixel code, shared with bf::ObjectRenderer (object_render.h).
+    // The host paths' pixel code, shared with bf::ObjectMerger (object_merge.h) and bf::ObjectRenderer (object_render.h).
     struct HostWindow {   // the window of the sensor widened by the margin: optimizer_rolling.h:248-283
         int s, hs, wsx, wsy, R, C, x_sh, y_sh;
     };
@@ -181,6 +140,13 @@ class MotionAssigner {
         w.x_sh = (int)x_shift; w.y_sh = (int)y_shift;                // the parameter conversion of accel_lib.h:147
         return w;
     }
+    // What bf_assign_groups, bf_merge_scores and bf_project_groups all check of the window's options and the model count
+    // (BF_ERR_ARG), and whether K vote planes of the window fit their 2^27 words (BF_ERR_CAPACITY).
+    static bool host_plane_opts_valid(int scale, int res_x, int res_y, int margin, int K) {
+        return !(scale < 1 || scale % 2 == 0 || scale / 2 > 4 || res_x < 1 || res_y < 1 || res_x > 65536 || res_y > 65536 || margin < 0 ||
+                 margin > 65536 || K < 1 || K > 64);
+    }
+    static bool host_planes_fit(int K, const HostWindow &w) { return (long long)K * w.R * w.C <= (1ll << 27); }
     // pix[i] = the pixel index X * C + Y of uploaded event i under set_model's warp of `m` from the reset state, -1: outside.
     // px, py: room for the events' positions.
     static int host_pixels(bf_ctx *ctx, const bf_model &m, const HostWindow &w, int res_x, int res_y, std::vector<double> &px,
@@ -222,14 +188,12 @@ class MotionAssigner {
 
     int assign_host(bf_ctx *ctx, const std::vector<bf_model> &cand, const bf_assign_opts &o) {
         const int K = (int)cand.size();
-        if (o.scale < 1 || o.scale % 2 == 0 || o.scale / 2 > 4 || o.sensor_res_x < 1 || o.sensor_res_y < 1 || o.sensor_res_x > 65536 ||
-            o.sensor_res_y > 65536 || o.margin < 0 || o.margin > 65536 || o.min_score < 1 || K < 1 || K > 64)
-            return BF_ERR_ARG;
+        if (!host_plane_opts_valid(o.scale, o.sensor_res_x, o.sensor_res_y, o.margin, K) || o.min_score < 1) return BF_ERR_ARG;
         if (o.use_prior && !have_prior_) return BF_ERR_STATE;
         if (o.use_prior && prior_K_ != K) return BF_ERR_ARG;
         const HostWindow w = host_window(o.scale, o.sensor_res_x, o.sensor_res_y, o.margin);
         const int s = w.s, R = w.R, C = w.C;
-        if ((long long)K * R * C > (1ll << 27)) return BF_ERR_CAPACITY;
+        if (!host_planes_fit(K, w)) return BF_ERR_CAPACITY;
         const size_t n = n_, P = (size_t)R * (size_t)C;
         if (n == 0) return BF_OK;
         std::vector<int32_t> best(n, 0), arg(n, 0), pix(n);

@@ -41,25 +41,19 @@ class ObjectMerger {
 
     bf_merge_opts opts;                   // scale, sensor, margin, targets_per_pass of the scores
     bf_assign_opts assign;                // the alternation's assignment ...
-    bf_group_opts fit;                    // ... and refit (bf::MotionAssigner)
+    Refit refit;                          // ... and refit (bf::MotionAssigner); its force_host also takes reduce()'s scores to scores_host()
     int rounds_per_fit = 2;
-    bool wide_groups = false;             // handed to the alternation's refit (bf::MotionAssigner::wide_groups)
     // what scores() / scores_host() leave: K x K gains and inside counts, [b * K + a]; K event counts; the info
     std::vector<uint64_t> gain;
     std::vector<int32_t> inside, events;
     bf_merge_info info;
-    // what reduce() leaves: the models, the ids in upload order, K + 1 counts (last: unassigned), the steps; gain, inside,
-    // events and info above are those of the final grouping
-    std::vector<bf_model> models;
-    std::vector<int32_t> gid, counts;
-    std::vector<int32_t> origin;          // per final group: its index among the start models
+    // what reduce() leaves beside the grouping it was given: the steps; gain, inside, events and info above are the final grouping's
     std::vector<Step> steps;
 
     ObjectMerger() : opts(), assign(), info() {
         opts.scale = assign.scale = 3;
         opts.sensor_res_x = assign.sensor_res_x = 180; opts.sensor_res_y = assign.sensor_res_y = 240;
         assign.min_score = 1;
-        fit = ObjectTasks().opts;
     }
 
     static bool device_available() { return bf_merge_scores != nullptr; }
@@ -73,13 +67,13 @@ class ObjectMerger {
     }
 
     // The same on host arrays: uploads the slice (the context's held grouping is forgotten, as by every upload).
-    int scores_host(bf_ctx *ctx, const MotionAssigner::Slice &s, const std::vector<int32_t> &ids, const std::vector<bf_model> &ms) {
+    int scores_host(bf_ctx *ctx, const Slice &s, const std::vector<int32_t> &ids, const std::vector<bf_model> &ms) {
         const int K = (int)ms.size();
         if (!valid(K) || ids.size() != s.n) return BF_ERR_ARG;
         for (size_t i = 0; i < s.n; ++i)
             if (ids[i] < -1 || ids[i] >= K) return BF_ERR_ARG;
         const MotionAssigner::HostWindow w = MotionAssigner::host_window(opts.scale, opts.sensor_res_x, opts.sensor_res_y, opts.margin);
-        if ((long long)K * w.R * w.C > (1ll << 27)) return BF_ERR_CAPACITY;
+        if (!MotionAssigner::host_planes_fit(K, w)) return BF_ERR_CAPACITY;
         size_outputs((size_t)K);
         const size_t n = s.n, P = (size_t)w.R * (size_t)w.C, Ks = (size_t)K;
         if (n == 0) return BF_OK;   // everything zero
@@ -169,42 +163,37 @@ class ObjectMerger {
         return best;
     }
 
-    // The loop, from `start` models and `ids` (upload order, -1 .. K-1) on the slice.  Repeats:
+    // The loop, from g's models and ids on the slice, on g itself (origin: per final group its index among the start models).  Repeats:
     //   1. every group with no event or with fewer than dissolve_below events is removed (ids -> -1), ids and models are
     //      compacted, and if anything was removed, one alternation follows and the loop starts over;
     //   2. bf_set_groups, scores(), pick(); it ends with no accepted pick or one group;
     //   3. b is relabelled a, model b is dropped, ids and models are compacted, one alternation.
     // One alternation: rounds_per_fit assignments with the current ids as the prior, then one grouped refit warm from the
-    // current models (MotionAssigner::alternate with a start prior and one alternation).  At most max_steps rounds.
-    // helper: as in MotionAssigner::alternate.
-    int reduce(bf_ctx *ctx, const MotionAssigner::Slice &s, const std::vector<bf_model> &start, const std::vector<int32_t> &ids,
-               uint64_t num, uint64_t den, int32_t dissolve_below, int max_steps, bf_ctx *helper = nullptr, bool force_host = false) {
-        if (ids.size() != s.n || den == 0) return BF_ERR_ARG;
-        models = start;
-        gid = ids;
-        origin.resize(start.size());
-        for (size_t k = 0; k < start.size(); ++k) origin[k] = (int32_t)k;
+    // current models (MotionAssigner::alternate from g's ids, one alternation).  At most max_steps rounds.
+    int reduce(bf_ctx *ctx, const Slice &s, Grouping &g, uint64_t num, uint64_t den, int32_t dissolve_below, int max_steps) {
+        if (g.gid.size() != s.n || den == 0) return BF_ERR_ARG;
+        g.reset_origin();
         steps.clear();
         bool scored = false;
         for (int round = 0; round < max_steps; ++round) {
-            const size_t K = models.size();
-            count_ids();
+            const size_t K = g.models.size();
+            g.count_ids();
             std::vector<int32_t> drop;
             for (size_t k = 0; k < K; ++k)
-                if (counts[k] == 0 || counts[k] < dissolve_below) drop.push_back((int32_t)k);
+                if (g.counts[k] == 0 || g.counts[k] < dissolve_below) drop.push_back((int32_t)k);
             scored = false;
             if (!drop.empty()) {
                 for (size_t j = 0; j < drop.size(); ++j) {
-                    const Step st = {DISSOLVE, drop[j], -1, 0, 0, counts[(size_t)drop[j]], (int32_t)(K - 1 - j)};
+                    const Step st = {DISSOLVE, drop[j], -1, 0, 0, g.counts[(size_t)drop[j]], (int32_t)(K - 1 - j)};
                     steps.push_back(st);
                 }
-                compact(drop);
-                if (models.empty()) break;
-                const int rc = one_alternation(ctx, s, helper, force_host);
+                g.compact(drop);
+                if (g.models.empty()) break;
+                const int rc = one_alternation(ctx, s, g);
                 if (rc < 0) return rc;
                 continue;   // (the alternation may have emptied a group)
             }
-            int rc = score_current(ctx, s, force_host);
+            int rc = score_current(ctx, s, g);
             if (rc < 0) return rc;
             scored = true;
             const Pick p = pick(gain, events, num, den);
@@ -212,18 +201,18 @@ class ObjectMerger {
             const Step st = {MERGE, p.b, p.a, gain[(size_t)p.b * K + (size_t)p.a], gain[(size_t)p.b * K + (size_t)p.b],
                              events[(size_t)p.b], (int32_t)(K - 1)};
             steps.push_back(st);
-            for (size_t i = 0; i < gid.size(); ++i)
-                if (gid[i] == p.b) gid[i] = p.a;
-            compact(std::vector<int32_t>(1, p.b));
-            rc = one_alternation(ctx, s, helper, force_host);
+            for (size_t i = 0; i < g.gid.size(); ++i)
+                if (g.gid[i] == p.b) g.gid[i] = p.a;
+            g.compact(std::vector<int32_t>(1, p.b));
+            rc = one_alternation(ctx, s, g);
             if (rc < 0) return rc;
             scored = false;
         }
-        count_ids();
+        g.count_ids();
         if (!scored) {   // (max_steps ran out behind a change, or nothing is left)
-            if (models.empty()) size_outputs(0);
+            if (g.models.empty()) size_outputs(0);
             else {
-                const int rc = score_current(ctx, s, force_host);
+                const int rc = score_current(ctx, s, g);
                 if (rc < 0) return rc;
             }
         }
@@ -251,9 +240,8 @@ class ObjectMerger {
 
   private:
     bool valid(int K) const {   // bf_merge_scores' argument checks
-        return !(opts.scale < 1 || opts.scale % 2 == 0 || opts.scale / 2 > 4 || opts.sensor_res_x < 1 || opts.sensor_res_y < 1 ||
-                 opts.sensor_res_x > 65536 || opts.sensor_res_y > 65536 || opts.margin < 0 || opts.margin > 65536 ||
-                 opts.targets_per_pass < 0 || K < 1 || K > 64);
+        return MotionAssigner::host_plane_opts_valid(opts.scale, opts.sensor_res_x, opts.sensor_res_y, opts.margin, K) &&
+               opts.targets_per_pass >= 0;
     }
     void size_outputs(size_t K) {
         gain.assign(K * K, 0);
@@ -261,43 +249,15 @@ class ObjectMerger {
         events.assign(K, 0);
         std::memset(&info, 0, sizeof(info));
     }
-    void count_ids() {
-        counts.assign(models.size() + 1, 0);
-        for (size_t i = 0; i < gid.size(); ++i) ++counts[gid[i] < 0 ? models.size() : (size_t)gid[i]];
-    }
-    // Without the groups in `drop` (ascending): their events -> -1, the others renumbered in order.
-    void compact(const std::vector<int32_t> &drop) {
-        const size_t K = models.size();
-        std::vector<int32_t> to(K, 0);
-        std::vector<bf_model> kept;
-        std::vector<int32_t> kept_origin;
-        size_t d = 0;
-        for (size_t k = 0; k < K; ++k) {
-            if (d < drop.size() && drop[d] == (int32_t)k) { to[k] = -1; ++d; continue; }
-            to[k] = (int32_t)kept.size();
-            kept.push_back(models[k]);
-            kept_origin.push_back(origin[k]);
-        }
-        for (size_t i = 0; i < gid.size(); ++i)
-            if (gid[i] >= 0) gid[i] = to[(size_t)gid[i]];
-        models.swap(kept);
-        origin.swap(kept_origin);
-    }
-    int one_alternation(bf_ctx *ctx, const MotionAssigner::Slice &s, bf_ctx *helper, bool force_host) {
+    int one_alternation(bf_ctx *ctx, const Slice &s, Grouping &g) {
         MotionAssigner ma;
-        ma.fit = fit;
-        ma.wide_groups = wide_groups;
-        const int rc = ma.alternate(ctx, s, models, assign, rounds_per_fit, 1, helper, force_host, &gid);
-        if (rc < 0) return rc;
-        models = ma.models;
-        gid = ma.gid;
-        return BF_OK;
+        ma.refit = refit;
+        return ma.alternate(ctx, s, g, assign, rounds_per_fit, 1, true);
     }
-    int score_current(bf_ctx *ctx, const MotionAssigner::Slice &s, bool force_host) {
-        if (!device_available() || force_host || !bf_set_groups) return scores_host(ctx, s, gid, models);
-        int rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);   // (a refit leaves a subset behind)
-        if (rc >= 0) rc = bf_set_groups(ctx, gid.data(), (int32_t)models.size());
-        return rc < 0 ? rc : scores(ctx, models);
+    int score_current(bf_ctx *ctx, const Slice &s, const Grouping &g) {
+        if (!device_available() || refit.force_host || !bf_set_groups) return scores_host(ctx, s, g.gid, g.models);
+        const int rc = hold_grouping(ctx, s, g.gid, g.models.size());   // (a refit leaves a subset behind)
+        return rc < 0 ? rc : scores(ctx, g.models);
     }
 };
 

@@ -52,7 +52,7 @@ class ObjectRenderer {
     }
 
     // The same on host arrays: uploads the slice (the context's held grouping is forgotten, as by every upload).
-    int project_host(bf_ctx *ctx, const MotionAssigner::Slice &s, const std::vector<int32_t> &ids, const std::vector<bf_model> &models) {
+    int project_host(bf_ctx *ctx, const Slice &s, const std::vector<int32_t> &ids, const std::vector<bf_model> &models) {
         const int K = (int)models.size();
         if (!valid(K) || ids.size() != s.n) return BF_ERR_ARG;
         for (size_t i = 0; i < s.n; ++i)
@@ -114,12 +114,9 @@ class ObjectRenderer {
     }
 
     // Uploads the slice, holds `ids` (-1 .. K-1, upload order) as its grouping and projects it under `models`.
-    int render(bf_ctx *ctx, const MotionAssigner::Slice &s, const std::vector<int32_t> &ids, const std::vector<bf_model> &models,
-               bool force_host = false) {
-        if (!device_available() || force_host || !bf_set_groups) return project_host(ctx, s, ids, models);
-        if (ids.size() != s.n) return BF_ERR_ARG;
-        int rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
-        if (rc >= 0) rc = bf_set_groups(ctx, ids.data(), (int32_t)models.size());
+    int render(bf_ctx *ctx, const Slice &s, const std::vector<int32_t> &ids, const std::vector<bf_model> &models) {
+        if (!device_available() || !bf_set_groups) return project_host(ctx, s, ids, models);
+        const int rc = hold_grouping(ctx, s, ids, models.size());
         return rc < 0 ? rc : project(ctx, models);
     }
 
@@ -171,17 +168,14 @@ class ObjectRenderer {
 
   private:
     bool valid(int K) const {   // bf_project_groups' argument checks
-        return !(opts.scale < 1 || opts.scale % 2 == 0 || opts.scale / 2 > 4 || opts.sensor_res_x < 1 || opts.sensor_res_y < 1 ||
-                 opts.sensor_res_x > 65536 || opts.sensor_res_y > 65536 || opts.margin < 0 || opts.margin > 65536 || opts.gain < 1 ||
-                 K < 1 || K > 64);
+        return MotionAssigner::host_plane_opts_valid(opts.scale, opts.sensor_res_x, opts.sensor_res_y, opts.margin, K) && opts.gain >= 1;
     }
     // Zeroed outputs of the call's window; false when K planes of it exceed the entry's 2^27 words.
     bool size_outputs(size_t K) {
-        const long long R = (long long)opts.scale * (opts.sensor_res_x + 2ll * opts.margin);
-        const long long C = (long long)opts.scale * (opts.sensor_res_y + 2ll * opts.margin);
-        if ((long long)K * R * C > (1ll << 27)) return false;
-        rows = (int)R; cols = (int)C;
-        const size_t P = (size_t)R * (size_t)C;
+        const MotionAssigner::HostWindow w = MotionAssigner::host_window(opts.scale, opts.sensor_res_x, opts.sensor_res_y, opts.margin);
+        if (!MotionAssigner::host_planes_fit((int)K, w)) return false;
+        rows = w.R; cols = w.C;
+        const size_t P = (size_t)w.R * (size_t)w.C;
         count.assign(P, 0u);
         label.assign(P, 0);
         bgr.assign(3 * P, 0);

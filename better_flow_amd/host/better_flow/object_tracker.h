@@ -3,7 +3,7 @@
 // next.  The tracker carries identities from slice to slice and starts a slice from the previous slice's models:
 //   1. candidates: ObjectFinder::find (search, proposals) when it must -- no live track, `research_every` slices since the last
 //      search, or the previous slice left more than research_unassigned_num / _den of its events unassigned -- and otherwise WARM:
-//      the live tracks' models go straight into the alternation (ObjectFinder::find_from: no bf_global_set_window,
+//      the live tracks' models go straight into the alternation (ObjectFinder::group_from: no bf_global_set_window,
 //      bf_global_search or bf_propose_models), then the merger when it is on: the same code after the candidates on both paths;
 //   2. identity, by one rule on both paths: the final grouping is put on the context (upload, bf_set_groups), bf_track_overlap
 //      counts its groups against the owner plane kept from the previous slice, the events carried back by dt_ns, and match()
@@ -33,8 +33,8 @@ namespace bf {
 
 class ObjectTracker {
   public:
-    // The configuration of every slice's search and alternation, and what next() leaves of the slice: finder.models, gid,
-    // counts, flow_u / flow_v, records, steps (finder.hold_flow is the tracker's hold_flow: set that one).
+    // The configuration of every slice's search, alternation and refit (finder.refit), whether the slice ends with its flow held
+    // (finder.hold_flow), and what next() leaves of the slice: finder.grouping, flow_u / flow_v, records, steps.
     ObjectFinder finder;
     int research_every = 0;   // > 0: a search every that many slices; 0: only when it must
     int64_t research_unassigned_num = 1, research_unassigned_den = 2;   // ... or when the previous slice left more than this share unassigned
@@ -42,8 +42,6 @@ class ObjectTracker {
     // (tests/track_scene.py): there the right track holds at least 0.83 of a group's inside events and the
     // wrong one at most 0.034; no other scene has been looked at.
     uint64_t match_num = 1, match_den = 2;
-    bool hold_flow = false;
-    bool wide_groups = false;   // the finder's wide_groups, set by every next(): set this one
 
     struct Track {
         int32_t id;
@@ -103,33 +101,27 @@ class ObjectTracker {
     }
 
     // dt: this slice's time origin minus the previous slice's, in ns (not read for the first slice of a stream).
-    int next(bf_ctx *ctx, const MotionAssigner::Slice &s, int64_t dt, bf_ctx *helper = nullptr) {
+    int next(bf_ctx *ctx, const Slice &s, int64_t dt) {
         error.clear();
         ended.clear(); overlap.clear(); inside.clear(); on_track.clear();
         dt_ns = dt;
-        const bool merging = finder.merge_num > 0;
-        if (const char *m = missing_entry(merging, hold_flow)) {
+        const bool merging = finder.merge_num > 0, holding = finder.hold_flow;
+        if (const char *m = missing_entry(merging, holding)) {
             error = std::string("bf::ObjectTracker: the linked library has no ") + m;
             return BF_ERR_STATE;
         }
         searched = tracks.empty() || (research_every > 0 && since_search >= research_every) ||
                    last_unassigned * research_unassigned_den > last_events * research_unassigned_num;
-        finder.wide_groups = wide_groups;
-        finder.hold_flow = false;   // (the flow is held below, after the keep: the overlap and the keep need the slice uploaded again)
-        int rc;
-        if (searched) {
-            rc = finder.find(ctx, s, helper);
-            since_search = 1;
-        } else {
-            std::vector<bf_model> warm;
-            for (const Track &t : tracks) warm.push_back(t.model);
-            rc = finder.find_from(ctx, s, warm, helper);
-            ++since_search;
-        }
+        std::vector<bf_model> warm;
+        for (const Track &t : tracks) warm.push_back(t.model);
+        int rc = searched ? finder.group(ctx, s) : finder.group_from(ctx, s, warm);
+        since_search = searched ? 1 : since_search + 1;
+        if (rc >= 0 && !holding) rc = finder.flows(ctx, s);   // (holding: after the keep, which needs the slice uploaded again)
         if (rc < 0) { error = finder.error; return rc; }
+        const Grouping &g = finder.grouping;
         last_events = (int64_t)s.n;
-        last_unassigned = finder.counts.empty() ? 0 : (int64_t)finder.counts.back();
-        const int32_t K = (int32_t)finder.models.size();
+        last_unassigned = g.counts.empty() ? 0 : (int64_t)g.counts.back();
+        const int32_t K = (int32_t)g.models.size();
         std::vector<Track> before;
         before.swap(tracks);
         kept = have_plane ? (int32_t)before.size() : 0;
@@ -137,25 +129,23 @@ class ObjectTracker {
             for (const Track &t : before) ended.push_back(t.id);
             have_plane = false;
             rc = bf_track_drop(ctx);
-            return rc < 0 ? fail(ctx, rc) : BF_OK;
+            return rc < 0 ? ObjectFinder::fail(ctx, rc, error) : BF_OK;
         }
         bf_track_opts o = bf_track_opts();
         o.scale = finder.assign.scale;
         o.sensor_res_x = finder.assign.sensor_res_x; o.sensor_res_y = finder.assign.sensor_res_y;
         o.margin = finder.assign.margin;
-        // the final grouping on the context, as the finder's held_flows puts it there
-        rc = bf_upload_events(ctx, s.fr_x, s.fr_y, s.t_ns, nullptr, (int64_t)s.n);
-        if (rc >= 0 && hold_flow) rc = bf_global_set_window(ctx, finder.search_scale, finder.search_wsize, nullptr);
-        if (rc >= 0) rc = bf_set_groups(ctx, finder.gid.data(), K);
+        // the final grouping on the context, under the held flow's window when a flow is going to be held
+        rc = hold_grouping(ctx, s, g.gid, g.models.size(), holding ? finder.search_scale : 0, finder.search_wsize);
         std::vector<int32_t> continues((size_t)K, -1);
         if (rc >= 0 && have_plane) {
             overlap.assign((size_t)K * (size_t)(kept + 1), 0);
             inside.assign((size_t)K, 0);
-            rc = bf_track_overlap(ctx, &o, finder.models.data(), K, dt, overlap.data(), inside.data(), nullptr);
+            rc = bf_track_overlap(ctx, &o, g.models.data(), K, dt, overlap.data(), inside.data(), nullptr);
             if (rc >= 0) continues = match(overlap, inside, K, kept, match_num, match_den);
         }
-        if (rc >= 0) rc = bf_track_keep(ctx, &o, finder.models.data(), K, nullptr, nullptr);
-        if (rc < 0) { have_plane = false; return fail(ctx, rc); }
+        if (rc >= 0) rc = bf_track_keep(ctx, &o, g.models.data(), K, nullptr, nullptr);
+        if (rc < 0) { have_plane = false; return ObjectFinder::fail(ctx, rc, error); }
         have_plane = true;
         std::vector<char> continued(before.size(), 0);
         on_track.assign((size_t)K, 0);
@@ -171,30 +161,38 @@ class ObjectTracker {
                 t.id = next_id++;
                 t.age = 0;
             }
-            t.model = finder.models[(size_t)k];
-            t.events = finder.counts[(size_t)k];
+            t.model = g.models[(size_t)k];
+            t.events = g.counts[(size_t)k];
             tracks.push_back(t);
         }
         for (size_t j = 0; j < before.size(); ++j)
             if (!continued[j]) ended.push_back(before[j].id);
-        if (hold_flow) {
-            finder.hold_flow = true;
-            rc = bf_hold_groups(ctx, finder.models.data(), K);
-            if (rc >= 0) rc = bf_group_flow_medians(ctx, finder.flow_u.data(), finder.flow_v.data(), nullptr);
-            if (rc < 0) return fail(ctx, rc);
+        if (holding) {
+            rc = finder.held_flows(ctx);
+            if (rc < 0) return ObjectFinder::fail(ctx, rc, error);
         }
         return BF_OK;
+    }
+
+    // objects_N.tracks.txt: the path the slice took, then per group its track, the track's age, its events, those inside under
+    // its model carried back by dt and those of them on its own track's pixels, then the tracks that ended.
+    bool write_tracks(const std::string &path) const {
+        FILE *f = std::fopen(path.c_str(), "w");
+        if (!f) return false;
+        std::fprintf(f, "searched %d dt_ns %lld\n", searched ? 1 : 0, (long long)dt_ns);
+        for (size_t k = 0; k < tracks.size(); ++k)
+            std::fprintf(f, "%zu %d %d %d %d %d\n", k, (int)tracks[k].id, (int)tracks[k].age, (int)tracks[k].events,
+                         inside.empty() ? 0 : (int)inside[k], (int)on_track[k]);
+        std::fprintf(f, "ended");
+        for (int32_t id : ended) std::fprintf(f, " %d", (int)id);
+        std::fprintf(f, "\n");
+        return std::fclose(f) == 0;
     }
 
   private:
     int since_search = 0;
     int64_t last_events = 0, last_unassigned = 0;
     bool have_plane = false;
-    int fail(bf_ctx *ctx, int rc) {
-        const char *m = bf_last_error(ctx);
-        error = m ? m : "";
-        return rc;
-    }
 };
 
 }  // namespace bf

@@ -397,11 +397,11 @@ int run_ring(const Options &o) {
         cfg.lattice.x_step = cfg.lattice.y_step = o.objects_step * k;
         cfg.propose.radius = o.objects_radius; cfg.propose.suppress = o.objects_suppress;
         cfg.propose.max_models = o.objects; cfg.propose.min_votes = o.objects_min_votes;
-        cfg.assign.scale = cfg.fit.scale = o.objects_scale;
-        cfg.wide_groups = o.objects_wide;
+        cfg.assign.scale = cfg.refit.fit.scale = o.objects_scale;
+        cfg.refit.wide = o.objects_wide;
         if (merging) {
             cfg.merge_num = o.objects_merge_num; cfg.merge_den = o.objects_merge_den;
-            cfg.dissolve_below = o.objects_min_events >= 0 ? o.objects_min_events : cfg.fit.min_events;
+            cfg.dissolve_below = o.objects_min_events >= 0 ? o.objects_min_events : cfg.refit.fit.min_events;
         }
         estimator.set_generate_objects(cfg, o.frame_prefix);
         if (o.objects_flow) {
@@ -418,7 +418,7 @@ int run_ring(const Options &o) {
             }
             estimator.set_generate_objects_img(o.objects_img_gain);
         }
-        if (o.objects_track) {   // (last: the tracker takes the finder's configuration as it stands)
+        if (o.objects_track) {
             if (const char *missing = bf::ObjectTracker::missing_entry(merging, o.objects_flow)) {
                 std::fprintf(stderr, "--objects-track needs %s, which this build of the library does not have\n", missing);
                 return 2;

@@ -1,6 +1,6 @@
-// test_groups_wide.cpp -- the host classes with wide groups (bf::MotionAssigner::wide_groups and what hands it down) as a
-// stand-alone program linked against libbf_accel.so: everything is run two ways -- wide_groups = true with helper = nullptr, and
-// wide_groups = false with a helper context -- and must leave the same bytes.
+// test_groups_wide.cpp -- the host classes with wide groups (bf::Refit::wide, held by every class that refits) as a
+// stand-alone program linked against libbf_accel.so: everything is run two ways -- wide = true with helper = nullptr, and
+// wide = false with a helper context -- and must leave the same bytes.
 //
 //   test_groups_wide <prefix> <models.bin> <K> <step_ns> <res_x> <res_y> <events_0.txt> [<events_1.txt> ...]
 //
@@ -11,60 +11,15 @@
 // host wall clock of every call in ms, both ways (each call ends synchronised).  Exit 0 when all three are the same.
 #include <better_flow/object_tracker.h>
 
+#include "object_test_common.h"
+
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
 
-struct Events {
-    std::vector<int32_t> fx, fy, t;
-};
-
-static bool read_events(const char *path, Events &e) {
-    FILE *f = std::fopen(path, "r");
-    if (!f) return false;
-    char line[256];
-    while (std::fgets(line, sizeof(line), f)) {
-        long a, b, c;
-        if (std::sscanf(line, "%ld %ld %ld", &a, &b, &c) != 3) continue;
-        e.fx.push_back((int32_t)a); e.fy.push_back((int32_t)b); e.t.push_back((int32_t)c);
-    }
-    std::fclose(f);
-    return true;
-}
-
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-// everything compared goes through one byte string
-struct Bytes {
-    std::string s;
-    template <class T> void add(const std::vector<T> &v) {
-        const uint64_t n = v.size();
-        s.append(reinterpret_cast<const char *>(&n), sizeof(n));
-        if (n) s.append(reinterpret_cast<const char *>(v.data()), n * sizeof(T));
-    }
-    void add(int64_t v) { s.append(reinterpret_cast<const char *>(&v), sizeof(v)); }
-    void add(const std::vector<bf::MotionAssigner::Record> &recs) {
-        add((int64_t)recs.size());
-        for (const bf::MotionAssigner::Record &r : recs) {
-            add((int64_t)r.changed);
-            add(r.counts);
-            add(r.iterations);
-        }
-    }
-};
-
-static void configure(bf::ObjectFinder &of, int K, int res_x, int res_y) {   // (as tests/cpp/test_object_tracker.cpp)
-    of.lattice.x_low = of.lattice.y_low = -0.72;
-    of.lattice.x_hi = of.lattice.y_hi = 0.72;
-    of.lattice.x_step = of.lattice.y_step = 0.04;
-    of.propose.max_models = K;
-    of.assign.sensor_res_x = of.fit.sensor_res_x = of.fit.guard_res_x = res_x;
-    of.assign.sensor_res_y = of.fit.sensor_res_y = of.fit.guard_res_y = res_y;
-    of.fit.min_events = 100;
-    of.fit.hard_iter_cap = 20000;
 }
 
 int main(int argc, char **argv) {
@@ -102,16 +57,19 @@ int main(int argc, char **argv) {
             return 1;
         }
         const Events &e0 = slices[0];
-        const bf::MotionAssigner::Slice s0 = {e0.fx.data(), e0.fy.data(), e0.t.data(), e0.fx.size()};
+        const bf::Slice s0 = e0.slice();
         {   // the alternation from the given models
             bf::ObjectFinder cfg;
             configure(cfg, K, res_x, res_y);
+            cfg.refit.wide = wide;
+            cfg.refit.helper = helper;
             bf::MotionAssigner ma;
-            ma.fit = cfg.fit;
-            ma.wide_groups = wide;
+            ma.refit = cfg.refit;
+            bf::Grouping g;
             for (int rep = 0; rep < 2; ++rep) {   // (the second is the warm figure: the first also loads the kernels)
                 const auto t0 = std::chrono::steady_clock::now();
-                const int rc = ma.alternate(ctx, s0, start, cfg.assign, cfg.rounds_per_fit, cfg.max_alternations, helper);
+                g = bf::Grouping(start, s0.n);
+                const int rc = ma.alternate(ctx, s0, g, cfg.assign, cfg.rounds_per_fit, cfg.max_alternations);
                 std::fprintf(times, "%s alternate (run %d, %zu alternations): %.3f ms\n", name, rep, ma.records.size(), ms_since(t0));
                 if (rc != BF_OK) {
                     std::fprintf(stderr, "test_groups_wide: %s alternate: %d: %s\n", name, rc, bf_last_error(ctx));
@@ -119,40 +77,41 @@ int main(int argc, char **argv) {
                 }
             }
             Bytes b;
-            b.add(ma.gid); b.add(ma.models); b.add(ma.counts); b.add(ma.records);
+            b.add(g.gid); b.add(g.models); b.add(g.counts); b.add(ma.records);
             got[way][0] = b.s;
         }
         {   // the finder on slice 0
             bf::ObjectFinder of;
             configure(of, K, res_x, res_y);
-            of.wide_groups = wide;
+            of.refit.wide = wide;
+            of.refit.helper = helper;
             const auto t0 = std::chrono::steady_clock::now();
-            const int rc = of.find(ctx, s0, helper);
+            const int rc = of.find(ctx, s0);
             std::fprintf(times, "%s find slice 0: %.3f ms\n", name, ms_since(t0));
             if (rc != BF_OK) {
                 std::fprintf(stderr, "test_groups_wide: %s find: %d: %s\n", name, rc, of.error.c_str());
                 return 1;
             }
             Bytes b;
-            b.add(of.gid); b.add(of.models); b.add(of.counts); b.add(of.records); b.add(of.flow_u); b.add(of.flow_v); b.add(of.origin);
+            b.add(of.grouping.gid); b.add(of.grouping.models); b.add(of.grouping.counts); b.add(of.records); b.add(of.flow_u); b.add(of.flow_v); b.add(of.grouping.origin);
             got[way][1] = b.s;
         }
         {   // the tracker over the slices
             bf::ObjectTracker tr;
             configure(tr.finder, K, res_x, res_y);
-            tr.wide_groups = wide;
+            tr.finder.refit.wide = wide;
+            tr.finder.refit.helper = helper;
             Bytes b;
             for (size_t n = 0; n < slices.size(); ++n) {
                 const Events &e = slices[n];
-                const bf::MotionAssigner::Slice sl = {e.fx.data(), e.fy.data(), e.t.data(), e.fx.size()};
                 const auto t0 = std::chrono::steady_clock::now();
-                const int rc = tr.next(ctx, sl, n ? step : 0, helper);
+                const int rc = tr.next(ctx, e.slice(), n ? step : 0);
                 std::fprintf(times, "%s next slice %zu (searched %d): %.3f ms\n", name, n, tr.searched ? 1 : 0, ms_since(t0));
                 if (rc != BF_OK) {
                     std::fprintf(stderr, "test_groups_wide: %s next (slice %zu): %d: %s\n", name, n, rc, tr.error.c_str());
                     return 1;
                 }
-                b.add(tr.finder.gid); b.add(tr.finder.models); b.add(tr.finder.counts); b.add(tr.finder.records);
+                b.add(tr.finder.grouping.gid); b.add(tr.finder.grouping.models); b.add(tr.finder.grouping.counts); b.add(tr.finder.records);
                 b.add(tr.overlap); b.add(tr.inside); b.add(tr.on_track); b.add(tr.ended);
                 b.add((int64_t)tr.searched); b.add((int64_t)tr.kept);
                 for (const bf::ObjectTracker::Track &t : tr.tracks) { b.add((int64_t)t.id); b.add((int64_t)t.age); b.add((int64_t)t.events); }

@@ -76,11 +76,11 @@ int main(int argc, char **argv) {
     o.margin = std::atoi(argv[7]);
     o.min_score = std::atoi(argv[8]);
     bf::MotionAssigner ma;
-    ma.fit.scale = o.scale;
-    ma.fit.sensor_res_x = o.sensor_res_x; ma.fit.sensor_res_y = o.sensor_res_y;
-    ma.fit.guard_res_x = std::atoi(argv[9]); ma.fit.guard_res_y = std::atoi(argv[10]);
-    ma.fit.min_events = std::atoi(argv[11]);
-    ma.fit.hard_iter_cap = std::atoi(argv[12]);
+    ma.refit.fit.scale = o.scale;
+    ma.refit.fit.sensor_res_x = o.sensor_res_x; ma.refit.fit.sensor_res_y = o.sensor_res_y;
+    ma.refit.fit.guard_res_x = std::atoi(argv[9]); ma.refit.fit.guard_res_y = std::atoi(argv[10]);
+    ma.refit.fit.min_events = std::atoi(argv[11]);
+    ma.refit.fit.hard_iter_cap = std::atoi(argv[12]);
     const int rounds = std::atoi(argv[13]), max_alt = std::atoi(argv[14]);
     const std::string prefix = argv[15];
 
@@ -89,7 +89,7 @@ int main(int argc, char **argv) {
     if (bf_create(0, (int64_t)fx.size() + 1, s * o.sensor_res_x + s, s * o.sensor_res_y + s, nullptr, &ctx) != BF_OK ||
         bf_create(0, (int64_t)fx.size() + 1, s * o.sensor_res_x + s, s * o.sensor_res_y + s, nullptr, &helper) != BF_OK)
         return die("bf_create", nullptr);
-    const bf::MotionAssigner::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
+    const bf::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
     std::printf("path %s\n", bf::MotionAssigner::device_available() ? "device" : "host");
 
     // a round with a prior before any grouping is held is refused on either path
@@ -103,14 +103,16 @@ int main(int argc, char **argv) {
     if (ma.assign(ctx, cand, o) != BF_OK) return die("assign with a prior", ctx);
     if (!dump(prefix + "second.i32", flat(ma))) return die("cannot write the outputs", nullptr);
 
-    if (ma.alternate(ctx, sl, cand, o, rounds, max_alt, helper) != BF_OK) return die("alternate", ctx);
+    ma.refit.helper = helper;
+    bf::Grouping g(cand, sl.n);
+    if (ma.alternate(ctx, sl, g, o, rounds, max_alt) != BF_OK) return die("alternate", ctx);
     std::vector<int32_t> rec;
     for (const bf::MotionAssigner::Record &r : ma.records) {
         rec.push_back(r.changed);
         rec.insert(rec.end(), r.counts.begin(), r.counts.end());
         for (int k = 0; k < K; ++k) rec.push_back(r.iterations.empty() ? -1 : r.iterations[(size_t)k]);
     }
-    if (!dump(prefix + "models.bin", ma.models) || !dump(prefix + "gid.i32", ma.gid) || !dump(prefix + "records.i32", rec))
+    if (!dump(prefix + "models.bin", g.models) || !dump(prefix + "gid.i32", g.gid) || !dump(prefix + "records.i32", rec))
         return die("cannot write the outputs", nullptr);
     bf_destroy(helper);
     bf_destroy(ctx);

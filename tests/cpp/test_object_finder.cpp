@@ -40,26 +40,27 @@ int main(int argc, char **argv) {
     of.lattice.x_hi = of.lattice.y_hi = 0.72;
     of.lattice.x_step = of.lattice.y_step = 0.04;
     of.propose.max_models = std::atoi(argv[2]);
-    of.assign.sensor_res_x = of.fit.sensor_res_x = std::atoi(argv[3]);
-    of.assign.sensor_res_y = of.fit.sensor_res_y = std::atoi(argv[4]);
-    of.fit.guard_res_x = std::atoi(argv[5]); of.fit.guard_res_y = std::atoi(argv[6]);
-    of.fit.min_events = std::atoi(argv[7]);
-    of.fit.hard_iter_cap = std::atoi(argv[8]);
+    of.assign.sensor_res_x = of.refit.fit.sensor_res_x = std::atoi(argv[3]);
+    of.assign.sensor_res_y = of.refit.fit.sensor_res_y = std::atoi(argv[4]);
+    of.refit.fit.guard_res_x = std::atoi(argv[5]); of.refit.fit.guard_res_y = std::atoi(argv[6]);
+    of.refit.fit.min_events = std::atoi(argv[7]);
+    of.refit.fit.hard_iter_cap = std::atoi(argv[8]);
     const std::string prefix = argv[9];
     bf_ctx *ctx = nullptr, *helper = nullptr;
-    const int rows = 3 * of.fit.sensor_res_x + 3, cols = 3 * of.fit.sensor_res_y + 3;
+    const int rows = 3 * of.refit.fit.sensor_res_x + 3, cols = 3 * of.refit.fit.sensor_res_y + 3;
     if (bf_create(0, (int64_t)fx.size() + 1, rows, cols, nullptr, &ctx) != BF_OK ||
         bf_create(0, (int64_t)fx.size() + 1, rows, cols, nullptr, &helper) != BF_OK) {
         std::fprintf(stderr, "test_object_finder: bf_create failed\n");
         return 1;
     }
-    const bf::MotionAssigner::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
-    const int rc = of.find(ctx, sl, helper);
+    const bf::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
+    of.refit.helper = helper;
+    const int rc = of.find(ctx, sl);
     if (rc != BF_OK) {
         std::fprintf(stderr, "test_object_finder: find: %d: %s\n", rc, of.error.c_str());
         return 1;
     }
-    const size_t K = of.models.size();
+    const size_t K = of.grouping.models.size();
     std::vector<int32_t> rec;
     for (const bf::MotionAssigner::Record &r : of.records) {
         rec.push_back(r.changed);
@@ -68,7 +69,7 @@ int main(int argc, char **argv) {
     }
     std::vector<double> flows(of.flow_u);
     flows.insert(flows.end(), of.flow_v.begin(), of.flow_v.end());
-    const bool ok = dump(prefix + "gid.i32", of.gid) && dump(prefix + "models.bin", of.models) &&
+    const bool ok = dump(prefix + "gid.i32", of.grouping.gid) && dump(prefix + "models.bin", of.grouping.models) &&
                     dump(prefix + "proposals.bin", of.proposals) && dump(prefix + "flows.f64", flows) && dump(prefix + "records.i32", rec);
     bf_destroy(helper);
     bf_destroy(ctx);

@@ -17,6 +17,8 @@
 //       prints what bf::ObjectFinder::missing_entry names without and with hold_flow, one per line ("-": nothing).
 #include <better_flow/object_finder.h>
 
+#include "object_test_common.h"
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,31 +33,6 @@ static bool dump(const std::string &path, const T *v, size_t n) {
     return std::fclose(f) == 0;
 }
 
-static bool read_events(const char *path, std::vector<int32_t> &fx, std::vector<int32_t> &fy, std::vector<int32_t> &t) {
-    FILE *f = std::fopen(path, "r");
-    if (!f) return false;
-    char line[256];
-    while (std::fgets(line, sizeof(line), f)) {
-        long a, b, c;
-        if (std::sscanf(line, "%ld %ld %ld", &a, &b, &c) != 3) continue;
-        fx.push_back((int32_t)a); fy.push_back((int32_t)b); t.push_back((int32_t)c);
-    }
-    std::fclose(f);
-    return true;
-}
-
-static void configure(bf::ObjectFinder &of, char **argv) {
-    of.lattice.x_low = of.lattice.y_low = -0.72;
-    of.lattice.x_hi = of.lattice.y_hi = 0.72;
-    of.lattice.x_step = of.lattice.y_step = 0.04;
-    of.propose.max_models = std::atoi(argv[3]);
-    of.assign.sensor_res_x = of.fit.sensor_res_x = std::atoi(argv[4]);
-    of.assign.sensor_res_y = of.fit.sensor_res_y = std::atoi(argv[5]);
-    of.fit.guard_res_x = std::atoi(argv[6]); of.fit.guard_res_y = std::atoi(argv[7]);
-    of.fit.min_events = std::atoi(argv[8]);
-    of.fit.hard_iter_cap = std::atoi(argv[9]);
-}
-
 static void configure_merge(bf::ObjectFinder &of, char **argv) {
     of.merge_num = std::strtoull(argv[11], nullptr, 10);
     of.merge_den = std::strtoull(argv[12], nullptr, 10);
@@ -63,32 +40,35 @@ static void configure_merge(bf::ObjectFinder &of, char **argv) {
 }
 
 static int run_find(int argc, char **argv) {
-    std::vector<int32_t> fx, fy, t;
-    if (!read_events(argv[2], fx, fy, t)) return 1;
+    Events e;
+    if (!read_events(argv[2], e)) return 1;
+    const std::vector<int32_t> &fx = e.fx;
     const std::string prefix = argv[10];
     bf::ObjectFinder plain, held;
-    configure(plain, argv);
-    configure(held, argv);
+    for (bf::ObjectFinder *of : {&plain, &held})
+        configure(*of, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]), std::atoi(argv[7]), std::atoi(argv[8]),
+                  std::atoi(argv[9]));
     if (argc == 14) {
         configure_merge(plain, argv);
         configure_merge(held, argv);
     }
     held.hold_flow = true;
-    const int res_x = plain.fit.sensor_res_x, res_y = plain.fit.sensor_res_y;
+    const int res_x = plain.refit.fit.sensor_res_x, res_y = plain.refit.fit.sensor_res_y;
     bf_ctx *ctx = nullptr, *helper = nullptr;
     if (bf_create(0, (int64_t)fx.size() + 1, 3 * res_x + 3, 3 * res_y + 3, nullptr, &ctx) != BF_OK ||
         bf_create(0, (int64_t)fx.size() + 1, 3 * res_x + 3, 3 * res_y + 3, nullptr, &helper) != BF_OK)
         return 1;
-    const bf::MotionAssigner::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
-    int rc = plain.find(ctx, sl, helper);
-    if (rc == BF_OK) rc = held.find(ctx, sl, helper);
+    plain.refit.helper = held.refit.helper = helper;
+    const bf::Slice sl = e.slice();
+    int rc = plain.find(ctx, sl);
+    if (rc == BF_OK) rc = held.find(ctx, sl);
     if (rc != BF_OK) {
         std::fprintf(stderr, "test_object_flow: find: %d: %s%s\n", rc, plain.error.c_str(), held.error.c_str());
         return 1;
     }
-    const size_t K = plain.models.size();
-    if (held.models.size() != K || held.gid != plain.gid || held.counts != plain.counts ||
-        (K && std::memcmp(held.models.data(), plain.models.data(), K * sizeof(bf_model)) != 0)) {
+    const size_t K = plain.grouping.models.size();
+    if (held.grouping.models.size() != K || held.grouping.gid != plain.grouping.gid || held.grouping.counts != plain.grouping.counts ||
+        (K && std::memcmp(held.grouping.models.data(), plain.grouping.models.data(), K * sizeof(bf_model)) != 0)) {
         std::fprintf(stderr, "test_object_flow: hold_flow changed the grouping or the models\n");
         return 3;
     }
@@ -100,8 +80,8 @@ static int run_find(int argc, char **argv) {
             return 5;
         }
         if (!held.flow_u.empty() || !held.flow_v.empty() || !plain.flow_u.empty()) return 3;
-        const bool ok = dump(prefix + "gid.i32", held.gid.data(), held.gid.size()) &&
-                        dump(prefix + "counts.i32", held.counts.data(), held.counts.size());
+        const bool ok = dump(prefix + "gid.i32", held.grouping.gid.data(), held.grouping.gid.size()) &&
+                        dump(prefix + "counts.i32", held.grouping.counts.data(), held.grouping.counts.size());
         bf_destroy(helper);
         bf_destroy(ctx);
         return ok ? 0 : 1;
@@ -112,15 +92,15 @@ static int run_find(int argc, char **argv) {
     std::vector<int32_t> counts(K + 1);
     if (bf_global_get_flow(ctx, nullptr, nullptr, u.data(), v.data(), nullptr, nullptr) != BF_OK ||
         bf_global_render_flow_frame(ctx, res_x, res_y, BF_FLOW_LAST_UPLOADED, ppm.data(), nullptr, flo.data()) != BF_OK ||
-        bf_group_flow_medians(ctx, nullptr, nullptr, counts.data()) != BF_OK || counts != held.counts) {
+        bf_group_flow_medians(ctx, nullptr, nullptr, counts.data()) != BF_OK || counts != held.grouping.counts) {
         std::fprintf(stderr, "test_object_flow: the context holds no flow of the slice: %s\n", bf_last_error(ctx));
         return 4;
     }
     std::vector<double> a(plain.flow_u), b(held.flow_u);
     a.insert(a.end(), plain.flow_v.begin(), plain.flow_v.end());
     b.insert(b.end(), held.flow_v.begin(), held.flow_v.end());
-    const bool ok = dump(prefix + "gid.i32", held.gid.data(), held.gid.size()) && dump(prefix + "models.bin", held.models.data(), K) &&
-                    dump(prefix + "counts.i32", held.counts.data(), held.counts.size()) && dump(prefix + "flow_host.f64", a.data(), a.size()) &&
+    const bool ok = dump(prefix + "gid.i32", held.grouping.gid.data(), held.grouping.gid.size()) && dump(prefix + "models.bin", held.grouping.models.data(), K) &&
+                    dump(prefix + "counts.i32", held.grouping.counts.data(), held.grouping.counts.size()) && dump(prefix + "flow_host.f64", a.data(), a.size()) &&
                     dump(prefix + "flow_held.f64", b.data(), b.size()) && dump(prefix + "held_u.f64", u.data(), u.size()) &&
                     dump(prefix + "held_v.f64", v.data(), v.size()) && dump(prefix + "frame.ppm.u8", ppm.data(), ppm.size()) &&
                     dump(prefix + "frame.flo.f32", flo.data(), flo.size());

@@ -16,6 +16,8 @@
 #include <better_flow/object_finder.h>
 #include <better_flow/object_merge.h>
 
+#include "object_test_common.h"
+
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,24 +37,12 @@ static bool dump(const std::string &path, const T *v, size_t n) {
     return std::fclose(f) == 0;
 }
 
-static bool read_events(const char *path, std::vector<int32_t> &fx, std::vector<int32_t> &fy, std::vector<int32_t> &t) {
-    FILE *f = std::fopen(path, "r");
-    if (!f) return false;
-    char line[256];
-    while (std::fgets(line, sizeof(line), f)) {
-        long a, b, c;
-        if (std::sscanf(line, "%ld %ld %ld", &a, &b, &c) != 3) continue;
-        fx.push_back((int32_t)a); fy.push_back((int32_t)b); t.push_back((int32_t)c);
-    }
-    std::fclose(f);
-    return true;
-}
-
 static int run_scores(char **argv) {
     const int K = std::atoi(argv[5]);
     if (K < 1) return die("bad model count", nullptr);
-    std::vector<int32_t> fx, fy, t;
-    if (!read_events(argv[2], fx, fy, t)) return die("cannot read the events", nullptr);
+    Events e;
+    if (!read_events(argv[2], e)) return die("cannot read the events", nullptr);
+    const std::vector<int32_t> &fx = e.fx;
     std::vector<int32_t> ids(fx.size());
     std::vector<bf_model> models((size_t)K);
     FILE *f = std::fopen(argv[3], "rb");
@@ -76,7 +66,7 @@ static int run_scores(char **argv) {
         return die("bf_create", nullptr);
     const bool device = bf::ObjectMerger::device_available() && bf_set_groups;
     std::printf("path %s\n", device ? "device" : "host");
-    const bf::MotionAssigner::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
+    const bf::Slice sl = e.slice();
     // refused: an id outside -1 .. K-1 (host path), a negative targets_per_pass (either path)
     if (!ids.empty()) {
         std::vector<int32_t> bad(ids);
@@ -88,8 +78,7 @@ static int run_scores(char **argv) {
     m.opts.targets_per_pass = 0;
     int rc;
     if (device) {
-        rc = bf_upload_events(ctx, sl.fr_x, sl.fr_y, sl.t_ns, nullptr, (int64_t)sl.n);
-        if (rc >= 0) rc = bf_set_groups(ctx, ids.data(), K);
+        rc = bf::hold_grouping(ctx, sl, ids, K);
         if (rc >= 0) rc = m.scores(ctx, models);
     } else {
         rc = m.scores_host(ctx, sl, ids, models);
@@ -127,37 +116,32 @@ static int run_pick(char **argv) {
 }
 
 static int run_find(char **argv) {
-    std::vector<int32_t> fx, fy, t;
-    if (!read_events(argv[2], fx, fy, t)) return die("cannot read the events", nullptr);
+    Events e;
+    if (!read_events(argv[2], e)) return die("cannot read the events", nullptr);
+    const std::vector<int32_t> &fx = e.fx;
     bf::ObjectFinder of;
-    of.lattice.x_low = of.lattice.y_low = -0.72;
-    of.lattice.x_hi = of.lattice.y_hi = 0.72;
-    of.lattice.x_step = of.lattice.y_step = 0.04;
-    of.propose.max_models = std::atoi(argv[3]);
-    of.assign.sensor_res_x = of.fit.sensor_res_x = std::atoi(argv[4]);
-    of.assign.sensor_res_y = of.fit.sensor_res_y = std::atoi(argv[5]);
-    of.fit.guard_res_x = std::atoi(argv[6]); of.fit.guard_res_y = std::atoi(argv[7]);
-    of.fit.min_events = std::atoi(argv[8]);
-    of.fit.hard_iter_cap = std::atoi(argv[9]);
+    configure(of, std::atoi(argv[3]), std::atoi(argv[4]), std::atoi(argv[5]), std::atoi(argv[6]), std::atoi(argv[7]), std::atoi(argv[8]),
+              std::atoi(argv[9]));
     of.merge_num = std::strtoull(argv[10], nullptr, 10);
     of.merge_den = std::strtoull(argv[11], nullptr, 10);
     of.dissolve_below = std::atoi(argv[12]);
     const std::string prefix = argv[13];
     bf_ctx *ctx = nullptr, *helper = nullptr;
-    const int rows = 3 * of.fit.sensor_res_x + 3, cols = 3 * of.fit.sensor_res_y + 3;
+    const int rows = 3 * of.refit.fit.sensor_res_x + 3, cols = 3 * of.refit.fit.sensor_res_y + 3;
     if (bf_create(0, (int64_t)fx.size() + 1, rows, cols, nullptr, &ctx) != BF_OK ||
         bf_create(0, (int64_t)fx.size() + 1, rows, cols, nullptr, &helper) != BF_OK)
         return die("bf_create", nullptr);
-    const bf::MotionAssigner::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
-    const int rc = of.find(ctx, sl, helper);
+    of.refit.helper = helper;
+    const int rc = of.find(ctx, e.slice());
     if (rc != BF_OK) {
         std::fprintf(stderr, "test_object_merge: find: %d: %s\n", rc, of.error.c_str());
         return 1;
     }
-    const bool ok = dump(prefix + "gid.i32", of.gid.data(), of.gid.size()) && dump(prefix + "models.bin", of.models.data(), of.models.size()) &&
-                    dump(prefix + "origin.i32", of.origin.data(), of.origin.size()) &&
-                    dump(prefix + "counts.i32", of.counts.data(), of.counts.size()) &&
-                    bf::ObjectMerger::write_steps(prefix + "steps.txt", of.steps, of.models.size(), of.merged_sum_sq);
+    const bf::Grouping &g = of.grouping;
+    const bool ok = dump(prefix + "gid.i32", g.gid.data(), g.gid.size()) && dump(prefix + "models.bin", g.models.data(), g.models.size()) &&
+                    dump(prefix + "origin.i32", g.origin.data(), g.origin.size()) &&
+                    dump(prefix + "counts.i32", g.counts.data(), g.counts.size()) &&
+                    bf::ObjectMerger::write_steps(prefix + "steps.txt", of.steps, g.models.size(), of.merged_sum_sq);
     bf_destroy(helper);
     bf_destroy(ctx);
     return ok ? 0 : 1;

@@ -72,7 +72,7 @@ int main(int argc, char **argv) {
     if (bf_create(0, (int64_t)fx.size() + 1, s * r.opts.sensor_res_x + s, s * r.opts.sensor_res_y + s, nullptr, &ctx) != BF_OK)
         return die("bf_create", nullptr);
     std::printf("path %s\n", bf::ObjectRenderer::device_available() ? "device" : "host");
-    const bf::MotionAssigner::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
+    const bf::Slice sl = {fx.data(), fy.data(), t.data(), fx.size()};
 
     // refused on either path: an id outside -1 .. K-1, a gain of zero
     if (!ids.empty()) {

@@ -11,6 +11,8 @@
 // call ends synchronised: its results are on the host).
 #include <better_flow/object_tracker.h>
 
+#include "object_test_common.h"
+
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -23,36 +25,8 @@ static bool dump(const std::string &path, const std::vector<T> &v) {
     return std::fclose(f) == 0;
 }
 
-struct Events {
-    std::vector<int32_t> fx, fy, t;
-};
-
-static bool read_events(const char *path, Events &e) {
-    FILE *f = std::fopen(path, "r");
-    if (!f) return false;
-    char line[256];
-    while (std::fgets(line, sizeof(line), f)) {
-        long a, b, c;
-        if (std::sscanf(line, "%ld %ld %ld", &a, &b, &c) != 3) continue;
-        e.fx.push_back((int32_t)a); e.fy.push_back((int32_t)b); e.t.push_back((int32_t)c);
-    }
-    std::fclose(f);
-    return true;
-}
-
 static double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-static void configure(bf::ObjectFinder &of, int K, int res_x, int res_y) {
-    of.lattice.x_low = of.lattice.y_low = -0.72;
-    of.lattice.x_hi = of.lattice.y_hi = 0.72;
-    of.lattice.x_step = of.lattice.y_step = 0.04;
-    of.propose.max_models = K;
-    of.assign.sensor_res_x = of.fit.sensor_res_x = of.fit.guard_res_x = res_x;
-    of.assign.sensor_res_y = of.fit.sensor_res_y = of.fit.guard_res_y = res_y;
-    of.fit.min_events = 100;
-    of.fit.hard_iter_cap = 20000;
 }
 
 int main(int argc, char **argv) {
@@ -84,32 +58,32 @@ int main(int argc, char **argv) {
         bf::ObjectFinder of;
         configure(of, K, res_x, res_y);
         const Events &e = slices[0];
-        const bf::MotionAssigner::Slice sl = {e.fx.data(), e.fy.data(), e.t.data(), e.fx.size()};
+        of.refit.helper = helper;
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = of.find(alone, sl, helper);
+        const int rc = of.find(alone, e.slice());
         std::fprintf(times, "find slice 0: %.3f ms\n", ms_since(t0));
         if (rc != BF_OK) {
             std::fprintf(stderr, "test_object_tracker: find: %d: %s\n", rc, of.error.c_str());
             return 1;
         }
-        ok = dump(prefix + "find_gid.i32", of.gid) && dump(prefix + "find_models.bin", of.models) && dump(prefix + "find_counts.i32", of.counts);
+        ok = dump(prefix + "find_gid.i32", of.grouping.gid) && dump(prefix + "find_models.bin", of.grouping.models) && dump(prefix + "find_counts.i32", of.grouping.counts);
     }
     bf::ObjectTracker tr;
     configure(tr.finder, K, res_x, res_y);
+    tr.finder.refit.helper = helper;
     tr.research_every = std::atoi(argv[3]);
     for (size_t n = 0; n < slices.size() && ok; ++n) {
         const Events &e = slices[n];
-        const bf::MotionAssigner::Slice sl = {e.fx.data(), e.fy.data(), e.t.data(), e.fx.size()};
         const auto t0 = std::chrono::steady_clock::now();
-        const int rc = tr.next(ctx, sl, n ? step : 0, helper);
+        const int rc = tr.next(ctx, e.slice(), n ? step : 0);
         std::fprintf(times, "next slice %zu (searched %d): %.3f ms\n", n, tr.searched ? 1 : 0, ms_since(t0));
         if (rc != BF_OK) {
             std::fprintf(stderr, "test_object_tracker: next (slice %zu): %d: %s\n", n, rc, tr.error.c_str());
             return 1;
         }
         const std::string base = prefix + std::to_string(n);
-        ok = dump(base + "_gid.i32", tr.finder.gid) && dump(base + "_models.bin", tr.finder.models) &&
-             dump(base + "_counts.i32", tr.finder.counts) && dump(base + "_overlap.i32", tr.overlap) && dump(base + "_inside.i32", tr.inside);
+        ok = dump(base + "_gid.i32", tr.finder.grouping.gid) && dump(base + "_models.bin", tr.finder.grouping.models) &&
+             dump(base + "_counts.i32", tr.finder.grouping.counts) && dump(base + "_overlap.i32", tr.overlap) && dump(base + "_inside.i32", tr.inside);
         FILE *f = std::fopen((base + ".txt").c_str(), "w");
         if (!f) return 1;
         std::fprintf(f, "searched %d kept %d dt_ns %lld\n", tr.searched ? 1 : 0, (int)tr.kept, (long long)tr.dt_ns);

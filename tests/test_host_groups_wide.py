@@ -1,9 +1,9 @@
-"""The host classes with wide groups (bf::MotionAssigner::wide_groups, handed down by bf::ObjectFinder, bf::ObjectMerger and
-bf::ObjectTracker to bf::ObjectTasks::wide) and bf_motion_compensator --objects-wide, on the GPU.
+"""The host classes with wide groups (bf::Refit::wide, held by bf::MotionAssigner, bf::ObjectMerger and bf::ObjectFinder and
+given to bf::ObjectTasks::wide) and bf_motion_compensator --objects-wide, on the GPU.
 
 tests/cpp/test_groups_wide.cpp linked against the product library runs MotionAssigner::alternate from the scene's two true models,
-ObjectFinder::find, and the three slices of tests/track_scene.py through ObjectTracker::next, each two ways -- wide_groups = true
-with helper = nullptr, and wide_groups = false with a helper context -- and compares ids, models, counts and records as bytes.
+ObjectFinder::find, and the three slices of tests/track_scene.py through ObjectTracker::next, each two ways -- wide = true
+with helper = nullptr, and wide = false with a helper context -- and compares ids, models, counts and records as bytes.
 The command line writes objects_N.txt and objects_N.tracks.txt byte for byte as without the flag."""
 import os
 import subprocess
