@@ -1,8 +1,9 @@
-// bf_assign.h -- launchers of the assignment kernels (bf_assign.hip) and of the kernels that project a grouping (bf_project.hip),
-// both for bf_assign_abi.cpp, which sets up the K vote planes they share once; and of the kernels that propose the candidate
-// models (bf_propose.hip) for bf_propose_abi.cpp.  The definitions they implement are in include/bf_accel.h ("event groups:
-// assignment", "event groups: candidate models", "event groups: projection").  Every launcher enqueues plain launches on the
-// given stream; no kernel waits for another work-group.  What the kernel files share on the device is in bf_device_fns.h: the box
+// bf_assign.h -- launchers of the kernels on the K models' vote planes -- assignment (bf_assign.hip), projection of a grouping
+// (bf_project.hip) and merge gains (bf_merge.hip) -- for bf_assign_abi.cpp, which sets up the planes they share once; and of the
+// kernels that propose the candidate models (bf_propose.hip) for bf_propose_abi.cpp.  The definitions they implement are in
+// include/bf_accel.h ("event groups: assignment", "event groups: candidate models", "event groups: projection", "event groups:
+// merge gains").  Where the words of a result block sit is bf_group_blocks.h's, for the kernels and the host alike.  Every
+// launcher enqueues plain launches on the given stream; no kernel waits for another work-group.  What the kernel files share on the device is in bf_device_fns.h: the box
 // sum of a tile (box_sum_tile: k_assign_box, k_propose_box), the tally per distinct key of a wave (for_each_wave_key) and the
 // wave reductions.
 #pragma once
@@ -11,6 +12,7 @@
 #include <cstdint>
 
 #include "bf_device.h"
+#include "bf_group_blocks.h"
 
 namespace bf {
 
@@ -26,14 +28,11 @@ struct AssignArgs {
     int K, scale, x_sh, y_sh, wsx, wsy, R, C;
 };
 
-// Words of the result block: counts[K + 1] (last: unassigned), then changed, then max_score.
-inline int assign_out_words(int K) { return K + 3; }
-
 // V (K x R x C words, zero) += the votes.
 void launch_assign_vote(const AssignArgs& a, uint32_t* V, hipStream_t s);
 // B_k = the scale x scale box sum of V_k, every word of B written (scale > 1).
 void launch_assign_box(const uint32_t* V, uint32_t* B, int K, int R, int C, int scale, hipStream_t s);
-// gid / score through perm, and the result block (zero on entry).  B: the box sums, or V itself at scale 1.
+// gid / score through perm, and the result block (AssignBlock, zero on entry).  B: the box sums, or V itself at scale 1.
 void launch_assign_pick(const AssignArgs& a, const uint32_t* B, int min_score, int32_t* gid, int32_t* score, uint32_t* out,
                         hipStream_t s);
 
@@ -64,13 +63,8 @@ void launch_propose_pick(const uint32_t* H, const uint32_t* B, int n_x, int n_y,
 
 // The projection kernels (bf_project.hip; include/bf_accel.h, "event groups: projection").  They share the assignment's window,
 // warps (AssignArgs, its prior the held grouping: here an event's ONE model) and vote planes.
-// The result block, 64-bit words: per group events, inside, pixels_hit, pixels_owned, max, sum_sq (six tables of K), then
-// unassigned, pixels, sum, sum_sq.  Every word sits on a 128-byte line of its own (word w at index w * kProjectStride): the
-// work-groups' atomics on words of one line queue behind each other.
-constexpr int kProjectTables = 6, kProjectTail = 4;
-constexpr int kProjectStride = 16;
-inline int project_out_words(int K) { return (kProjectTables * K + kProjectTail) * kProjectStride; }
-// V (K x R x C words, zero) += one vote per event on its own group's plane; out (zero) += events, inside, unassigned.
+// V (K x R x C words, zero) += one vote per event on its own group's plane; out (ProjectBlock, zero) += events, inside,
+// unassigned.
 void launch_project_vote(const AssignArgs& a, uint32_t* V, unsigned long long* out, hipStream_t s);
 // Per pixel N, the owner and its colour from the K planes B (the box sums, or V itself at scale 1); out += the rest.
 void launch_project_compose(const uint32_t* B, int K, int R, int C, int gain, uint32_t* count, int32_t* label, uint8_t* bgr,
@@ -79,10 +73,7 @@ void launch_project_compose(const uint32_t* B, int K, int R, int C, int gain, ui
 // The merge-gain kernels (bf_merge.hip; include/bf_accel.h, "event groups: merge gains").  The base planes B_k are the
 // projection's (launch_project_vote, launch_assign_box); a pass holds the trial planes of `targets` target models, plane
 // (a_local * K + b) the events of group b under model a0 + a_local.
-// The result block, 64-bit words, each on a line of its own as the projection's: gain[K x K] (word b * K + a), inside[K x K],
-// then sum, sum_sq.
-constexpr int kMergeTail = 2;
-inline int merge_out_words(int K) { return (2 * K * K + kMergeTail) * kProjectStride; }
+// The result block is MergeBlock.
 // A = min(K, targets_per_pass or K, floor(2^27 / (K R C))): the target models of one pass (K R C <= 2^27, so A >= 1).
 inline int merge_targets_per_pass(int K, long long plane, int targets_per_pass) {
     long long A = kAssignMaxWords / ((long long)K * plane);

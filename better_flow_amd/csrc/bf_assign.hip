@@ -96,13 +96,14 @@ __global__ __launch_bounds__(kThreads) void k_assign_pick(AssignArgs a, const ui
     // wave's events carry interleaved ids, so a per-wave flush on every change of id (k_seg_events' scheme, where consecutive
     // rounds name one component) issued ~3 same-address global atomics per wave and round -- 407 us of this kernel's time at K = 2
     // and 1.5 ms at K = 8 on 1M events.
-    __shared__ uint32_t s_out[kAssignMaxModels + 3];
-    for (int w = threadIdx.x; w < a.K + 3; w += kThreads) s_out[w] = 0u;
+    __shared__ uint32_t s_out[AssignBlock::size(kAssignMaxModels)];   // (the block is unstrided: the table is its image)
+    const int nout = AssignBlock::size(a.K);
+    for (int w = threadIdx.x; w < nout; w += kThreads) s_out[w] = 0u;
     __syncthreads();
     int changed = 0, top = 0;
 #pragma unroll
     for (int j = 0; j < kAssignEv; ++j) {
-        int slot = -1;   // the word of `out` this event counts in: its id, K for -1; -1: no event
+        int slot = -1;   // the word of `out` this event counts in (AssignBlock::count): its id, K for -1; -1: no event
         if (e.pri[j] != -2) {
             const int g = best[j] >= min_score ? arg[j] : -1;
             gid[e.up[j]] = g;
@@ -119,14 +120,14 @@ __global__ __launch_bounds__(kThreads) void k_assign_pick(AssignArgs a, const ui
     changed = (int)wave_sum((long long)changed);
     top = wave_max(top);
     if ((threadIdx.x & 63) == 0) {
-        if (changed) atomicAdd(&s_out[a.K + 1], (uint32_t)changed);
-        if (top) atomicMax(&s_out[a.K + 2], (uint32_t)top);
+        if (changed) atomicAdd(&s_out[AssignBlock::changed(a.K)], (uint32_t)changed);
+        if (top) atomicMax(&s_out[AssignBlock::max_score(a.K)], (uint32_t)top);
     }
     __syncthreads();
-    for (int w = threadIdx.x; w < a.K + 3; w += kThreads) {
+    for (int w = threadIdx.x; w < nout; w += kThreads) {
         const uint32_t v = s_out[w];
         if (!v) continue;
-        if (w == a.K + 2) atomicMax(out + w, v);
+        if (w == AssignBlock::max_score(a.K)) atomicMax(out + w, v);
         else atomicAdd(out + w, v);
     }
 }

@@ -7,76 +7,122 @@
 //                      owning group and its colour -- and scores it: per group and overall the integer moments of that image.
 //   bf_merge_scores    says, for every ordered pair (b, a) of groups, how much of the contrast sum N^2 the events of group b
 //                      add under model a: the projection's planes once, then the trial planes of A target models per pass.
-// What they share is here once: the option checks, the window of the widened sensor and its capacity check (vote_planes_check),
-// and the planes, the staged warps and the kernels' AssignArgs (vote_planes_stage).  Between the two each entry zeroes its own
-// outputs and applies its own rule for a slice without events.
-// (bf_track_keep, bf_track_abi.cpp, drives the projection's kernels through the same three helpers: declared in bf_ctx.h.)
-#include "bf_ctx.h"
+// What they share -- with bf_track_abi.cpp and bf_hold_groups, through bf_vote_planes.h -- is here once: the check that K models
+// are given for the held grouping, the window's checks, the window of the widened sensor and its capacity check; the staging of
+// the K warps and of the planes; and the projection's base pass with the decode of its shared words, which bf_project_groups,
+// bf_merge_scores and bf_track_keep all run.  Around these each entry checks its own option, zeroes its own outputs and applies
+// its own rule for a slice without events.  The scratch is bf_ctx::vote; the result blocks' words are bf_group_blocks.h's.
+#include "bf_vote_planes.h"
 
-// The checks both entries make after those of their own pointers, in their order; `who`: the entry point's name; `knob`: the
-// entry's own option, which must be >= 1, and its name; `prior`: null when the held grouping is not read, else what the message
-// says before "no grouping ... is held".  Then the window and the capacity check.  Fills everything of vp but a's pointers.
-// vote_planes_window: the window alone, of options that have passed these checks (bf_track_overlap: the kept plane's).
-int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_y, int margin, const char* knob_name, int knob,
-                      int n_models, const char* prior, VotePlanes& vp) {
-    if (scale < 1 || scale % 2 == 0 || scale / 2 > kMaxHalfScale)
-        return fail(c, BF_ERR_ARG, "scale must be odd and <= %d (got %d)", 2 * kMaxHalfScale + 1, scale);
-    if (res_x < 1 || res_y < 1 || res_x > 65536 || res_y > 65536) return fail(c, BF_ERR_ARG, "bad sensor size");
-    if (margin < 0 || margin > 65536 || knob < 1)
-        return fail(c, BF_ERR_ARG, "%s: margin %d (0 .. 65536), %s %d (>= 1)", who, margin, knob_name, knob);
+int held_grouping_check(bf_ctx* c, const char* who, int n_models, const char* prior) {
     if (n_models < 1 || n_models > kAssignMaxModels) return fail(c, BF_ERR_ARG, "%s: %d models (1 .. %d)", who, n_models, kAssignMaxModels);
     if (c->has_noise) return fail(c, BF_ERR_ARG, "%s does not take a noise mask", who);
+    if (!prior) return BF_OK;
+    if (!c->groups_valid) return fail(c, BF_ERR_STATE, "%s: %sno grouping of the uploaded slice is held", who, prior);
+    if (c->groups_K != n_models)
+        return fail(c, BF_ERR_ARG, "%s: the held grouping has %d groups, %d models given", who, c->groups_K, n_models);
+    return BF_OK;
+}
+
+int vote_window_check(bf_ctx* c, const VoteWindow& w) {
+    if (w.scale < 1 || w.scale % 2 == 0 || w.scale / 2 > kMaxHalfScale)
+        return fail(c, BF_ERR_ARG, "scale must be odd and <= %d (got %d)", 2 * kMaxHalfScale + 1, w.scale);
+    if (w.res_x < 1 || w.res_y < 1 || w.res_x > 65536 || w.res_y > 65536) return fail(c, BF_ERR_ARG, "bad sensor size");
+    return BF_OK;
+}
+
+int vote_planes_check(bf_ctx* c, const char* who, const VoteWindow& w, int n_models, const char* prior, VotePlanes& vp) {
+    const int rc = held_grouping_check(c, who, n_models, prior);
+    if (rc != BF_OK) return rc;
     const int K = n_models;
-    if (prior) {
-        if (!c->groups_valid) return fail(c, BF_ERR_STATE, "%s: %sno grouping of the uploaded slice is held", who, prior);
-        if (c->groups_K != K) return fail(c, BF_ERR_ARG, "%s: the held grouping has %d groups, %d models given", who, c->groups_K, K);
-    }
-    vote_planes_window(c, scale, res_x, res_y, margin, K, vp);
+    vote_planes_window(c, w, K, vp);
     if ((long long)K * (long long)vp.plane > kAssignMaxWords)
         return fail(c, BF_ERR_CAPACITY, "%s: %d planes of %d x %d exceed 2^27 words", who, K, vp.R, vp.C);
     return BF_OK;
 }
 
-void vote_planes_window(const bf_ctx* c, int scale, int res_x, int res_y, int margin, int K, VotePlanes& vp) {
+void vote_planes_window(const bf_ctx* c, const VoteWindow& o, int K, VotePlanes& vp) {
     // the window of the whole sensor widened by the margin (optimizer_rolling.h:248-283): the same for every call on a sensor
-    const bf_window w = window_of_box(scale, -margin, res_x - 1 + margin, -margin, res_y - 1 + margin);
+    const bf_window w = window_of_box(o.scale, -o.margin, o.res_x - 1 + o.margin, -o.margin, o.res_y - 1 + o.margin);
     vp.R = w.scale_img_x;
     vp.C = w.scale_img_y;
     vp.plane = (size_t)vp.R * (size_t)vp.C;
     AssignArgs& a = vp.a;
-    a.xy = nullptr; a.t = nullptr; a.perm = nullptr; a.wp = nullptr;
-    a.prior = nullptr;
+    a = AssignArgs{};   // (the pointers: null until the staging)
     a.n = c->n;
-    a.K = K; a.scale = scale;
+    a.K = K; a.scale = o.scale;
     a.x_sh = (int)w.x_shift;   // double -> int parameter conversion of accel_lib.h:147
     a.y_sh = (int)w.y_shift;
     a.wsx = w.metric_wsizex; a.wsy = w.metric_wsizey;
     a.R = vp.R; a.C = vp.C;
 }
 
-// (n > 0, the device set) The vote planes grown and V cleared, the box planes grown when they are used, the K warps staged, and
-// a's pointers; `prior`: the held grouping is the kernels' prior.
-int vote_planes_stage(bf_ctx* c, const bf_model* models, bool prior, VotePlanes& vp) {
-    AssignArgs& a = vp.a;
-    const size_t words = (size_t)a.K * vp.plane;
-    HIP_TRY(c, c->d_assign_votes.grow(words));
-    if (a.scale > 1) HIP_TRY(c, c->d_assign_box.grow(words));
-    HIP_TRY(c, c->d_assign_wp.grow((size_t)kAssignMaxModels));
-    HIP_TRY(c, c->h_assign_wp.grow((size_t)kAssignMaxModels));
-    for (int k = 0; k < a.K; ++k) set_model_warp(c->h_assign_wp[k], models[k]);   // (sine and cosine from the host's libm)
-    HIP_TRY(c, hipMemcpyAsync(c->d_assign_wp, c->h_assign_wp, (size_t)a.K * sizeof(WarpParams), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->d_assign_votes, 0, words * sizeof(uint32_t), c->stream));
+int vote_warps_stage(bf_ctx* c, const bf_model* models, int K, bool prior, AssignArgs& a) {
+    bf_ctx::VoteScratch::Shared& sh = c->vote.shared;
+    HIP_TRY(c, sh.d_wp.grow((size_t)kAssignMaxModels));
+    HIP_TRY(c, sh.h_wp.grow((size_t)kAssignMaxModels));
+    for (int k = 0; k < K; ++k) set_model_warp(sh.h_wp[k], models[k]);   // (sine and cosine from the host's libm)
+    HIP_TRY(c, hipMemcpyAsync(sh.d_wp, sh.h_wp, (size_t)K * sizeof(WarpParams), hipMemcpyHostToDevice, c->stream));
     const bf_ctx::EvSet& e = c->set[c->cs];
     a.xy = e.xy; a.t = e.t;
     a.perm = c->has_perm ? e.perm.get() : nullptr;
-    a.wp = c->d_assign_wp;
+    a.wp = sh.d_wp;
     a.prior = prior ? c->d_group_id.get() : nullptr;
     return BF_OK;
 }
 
-// The planes the second kernel of either entry reads: the box sums, or V itself at scale 1.
+int vote_planes_stage(bf_ctx* c, const bf_model* models, bool prior, VotePlanes& vp) {
+    bf_ctx::VoteScratch::Shared& sh = c->vote.shared;
+    const size_t words = (size_t)vp.a.K * vp.plane;
+    HIP_TRY(c, sh.votes.grow(words));
+    if (vp.a.scale > 1) HIP_TRY(c, sh.box.grow(words));
+    const int rc = vote_warps_stage(c, models, vp.a.K, prior, vp.a);   // (the small copy ahead of the long clear, as it always was)
+    if (rc != BF_OK) return rc;
+    HIP_TRY(c, hipMemsetAsync(sh.votes, 0, words * sizeof(uint32_t), c->stream));
+    return BF_OK;
+}
+
 const uint32_t* vote_planes_summed(bf_ctx* c, const VotePlanes& vp) {
-    return vp.a.scale > 1 ? c->d_assign_box.get() : c->d_assign_votes.get();
+    return vp.a.scale > 1 ? c->vote.shared.box.get() : c->vote.shared.votes.get();
+}
+
+int project_base_pass(bf_ctx* c, const bf_model* models, VotePlanes& vp, int gain, int32_t* label) {
+    bf_ctx::VoteScratch::Project& pr = c->vote.project;
+    const AssignArgs& a = vp.a;
+    hipStream_t s = c->stream;
+    const int rc = vote_planes_stage(c, models, true, vp);
+    if (rc != BF_OK) return rc;
+    if (label) {
+        HIP_TRY(c, pr.count.grow(vp.plane));
+        HIP_TRY(c, pr.bgr.grow(3 * vp.plane));
+    }
+    HIP_TRY(c, pr.d_out.grow(ProjectBlock::size(kAssignMaxModels)));
+    HIP_TRY(c, pr.h_out.grow(ProjectBlock::size(kAssignMaxModels)));
+    const size_t bytes = ProjectBlock::size(a.K) * sizeof(unsigned long long);
+    HIP_TRY(c, hipMemsetAsync(pr.d_out, 0, bytes, s));
+    {
+        ProfScope ps(c, 3);
+        launch_project_vote(a, c->vote.shared.votes, pr.d_out, s);
+        if (a.scale > 1) launch_assign_box(c->vote.shared.votes, c->vote.shared.box, a.K, vp.R, vp.C, a.scale, s);
+        if (label) launch_project_compose(vote_planes_summed(c, vp), a.K, vp.R, vp.C, gain, pr.count, label, pr.bgr, pr.d_out, s);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(pr.h_out, pr.d_out, bytes, hipMemcpyDeviceToHost, s));
+    return BF_OK;
+}
+
+ProjectBase project_base_decode(const bf_ctx* c, int K) {
+    const unsigned long long* h = c->vote.project.h_out;
+    ProjectBase b;
+    long long outside = 0;
+    for (int k = 0; k < K; ++k) {
+        b.events[k] = (int32_t)h[ProjectBlock::events(K, k)];
+        b.inside[k] = (int32_t)h[ProjectBlock::inside(K, k)];
+        outside += (long long)h[ProjectBlock::events(K, k)] - (long long)h[ProjectBlock::inside(K, k)];
+    }
+    b.unassigned = (int32_t)h[ProjectBlock::unassigned(K)];
+    b.outside = (int32_t)outside;
+    return b;
 }
 
 extern "C" {
@@ -86,9 +132,12 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
     if (!c) return BF_ERR_ARG;
     if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_assign_groups before bf_upload_events");
     if (!o || !models) return fail(c, BF_ERR_ARG, "bf_assign_groups: opts %p, models %p", (const void*)o, (const void*)models);
+    const VoteWindow w{o->scale, o->sensor_res_x, o->sensor_res_y, o->margin};
     VotePlanes vp;
-    int rc = vote_planes_check(c, "bf_assign_groups", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "min_score",
-                               o->min_score, n_models, o->use_prior ? "use_prior, but " : nullptr, vp);
+    int rc = vote_window_check(c, w);
+    if (rc == BF_OK && (!vote_margin_ok(o->margin) || o->min_score < 1))
+        rc = fail(c, BF_ERR_ARG, "bf_assign_groups: margin %d (0 .. 65536), min_score %d (>= 1)", o->margin, o->min_score);
+    if (rc == BF_OK) rc = vote_planes_check(c, "bf_assign_groups", w, n_models, o->use_prior ? "use_prior, but " : nullptr, vp);
     if (rc != BF_OK) return rc;
     const AssignArgs& a = vp.a;
     const int K = a.K;
@@ -101,38 +150,38 @@ int bf_assign_groups(bf_ctx* c, const bf_assign_opts* o, const bf_model* models,
         return o->install ? install_grouping(c, nullptr, hipMemcpyDeviceToDevice, K) : BF_OK;
     }
 
-    const int nout = assign_out_words(K);
+    bf_ctx::VoteScratch::Shared& sh = c->vote.shared;
+    bf_ctx::VoteScratch::Assign& as = c->vote.assign;
+    const size_t bytes = (size_t)AssignBlock::size(K) * sizeof(uint32_t);
     rc = vote_planes_stage(c, models, o->use_prior != 0, vp);
     if (rc != BF_OK) return rc;
-    HIP_TRY(c, c->d_assign_gid.grow((size_t)c->n));
-    HIP_TRY(c, c->d_assign_score.grow((size_t)c->n));
-    HIP_TRY(c, c->d_assign_out.grow((size_t)assign_out_words(kAssignMaxModels)));
-    HIP_TRY(c, c->h_assign_out.grow((size_t)assign_out_words(kAssignMaxModels)));
-    HIP_TRY(c, hipMemsetAsync(c->d_assign_out, 0, (size_t)nout * sizeof(uint32_t), s));
+    HIP_TRY(c, as.gid.grow((size_t)c->n));
+    HIP_TRY(c, as.score.grow((size_t)c->n));
+    HIP_TRY(c, as.d_out.grow((size_t)AssignBlock::size(kAssignMaxModels)));
+    HIP_TRY(c, as.h_out.grow((size_t)AssignBlock::size(kAssignMaxModels)));
+    HIP_TRY(c, hipMemsetAsync(as.d_out, 0, bytes, s));
     {
         ProfScope ps(c, 3);
-        launch_assign_vote(a, c->d_assign_votes, s);
-        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
-        launch_assign_pick(a, vote_planes_summed(c, vp), o->min_score, c->d_assign_gid, c->d_assign_score, c->d_assign_out, s);
+        launch_assign_vote(a, sh.votes, s);
+        if (a.scale > 1) launch_assign_box(sh.votes, sh.box, K, vp.R, vp.C, a.scale, s);
+        launch_assign_pick(a, vote_planes_summed(c, vp), o->min_score, as.gid, as.score, as.d_out, s);
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_assign_out, c->d_assign_out, (size_t)nout * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (group_id_out)
-        HIP_TRY(c, hipMemcpyAsync(group_id_out, c->d_assign_gid, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (score_out)
-        HIP_TRY(c, hipMemcpyAsync(score_out, c->d_assign_score, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (o->install && (rc = install_grouping(c, c->d_assign_gid, hipMemcpyDeviceToDevice, K)) != BF_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(as.h_out, as.d_out, bytes, hipMemcpyDeviceToHost, s));
+    if (group_id_out) HIP_TRY(c, hipMemcpyAsync(group_id_out, as.gid, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (score_out) HIP_TRY(c, hipMemcpyAsync(score_out, as.score, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (o->install && (rc = install_grouping(c, as.gid, hipMemcpyDeviceToDevice, K)) != BF_OK) return rc;
     HIP_TRY(c, hipStreamSynchronize(s));
-    const uint32_t* r = c->h_assign_out;
+    const uint32_t* r = as.h_out;
     if (counts_out)
-        for (int k = 0; k <= K; ++k) counts_out[k] = (int32_t)r[k];
+        for (int k = 0; k <= K; ++k) counts_out[k] = (int32_t)r[AssignBlock::count(K, k)];
     if (info) {
         info->models = K;
         info->rows = vp.R; info->cols = vp.C;
-        info->unassigned = (int32_t)r[K];
-        info->assigned = (int32_t)(c->n - (long long)r[K]);
-        info->changed = (int32_t)r[K + 1];
-        info->max_score = (int32_t)r[K + 2];
+        info->unassigned = (int32_t)r[AssignBlock::count(K, K)];
+        info->assigned = (int32_t)(c->n - (long long)r[AssignBlock::count(K, K)]);
+        info->changed = (int32_t)r[AssignBlock::changed(K)];
+        info->max_score = (int32_t)r[AssignBlock::max_score(K)];
     }
     return BF_OK;
 }
@@ -142,12 +191,14 @@ int bf_project_groups(bf_ctx* c, const bf_project_opts* o, const bf_model* model
     if (!c) return BF_ERR_ARG;
     if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_project_groups before bf_upload_events");
     if (!o || !models) return fail(c, BF_ERR_ARG, "bf_project_groups: opts %p, models %p", (const void*)o, (const void*)models);
+    const VoteWindow w{o->scale, o->sensor_res_x, o->sensor_res_y, o->margin};
     VotePlanes vp;
-    int rc = vote_planes_check(c, "bf_project_groups", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "gain", o->gain,
-                               n_models, "", vp);   // (the held grouping is required: here an event's ONE model)
+    int rc = vote_window_check(c, w);
+    if (rc == BF_OK && (!vote_margin_ok(o->margin) || o->gain < 1))
+        rc = fail(c, BF_ERR_ARG, "bf_project_groups: margin %d (0 .. 65536), gain %d (>= 1)", o->margin, o->gain);
+    if (rc == BF_OK) rc = vote_planes_check(c, "bf_project_groups", w, n_models, "", vp);   // (the held grouping is required: here an event's ONE model)
     if (rc != BF_OK) return rc;
-    const AssignArgs& a = vp.a;
-    const int K = a.K;
+    const int K = vp.a.K;
     const size_t plane = vp.plane;
 
     if (scores_out) memset(scores_out, 0, (size_t)K * sizeof(bf_group_score));
@@ -161,51 +212,33 @@ int bf_project_groups(bf_ctx* c, const bf_project_opts* o, const bf_model* model
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
 
-    const int nout = project_out_words(K);
-    rc = vote_planes_stage(c, models, true, vp);
+    bf_ctx::VoteScratch::Project& pr = c->vote.project;
+    HIP_TRY(c, pr.label.grow(plane));
+    rc = project_base_pass(c, models, vp, o->gain, pr.label);
     if (rc != BF_OK) return rc;
-    HIP_TRY(c, c->d_project_count.grow(plane));
-    HIP_TRY(c, c->d_project_label.grow(plane));
-    HIP_TRY(c, c->d_project_bgr.grow(3 * plane));
-    HIP_TRY(c, c->d_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
-    HIP_TRY(c, c->h_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
-    HIP_TRY(c, hipMemsetAsync(c->d_project_out, 0, (size_t)nout * sizeof(unsigned long long), s));
-    {
-        ProfScope ps(c, 3);
-        launch_project_vote(a, c->d_assign_votes, c->d_project_out, s);
-        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
-        launch_project_compose(vote_planes_summed(c, vp), K, vp.R, vp.C, o->gain, c->d_project_count, c->d_project_label,
-                               c->d_project_bgr, c->d_project_out, s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_project_out, c->d_project_out, (size_t)nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, c->d_project_count, plane * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    if (label_out) HIP_TRY(c, hipMemcpyAsync(label_out, c->d_project_label, plane * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    if (bgr_out) HIP_TRY(c, hipMemcpyAsync(bgr_out, c->d_project_bgr, 3 * plane, hipMemcpyDeviceToHost, s));
+    if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, pr.count, plane * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    if (label_out) HIP_TRY(c, hipMemcpyAsync(label_out, pr.label, plane * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (bgr_out) HIP_TRY(c, hipMemcpyAsync(bgr_out, pr.bgr, 3 * plane, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    const unsigned long long* h = c->h_project_out;
-    auto r = [h](int word) { return h[(size_t)word * kProjectStride]; };
-    long long outside = 0;
-    for (int k = 0; k < K; ++k) {
-        outside += (long long)r(k) - (long long)r(K + k);
-        if (!scores_out) continue;
+    const unsigned long long* h = pr.h_out;
+    const ProjectBase base = project_base_decode(c, K);
+    for (int k = 0; scores_out && k < K; ++k) {
         bf_group_score& g = scores_out[k];
-        g.events = (int32_t)r(k);
-        g.inside = (int32_t)r(K + k);
-        g.pixels_hit = (int32_t)r(2 * K + k);
-        g.pixels_owned = (int32_t)r(3 * K + k);
-        g.max = (int32_t)r(4 * K + k);
-        g.sum_sq = r(5 * K + k);
+        g.events = base.events[k];
+        g.inside = base.inside[k];
+        g.pixels_hit = (int32_t)h[ProjectBlock::pixels_hit(K, k)];
+        g.pixels_owned = (int32_t)h[ProjectBlock::pixels_owned(K, k)];
+        g.max = (int32_t)h[ProjectBlock::max(K, k)];
+        g.sum_sq = h[ProjectBlock::sum_sq(K, k)];
     }
     if (info) {
-        const int t = kProjectTables * K;
         info->models = K;
         info->rows = vp.R; info->cols = vp.C;
-        info->unassigned = (int32_t)r(t);
-        info->outside = (int32_t)outside;
-        info->pixels = (int32_t)r(t + 1);
-        info->sum = r(t + 2);
-        info->sum_sq = r(t + 3);
+        info->unassigned = base.unassigned;
+        info->outside = base.outside;
+        info->pixels = (int32_t)h[ProjectBlock::pixels(K)];
+        info->sum = h[ProjectBlock::sum(K)];
+        info->sum_sq = h[ProjectBlock::sum_sq_total(K)];
     }
     return BF_OK;
 }
@@ -216,9 +249,12 @@ int bf_merge_scores(bf_ctx* c, const bf_merge_opts* o, const bf_model* models, i
     if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_merge_scores before bf_upload_events");
     if (!o || !models) return fail(c, BF_ERR_ARG, "bf_merge_scores: opts %p, models %p", (const void*)o, (const void*)models);
     if (o->targets_per_pass < 0) return fail(c, BF_ERR_ARG, "bf_merge_scores: targets_per_pass %d (>= 0)", o->targets_per_pass);
+    const VoteWindow w{o->scale, o->sensor_res_x, o->sensor_res_y, o->margin};
     VotePlanes vp;
-    int rc = vote_planes_check(c, "bf_merge_scores", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "targets_per_pass + 1",
-                               o->targets_per_pass + 1, n_models, "", vp);   // (the held grouping is required, as for the projection)
+    int rc = vote_window_check(c, w);
+    if (rc == BF_OK && !vote_margin_ok(o->margin))   // (targets_per_pass + 1 >= 1 was checked above: the text is kept)
+        rc = fail(c, BF_ERR_ARG, "bf_merge_scores: margin %d (0 .. 65536), targets_per_pass + 1 %d (>= 1)", o->margin, o->targets_per_pass + 1);
+    if (rc == BF_OK) rc = vote_planes_check(c, "bf_merge_scores", w, n_models, "", vp);   // (the held grouping is required, as for the projection)
     if (rc != BF_OK) return rc;
     const AssignArgs& a = vp.a;
     const int K = a.K;
@@ -236,57 +272,50 @@ int bf_merge_scores(bf_ctx* c, const bf_merge_opts* o, const bf_model* models, i
     const int A = merge_targets_per_pass(K, (long long)plane, o->targets_per_pass);
     const int passes = (K + A - 1) / A;
     const size_t trial = (size_t)A * (size_t)K * plane;
-    const int nbase = project_out_words(K), nout = merge_out_words(K);
-    rc = vote_planes_stage(c, models, true, vp);
+    bf_ctx::VoteScratch::Merge& mg = c->vote.merge;
+    const size_t bytes = MergeBlock::size(K) * sizeof(unsigned long long);
+    HIP_TRY(c, mg.n.grow(plane));   // (everything is grown before the first launch)
+    HIP_TRY(c, mg.votes.grow(trial));
+    if (a.scale > 1) HIP_TRY(c, mg.box.grow(trial));
+    HIP_TRY(c, mg.d_out.grow(MergeBlock::size(kAssignMaxModels)));
+    HIP_TRY(c, mg.h_out.grow(MergeBlock::size(kAssignMaxModels)));
+    // the base planes: every group under its own model, exactly the projection's, without its compose
+    rc = project_base_pass(c, models, vp, 0, nullptr);
     if (rc != BF_OK) return rc;
-    HIP_TRY(c, c->d_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
-    HIP_TRY(c, c->h_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
-    HIP_TRY(c, c->d_merge_n.grow(plane));
-    HIP_TRY(c, c->d_merge_votes.grow(trial));
-    if (a.scale > 1) HIP_TRY(c, c->d_merge_box.grow(trial));
-    HIP_TRY(c, c->d_merge_out.grow((size_t)merge_out_words(kAssignMaxModels)));
-    HIP_TRY(c, c->h_merge_out.grow((size_t)merge_out_words(kAssignMaxModels)));
-    HIP_TRY(c, hipMemsetAsync(c->d_project_out, 0, (size_t)nbase * sizeof(unsigned long long), s));
-    HIP_TRY(c, hipMemsetAsync(c->d_merge_out, 0, (size_t)nout * sizeof(unsigned long long), s));
+    HIP_TRY(c, hipMemsetAsync(mg.d_out, 0, bytes, s));
     {
         ProfScope ps(c, 3);
-        // the base planes: every group under its own model, exactly the projection's
-        launch_project_vote(a, c->d_assign_votes, c->d_project_out, s);
-        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
         const uint32_t* B = vote_planes_summed(c, vp);
-        launch_merge_total(B, K, vp.R, vp.C, c->d_merge_n, c->d_merge_out, s);
+        launch_merge_total(B, K, vp.R, vp.C, mg.n, mg.d_out, s);
         for (int a0 = 0; a0 < K; a0 += A) {   // (the passes follow each other on the stream: they share the trial planes)
             const int targets = K - a0 < A ? K - a0 : A;
             const size_t words = (size_t)targets * (size_t)K * plane;
-            HIP_TRY(c, hipMemsetAsync(c->d_merge_votes, 0, words * sizeof(uint32_t), s));
-            launch_merge_vote(a, a0, targets, c->d_merge_votes, c->d_merge_out, s);
-            if (a.scale > 1) launch_assign_box(c->d_merge_votes, c->d_merge_box, targets * K, vp.R, vp.C, a.scale, s);
-            launch_merge_gain(a.scale > 1 ? c->d_merge_box.get() : c->d_merge_votes.get(), B, c->d_merge_n, K, a0, targets, vp.R,
-                              vp.C, c->d_merge_out, s);
+            HIP_TRY(c, hipMemsetAsync(mg.votes, 0, words * sizeof(uint32_t), s));
+            launch_merge_vote(a, a0, targets, mg.votes, mg.d_out, s);
+            if (a.scale > 1) launch_assign_box(mg.votes, mg.box, targets * K, vp.R, vp.C, a.scale, s);
+            launch_merge_gain(a.scale > 1 ? mg.box.get() : mg.votes.get(), B, mg.n, K, a0, targets, vp.R, vp.C, mg.d_out, s);
         }
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_project_out, c->d_project_out, (size_t)nbase * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIP_TRY(c, hipMemcpyAsync(c->h_merge_out, c->d_merge_out, (size_t)nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(mg.h_out, mg.d_out, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    const unsigned long long* hb = c->h_project_out;
-    const unsigned long long* hm = c->h_merge_out;
-    auto r = [hm](size_t word) { return hm[word * kProjectStride]; };
-    for (size_t w = 0; w < pairs; ++w) {
-        if (gain_out) gain_out[w] = r(w);
-        if (inside_out) inside_out[w] = (int32_t)r(pairs + w);
-    }
-    if (inside_out)   // the diagonal is the base pass's: events of k inside under their own model
-        for (int k = 0; k < K; ++k) inside_out[(size_t)k * K + k] = (int32_t)hb[(size_t)(K + k) * kProjectStride];
-    if (events_out)
-        for (int k = 0; k < K; ++k) events_out[k] = (int32_t)hb[(size_t)k * kProjectStride];
+    const unsigned long long* h = mg.h_out;
+    const ProjectBase base = project_base_decode(c, K);
+    for (int b = 0; b < K; ++b)
+        for (int t = 0; t < K; ++t) {
+            const size_t w = (size_t)b * K + t;
+            if (gain_out) gain_out[w] = h[MergeBlock::gain(K, b, t)];
+            // (the diagonal is the base pass's: events of b inside under their own model)
+            if (inside_out) inside_out[w] = b == t ? base.inside[b] : (int32_t)h[MergeBlock::inside(K, b, t)];
+        }
+    if (events_out) memcpy(events_out, base.events, (size_t)K * sizeof(int32_t));
     if (info) {
         info->models = K;
         info->rows = vp.R; info->cols = vp.C;
-        info->unassigned = (int32_t)hb[(size_t)(kProjectTables * K) * kProjectStride];
+        info->unassigned = base.unassigned;
         info->passes = passes;
-        info->sum = r(2 * pairs);
-        info->sum_sq = r(2 * pairs + 1);
+        info->sum = h[MergeBlock::sum(K)];
+        info->sum_sq = h[MergeBlock::sum_sq(K)];
     }
     return BF_OK;
 }

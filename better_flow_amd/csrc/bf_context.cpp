@@ -249,7 +249,7 @@ int bf_get_stat(bf_ctx* c, const char* key, int64_t* value) {
         // ... and the groups of the grouping held for the uploaded slice (-1: none is held)
         {"groups_held", c->groups_valid ? c->groups_K : -1},
         // ... and the groups of the owner plane kept by bf_track_keep (-1: none is kept); not slice state
-        {"tracks_held", c->track.valid ? c->track.Kp : -1},
+        {"tracks_held", c->vote.track.kept.valid ? c->vote.track.kept.Kp : -1},
         // ... and the vote kernel of the last bf_propose_models: 1 a histogram per work-group in LDS, 2 global atomics, 0 none
         {"propose_form", c->propose_form}};
     for (const auto& e : launched)

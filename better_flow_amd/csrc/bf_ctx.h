@@ -6,7 +6,8 @@
 // entry reads -- is the base struct bf_state::SliceState (bf_ctx_state.h), changed through its named transitions only.  Every HIP resource of a
 // context lives in a handle of bf_mem.h; the raw pointers left below are aliases into those and say so.  The asynchronous
 // uploads keep all their state in one member, `up`: the copy stream and two staging slots, each FREE, RECORDED, ISSUED or EARLY
-// (bf_ctx::UploadSlot).  Nothing here is part of the ABI (include/bf_accel.h).
+// (bf_ctx::UploadSlot); the entries on the K models' vote planes keep their scratch in one member, `vote`, and what they share on
+// the host is declared in bf_vote_planes.h.  Nothing here is part of the ABI (include/bf_accel.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -137,38 +138,39 @@ struct bf_ctx : bf_state::SliceState {
     bool opt_groups_wide = false;            // read by bf_run_groups
     int groups_wide = 0;                     // groups the last bf_run_groups solved wide (bf_get_stat)
     bf_ctx* wide_inner = nullptr;            // owned
-    // assignment (bf_assign_groups): the K vote planes and their box sums (K x R x C words each), the K warps, the ids and scores
-    // in upload order, the result block (counts, changed, max_score); grown on first use
-    DevArray<uint32_t> d_assign_votes, d_assign_box, d_assign_out;
-    DevArray<WarpParams> d_assign_wp;
-    HostArray<WarpParams> h_assign_wp;
-    DevArray<int32_t> d_assign_gid, d_assign_score;
-    HostArray<uint32_t> h_assign_out;
-    // projection (bf_project_groups): the planes and warps are the assignment's; per pixel N, the owner and the colour, and the
-    // result block of 64-bit words (bf_assign.h: project_out_words); grown on first use
-    DevArray<uint32_t> d_project_count;
-    DevArray<int32_t> d_project_label;
-    DevArray<uint8_t> d_project_bgr;
-    DevArray<unsigned long long> d_project_out;
-    HostArray<unsigned long long> h_project_out;
-    // merge gains (bf_merge_scores): the base planes, warps and their result block are the projection's; the N plane, the trial
-    // planes of one pass and their box sums (A x K x R x C words each), and the result block of 64-bit words (bf_assign.h:
-    // merge_out_words); grown on first use
-    DevArray<uint32_t> d_merge_n, d_merge_votes, d_merge_box;
-    DevArray<unsigned long long> d_merge_out;
-    HostArray<unsigned long long> h_merge_out;
-    // tracks (bf_track_keep / bf_track_overlap, bf_track_abi.cpp): the kept owner plane (R x C labels), a buffer of its own that
-    // no other entry writes, and the overlap's result block.  NOT slice state: an upload leaves it, bf_track_keep replaces it,
-    // bf_track_drop and bf_destroy release it -- so its validity is here and not in SliceState.
-    DevArray<int32_t> d_track_plane;
-    DevArray<uint32_t> d_track_out;
-    HostArray<uint32_t> h_track_out;
-    struct TrackKept {
-        bool valid = false;
-        int Kp = 0;                                          // the groups of the kept grouping
-        int scale = 0, res_x = 0, res_y = 0, margin = 0;     // the window's options ...
-        int R = 0, C = 0;                                    // ... and its planes
-    } track;
+    // The scratch of the entries on the K models' vote planes (bf_assign_abi.cpp, bf_track_abi.cpp; bf_hold_groups borrows the
+    // staged warps), everything grown on first use.  Who owns what reads off the type; what an entry takes from `shared` or from
+    // another entry's part, it takes through the helpers of bf_vote_planes.h.
+    struct VoteScratch {
+        // the window's options as every entry takes them (its opts struct's scale, sensor_res_x / _y and margin)
+        struct Window {
+            int scale, res_x, res_y, margin;
+            bool operator==(const Window& o) const { return scale == o.scale && res_x == o.res_x && res_y == o.res_y && margin == o.margin; }
+        };
+        // shared: the K vote planes and their box sums (K x R x C words each), the K warps and their pinned staging copy
+        struct Shared { DevArray<uint32_t> votes, box; DevArray<WarpParams> d_wp; HostArray<WarpParams> h_wp; } shared;
+        // bf_assign_groups: the ids and scores in upload order, the result block (AssignBlock)
+        struct Assign { DevArray<int32_t> gid, score; DevArray<uint32_t> d_out; HostArray<uint32_t> h_out; } assign;
+        // the base pass (bf_project_groups, bf_merge_scores, bf_track_keep): per pixel N, the owner (bf_project_groups alone:
+        // bf_track_keep directs it into its kept plane) and the colour, and the result block (ProjectBlock)
+        struct Project {
+            DevArray<uint32_t> count; DevArray<int32_t> label; DevArray<uint8_t> bgr;
+            DevArray<unsigned long long> d_out; HostArray<unsigned long long> h_out;
+        } project;
+        // bf_merge_scores: the N plane, the trial planes of one pass and their box sums (A x K x R x C words each), the result
+        // block (MergeBlock)
+        struct Merge { DevArray<uint32_t> n, votes, box; DevArray<unsigned long long> d_out; HostArray<unsigned long long> h_out; } merge;
+        // bf_track_keep / bf_track_overlap: the kept owner plane (R x C labels), a buffer of its own that no other entry writes,
+        // what it was kept under, and the overlap's result block (TrackBlock).  The kept plane is NOT slice state: an upload leaves
+        // it, bf_track_keep replaces it, bf_track_drop and bf_destroy release it -- so its validity is here and not in SliceState.
+        struct TrackKept {
+            bool valid = false;
+            int Kp = 0;          // the groups of the kept grouping
+            Window win{};        // the window's options ...
+            int R = 0, C = 0;    // ... and its planes
+        };
+        struct Track { DevArray<int32_t> plane; TrackKept kept; DevArray<uint32_t> d_out; HostArray<uint32_t> h_out; } track;
+    } vote;
     // candidate models (bf_propose_models): the lattice's value tables (n_x doubles, then n_y), the vote plane H and its box
     // sums B (n_x * n_y words each), the result block (counts, proposals); grown on first use
     DevArray<double> d_propose_tab;
@@ -446,25 +448,6 @@ int fold_stats(bf_ctx* c, const SliceStats* overwritten = nullptr);
 // Installs n group ids (n = c->n; `src` on the host or on the device, as `kind` says; not read when the slice is empty) as the
 // held grouping of K groups: the context's own plane, held until the next upload.  A host source is free again on return.
 int install_grouping(bf_ctx* c, const int32_t* src, hipMemcpyKind kind, int K);
-
-// The K-model vote planes of one call (bf_assign_abi.cpp; shared with bf_track_abi.cpp): the kernels' arguments, and the R x C
-// window with its words per plane.
-struct VotePlanes {
-    AssignArgs a;
-    int R, C;
-    size_t plane;
-};
-// The option checks of the entries on the vote planes, in their order, then the window of the widened sensor and the capacity
-// check; fills everything of vp but a's pointers.  `knob`: the entry's own option, which must be >= 1; `prior`: null when the
-// held grouping is not read, else what the message says before "no grouping ... is held".
-int vote_planes_check(bf_ctx* c, const char* who, int scale, int res_x, int res_y, int margin, const char* knob_name, int knob,
-                      int n_models, const char* prior, VotePlanes& vp);
-// The window part of it alone (options that have passed those checks): everything of vp but a's pointers, a.K = K.
-void vote_planes_window(const bf_ctx* c, int scale, int res_x, int res_y, int margin, int K, VotePlanes& vp);
-// (n > 0, the device set) The vote planes grown and V cleared, the box planes grown when they are used, the K warps staged, a's pointers.
-int vote_planes_stage(bf_ctx* c, const bf_model* models, bool prior, VotePlanes& vp);
-// The planes the second kernel of an entry reads: the box sums, or V itself at scale 1.
-const uint32_t* vote_planes_summed(bf_ctx* c, const VotePlanes& vp);
 
 // ---- what bf_run.cpp calls once per kernel launch: inline, the host's launch time is on a warm-started chain's critical path ----
 

@@ -138,6 +138,18 @@ __device__ __forceinline__ int assign_pixel(const WarpParams& wp, uint32_t v, in
     return assign_pixel_ft(wp, v, (float)t, scale, x_sh, y_sh, wsx, wsy, C);
 }
 
+// The K warps of a call from global memory into a work-group's LDS, 8 bytes at a time, strided over its kThreads threads
+// (k_hold_groups, k_track_overlap: the model differs per lane, so each lane reads its group's from LDS; k_project_vote keeps
+// its own copy in 32-bit words).  The
+// caller's __syncthreads() follows, where it also clears its tables.
+__device__ __forceinline__ void stage_warps_lds(WarpParams* s_wp, const WarpParams* wp, int K) {
+    constexpr int kWpDoubles = (int)(sizeof(WarpParams) / sizeof(double));
+    static_assert(sizeof(WarpParams) % sizeof(double) == 0, "whole doubles");
+    const double* src = reinterpret_cast<const double*>(wp);
+    double* dst = reinterpret_cast<double*>(s_wp);
+    for (int w = threadIdx.x; w < K * kWpDoubles; w += kThreads) dst[w] = src[w];
+}
+
 // A load the compiler must issue on the SCALAR unit: through the constant address space.  For data that no work-group
 // of the running kernel writes (kernel arguments passed inside a struct lose their __restrict__, and the compiler
 // then falls back to vector loads for uniform addresses: they complete in order with every other vector load of the

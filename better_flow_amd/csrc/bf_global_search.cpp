@@ -3,8 +3,8 @@
 // sensor), and the per-event state.  The kernels are in bf_global.hip; the definitions this build adds (the per-event best
 // candidate, the objective S, the objective per cell, the candidate set of a pyramid level, the piecewise projection, the
 // interpolated field, the held flow) are stated in include/bf_accel.h and DESIGN.md.
-#include "bf_ctx.h"
 #include "bf_hold_groups.h"
+#include "bf_vote_planes.h"
 
 constexpr int kGlobalHoldBest = 3;   // GlobalSearch::Held::mode after bf_global_hold_best (1, 2: BF_GLOBAL_HOLD_CELLS / _FIELD)
 constexpr int kGlobalHoldGroups = 4; // ... after bf_hold_groups
@@ -971,25 +971,19 @@ int bf_hold_groups(bf_ctx* c, const bf_model* models, int32_t n_models) {
     if (!gs || !gs->have || !c->glob_valid || c->n != gs->n)
         return fail(c, BF_ERR_STATE, "bf_hold_groups: no window of the uploaded slice: call bf_global_set_window first");
     if (!models) return fail(c, BF_ERR_ARG, "bf_hold_groups: models %p", (const void*)models);
-    if (n_models < 1 || n_models > kAssignMaxModels) return fail(c, BF_ERR_ARG, "bf_hold_groups: %d models (1 .. %d)", n_models, kAssignMaxModels);
-    if (c->has_noise) return fail(c, BF_ERR_ARG, "bf_hold_groups does not take a noise mask");
-    if (!c->groups_valid) return fail(c, BF_ERR_STATE, "bf_hold_groups: no grouping of the uploaded slice is held");
+    int rc = held_grouping_check(c, "bf_hold_groups", n_models, "");
+    if (rc != BF_OK) return rc;
     const int K = n_models;
-    if (c->groups_K != K) return fail(c, BF_ERR_ARG, "bf_hold_groups: the held grouping has %d groups, %d models given", c->groups_K, K);
     HIP_TRY(c, hipSetDevice(c->device));
     gs->held.mode = 0;   // (a failure below leaves no held flow)
     if (gs->n > 0) {
         GlobalHeld h;
-        int rc = ensure_held(c, gs, true, h);
-        if (rc != BF_OK) return rc;
-        HIP_TRY(c, c->d_assign_wp.grow((size_t)kAssignMaxModels));
-        HIP_TRY(c, c->h_assign_wp.grow((size_t)kAssignMaxModels));
-        for (int k = 0; k < K; ++k) set_model_warp(c->h_assign_wp[k], models[k]);   // (sine and cosine from the host's libm)
-        HIP_TRY(c, hipMemcpyAsync(c->d_assign_wp, c->h_assign_wp, (size_t)K * sizeof(WarpParams), hipMemcpyHostToDevice, c->stream));
-        const bf_ctx::EvSet& e = c->set[c->cs];
+        if ((rc = ensure_held(c, gs, true, h)) != BF_OK) return rc;
+        AssignArgs a{};   // (the events as stored, the staged warps and the held grouping: only the pointers are read)
+        if ((rc = vote_warps_stage(c, models, K, true, a)) != BF_OK) return rc;
         {
             ProfScope ps(c, 3);
-            launch_hold_groups(e.xy, e.t, c->has_perm ? e.perm.get() : nullptr, c->d_group_id, c->d_assign_wp, K, gs->n, h, c->stream);
+            launch_hold_groups(a.xy, a.t, a.perm, a.prior, a.wp, K, gs->n, h, c->stream);
         }
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipStreamSynchronize(c->stream));   // (the staged warps are the assignment's too: free again from here)

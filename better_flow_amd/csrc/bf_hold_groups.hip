@@ -32,12 +32,7 @@ __global__ __launch_bounds__(kThreads) void k_hold_groups(const uint32_t* __rest
                                                           const uint32_t* __restrict__ perm, const int32_t* __restrict__ gid,
                                                           const WarpParams* __restrict__ wps, int K, long long n, GlobalHeld h) {
     __shared__ WarpParams s_wp[kAssignMaxModels];
-    {
-        constexpr int kWpDoubles = (int)(sizeof(WarpParams) / sizeof(double));
-        const double* src = reinterpret_cast<const double*>(wps);
-        double* dst = reinterpret_cast<double*>(s_wp);
-        for (int w = threadIdx.x; w < K * kWpDoubles; w += kThreads) dst[w] = src[w];
-    }
+    stage_warps_lds(s_wp, wps, K);
     __syncthreads();
     const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
     if (i >= n) return;

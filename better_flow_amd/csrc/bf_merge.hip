@@ -21,7 +21,8 @@
 //                      plane without a non-zero word in the wave is skipped by ballot and its B_b is not loaded; else the
 //                      64-bit term T (2 (N - B_b) + T), a wave sum, and one lane's 64-bit add into an LDS table of K words.
 //                      One global atomic per work-group and non-zero word.
-// Every word of the result block sits on a 128-byte line of its own (kProjectStride; DESIGN section 17 measured why).
+// Every word of the result block sits on a 128-byte line of its own (MergeBlock, bf_group_blocks.h; DESIGN section 17 measured
+// why).
 #include <hip/hip_runtime.h>
 
 #include "bf_assign.h"
@@ -40,7 +41,7 @@ constexpr int kGainBatch = 4;             // trial planes loaded before the firs
 
 __global__ __launch_bounds__(kGainThreads) void k_merge_total(const uint32_t* __restrict__ B, int K, long long P,
                                                               uint32_t* __restrict__ Nout, unsigned long long* __restrict__ out) {
-    __shared__ unsigned long long s_tot[2];   // sum, sum_sq
+    __shared__ unsigned long long s_tot[2];   // sum, sum_sq: MergeBlock::total's order
     if (threadIdx.x < 2) s_tot[threadIdx.x] = 0ull;
     __syncthreads();
     unsigned long long t_sum = 0, t_sq = 0;
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(kGainThreads) void k_merge_total(const uint32_t* __
     }
     __syncthreads();
     if (threadIdx.x < 2 && s_tot[threadIdx.x])
-        atomicAdd(out + (size_t)(2 * K * K + threadIdx.x) * kProjectStride, s_tot[threadIdx.x]);
+        atomicAdd(out + MergeBlock::total(K, threadIdx.x), s_tot[threadIdx.x]);
 }
 
 // (blockIdx.y: the target model of the pass, a = a0 + blockIdx.y)
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_merge_vote(AssignArgs a, int a0, u
     __syncthreads();
     for (int w = threadIdx.x; w < K; w += kThreads) {
         const uint32_t c = s_in[w];
-        if (c) atomicAdd(out + (size_t)(K * K + w * K + target) * kProjectStride, (unsigned long long)c);
+        if (c) atomicAdd(out + MergeBlock::inside(K, w, target), (unsigned long long)c);
     }
 }
 
@@ -138,7 +139,7 @@ __global__ __launch_bounds__(kGainThreads) void k_merge_gain(const uint32_t* __r
     }
     __syncthreads();
     for (int w = threadIdx.x; w < K; w += kGainThreads)
-        if (s_gain[w]) atomicAdd(out + (size_t)(w * K + target) * kProjectStride, s_gain[w]);
+        if (s_gain[w]) atomicAdd(out + MergeBlock::gain(K, w, target), s_gain[w]);
 }
 
 unsigned pixel_groups(long long P) {

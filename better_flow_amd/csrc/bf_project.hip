@@ -41,7 +41,7 @@ __global__ __launch_bounds__(kThreads) void k_project_vote(AssignArgs a, uint32_
     const int K = a.K;
     __shared__ uint32_t s_cnt[2 * kAssignMaxModels + 1];   // events[K], unassigned, inside[K]
     __shared__ WarpParams s_wp[kAssignMaxModels];
-    {
+    {   // (32-bit words, not stage_warps_lds' 8-byte form: this kernel's measured code is kept as it is)
         constexpr int kWords = (int)(sizeof(WarpParams) / sizeof(uint32_t));
         const uint32_t* src = reinterpret_cast<const uint32_t*>(a.wp);
         uint32_t* dst = reinterpret_cast<uint32_t*>(s_wp);
@@ -81,8 +81,7 @@ __global__ __launch_bounds__(kThreads) void k_project_vote(AssignArgs a, uint32_
     for (int w = threadIdx.x; w < 2 * K + 1; w += kThreads) {
         const uint32_t c = s_cnt[w];
         if (!c) continue;
-        const int word = w < K ? w : (w == K ? kProjectTables * K : K + (w - K - 1));
-        atomicAdd(out + (size_t)word * kProjectStride, (unsigned long long)c);
+        atomicAdd(out + ProjectBlock::vote_word(K, w), (unsigned long long)c);
     }
 }
 
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(kComposeThreads) void k_project_compose(const uint3
                                                                      unsigned long long* __restrict__ out) {
     __shared__ unsigned long long s_sq[kAssignMaxModels];
     __shared__ uint32_t s_hit[kAssignMaxModels], s_own[kAssignMaxModels], s_max[kAssignMaxModels];
-    __shared__ unsigned long long s_tot[3];   // pixels, sum, sum_sq
+    __shared__ unsigned long long s_tot[3];   // pixels, sum, sum_sq: ProjectBlock::total's order
     for (int w = threadIdx.x; w < K; w += kComposeThreads) { s_sq[w] = 0ull; s_hit[w] = 0u; s_own[w] = 0u; s_max[w] = 0u; }
     if (threadIdx.x < 3) s_tot[threadIdx.x] = 0ull;
     __syncthreads();
@@ -148,13 +147,13 @@ __global__ __launch_bounds__(kComposeThreads) void k_project_compose(const uint3
     }
     __syncthreads();
     for (int w = threadIdx.x; w < K; w += kComposeThreads) {
-        if (s_hit[w]) atomicAdd(out + (size_t)(2 * K + w) * kProjectStride, (unsigned long long)s_hit[w]);
-        if (s_own[w]) atomicAdd(out + (size_t)(3 * K + w) * kProjectStride, (unsigned long long)s_own[w]);
-        if (s_max[w]) atomicMax(out + (size_t)(4 * K + w) * kProjectStride, (unsigned long long)s_max[w]);
-        if (s_sq[w]) atomicAdd(out + (size_t)(5 * K + w) * kProjectStride, s_sq[w]);
+        if (s_hit[w]) atomicAdd(out + ProjectBlock::pixels_hit(K, w), (unsigned long long)s_hit[w]);
+        if (s_own[w]) atomicAdd(out + ProjectBlock::pixels_owned(K, w), (unsigned long long)s_own[w]);
+        if (s_max[w]) atomicMax(out + ProjectBlock::max(K, w), (unsigned long long)s_max[w]);
+        if (s_sq[w]) atomicAdd(out + ProjectBlock::sum_sq(K, w), s_sq[w]);
     }
     if (threadIdx.x < 3 && s_tot[threadIdx.x])
-        atomicAdd(out + (size_t)(kProjectTables * K + 1 + threadIdx.x) * kProjectStride, s_tot[threadIdx.x]);
+        atomicAdd(out + ProjectBlock::total(K, threadIdx.x), s_tot[threadIdx.x]);
 }
 
 }  // namespace

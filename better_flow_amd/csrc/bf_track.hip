@@ -29,21 +29,16 @@ namespace {
 
 constexpr int kTrackEv = 4;       // events per thread
 constexpr int kTrackRounds = 4;   // leader rounds per wave and event round; the lanes left over add for themselves
-constexpr int kTrackTabWords = kAssignMaxModels * (kAssignMaxModels + 1) + kTrackTail;   // 16.6 KiB
+constexpr int kTrackTabWords = TrackBlock::words(kAssignMaxModels, kAssignMaxModels);   // 16.6 KiB
 
 __global__ __launch_bounds__(kThreads) void k_track_overlap(AssignArgs a, const int32_t* __restrict__ kept, int Kp, long long dt,
                                                             uint32_t* __restrict__ out) {
-    __shared__ uint32_t s_tab[kTrackTabWords];   // overlap[K][Kp + 1], outside, unassigned
+    __shared__ uint32_t s_tab[kTrackTabWords];   // the block's words, compact: overlap[K][Kp + 1], outside, unassigned
     __shared__ WarpParams s_wp[kAssignMaxModels];
     const int K = a.K, W = Kp + 1;
-    const int words = K * W;
-    {
-        constexpr int kWpDoubles = (int)(sizeof(WarpParams) / sizeof(double));
-        const double* src = reinterpret_cast<const double*>(a.wp);
-        double* dst = reinterpret_cast<double*>(s_wp);
-        for (int w = threadIdx.x; w < K * kWpDoubles; w += kThreads) dst[w] = src[w];
-    }
-    for (int w = threadIdx.x; w < words + kTrackTail; w += kThreads) s_tab[w] = 0u;
+    const int words = K * W, all = TrackBlock::words(K, Kp);   // the table's words, and with outside and unassigned behind them
+    stage_warps_lds(s_wp, a.wp, K);
+    for (int w = threadIdx.x; w < all; w += kThreads) s_tab[w] = 0u;
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const bool leader = lane == 0;
@@ -83,9 +78,9 @@ __global__ __launch_bounds__(kThreads) void k_track_overlap(AssignArgs a, const 
         }
     }
     __syncthreads();
-    for (int w = threadIdx.x; w < words + kTrackTail; w += kThreads) {
+    for (int w = threadIdx.x; w < all; w += kThreads) {
         const uint32_t c = s_tab[w];
-        if (c) atomicAdd(out + (size_t)w * kTrackStride, c);
+        if (c) atomicAdd(out + TrackBlock::word(w), c);
     }
 }
 

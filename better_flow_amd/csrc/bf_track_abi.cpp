@@ -1,13 +1,15 @@
 // bf_track_abi.cpp -- C-ABI of tracking objects across slices (include/bf_accel.h, "event groups: tracks"):
 //   bf_track_keep     keeps the owner plane of the held grouping under its models -- bf_project_groups' label_out, by the
-//                     projection's own kernels with the label directed into a buffer that no other entry writes -- together with
-//                     its window and its number of groups.  The kept plane is not slice state: it survives the next upload.
+//                     projection's own base pass (project_base_pass) with the label directed into a buffer that no other entry
+//                     writes -- together with its window and its number of groups.  The kept plane is not slice state: it
+//                     survives the next upload.
 //   bf_track_overlap  counts, per group of the slice uploaded NOW, on whose pixels of the kept plane its events land once they
 //                     are carried back by the time between the two slices (kernel in bf_track.hip).
 //   bf_track_drop     releases the kept plane.
-// The option checks, the window and the staging of the K warps are bf_assign_abi.cpp's (vote_planes_*).
-#include "bf_ctx.h"
+// The checks, the window, the staging of the K warps and the base pass are bf_assign_abi.cpp's (bf_vote_planes.h); the scratch is
+// bf_ctx::vote.track, the overlap's result block TrackBlock (bf_group_blocks.h).
 #include "bf_track.h"
+#include "bf_vote_planes.h"
 
 extern "C" {
 
@@ -16,65 +18,44 @@ int bf_track_keep(bf_ctx* c, const bf_track_opts* o, const bf_model* models, int
     if (!c) return BF_ERR_ARG;
     if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_track_keep before bf_upload_events");
     if (!o || !models) return fail(c, BF_ERR_ARG, "bf_track_keep: opts %p, models %p", (const void*)o, (const void*)models);
+    const VoteWindow w{o->scale, o->sensor_res_x, o->sensor_res_y, o->margin};
     VotePlanes vp;
-    int rc = vote_planes_check(c, "bf_track_keep", o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, "gain", 1, n_models, "",
-                               vp);   // (the held grouping is required, as for the projection)
+    int rc = vote_window_check(c, w);
+    if (rc == BF_OK && !vote_margin_ok(o->margin)) rc = fail(c, BF_ERR_ARG, "bf_track_keep: margin %d (0 .. 65536)", o->margin);
+    if (rc == BF_OK) rc = vote_planes_check(c, "bf_track_keep", w, n_models, "", vp);   // (the held grouping is required, as for the projection)
     if (rc != BF_OK) return rc;
-    const AssignArgs& a = vp.a;
-    const int K = a.K;
+    const int K = vp.a.K;
     const size_t plane = vp.plane;
 
     // from here on the call is accepted: the previous plane goes, and a failure below leaves none
     if (info) memset(info, 0, sizeof(*info));
     HIP_TRY(c, hipSetDevice(c->device));
     hipStream_t s = c->stream;
-    c->track.valid = false;
-    HIP_TRY(c, c->d_track_plane.grow(plane));
-    bf_ctx::TrackKept kept;
-    kept.Kp = K;
-    kept.scale = o->scale; kept.res_x = o->sensor_res_x; kept.res_y = o->sensor_res_y; kept.margin = o->margin;
-    kept.R = vp.R; kept.C = vp.C;
+    bf_ctx::VoteScratch::Track& tr = c->vote.track;
+    tr.kept.valid = false;
+    HIP_TRY(c, tr.plane.grow(plane));
+    const bf_ctx::VoteScratch::TrackKept kept{true, K, w, vp.R, vp.C};
     if (c->n == 0) {   // N == 0 everywhere: every label -1
-        HIP_TRY(c, hipMemsetAsync(c->d_track_plane, 0xff, plane * sizeof(int32_t), s));
+        HIP_TRY(c, hipMemsetAsync(tr.plane, 0xff, plane * sizeof(int32_t), s));
         HIP_TRY(c, hipStreamSynchronize(s));
         if (plane_out) memset(plane_out, 0xff, plane * sizeof(int32_t));
-        kept.valid = true;
-        c->track = kept;
+        tr.kept = kept;
         return BF_OK;
     }
 
-    // bf_project_groups' launches, the label into the kept buffer; count, colour and the result block are the projection's scratch
-    const int nout = project_out_words(K);
-    rc = vote_planes_stage(c, models, true, vp);
+    // bf_project_groups' base pass under gain 1, the owner plane into the kept buffer
+    rc = project_base_pass(c, models, vp, 1, tr.plane);
     if (rc != BF_OK) return rc;
-    HIP_TRY(c, c->d_project_count.grow(plane));
-    HIP_TRY(c, c->d_project_bgr.grow(3 * plane));
-    HIP_TRY(c, c->d_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
-    HIP_TRY(c, c->h_project_out.grow((size_t)project_out_words(kAssignMaxModels)));
-    HIP_TRY(c, hipMemsetAsync(c->d_project_out, 0, (size_t)nout * sizeof(unsigned long long), s));
-    {
-        ProfScope ps(c, 3);
-        launch_project_vote(a, c->d_assign_votes, c->d_project_out, s);
-        if (a.scale > 1) launch_assign_box(c->d_assign_votes, c->d_assign_box, K, vp.R, vp.C, a.scale, s);
-        launch_project_compose(vote_planes_summed(c, vp), K, vp.R, vp.C, 1, c->d_project_count, c->d_track_plane, c->d_project_bgr,
-                               c->d_project_out, s);
-    }
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_project_out, c->d_project_out, (size_t)nout * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (plane_out) HIP_TRY(c, hipMemcpyAsync(plane_out, c->d_track_plane, plane * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (plane_out) HIP_TRY(c, hipMemcpyAsync(plane_out, tr.plane, plane * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    kept.valid = true;
-    c->track = kept;
+    tr.kept = kept;
     if (info) {
-        const unsigned long long* h = c->h_project_out;
-        auto r = [h](int word) { return h[(size_t)word * kProjectStride]; };
-        long long outside = 0;
-        for (int k = 0; k < K; ++k) outside += (long long)r(k) - (long long)r(K + k);
+        const ProjectBase base = project_base_decode(c, K);
         info->models = K;
         info->kept_models = K;
         info->rows = vp.R; info->cols = vp.C;
-        info->unassigned = (int32_t)r(kProjectTables * K);
-        info->outside = (int32_t)outside;
+        info->unassigned = base.unassigned;
+        info->outside = base.outside;
     }
     return BF_OK;
 }
@@ -84,18 +65,16 @@ int bf_track_overlap(bf_ctx* c, const bf_track_opts* o, const bf_model* models, 
     if (!c) return BF_ERR_ARG;
     if (!c->uploaded) return fail(c, BF_ERR_STATE, "bf_track_overlap before bf_upload_events");
     if (!o || !models) return fail(c, BF_ERR_ARG, "bf_track_overlap: opts %p, models %p", (const void*)o, (const void*)models);
-    if (n_models < 1 || n_models > kAssignMaxModels)
-        return fail(c, BF_ERR_ARG, "bf_track_overlap: %d models (1 .. %d)", n_models, kAssignMaxModels);
-    if (c->has_noise) return fail(c, BF_ERR_ARG, "bf_track_overlap does not take a noise mask");
+    int rc = held_grouping_check(c, "bf_track_overlap", n_models, "");
+    if (rc != BF_OK) return rc;
     const int K = n_models;
-    if (!c->groups_valid) return fail(c, BF_ERR_STATE, "bf_track_overlap: no grouping of the uploaded slice is held");
-    if (c->groups_K != K)
-        return fail(c, BF_ERR_ARG, "bf_track_overlap: the held grouping has %d groups, %d models given", c->groups_K, K);
-    const bf_ctx::TrackKept& kept = c->track;
+    bf_ctx::VoteScratch::Track& tr = c->vote.track;
+    const bf_ctx::VoteScratch::TrackKept& kept = tr.kept;
     if (!kept.valid) return fail(c, BF_ERR_STATE, "bf_track_overlap: no plane is kept (bf_track_keep)");
-    if (o->scale != kept.scale || o->sensor_res_x != kept.res_x || o->sensor_res_y != kept.res_y || o->margin != kept.margin)
+    const VoteWindow w{o->scale, o->sensor_res_x, o->sensor_res_y, o->margin};
+    if (!(w == kept.win))
         return fail(c, BF_ERR_ARG, "bf_track_overlap: window (scale %d, sensor %d x %d, margin %d) differs from the kept plane's (%d, %d x %d, %d)",
-                    o->scale, o->sensor_res_x, o->sensor_res_y, o->margin, kept.scale, kept.res_x, kept.res_y, kept.margin);
+                    w.scale, w.res_x, w.res_y, w.margin, kept.win.scale, kept.win.res_x, kept.win.res_y, kept.win.margin);
     constexpr int64_t kMaxDt = (int64_t)1 << 40;
     if (dt_ns > kMaxDt || dt_ns < -kMaxDt) return fail(c, BF_ERR_ARG, "bf_track_overlap: |dt_ns| %lld exceeds 2^40", (long long)dt_ns);
     const int Kp = kept.Kp, W = Kp + 1;
@@ -108,34 +87,25 @@ int bf_track_overlap(bf_ctx* c, const bf_track_opts* o, const bf_model* models, 
     hipStream_t s = c->stream;
 
     VotePlanes vp;
-    vote_planes_window(c, kept.scale, kept.res_x, kept.res_y, kept.margin, K, vp);   // (the kept options passed bf_track_keep's checks)
-    AssignArgs& a = vp.a;
-    const size_t out_size = track_out_size(K, Kp);
-    HIP_TRY(c, c->d_assign_wp.grow((size_t)kAssignMaxModels));
-    HIP_TRY(c, c->h_assign_wp.grow((size_t)kAssignMaxModels));
-    HIP_TRY(c, c->d_track_out.grow(track_out_size(kAssignMaxModels, kAssignMaxModels)));
-    HIP_TRY(c, c->h_track_out.grow(track_out_size(kAssignMaxModels, kAssignMaxModels)));
-    for (int k = 0; k < K; ++k) set_model_warp(c->h_assign_wp[k], models[k]);   // (sine and cosine from the host's libm)
-    HIP_TRY(c, hipMemcpyAsync(c->d_assign_wp, c->h_assign_wp, (size_t)K * sizeof(WarpParams), hipMemcpyHostToDevice, s));
-    HIP_TRY(c, hipMemsetAsync(c->d_track_out, 0, out_size * sizeof(uint32_t), s));
-    const bf_ctx::EvSet& e = c->set[c->cs];
-    a.xy = e.xy; a.t = e.t;
-    a.perm = c->has_perm ? e.perm.get() : nullptr;
-    a.wp = c->d_assign_wp;
-    a.prior = c->d_group_id.get();
+    vote_planes_window(c, kept.win, K, vp);   // (the kept options passed bf_track_keep's checks)
+    rc = vote_warps_stage(c, models, K, true, vp.a);
+    if (rc != BF_OK) return rc;
+    const size_t bytes = TrackBlock::size(K, Kp) * sizeof(uint32_t);
+    HIP_TRY(c, tr.d_out.grow(TrackBlock::size(kAssignMaxModels, kAssignMaxModels)));
+    HIP_TRY(c, tr.h_out.grow(TrackBlock::size(kAssignMaxModels, kAssignMaxModels)));
+    HIP_TRY(c, hipMemsetAsync(tr.d_out, 0, bytes, s));
     {
         ProfScope ps(c, 3);
-        launch_track_overlap(a, c->d_track_plane, Kp, (long long)dt_ns, c->d_track_out, s);
+        launch_track_overlap(vp.a, tr.plane, Kp, (long long)dt_ns, tr.d_out, s);
     }
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(c->h_track_out, c->d_track_out, out_size * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(c, hipMemcpyAsync(tr.h_out, tr.d_out, bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(c, hipStreamSynchronize(s));
-    const uint32_t* h = c->h_track_out;
-    auto r = [h](size_t word) { return h[word * kTrackStride]; };
+    const uint32_t* h = tr.h_out;
     for (int k = 0; k < K; ++k) {
         uint32_t row = 0;
         for (int j = 0; j < W; ++j) {
-            const uint32_t v = r((size_t)k * W + j);
+            const uint32_t v = h[TrackBlock::overlap(K, Kp, k, j)];
             row += v;
             if (overlap_out) overlap_out[(size_t)k * W + j] = (int32_t)v;
         }
@@ -145,8 +115,8 @@ int bf_track_overlap(bf_ctx* c, const bf_track_opts* o, const bf_model* models, 
         info->models = K;
         info->kept_models = Kp;
         info->rows = vp.R; info->cols = vp.C;
-        info->outside = (int32_t)r((size_t)K * W);
-        info->unassigned = (int32_t)r((size_t)K * W + 1);
+        info->outside = (int32_t)h[TrackBlock::outside(K, Kp)];
+        info->unassigned = (int32_t)h[TrackBlock::unassigned(K, Kp)];
     }
     return BF_OK;
 }
@@ -154,8 +124,8 @@ int bf_track_overlap(bf_ctx* c, const bf_track_opts* o, const bf_model* models, 
 int bf_track_drop(bf_ctx* c) {
     if (!c) return BF_ERR_ARG;
     HIP_TRY(c, hipSetDevice(c->device));
-    c->track = bf_ctx::TrackKept();
-    c->d_track_plane = DevArray<int32_t>();   // (the handle waits for the device before it frees)
+    c->vote.track.kept = bf_ctx::VoteScratch::TrackKept();
+    c->vote.track.plane = DevArray<int32_t>();   // (the handle waits for the device before it frees)
     return BF_OK;
 }
 
